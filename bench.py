@@ -74,7 +74,14 @@ def parse():
     ap.add_argument("--inflight", type=int, default=1, help="pictures in flight: step k + 1 starts on a second stream set while step k's tail still runs (each has its own tables)")
     ap.add_argument("--serial", action="store_true", help="one stream, no overlap of the levels' chains: clean per-kernel times for profiling")
     ap.add_argument("--launch-check", action="store_true", help="every rank prints {rank, world} as one JSON line and exits before any GPU work (the CPU test of the --gpus N self-launch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write the result records of the last timed step (per level: PU decisions, TU "
+                    "results, MTS flags, chroma TU results, affine results) as DIR/<name>.npy in float64, at most 60 MiB in all (a fixed, seeded row sample of the larger "
+                    "tables, its row numbers in DIR/<name>_rows.npy); one GPU only")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1 (the gathered records of N ranks are not decoded)")
     if not a.lite:
         a.smvd, a.affine, a.transform_skip = True, True, True
     a.dpoc_list = [int(x) for x in a.dpoc.split(",") if x] if a.dpoc else [2 * (k + 1) for k in range(a.refs)]
@@ -115,6 +122,56 @@ def counters_for(kernel, meta, wkey, same_args=True):
     f = KERNEL_SRC.get(kernel)
     m, w = meta["src_sha1"], wkey["src_sha1"]
     return f is not None and m.get(f) == w.get(f) and m.get("headers") == w.get("headers") and (not same_args or meta.get("args") == wkey["args"])
+
+
+DUMP_BUDGET = 60 << 20      # bytes of all .npy payloads of --dump-outputs (below 64 MB with the file headers)
+
+
+def result_arrays(f):
+    """the result records of f's last run() -- what FrameHotPath.result_tensors() hands on -- decoded to numbers, one 2-D array per (level, table)"""
+    from numpy.lib import recfunctions as rf
+    from vtm_amd.pipeline import AFFOUT_DT, PU_DT
+
+    def rec(t, dt):
+        r = t.cpu().numpy().view(dt).reshape(-1)
+        return rf.structured_to_unstructured(r[[n for n in dt.names if n != "pad"]], dtype=np.float64)
+
+    out = {}
+    for i, lvl in enumerate(f.levels):
+        tag = "L%d_%dx%d" % (i, lvl["w"], lvl["h"])
+        out[tag + "_pus"] = rec(lvl["pus"], PU_DT)
+        out[tag + "_tu_res"] = lvl["tu_res"].cpu().numpy()
+        out[tag + "_mts_test"] = lvl["mts_test"].cpu().numpy()
+        if f.chroma is not None:
+            out[tag + "_tu_res_c"] = lvl["tu_res_c"].cpu().numpy()
+        if "aff_out" in lvl:
+            out[tag + "_aff_out"] = rec(lvl["aff_out"], AFFOUT_DT)
+    return out
+
+
+def dump_outputs(arrays, d, budget=DUMP_BUDGET):
+    """arrays -> d/<name>.npy (float64, rows x columns).  The budget is shared out smallest table first; a table larger than its share is replaced by a
+    row sample drawn from a seed fixed by its name (the same rows for the same arguments), with the row numbers in d/<name>_rows.npy."""
+    import zlib
+    os.makedirs(d, exist_ok=True)
+    items = sorted(((k, np.asarray(v, np.float64).reshape(len(v), -1)) for k, v in arrays.items()), key=lambda kv: kv[1].nbytes)
+    left, info = budget, {"bytes": 0, "files": 0, "sampled": {}}
+    for i, (name, a) in enumerate(items):
+        share = left // (len(items) - i)
+        rows_path = os.path.join(d, name + "_rows.npy")
+        if a.nbytes > share:
+            k = max(1, share // (8 * (a.shape[1] + 1)))
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.shape[0], k, replace=False)).astype(np.float64)
+            np.save(rows_path, idx)
+            info["sampled"][name] = {"rows": a.shape[0], "kept": int(k)}
+            a, left, info["files"] = a[idx.astype(np.int64)], left - idx.nbytes, info["files"] + 1
+            info["bytes"] += idx.nbytes
+        elif os.path.exists(rows_path):
+            os.remove(rows_path)      # left by an earlier dump of a larger table under the same name
+        np.save(os.path.join(d, name + ".npy"), a)
+        left, info["bytes"], info["files"] = left - a.nbytes, info["bytes"] + a.nbytes, info["files"] + 1
+    info["dir"] = d
+    return info
 
 
 def cpu_baseline(hp, cur_np, dpb_np, refs, sr, W, H, lam, qp, budget_s, pocs=None, chroma=None, affine=False, low_delay=False, smvd=None):
@@ -380,16 +437,20 @@ def main():
             graphs[id(f)] = g
         g.replay()
 
+    last = [fme]      # the table set of the step queued last: its result records are that step's outputs
+
     def step():
         if xchg is not None:
             slot = xchg.next()
             run_picture(fme_slot[slot], dpb.data_ptr())
             gath.submit(res_slot[slot])
+            last[0] = fme_slot[slot]
         elif len(fmes) == 1:
             run_picture(fme, dpb.data_ptr())
         else:
             k = turn[0] % len(fmes)
             turn[0] += 1
+            last[0] = fmes[k]
             with torch.cuda.stream(lanes[k]):
                 ctx.set_stream(lanes[k].cuda_stream)
                 fmes[k].run(cur.data_ptr(), dpb.data_ptr())
@@ -420,6 +481,7 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = dump_outputs(result_arrays(last[0]), a.dump_outputs) if a.dump_outputs and rank == 0 else None
 
     # ---- per-stage and per-kernel time: a separate, event-instrumented pass after the timed region ---------------------------------
     # stage_ms: events between the steps of the serial order; kernel times: HIP events around every launch of the main kernels, recorded by the
@@ -559,6 +621,8 @@ def main():
             "satd_gblocks_per_s": float(satd_g.item()),
             "stages_ms": stage_acc, "kernels": kern, "workload_key": wkey,
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         if sad_cands:
             tz_ms = sum(kern[k]["ms_per_step"] for k in ("tz_search_kernel", "tz_group_kernel", "tz_raster_cols_kernel") if k in kern)
             alg = sum(c * ((4 * w * h) >> ss) for (w, h, ss, n, c) in sad_cands)
