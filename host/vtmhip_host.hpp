@@ -44,6 +44,9 @@ struct CPelBuf
 };
 
 enum ComponentID { COMPONENT_Y = 0, COMPONENT_Cb = 1, COMPONENT_Cr = 2, MAX_NUM_COMPONENT = 3 };
+enum ChromaFormat { CHROMA_400 = 0, CHROMA_420 = 1, CHROMA_422 = 2, CHROMA_444 = 3 };   // TypeDef.h
+inline int getComponentScaleX( ComponentID c, ChromaFormat cf ) { return c != COMPONENT_Y && ( cf == CHROMA_420 || cf == CHROMA_422 ) ? 1 : 0; }   // ChromaFormat.h
+inline int getComponentScaleY( ComponentID c, ChromaFormat cf ) { return c != COMPONENT_Y && cf == CHROMA_420 ? 1 : 0; }
 
 // DFunc numbering of the slots this path uses (TypeDef.h:476-554): base + floorLog2(width), dedicated slots for 12/24/48
 enum DFunc
@@ -53,6 +56,7 @@ enum DFunc
   DF_HAD, DF_HAD2, DF_HAD4, DF_HAD8, DF_HAD16, DF_HAD32, DF_HAD64, DF_HAD16N,
   DF_SAD12, DF_SAD24, DF_SAD48,
   DF_SAD_WITH_MASK,
+  DF_SSE_WTD, DF_SSE2_WTD, DF_SSE4_WTD, DF_SSE8_WTD, DF_SSE16_WTD, DF_SSE32_WTD, DF_SSE64_WTD, DF_SSE16N_WTD,   // luma-level weighted SSE (TypeDef.h:540-547, WCG_EXT)
   DF_TOTAL_FUNCTIONS
 };
 
@@ -72,6 +76,8 @@ public:
   int         subShift = 0;
   const Pel  *mask = nullptr;   // GEO merge estimation (RdCost.h:97-100)
   int         maskStride = 0, stepX = 0, maskStride2 = 0;
+  CPelBuf     orgLuma;              // WCG_EXT (RdCost.h:73, 93-94): the co-located luma original a chroma DF_SSE_WTD block is weighted by
+  int         cShiftX = 0, cShiftY = 0;
 };
 
 inline int floorLog2( unsigned v ) { int r = -1; while( v ) { v >>= 1; r++; } return r; }
@@ -83,6 +89,7 @@ class RdCost
   double m_distortionWeight[MAX_NUM_COMPONENT] = { 1.0, 1.0, 1.0 };   // RdCost.h:117 (only chroma is weighted)
   int    m_iCostScale   = 0;
   int    m_predHor = 0, m_predVer = 0;
+  ChromaFormat m_cf = CHROMA_420;   // RdCost::m_cf (set by RdCost::setChromaFormat)
 
   static void guard( const DistParam &p )
   {
@@ -107,6 +114,16 @@ class RdCost
     return d;
   }
 
+  // DF_SSE*_WTD (RdCost.cpp:3088-3463): the weight tables come from vtmhip_set_luma_level_weights; applyWeight is RdCostWeightPrediction::xGetSSEw (:3095-3098)
+  static Distortion xGetSSE_WTD( const DistParam &p )
+  {
+    if( p.applyWeight ) throw Exception( "unsupported on the device path: applyWeight (keep the scalar function)" );
+    uint64_t d = 0;
+    check( vtmhip_xGetSSE_WTD( context(), p.org.buf, p.org.stride, p.cur.buf, p.cur.stride, p.org.width, p.org.height, p.compID, p.orgLuma.buf, p.orgLuma.stride,
+                               p.cShiftX, p.cShiftY, &d ), "xGetSSE_WTD" );
+    return d;
+  }
+
   static Distortion xGetSADwMask( const DistParam &p )   // RdCost.cpp:3513-3549
   {
     guard( p ); uint64_t d = 0;
@@ -127,6 +144,7 @@ public:
     for( int i = DF_HAD; i <= DF_HAD16N; i++ ) table()[i] = xGetHADs;
     table()[DF_SAD12] = table()[DF_SAD24] = table()[DF_SAD48] = xGetSAD;
     table()[DF_SAD_WITH_MASK] = xGetSADwMask;
+    for( int i = DF_SSE_WTD; i <= DF_SSE16N_WTD; i++ ) table()[i] = xGetSSE_WTD;
   }
 
   // RdCost::setDistParam( rcDP, org, piRefY, iRefStride, bitDepth, compID, subShiftMode, step, useHadamard ) (RdCost.cpp:238-324)
@@ -178,6 +196,24 @@ public:
   {
     DistParam dp;
     dp.org = org; dp.cur = cur; dp.step = 1; dp.bitDepth = bitDepth; dp.compID = compID;
+    const bool p2 = ( org.width & ( org.width - 1 ) ) == 0;
+    dp.distFunc = table()[eDFunc + ( p2 ? floorLog2( org.width ) : 0 )];
+    if( compID != COMPONENT_Y ) return ( Distortion ) ( m_distortionWeight[compID] * dp.distFunc( dp ) );
+    return dp.distFunc( dp );
+  }
+  // RdCost::getDistPart( org, cur, bitDepth, compID, eDFunc, orgLuma ) (RdCost.cpp:411-455, WCG_EXT): with orgLuma the cShift of the chroma format and the luma
+  // original (the block itself for Y) go into the DistParam; slot choice and chroma weighting as above
+  void setChromaFormat( ChromaFormat cf ) { m_cf = cf; }   // RdCost.h:148
+  Distortion getDistPart( const CPelBuf &org, const CPelBuf &cur, int bitDepth, ComponentID compID, DFunc eDFunc, const CPelBuf *orgLuma )
+  {
+    DistParam dp;
+    dp.org = org; dp.cur = cur; dp.step = 1; dp.bitDepth = bitDepth; dp.compID = compID;
+    if( orgLuma )
+    {
+      dp.cShiftX = getComponentScaleX( compID, m_cf );
+      dp.cShiftY = getComponentScaleY( compID, m_cf );
+      dp.orgLuma = compID != COMPONENT_Y ? *orgLuma : org;
+    }
     const bool p2 = ( org.width & ( org.width - 1 ) ) == 0;
     dp.distFunc = table()[eDFunc + ( p2 ? floorLog2( org.width ) : 0 )];
     if( compID != COMPONENT_Y ) return ( Distortion ) ( m_distortionWeight[compID] * dp.distFunc( dp ) );

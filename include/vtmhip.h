@@ -217,6 +217,52 @@ int vtmhip_dist_uniform_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, co
 int vtmhip_intra_cand_cost_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, int64_t orgOff, int orgStride, const int16_t *d_predBase, int64_t predOff, int n, int width,
                                       int height, uint64_t *d_dist );
 
+/* ---- luma-level-weighted SSE: RdCost::m_afpDistortFunc[DF_SSE_WTD .. DF_SSE16N_WTD] (RdCost::xGetSSE*_WTD, CommonLib/RdCost.cpp:3088-3463; slots :190-197;
+ * per-sample rule RdCost::getWeightedMSE :3055-3086) -- the CU-level final distortion with LMCS (LMCSEnable) or the luma-level-to-delta-QP (WCG) mode on:
+ * InterSearch::encodeResAndCalcRdInterCU (EncoderLib/InterSearch.cpp:7247-7264, 7585-7596), EncCu's skip / merge reconstruction distortion
+ * (EncCu.cpp:4180-4184, 4687-4690), the intra RD loops (IntraSearch.cpp:1711, 3299-3306, 4631-4742).  Per sample of a W x H block (x < W, y < H):
+ *   d      = org - cur
+ *   lumaLv = Y: org;  Cb / Cr: orgLuma[(x << cShiftX) + (y << cShiftY) * orgLumaStride]
+ *   w      = Y: LUT[lumaLv];  Cb / Cr: signalType SDR (0) / HLG (2) ? chromaWeight : LUT[lumaLv]
+ *   mse    = (int32_t) ( ( (int64_t) ( w * 65536.0 ) * ( d * d ) + 32768 ) >> 16 )        (Intermediate_Int is int: TRUNCATED to 32 bits)
+ *   dist  += (uint64_t) (int64_t) mse                                                        (DISTORTION_PRECISION_ADJUSTMENT = 0, FULL_NBIT)
+ * Sample contract: org, cur and orgLuma in [0, 2^bitDepth), bitDepth <= 12 (the reference CHECKs org >= 0; |d| < 2^12 keeps d * d < 2^24).
+ * The tables are the host's (RdCost::m_reshapeLumaLevelToWeightPLUT, m_chromaWeight, m_signalType; EncGOP.cpp:228-234, 1810-1853); the chroma
+ * m_distortionWeight scaling of RdCost::getDistPart (:411-455) stays with the caller, as for DF_SSE.  applyWeight (RdCostWeightPrediction::xGetSSEw)
+ * stays on the host: the trampoline falls back to the scalar function. */
+
+/* The weight tables of a context: lut[1 << lumaBD] = m_reshapeLumaLevelToWeightPLUT, converted here to the reference's fixed point (int64_t)( w * 65536.0 );
+ * every converted weight (and chromaWeight's) must lie in [0, 2^31) or the call fails.  invLut: the reshaper's inverse LUT (Reshape::getInvLUT(), 1 << lumaBD
+ * entries) for VTMHIP_WTD_INV_RESHAPE_CUR jobs, or NULL.  lumaBD: 8..12.  The copies are ordered on the context's stream before every later launch and done
+ * when the call returns (the caller may free its arrays).  Call it after RdCost::initLumaLevelToWeightTableReshape() and after every updateReshape... /
+ * restore... of EncGOP.cpp:1810-1853.  Every DF_SSE_WTD entry fails with VTMHIP_E_INVALID until it has been called. */
+int vtmhip_set_luma_level_weights( vtmhip_ctx *ctx, const double *lut, int lumaBD, int signalType, double chromaWeight, const int16_t *invLut );
+
+/* DistParam::distFunc for all eight DF_SSE*_WTD slots (host pointers, like vtmhip_xGetSSE).  compID: 0 = Y, 1 = Cb, 2 = Cr; cShiftX / cShiftY: 0 or 1
+ * (getComponentScaleX / Y of the chroma format; 0 for Y).  orgLuma / orgLumaStride: DistParam::orgLuma of a chroma block (the co-located luma original);
+ * ignored for Y, whose weight index is org itself (the reference CHECKs orgLuma == org).  A negative org sample is VTMHIP_E_INVALID (the reference's CHECK). */
+int vtmhip_xGetSSE_WTD( vtmhip_ctx *ctx, const int16_t *org, int orgStride, const int16_t *cur, int curStride, int width, int height, int compID,
+                        const int16_t *orgLuma, int orgLumaStride, int cShiftX, int cShiftY, uint64_t *dist );
+
+#define VTMHIP_WTD_INV_RESHAPE_CUR 1   /* map cur through the inverse LUT first: tmpRecLuma.rspSignal( m_pcReshape->getInvLUT() ) (Buffer.cpp:400-413), Y only */
+#define VTMHIP_WTD_INVALID_DIST    UINT64_MAX   /* d_dist of a job the kernel rejected (see vtmhip_sse_wtd_batch_dev) */
+typedef struct
+{
+  int64_t orgOff, curOff, orgLumaOff;          /* samples inside d_orgBase / d_curBase / d_orgLumaBase (orgLumaOff: chroma jobs only) */
+  int32_t orgStride, curStride, orgLumaStride;
+  int16_t width, height;                       /* 1..128 */
+  uint8_t compID, cShiftX, cShiftY, flags;     /* flags: VTMHIP_WTD_* */
+  int32_t pad;
+} vtmhip_wtd_job;
+
+/* n DF_SSE*_WTD evaluations in one launch, e.g. the Y, Cb and Cr final distortions of every CU of a level; d_dist[i] = the raw distFunc value (the
+ * caller applies m_distortionWeight to chroma, as with vtmhip_dist_batch_dev).  Small blocks share a wave (their row segments are spread over its lanes).
+ * The jobs are device-resident, so a job the kernel cannot evaluate -- width / height outside 1..128, compID > 2, a cShift > 1 or a Y job with a cShift,
+ * unknown flags, VTMHIP_WTD_INV_RESHAPE_CUR on chroma or without an inverse LUT -- gets d_dist = VTMHIP_WTD_INVALID_DIST and is not read; the call itself
+ * fails only on what the host can see (no table set, null pointers). */
+int vtmhip_sse_wtd_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_curBase, const int16_t *d_orgLumaBase, const vtmhip_wtd_job *d_jobs,
+                              int n, uint64_t *d_dist );
+
 /* SATD 8x8 block-grid micro-benchmark: every 8-aligned 8x8 block of the W x H org picture against the
  * reference picture displaced by (dx,dy) in [-r,r]^2.  d_ref must carry >= r samples of valid margin on every side.
  * d_dist[(by*(W/8)+bx)*(2r+1)^2 + (dy+r)*(2r+1) + (dx+r)], 32-bit (an 8x8 SATD of int16 samples fits). */

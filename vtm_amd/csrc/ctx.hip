@@ -43,6 +43,7 @@ int vtmhip_struct_size( int which )
   case 30: return ( int ) sizeof( vtmhip_pis_buffers );
   case 31: return ( int ) sizeof( vtmhip_smvd_job );
   case 32: return ( int ) sizeof( vtmhip_pis_pu_in );
+  case 33: return ( int ) sizeof( vtmhip_wtd_job );
   default: return -1;
   }
 }
@@ -101,6 +102,8 @@ int vtmhip_destroy( vtmhip_ctx *ctx )
   for( auto &kv : ctx->work ) if( kv.second.ptr ) ( void ) hipFree( kv.second.ptr );
   if( ctx->lfnstTab ) ( void ) hipFree( ctx->lfnstTab );
   if( ctx->trTabBuf ) ( void ) hipFree( ctx->trTabBuf );
+  if( ctx->wtdFixed ) ( void ) hipFree( ctx->wtdFixed );
+  if( ctx->wtdInv ) ( void ) hipFree( ctx->wtdInv );
   if( ctx->pinned ) ( void ) hipHostFree( ctx->pinned );
   for( auto &t : ctx->timed ) { ( void ) hipEventDestroy( t.start ); ( void ) hipEventDestroy( t.stop ); }
   for( hipEvent_t e : ctx->forkEvents ) ( void ) hipEventDestroy( e );

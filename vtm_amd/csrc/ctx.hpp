@@ -30,6 +30,12 @@ struct vtmhip_ctx
   struct WorkArena { void *ptr = nullptr; size_t size = 0; };
   std::map<std::pair<hipStream_t, int>, WorkArena> work;   // key: (stream, slot) -- slot 0: the multi-stage calls, slot 1: calls they nest (the split TZ search)
   int8_t     *lfnstTab    = nullptr;   // the caller's LFNST core matrices: g_lfnst8x8 [4][2][16][48] then g_lfnst4x4 [4][2][16][16] (vtmhip_lfnst_set_tables)
+  int32_t    *wtdFixed    = nullptr;   // DF_SSE_WTD: fixed-point luma-level weights (int64_t)( w * 65536.0 ), 1 << wtdLumaBD entries (vtmhip_set_luma_level_weights)
+  int16_t    *wtdInv      = nullptr;   // DF_SSE_WTD: the reshaper's inverse LUT for VTMHIP_WTD_INV_RESHAPE_CUR jobs (valid while wtdHasInv)
+  int         wtdLumaBD   = 0;         // 0: no table set yet
+  int         wtdSignalType = 0;
+  int32_t     wtdChromaFixed = 0;      // m_chromaWeight in the same fixed point
+  bool        wtdHasInv   = false;
   int16_t    *trTabBuf    = nullptr;   // the transform core matrices of THIS context's device (transform.hip ensure_tables; freed by vtmhip_destroy)
   const int16_t *trTab[3][7] = {};     // [type][log2 N] -> N x N forward matrix inside trTabBuf
   std::mutex  initMutex;               // guards the lazy per-context initialisations (tables, staging / workspace growth)

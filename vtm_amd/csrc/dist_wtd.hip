@@ -1,0 +1,275 @@
+// dist_wtd.hip -- luma-level-weighted SSE: RdCost::m_afpDistortFunc[DF_SSE_WTD .. DF_SSE16N_WTD] (RdCost::xGetSSE*_WTD, reference CommonLib/RdCost.cpp:3088-3463,
+// per-sample rule RdCost::getWeightedMSE :3055-3086), the CU-level final distortion of LMCS / WCG encodes.  Bit-exact with the reference under the sample
+// contract of include/vtmhip.h (org, cur, orgLuma in [0, 2^bitDepth), bitDepth <= 12), including the truncation of the weighted square to 32 bits.
+//
+// sse_wtd_kernel (wave = 64 lanes, 4 waves per workgroup):
+//   - the fixed-point weight table (<= 4096 x int32) and the inverse reshape LUT (<= 4096 x int16) are staged in LDS once per workgroup with 16-byte loads;
+//     every per-sample weight / inverse-LUT lookup is an LDS read;
+//   - a wave takes G consecutive jobs (G <= 64, chosen by the host from n) and spreads the 4-sample row segments of all of them over its 64 lanes
+//     (wave prefix scan of the segment counts): 2x2 / 4x4 chroma blocks share a wave, a 128x128 luma block keeps all lanes busy;
+//   - a lane accumulates in 64 bits while its segments belong to one job and adds the partial into the job's LDS slot when it moves on (integer sum:
+//     order-free); the 64-bit weighted square is one 32 x 32 -> 64 multiply (fixed < 2^31, d * d < 2^24), never a generic 64 x 64 one.
+#include "ctx.hpp"
+
+namespace
+{
+
+constexpr int WTD_WAVES = 4;     // waves per workgroup
+constexpr int WTD_MAX_TAB = 4096;
+
+struct WtdJobL   // a job as the kernel uses it (LDS, one per lane of a group)
+{
+  const int16_t *org, *cur, *luma;
+  int os, cs, ls;
+  int w, segs;
+  unsigned magic;   // floor((2^32 - 1) / segs): segment index -> (row, segment) without a division
+  int mode;         // bit 0: inverse-reshape cur; bit 1: chroma with the constant weight; bit 2: chroma weighted by the co-located luma; bits 8..: cShiftX | cShiftY << 1
+};
+
+struct __attribute__( ( packed, aligned( 2 ) ) ) WPel4 { unsigned v[2]; };
+
+__device__ __forceinline__ unsigned long long wmse( int fixed, int o, int c )
+{
+  const int      d  = o - c;
+  const unsigned dd = ( unsigned ) d * ( unsigned ) d;                                                // < 2^24 under the sample contract
+  const unsigned long long p = ( unsigned long long ) ( unsigned ) fixed * dd;                        // v_mul_lo_u32 + v_mul_hi_u32
+  const int mse = ( int ) ( unsigned ) ( ( p + 32768ull ) >> 16 );                                   // Intermediate_Int( ... ): low 32 bits
+  return ( unsigned long long ) ( long long ) mse;                                                    // Distortion( mse >> 0 )
+}
+
+__global__ __launch_bounds__( 64 * WTD_WAVES ) void sse_wtd_kernel( const int16_t *__restrict__ orgBase, const int16_t *__restrict__ curBase,
+                                                                   const int16_t *__restrict__ lumaBase, const vtmhip_wtd_job *__restrict__ jobs, int n, int G,
+                                                                   const int32_t *__restrict__ fixedTab, const int16_t *__restrict__ invTab, int tabN,
+                                                                   int chromaFixed, int chromaConst, unsigned long long *__restrict__ out )
+{
+  extern __shared__ __attribute__( ( aligned( 16 ) ) ) int32_t sTab[];   // [tabN] fixed weights, then [tabN] int16 inverse LUT when invTab != nullptr
+  __shared__ WtdJobL            sJob[WTD_WAVES][64];
+  __shared__ int                sEnd[WTD_WAVES][64];   // inclusive prefix of the groups' segment counts
+  __shared__ unsigned long long sSum[WTD_WAVES][64];
+  int16_t *sInv = reinterpret_cast<int16_t *>( sTab + tabN );
+
+  for( int i = threadIdx.x; i < ( tabN >> 2 ); i += blockDim.x ) reinterpret_cast<int4 *>( sTab )[i] = reinterpret_cast<const int4 *>( fixedTab )[i];
+  if( invTab )
+    for( int i = threadIdx.x; i < ( tabN >> 3 ); i += blockDim.x ) reinterpret_cast<int4 *>( sInv )[i] = reinterpret_cast<const int4 *>( invTab )[i];
+
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, top = tabN - 1;
+  const int nGroups = ( n + G - 1 ) / G;
+  // every wave of a workgroup runs the same number of rounds (the barriers below)
+  for( int round = blockIdx.x * WTD_WAVES; round < nGroups; round += gridDim.x * WTD_WAVES )
+  {
+    const int grp = round + wv, base = grp * G, job = base + lane;
+    const bool mine = grp < nGroups && lane < G && job < n;
+    int  items = 0;
+    bool valid = false;
+    if( mine )
+    {
+      const vtmhip_wtd_job j = jobs[job];
+      const int  w = j.width, h = j.height, comp = j.compID, sx = j.cShiftX, sy = j.cShiftY, fl = j.flags;
+      const bool inv = ( fl & VTMHIP_WTD_INV_RESHAPE_CUR ) != 0;
+      valid = w >= 1 && w <= 128 && h >= 1 && h <= 128 && comp <= 2 && sx <= 1 && sy <= 1 && ( comp != 0 || ( sx | sy ) == 0 ) &&
+              ( fl & ~VTMHIP_WTD_INV_RESHAPE_CUR ) == 0 && ( !inv || ( comp == 0 && invTab ) );
+      if( valid )
+      {
+        WtdJobL &L = sJob[wv][lane];
+        L.org = orgBase + j.orgOff; L.cur = curBase + j.curOff; L.luma = lumaBase + j.orgLumaOff;
+        L.os = j.orgStride; L.cs = j.curStride; L.ls = j.orgLumaStride;
+        L.w = w; L.segs = ( w + 3 ) >> 2; L.magic = 0xffffffffu / ( unsigned ) L.segs;
+        L.mode = ( inv ? 1 : 0 ) | ( comp != 0 ? ( chromaConst ? 2 : 4 ) : 0 ) | ( ( sx | sy << 1 ) << 8 );
+        items = h * L.segs;
+      }
+    }
+    int incl = items;
+#pragma unroll
+    for( int o = 1; o < 64; o <<= 1 )
+    {
+      const int t = __shfl_up( incl, o, 64 );
+      if( lane >= o ) incl += t;
+    }
+    const int total = __shfl( incl, 63, 64 );
+    sEnd[wv][lane] = incl;
+    sSum[wv][lane] = 0;
+    __syncthreads();   // also orders the table staging of the first round
+
+    // lane walks the group's segments t = lane, lane + 64, ...: its job index only grows
+    int                cj = -1, start = 0, end = 0;
+    WtdJobL            L {};
+    unsigned long long acc = 0;
+    for( int t = lane; t < total; t += 64 )
+    {
+      if( t >= end )
+      {
+        if( cj >= 0 ) atomicAdd( &sSum[wv][cj], acc );
+        acc = 0;
+        do { start = end; end = sEnd[wv][++cj]; } while( t >= end );   // skips jobs without segments (rejected ones)
+        L = sJob[wv][cj];
+      }
+      const int local = t - start;
+      int       r     = ( int ) __umulhi( ( unsigned ) local, L.magic );
+      r += ( r + 1 ) * L.segs <= local ? 1 : 0;
+      const int x = ( local - r * L.segs ) << 2;
+      const int16_t *o = L.org + ( long ) r * L.os + x, *c = L.cur + ( long ) r * L.cs + x;
+      int ov[4], cv[4];
+      if( x + 4 <= L.w )
+      {
+        const WPel4 a = *reinterpret_cast<const WPel4 *>( o ), b = *reinterpret_cast<const WPel4 *>( c );
+#pragma unroll
+        for( int k = 0; k < 2; k++ )
+        {
+          ov[2 * k] = ( short ) ( a.v[k] & 0xffffu ); ov[2 * k + 1] = ( int ) a.v[k] >> 16;
+          cv[2 * k] = ( short ) ( b.v[k] & 0xffffu ); cv[2 * k + 1] = ( int ) b.v[k] >> 16;
+        }
+      }
+      else
+      {
+#pragma unroll
+        for( int k = 0; k < 4; k++ )
+        {
+          const bool in = x + k < L.w;   // past the block's right edge: d = 0 adds 0
+          ov[k] = in ? o[k] : 0;
+          cv[k] = in ? c[k] : 0;
+        }
+      }
+      if( L.mode & 1 )
+      {
+#pragma unroll
+        for( int k = 0; k < 4; k++ )
+          if( x + k < L.w ) cv[k] = sInv[min( max( cv[k], 0 ), top )];   // past the right edge org = cur = 0 must stay equal
+      }
+      if( L.mode & 2 )
+      {
+#pragma unroll
+        for( int k = 0; k < 4; k++ ) acc += wmse( chromaFixed, ov[k], cv[k] );
+      }
+      else if( L.mode & 4 )
+      {
+        const int      sx = ( L.mode >> 8 ) & 1, sy = ( L.mode >> 9 ) & 1;
+        const int16_t *lr = L.luma + ( long ) ( r << sy ) * L.ls;
+#pragma unroll
+        for( int k = 0; k < 4; k++ )
+        {
+          const int lv = x + k < L.w ? lr[( x + k ) << sx] : 0;
+          acc += wmse( sTab[min( max( lv, 0 ), top )], ov[k], cv[k] );
+        }
+      }
+      else
+      {
+#pragma unroll
+        for( int k = 0; k < 4; k++ ) acc += wmse( sTab[min( max( ov[k], 0 ), top )], ov[k], cv[k] );
+      }
+    }
+    if( cj >= 0 ) atomicAdd( &sSum[wv][cj], acc );
+    __syncthreads();
+    if( mine ) out[job] = valid ? sSum[wv][lane] : ~0ull;
+    __syncthreads();   // sJob / sEnd / sSum are rewritten by the next round
+  }
+}
+
+// jobs per wave: pack as many as still leave ~32 waves per CU (8 per SIMD, what the latency of the sample loads needs), at most 64
+int wtd_jobs_per_wave( const vtmhip_ctx *ctx, int n )
+{
+  const int g = n / ( ctx->numCUs * 32 );
+  return g < 1 ? 1 : g > 64 ? 64 : g;
+}
+
+int wtd_launch( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_curBase, const int16_t *d_lumaBase, const vtmhip_wtd_job *d_jobs, int n, int G,
+                unsigned long long *d_out )
+{
+  const int    tabN    = 1 << ctx->wtdLumaBD;
+  const size_t lds     = ( size_t ) tabN * sizeof( int32_t ) + ( ctx->wtdHasInv ? ( size_t ) tabN * sizeof( int16_t ) : 0 );
+  const int    nGroups = ( n + G - 1 ) / G;
+  int          blocks  = ( nGroups + WTD_WAVES - 1 ) / WTD_WAVES;
+  if( blocks > ctx->numCUs * 8 ) blocks = ctx->numCUs * 8;   // the rest loop: the tables are staged once per workgroup
+  const int chromaConst = ctx->wtdSignalType == 0 || ctx->wtdSignalType == 2;   // RESHAPE_SIGNAL_SDR / _HLG: m_chromaWeight (RdCost.cpp:3066-3076)
+  VTMHIP_TIME_KERNEL( ctx, "sse_wtd_kernel" );
+  hipLaunchKernelGGL( sse_wtd_kernel, dim3( blocks ), dim3( 64 * WTD_WAVES ), lds, ctx->stream, d_orgBase, d_curBase, d_lumaBase, d_jobs, n, G, ctx->wtdFixed,
+                      ctx->wtdHasInv ? ctx->wtdInv : nullptr, tabN, ( int ) ctx->wtdChromaFixed, chromaConst, d_out );
+  VTMHIP_LAUNCHED( ctx );
+  return VTMHIP_OK;
+}
+
+}   // namespace
+
+extern "C"
+{
+
+int vtmhip_set_luma_level_weights( vtmhip_ctx *ctx, const double *lut, int lumaBD, int signalType, double chromaWeight, const int16_t *invLut )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  VTMHIP_REQUIRE( ctx, lut != nullptr, "null weight table" );
+  VTMHIP_REQUIRE( ctx, lumaBD >= 8 && lumaBD <= 12, "lumaBD must be 8..12" );
+  const int                  tabN = 1 << lumaBD;
+  const double               lim  = 2147483648.0;   // the fixed weight times d * d (< 2^24) must stay inside the 32 x 32 -> 64 product
+  std::vector<int32_t>       fx( tabN );
+  for( int i = 0; i < tabN; i++ )
+  {
+    const double v = lut[i] * 65536.0;
+    VTMHIP_REQUIRE( ctx, v >= 0.0 && v < lim, "a luma-level weight * 65536 is outside [0, 2^31)" );
+    fx[i] = ( int32_t ) ( int64_t ) v;   // (int64_t)( weight * (double)( 1 << 16 ) ), RdCost.cpp:3082
+  }
+  const double cv = chromaWeight * 65536.0;
+  VTMHIP_REQUIRE( ctx, cv >= 0.0 && cv < lim, "chromaWeight * 65536 is outside [0, 2^31)" );
+  std::lock_guard<std::mutex> lock( ctx->initMutex );
+  if( !ctx->wtdFixed ) VTMHIP_HIP( ctx, hipMalloc( ( void ** ) &ctx->wtdFixed, WTD_MAX_TAB * sizeof( int32_t ) ) );
+  if( invLut && !ctx->wtdInv ) VTMHIP_HIP( ctx, hipMalloc( ( void ** ) &ctx->wtdInv, WTD_MAX_TAB * sizeof( int16_t ) ) );
+  VTMHIP_HIP( ctx, hipMemcpyAsync( ctx->wtdFixed, fx.data(), tabN * sizeof( int32_t ), hipMemcpyHostToDevice, ctx->stream ) );
+  if( invLut ) VTMHIP_HIP( ctx, hipMemcpyAsync( ctx->wtdInv, invLut, tabN * sizeof( int16_t ), hipMemcpyHostToDevice, ctx->stream ) );
+  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );   // fx and the caller's arrays may go away
+  ctx->wtdLumaBD = lumaBD; ctx->wtdSignalType = signalType; ctx->wtdChromaFixed = ( int32_t ) ( int64_t ) cv; ctx->wtdHasInv = invLut != nullptr;
+  return VTMHIP_OK;
+}
+
+int vtmhip_sse_wtd_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_curBase, const int16_t *d_orgLumaBase, const vtmhip_wtd_job *d_jobs,
+                              int n, uint64_t *d_dist )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  VTMHIP_REQUIRE( ctx, ctx->wtdLumaBD != 0, "vtmhip_set_luma_level_weights has not been called" );
+  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
+  if( n == 0 ) return VTMHIP_OK;
+  VTMHIP_REQUIRE( ctx, d_orgBase && d_curBase && d_orgLumaBase && d_jobs && d_dist, "null pointer" );
+  return wtd_launch( ctx, d_orgBase, d_curBase, d_orgLumaBase, d_jobs, n, wtd_jobs_per_wave( ctx, n ), ( unsigned long long * ) d_dist );
+}
+
+int vtmhip_xGetSSE_WTD( vtmhip_ctx *ctx, const int16_t *org, int orgStride, const int16_t *cur, int curStride, int width, int height, int compID,
+                        const int16_t *orgLuma, int orgLumaStride, int cShiftX, int cShiftY, uint64_t *dist )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  VTMHIP_REQUIRE( ctx, ctx->wtdLumaBD != 0, "vtmhip_set_luma_level_weights has not been called" );
+  VTMHIP_REQUIRE( ctx, org && cur && dist, "null pointer" );
+  VTMHIP_REQUIRE( ctx, width >= 1 && height >= 1 && width <= 128 && height <= 128, "block size must be 1..128" );
+  VTMHIP_REQUIRE( ctx, compID >= 0 && compID <= 2, "compID must be 0..2" );
+  VTMHIP_REQUIRE( ctx, cShiftX >= 0 && cShiftX <= 1 && cShiftY >= 0 && cShiftY <= 1 && ( compID != 0 || ( cShiftX | cShiftY ) == 0 ), "cShiftX / cShiftY" );
+  const bool lumaW = compID != 0 && !( ctx->wtdSignalType == 0 || ctx->wtdSignalType == 2 );   // chroma weighted by the co-located luma level
+  VTMHIP_REQUIRE( ctx, compID == 0 || orgLuma, "a chroma block needs orgLuma" );
+  // stage org, cur and (chroma) the luma samples the block reads compactly: stride = width, luma rows of lw = ((width - 1) << cShiftX) + 1 samples
+  const int    lw  = compID != 0 ? ( ( width - 1 ) << cShiftX ) + 1 : 1;
+  const size_t blk = ( size_t ) width * height * sizeof( int16_t ), lblk = ( size_t ) lw * height * sizeof( int16_t );
+  const size_t lumaOff = ( 2 * blk + 63 ) & ~( size_t ) 63, jobOff = ( lumaOff + lblk + 63 ) & ~( size_t ) 63, outOff = jobOff + 64;
+  int st = vtmhip_internal_scratch( ctx, outOff + 64 );
+  if( st ) return st;
+  char *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
+  for( int y = 0; y < height; y++ )
+  {
+    const int16_t *o = org + ( ptrdiff_t ) y * orgStride;
+    for( int x = 0; x < width; x++ ) VTMHIP_REQUIRE( ctx, o[x] >= 0, "negative org sample (RdCost.cpp:3060: CHECK( org < 0 ))" );
+    memcpy( hp + ( size_t ) y * width * 2, o, ( size_t ) width * 2 );
+    memcpy( hp + blk + ( size_t ) y * width * 2, cur + ( ptrdiff_t ) y * curStride, ( size_t ) width * 2 );
+    if( lumaW ) memcpy( hp + lumaOff + ( size_t ) y * lw * 2, orgLuma + ( ptrdiff_t ) ( y << cShiftY ) * orgLumaStride, ( size_t ) lw * 2 );
+  }
+  vtmhip_wtd_job j;
+  memset( &j, 0, sizeof( j ) );
+  j.orgOff = 0; j.curOff = ( int64_t ) width * height; j.orgLumaOff = ( int64_t ) ( lumaOff / 2 );
+  j.orgStride = width; j.curStride = width; j.orgLumaStride = lw;
+  j.width = ( int16_t ) width; j.height = ( int16_t ) height; j.compID = ( uint8_t ) compID;
+  j.cShiftX = ( uint8_t ) cShiftX; j.cShiftY = 0;   // the staged luma rows are already the (y << cShiftY) ones
+  memcpy( hp + jobOff, &j, sizeof( j ) );
+  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, outOff, hipMemcpyHostToDevice, ctx->stream ) );
+  st = wtd_launch( ctx, ( const int16_t * ) dp, ( const int16_t * ) dp, ( const int16_t * ) dp, ( const vtmhip_wtd_job * ) ( dp + jobOff ), 1, 1,
+                   ( unsigned long long * ) ( dp + outOff ) );
+  if( st ) return st;
+  VTMHIP_HIP( ctx, hipMemcpyAsync( hp + outOff, dp + outOff, 8, hipMemcpyDeviceToHost, ctx->stream ) );
+  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
+  memcpy( dist, hp + outOff, 8 );
+  return VTMHIP_OK;
+}
+
+}   // extern "C"

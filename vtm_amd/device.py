@@ -9,7 +9,7 @@ import numpy as np
 
 from . import lib as _lib
 from .lib import (AffineJob, DistJob, FracJob, FracResult, FullJob, IfJob, McJob, MeResult, PelOpJob, PicParams, QuantJob,   # noqa: F401
-                  TrJob, TuJob, TuResult, TzJob, VtmHipError)
+                  TrJob, TuJob, TuResult, TzJob, VtmHipError, WtdJob)
 
 
 class DevBuf:
@@ -119,6 +119,27 @@ class Context:
         self._check(self.L.vtmhip_xGetSSE(self.h, org.ctypes.data + 2 * org_off, org_stride, cur.ctypes.data + 2 * cur_off,
                                           cur_stride, w, h, C.byref(d)))
         return d.value
+
+    def set_luma_level_weights(self, lut, luma_bd, signal_type, chroma_weight, inv_lut=None):
+        """RdCost's luma-level weight table (float64, 1 << luma_bd entries), signal type and chroma weight, plus the reshaper's inverse LUT (int16) or None."""
+        lut = np.ascontiguousarray(lut, np.float64)
+        inv = None if inv_lut is None else np.ascontiguousarray(inv_lut, np.int16)
+        assert lut.size >= 1 << luma_bd and (inv is None or inv.size >= 1 << luma_bd)
+        self._check(self.L.vtmhip_set_luma_level_weights(self.h, lut.ctypes.data, luma_bd, signal_type, chroma_weight,
+                                                         None if inv is None else inv.ctypes.data))
+
+    def xGetSSE_WTD(self, org, org_stride, cur, cur_stride, w, h, comp_id, org_luma=None, org_luma_stride=0, cshift_x=0, cshift_y=0,
+                    org_off=0, cur_off=0, luma_off=0):
+        """DF_SSE*_WTD distFunc (raw, before the chroma m_distortionWeight) on host arrays; org_luma: the co-located luma original of a chroma block."""
+        d = C.c_uint64()
+        lp = None if org_luma is None else org_luma.ctypes.data + 2 * luma_off
+        self._check(self.L.vtmhip_xGetSSE_WTD(self.h, org.ctypes.data + 2 * org_off, org_stride, cur.ctypes.data + 2 * cur_off, cur_stride, w, h,
+                                              comp_id, lp, org_luma_stride, cshift_x, cshift_y, C.byref(d)))
+        return d.value
+
+    def sse_wtd_batch(self, d_org, d_cur, d_org_luma, d_jobs, n, d_out):
+        """n WtdJob evaluations; d_out[i] = the raw distFunc value (WTD_INVALID_DIST for a rejected job)."""
+        self._check(self.L.vtmhip_sse_wtd_batch_dev(self.h, d_org, d_cur, d_org_luma, d_jobs, n, d_out))
 
     def xGetSADwMask(self, org, org_stride, cur, cur_stride, w, h, mask, mask_off, mask_stride, step_x, mask_stride2, sub_shift=0):
         """DF_SAD_WITH_MASK on host arrays; `mask` is a 1-D int16 array, mask_off the index of DistParam::mask inside it."""

@@ -9,6 +9,8 @@ LIB_PATH = os.path.join(HERE, "libvtmhip.so")
 
 OK, E_INVALID, E_NODEVICE, E_HIP, E_NOMEM, E_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 DIST_SAD, DIST_SATD, DIST_SSE = 0, 1, 2
+WTD_INV_RESHAPE_CUR = 1           # vtmhip_wtd_job.flags
+WTD_INVALID_DIST = (1 << 64) - 1  # d_dist of a rejected vtmhip_wtd_job
 DCT2, DCT8, DST7 = 0, 1, 2
 
 
@@ -235,9 +237,15 @@ class LfnstTuJob(C.Structure):
                 ("inverse", C.c_uint8)]
 
 
+class WtdJob(C.Structure):
+    _fields_ = [("orgOff", C.c_int64), ("curOff", C.c_int64), ("orgLumaOff", C.c_int64), ("orgStride", C.c_int32), ("curStride", C.c_int32),
+                ("orgLumaStride", C.c_int32), ("width", C.c_int16), ("height", C.c_int16), ("compID", C.c_uint8), ("cShiftX", C.c_uint8),
+                ("cShiftY", C.c_uint8), ("flags", C.c_uint8), ("pad", C.c_int32)]
+
+
 _STRUCTS = [DistJob, TzJob, MeResult, PicParams, IfJob, FracJob, FracResult, TrJob, QuantJob, FullJob, McJob, PelOpJob,
             TuJob, TuResult, AffineJob, MeCfg, MeJob, MeOut, PredJob, MaskedSadJob, GeoBlendJob, DmvrJob, LfnstJob,
-            PisRow, PisPu, PisLevel, AffineMeJob, AffineMeOut, LfnstTuJob, PisLevelRun, PisBuffers, SmvdJob, PisPuIn]   # order of vtmhip_struct_size(which)
+            PisRow, PisPu, PisLevel, AffineMeJob, AffineMeOut, LfnstTuJob, PisLevelRun, PisBuffers, SmvdJob, PisPuIn, WtdJob]   # order of vtmhip_struct_size(which)
 
 # every symbol include/vtmhip.h declares (tests/test_abi.py checks the exports against the header text)
 _PROTOS = {
@@ -282,6 +290,10 @@ _PROTOS = {
     "vtmhip_weightedGeoBlk_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vtmhip_xGetSSE": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                  C.POINTER(C.c_uint64)]),
+    "vtmhip_set_luma_level_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]),
+    "vtmhip_xGetSSE_WTD": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                     C.POINTER(C.c_uint64)]),
+    "vtmhip_sse_wtd_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vtmhip_filterHor": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                    C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vtmhip_filterVer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
