@@ -12,6 +12,7 @@
 // multiplication correctly rounded, no contraction: the build uses -fno-fast-math -ffp-contract=off), so every decision is bit-identical.
 #include "ctx.hpp"
 #include "had.hpp"
+#include "mv_rules.hpp"
 
 #include <cmath>
 
@@ -26,13 +27,6 @@ __constant__ int16_t c_affTaps4x4[16][8] = {   // m_lumaFilter4x4 (Interpolation
 
 __device__ __forceinline__ int clip3( int lo, int hi, int v ) { return min( hi, max( lo, v ) ); }
 __device__ __forceinline__ void round_affine_mv( int &x, int &y, int shift ) { const int o = 1 << ( shift - 1 ); x = ( x + o - ( x >= 0 ) ) >> shift; y = ( y + o - ( y >= 0 ) ) >> shift; }
-__device__ __forceinline__ int ilog2i( int v ) { return 31 - __clz( v ); }
-__device__ __forceinline__ int prec_dn( int v, int rs ) { if( rs == 0 ) return v; const int o = 1 << ( rs - 1 ); return v >= 0 ? ( v + o - 1 ) >> rs : ( v + o ) >> rs; }
-__device__ __forceinline__ unsigned eg_bits( int v )
-{
-  const unsigned t = ( v <= 0 ) ? ( ( unsigned ) ( -v ) << 1 ) + 1 : ( unsigned ) ( v << 1 );
-  return 1u + ( ( unsigned ) ( 31 - __clz( ( int ) t ) ) << 1 );
-}
 
 struct Mv3 { int v[3][2]; };
 
@@ -200,8 +194,8 @@ __device__ __forceinline__ void subblock_column( const int16_t *r0, int rs, int 
 __device__ void affine_pred( const AffCtx &c, const Mv3 &m, int16_t *sPred )
 {
   const int iBit = 7, w = c.w, h = c.h;
-  int dHX = ( m.v[1][0] - m.v[0][0] ) << ( iBit - ilog2i( w ) ), dHY = ( m.v[1][1] - m.v[0][1] ) << ( iBit - ilog2i( w ) ), dVX, dVY;
-  if( c.six ) { dVX = ( m.v[2][0] - m.v[0][0] ) << ( iBit - ilog2i( h ) ); dVY = ( m.v[2][1] - m.v[0][1] ) << ( iBit - ilog2i( h ) ); }
+  int dHX = ( m.v[1][0] - m.v[0][0] ) << ( iBit - mvr::floor_log2_u( w ) ), dHY = ( m.v[1][1] - m.v[0][1] ) << ( iBit - mvr::floor_log2_u( w ) ), dVX, dVY;
+  if( c.six ) { dVX = ( m.v[2][0] - m.v[0][0] ) << ( iBit - mvr::floor_log2_u( h ) ); dVY = ( m.v[2][1] - m.v[0][1] ) << ( iBit - mvr::floor_log2_u( h ) ); }
   else { dVX = -dHY; dVY = dHX; }
   const int  baseH = m.v[0][0] << iBit, baseV = m.v[0][1] << iBit;
   const bool over = spread_over_limit( dHX, dHY, dVX, dVY, c.interDir );
@@ -336,13 +330,13 @@ __device__ __forceinline__ unsigned long long block_dist( const int16_t *sPred, 
 
 __device__ __forceinline__ unsigned affine_mv_bits( int six, int imv, const Mv3 &m, const int pred[3][2] )
 {
-  const int rsTab[3] = { 2, 0, 4 };
+  const int rsTab[3] = { 2, 0, 4 };   // mvr::affine_amvr_shift as a table: a call here changes this loop's code
   const int n = six ? 3 : 2, rs = rsTab[imv];
   unsigned  bits = 0;
   for( int v = 0; v < n; v++ )
   {
-    const int ph = prec_dn( v == 0 ? pred[0][0] : pred[v][0] + m.v[0][0] - pred[0][0], rs ), pv = prec_dn( v == 0 ? pred[0][1] : pred[v][1] + m.v[0][1] - pred[0][1], rs );
-    bits += eg_bits( prec_dn( m.v[v][0], rs ) - ph ) + eg_bits( prec_dn( m.v[v][1], rs ) - pv );
+    const int ph = mvr::prec_down_or_keep( v == 0 ? pred[0][0] : pred[v][0] + m.v[0][0] - pred[0][0], rs ), pv = mvr::prec_down_or_keep( v == 0 ? pred[0][1] : pred[v][1] + m.v[0][1] - pred[0][1], rs );
+    bits += mvr::eg_bits( mvr::prec_down_or_keep( m.v[v][0], rs ) - ph ) + mvr::eg_bits( mvr::prec_down_or_keep( m.v[v][1], rs ) - pv );
   }
   return bits;
 }
@@ -399,11 +393,6 @@ __device__ __forceinline__ void solve_equal( double eq[ORDER + 1][ORDER + 1], do
   }
 }
 
-__device__ __forceinline__ int uni( int v ) { return __builtin_amdgcn_readfirstlane( v ); }      // a block-uniform value: keep it on the scalar side
-__device__ __forceinline__ unsigned long long uni64( unsigned long long v )
-{
-  return ( ( unsigned long long ) ( unsigned ) __builtin_amdgcn_readfirstlane( ( int ) ( v >> 32 ) ) << 32 ) | ( unsigned ) __builtin_amdgcn_readfirstlane( ( int ) v );
-}
 __device__ __forceinline__ void uni_mv3( Mv3 &m ) { for( int i = 0; i < 3; i++ ) { m.v[i][0] = uni( m.v[i][0] ); m.v[i][1] = uni( m.v[i][1] ); } }
 
 // One job = one xAffineMotionEstimation (:5340-5775).  The member evaluates a SEQUENCE of models -- the start model, one per gradient iteration, then the control-point
@@ -438,16 +427,16 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( PACKED
   int16_t  *sPat = sMem, *sPred = sMem + w * h;
   AffCtx c;
   c.ref = refBase + j.refOff; c.refStride = j.refStride; c.w = w; c.h = h; c.bd = pic.bitDepth; c.six = SIX; c.interDir = j.interDir; c.imv = j.imv;
-  c.horMax = ( pic.picW + 8 - j.puX - 1 ) << 4; c.horMin = ( -pic.ctuSize - 8 - j.puX + 1 ) << 4;
-  c.verMax = ( pic.picH + 8 - j.puY - 1 ) << 4; c.verMin = ( -pic.ctuSize - 8 - j.puY + 1 ) << 4;
+  c.horMax = MVR_CLIP_MAX( pic.picW, j.puX ); c.horMin = MVR_CLIP_MIN( pic.ctuSize, j.puX );
+  c.verMax = MVR_CLIP_MAX( pic.picH, j.puY ); c.verMin = MVR_CLIP_MIN( pic.ctuSize, j.puY );
   c.profAllowed = j.profAllowed != 0; c.profLarge = j.profNeedsLargeGrad != 0; c.profIsBi = j.profIsBi != 0;
   const bool   bi = j.bi != 0, satd = j.useSatd != 0;
-  const double fWeight = bi ? ( bcw ? fabs( ( double ) bcw / 8.0 ) : 0.5 ) : 1.0, lam = j.motionLambda;      // xGetMEDistortionWeight (InterSearch.cpp:7666-7676)
-  const int    imv = j.imv, rs = imv == 0 ? 2 : imv == 1 ? 0 : 4;      // (rsTab of the reference: MV_PRECISION of the AMVR mode)
+  const double fWeight = mvr::me_dist_weight( bi, bcw, 0 ), lam = j.motionLambda;
+  const int    imv = j.imv, rs = mvr::affine_amvr_shift( imv );
   // pattern: org, or 2*org - otherPred (removeHighFreq, unclipped), or the weighted form ( org * w0 - otherPred * w1 + 2^15 ) >> 16 under a CU-level BCW weight (Buffer.h:417-460)
   {
     const int16_t *o = orgBase + j.orgOff, *p = bi ? otherBase + j.otherPredOff : nullptr;
-    const int      nrm = bcw ? ( ( 1 << 16 ) + ( bcw > 0 ? ( bcw >> 1 ) : -( bcw >> 1 ) ) ) / bcw : 0, bw0 = nrm << 3, bw1 = ( 8 - bcw ) * nrm;
+    const int      nrm = bcw ? mvr::bcw_normaliser( bcw ) : 0, bw0 = mvr::bcw_w0( nrm ), bw1 = mvr::bcw_w1( bcw, nrm );
     for( int i = threadIdx.x; i < w * h; i += blockDim.x )
     {
       const int y = i / w, x = i - y * w;
@@ -464,7 +453,7 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( PACKED
   for( int i = 0; i < MVNUM; i++ )
   {
     tmp.v[i][0] = clip3( c.horMin, c.horMax, tmp.v[i][0] ); tmp.v[i][1] = clip3( c.verMin, c.verMax, tmp.v[i][1] );
-    tmp.v[i][0] = prec_dn( tmp.v[i][0], rs ) << rs; tmp.v[i][1] = prec_dn( tmp.v[i][1], rs ) << rs;   // roundAffinePrecInternal2Amvr
+    tmp.v[i][0] = mvr::prec_down_or_keep( tmp.v[i][0], rs ) << rs; tmp.v[i][1] = mvr::prec_down_or_keep( tmp.v[i][1], rs ) << rs;   // roundAffinePrecInternal2Amvr
   }
   best = me = base = cand = tmp;
   unsigned long long costBest = ~0ull;
@@ -569,7 +558,7 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( PACKED
           for( int i = 0; i < MVNUM; i++ )
           {
             int d0 = delta[i][0], d1 = delta[i][1];
-            if( imv == 2 ) { d0 = prec_dn( d0, 3 ) << 3; d1 = prec_dn( d1, 3 ) << 3; }
+            if( imv == 2 ) { d0 = mvr::prec_down_or_keep( d0, 3 ) << 3; d1 = mvr::prec_down_or_keep( d1, 3 ) << 3; }
             if( d0 != 0 || d1 != 0 ) { allZero = false; break; }
             allZero = true;
           }
@@ -582,7 +571,7 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( PACKED
           {
             nt.v[i][0] = clip3( -( 1 << 17 ), ( 1 << 17 ) - 1, nt.v[i][0] + delta[i][0] );
             nt.v[i][1] = clip3( -( 1 << 17 ), ( 1 << 17 ) - 1, nt.v[i][1] + delta[i][1] );
-            nt.v[i][0] = prec_dn( nt.v[i][0], rs ) << rs; nt.v[i][1] = prec_dn( nt.v[i][1], rs ) << rs;
+            nt.v[i][0] = mvr::prec_down_or_keep( nt.v[i][0], rs ) << rs; nt.v[i][1] = mvr::prec_down_or_keep( nt.v[i][1], rs ) << rs;
             nt.v[i][0] = clip3( c.horMin, c.horMax, nt.v[i][0] ); nt.v[i][1] = clip3( c.verMin, c.verMax, nt.v[i][1] );
           }
           if( j.amvrEncOpt )
@@ -673,7 +662,7 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( PACKED
     // ---- the one evaluation site: prediction, distortion, bits, comparison ----
     affine_pred( c, cand, sPred );
     __syncthreads();
-    unsigned long long cost = uni64( block_dist<PACKED>( sPred, sPat, w, h, satd, sRed ) );
+    unsigned long long cost = uni( block_dist<PACKED>( sPred, sPat, w, h, satd, sRed ) );
     unsigned           bits;
     const bool         picking = pickMvp && ( cur == P_INIT || cur == P_ITER );
     if( picking )
@@ -693,7 +682,7 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( PACKED
       bits = dirBits + minBits;
     }
     else bits = j.bits + affine_mv_bits( SIX, imv, cand, pred );
-    cost = ( unsigned long long ) ( floor( fWeight * ( double ) cost ) + ( double ) ( unsigned long long ) ( lam * bits ) );
+    cost = ( unsigned long long ) ( floor( fWeight * ( double ) cost ) + ( double ) mvr::rate( lam, bits ) );
     const bool better = cur == P_INIT || cost < costBest;
     if( better ) { costBest = cost; bitsBest = bits; best = cand; if( picking ) mvpIdx = bestMvpIdx; }
     if( cur == P_INIT ) phase = P_ITER;
@@ -738,8 +727,8 @@ __global__ __launch_bounds__( 256 ) void affine_pred_kernel( vtmhip_pic_params p
   const vtmhip_affine_me_job &j = jobs[blockIdx.x];
   AffCtx c;
   c.ref = refBase + j.refOff; c.refStride = j.refStride; c.w = j.width; c.h = j.height; c.bd = pic.bitDepth; c.six = j.sixParam; c.interDir = j.interDir; c.imv = j.imv;
-  c.horMax = ( pic.picW + 8 - j.puX - 1 ) << 4; c.horMin = ( -pic.ctuSize - 8 - j.puX + 1 ) << 4;
-  c.verMax = ( pic.picH + 8 - j.puY - 1 ) << 4; c.verMin = ( -pic.ctuSize - 8 - j.puY + 1 ) << 4;
+  c.horMax = MVR_CLIP_MAX( pic.picW, j.puX ); c.horMin = MVR_CLIP_MIN( pic.ctuSize, j.puX );
+  c.verMax = MVR_CLIP_MAX( pic.picH, j.puY ); c.verMin = MVR_CLIP_MIN( pic.ctuSize, j.puY );
   c.profAllowed = j.profAllowed != 0; c.profLarge = j.profNeedsLargeGrad != 0; c.profIsBi = j.profIsBi != 0;
   Mv3 m;
   for( int i = 0; i < 3; i++ ) { m.v[i][0] = j.mv[i][0]; m.v[i][1] = j.mv[i][1]; }

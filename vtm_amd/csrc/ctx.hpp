@@ -140,6 +140,15 @@ __device__ __forceinline__ unsigned long long wave_reduce_add_u64( unsigned long
   return v;
 }
 
+// wave-uniform values: tell the compiler (SGPRs, scalar branches instead of exec-mask control flow)
+__device__ __forceinline__ int uni( int v ) { return __builtin_amdgcn_readfirstlane( v ); }
+__device__ __forceinline__ unsigned uni( unsigned v ) { return ( unsigned ) __builtin_amdgcn_readfirstlane( ( int ) v ); }
+__device__ __forceinline__ unsigned long long uni( unsigned long long v )
+{
+  const unsigned lo = uni( ( unsigned ) v ), hi = uni( ( unsigned ) ( v >> 32 ) );
+  return ( ( unsigned long long ) hi << 32 ) | lo;
+}
+
 // XCD-aware block order: workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8 share an L2), so block b takes
 // the work item at position (b % 8) * (n / 8) + b / 8 (bijective for any n): the workgroups running on one XCD at any moment
 // then hold NEIGHBOURING jobs of the table (PUs in raster order), whose search windows overlap and stay in that XCD's 4 MiB L2.

@@ -15,6 +15,7 @@
 // One wave per PU: window -> LDS once, 3 H passes per round (one per horizontal phase), 9 V passes + SATDs.
 #include "ctx.hpp"
 #include "mest_glue.hpp"
+#include "mv_rules.hpp"
 #include "had.hpp"
 
 #include <type_traits>
@@ -210,19 +211,10 @@ __device__ __forceinline__ unsigned long long block_dist( const int16_t *org, in
   return wave_reduce_add_u64( acc );
 }
 
-__device__ __forceinline__ int floor_log2_u( unsigned v ) { return 31 - __clz( ( int ) v ); }
-__device__ __forceinline__ unsigned eg_bits( int v )
-{
-  // xGetExpGolombNumberOfBits (RdCost.h:301-313): its `while( t > 128 ) { len += 14; t >>= 7; }` only splits floorLog2( t ) = 7 + floorLog2( t >> 7 ),
-  // so the length is 1 + 2 * floorLog2( t ) for every t >= 1 -- no loop
-  const unsigned t = ( v <= 0 ) ? ( ( unsigned ) ( -v ) << 1 ) + 1 : ( unsigned ) ( v << 1 );
-  return 1u + ( ( unsigned ) ( 31 - __clz( ( int ) t ) ) << 1 );
-}
 // getCostOfVectorWithPredictor( x, y, 0 ) with m_iCostScale = costScale (RdCost.h:314-315)
 __device__ __forceinline__ unsigned long long mv_cost( double lambda, int predHor, int predVer, int costScale, int x, int y )
 {
-  const unsigned bits = eg_bits( ( x << costScale ) - predHor ) + eg_bits( ( y << costScale ) - predVer );
-  return ( unsigned long long ) ( lambda * ( double ) bits );
+  return mvr::rate( lambda, mvr::mv_bits( x, y, predHor, predVer, costScale, 0 ) );
 }
 
 __constant__ int8_t c_refineH[9][2] = { { 0, 0 }, { 0, -1 }, { 0, 1 }, { -1, 0 }, { 1, 0 }, { -1, -1 }, { 1, -1 }, { -1, 1 }, { 1, 1 } };

@@ -7,6 +7,7 @@
 // addAvg :467-507 (dst = clip((a + b + offset) >> shift) on 14-bit intermediates).
 #include "ctx.hpp"
 #include "mc_block.hpp"
+#include "mv_rules.hpp"
 
 namespace
 {
@@ -115,8 +116,8 @@ __device__ __forceinline__ void motion_comp_body( const int16_t *__restrict__ or
   ep.w0 = ep.w1 = 0;
   if( ep.mode == 2 && j.bcwWeight != 0 && j.bcwWeight != 4 )
   {
-    const int bcw = j.bcwWeight, nrm = ( ( 1 << 16 ) + ( bcw > 0 ? ( bcw >> 1 ) : -( bcw >> 1 ) ) ) / bcw;
-    ep.w0 = nrm << 3; ep.w1 = ( 8 - bcw ) * nrm; ep.mode = 4;
+    const int bcw = j.bcwWeight, nrm = mvr::bcw_normaliser( bcw );
+    ep.w0 = mvr::bcw_w0( nrm ); ep.w1 = mvr::bcw_w1( bcw, nrm ); ep.mode = 4;
   }
   unsigned sadAcc = 0;
   ep.sad = &sadAcc;
@@ -177,8 +178,8 @@ __global__ __launch_bounds__( THREADS * JPB ) void motion_comp_amvp_kernel( vtmh
     const vtmhip_me_job &r = rows[i >> 1];
     const int c = ( i & 1 ) < r.numAmvpCand ? ( i & 1 ) : 0;   // a missing second candidate repeats the first (its cost is not looked at)
     int th = r.amvpCand[c][0], tv = r.amvpCand[c][1];
-    th = min( ( pic.picW + 8 - r.puX - 1 ) << 4, max( ( -pic.ctuSize - 8 - r.puX + 1 ) << 4, th ) );   // clipMvInPic (Mv.cpp:56-74)
-    tv = min( ( pic.picH + 8 - r.puY - 1 ) << 4, max( ( -pic.ctuSize - 8 - r.puY + 1 ) << 4, tv ) );
+    th = mvr::mv_clip_axis( th, pic.picW, pic.ctuSize, r.puX );   // clipMvInPic
+    tv = mvr::mv_clip_axis( tv, pic.picH, pic.ctuSize, r.puY );
     vtmhip_pred_job p;
     p.orgOff = r.orgOff; p.refOff[0] = r.refOff; p.refOff[1] = r.refOff; p.predOff = 0; p.outOff = 0;
     p.orgStride = r.orgStride; p.refStride[0] = p.refStride[1] = r.refStride; p.predStride = r.width; p.outStride = r.width;
@@ -198,7 +199,7 @@ __global__ __launch_bounds__( 256 ) void pelop_kernel( const int16_t *__restrict
   const int              headRoom = max( 2, 14 - ( int ) j.bitDepth ), shift = headRoom + 1, offset = ( 1 << ( shift - 1 ) ) + 2 * 8192;
   const int              cmax = ( 1 << j.bitDepth ) - 1;
   const int              bcw = j.bcwWeight ? j.bcwWeight : 4;   // BCW ops: weight of 8 (4 = the default pair, which these ops are not called with)
-  const int              nrm = ( ( 1 << 16 ) + ( bcw > 0 ? ( bcw >> 1 ) : -( bcw >> 1 ) ) ) / bcw, bw0 = nrm << 3, bw1 = ( 8 - bcw ) * nrm;
+  const int              nrm = mvr::bcw_normaliser( bcw ), bw0 = mvr::bcw_w0( nrm ), bw1 = mvr::bcw_w1( bcw, nrm );
   for( int i = threadIdx.x; i < w * h; i += blockDim.x )
   {
     const int y = i / w, x = i - y * w;
@@ -395,10 +396,10 @@ __global__ __launch_bounds__( 64 ) void bdof_kernel( const int16_t *__restrict__
 // bioApplied holds and the matching cost is not below 2*dx*dy (:2139).
 constexpr int DMVR_PS = 28, DMVR_BS = 20;
 
-__device__ __forceinline__ void clip_mv_pic( int &hor, int &ver, const vtmhip_pic_params &pp, int x, int y )   // clipMvInPic, Mv.cpp:56-74
+__device__ __forceinline__ void clip_mv_pic( int &hor, int &ver, const vtmhip_pic_params &pp, int x, int y )   // clipMvInPic
 {
-  hor = min( ( pp.picW + 8 - x - 1 ) << 4, max( ( -pp.ctuSize - 8 - x + 1 ) << 4, hor ) );
-  ver = min( ( pp.picH + 8 - y - 1 ) << 4, max( ( -pp.ctuSize - 8 - y + 1 ) << 4, ver ) );
+  hor = mvr::mv_clip_axis( hor, pp.picW, pp.ctuSize, x );
+  ver = mvr::mv_clip_axis( ver, pp.picH, pp.ctuSize, y );
 }
 
 __device__ __forceinline__ int div_for_maxq7( long long N, long long D )   // :1733-1767

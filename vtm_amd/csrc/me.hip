@@ -1,8 +1,7 @@
 // me.hip -- integer motion search on the device: one wave (64 lanes) runs one complete InterSearch::xTZSearch.
 //
 // Reference: EncoderLib/InterSearch.cpp xTZSearch :3640-3976, xTZSearchHelp :330-419, xTZ2PointSearch :422-447,
-// xTZ8PointDiamondSearch :504-705, xSetSearchRange :3496-3563, clipMv CommonLib/Mv.cpp:56-74,
-// MV rate CommonLib/RdCost.h:301-315.
+// xTZ8PointDiamondSearch :504-705, xSetSearchRange :3496-3563, clipMv CommonLib/Mv.cpp:56-74; the MV rate: mv_rules.hpp.
 //
 // The reference evaluates one candidate per distFunc call and updates the best point after each.  Its accept rule
 // (strict '<' in evaluation order, cost = SAD + MV rate) makes every search round equivalent to
@@ -13,6 +12,7 @@
 // thousands of jobs (all PUs x reference pictures of a picture).
 #include "ctx.hpp"
 #include "mest_glue.hpp"
+#include "mv_rules.hpp"
 
 #include <cstdlib>
 
@@ -46,39 +46,19 @@ struct MeJob   // wave-uniform view of one vtmhip_tz_job
   int            totCap;   // raster column kernel: entries of the scan's totals in LDS (the dummy slot of idle lanes sits behind them)
 };
 
-__device__ __forceinline__ int floor_log2_u( unsigned v ) { return 31 - __clz( ( int ) v ); }
-
-// wave-uniform values: tell the compiler (SGPRs, scalar branches instead of exec-mask control flow)
-__device__ __forceinline__ int uni( int v ) { return __builtin_amdgcn_readfirstlane( v ); }
-__device__ __forceinline__ unsigned uni( unsigned v ) { return ( unsigned ) __builtin_amdgcn_readfirstlane( ( int ) v ); }
-__device__ __forceinline__ unsigned long long uni( unsigned long long v )
-{
-  const unsigned lo = uni( ( unsigned ) v ), hi = uni( ( unsigned ) ( v >> 32 ) );
-  return ( ( unsigned long long ) hi << 32 ) | lo;
-}
-
-__device__ __forceinline__ unsigned eg_bits( int v )
-{
-  // xGetExpGolombNumberOfBits (RdCost.h:301-313): its `while( t > 128 ) { len += 14; t >>= 7; }` only splits floorLog2( t ) = 7 + floorLog2( t >> 7 ),
-  // so the length is 1 + 2 * floorLog2( t ) for every t >= 1 -- no loop
-  const unsigned t = ( v <= 0 ) ? ( ( unsigned ) ( -v ) << 1 ) + 1 : ( unsigned ) ( v << 1 );
-  return 1u + ( ( unsigned ) ( 31 - __clz( ( int ) t ) ) << 1 );
-}
-
 __device__ __forceinline__ unsigned long long mv_cost( const MeJob &j, int x, int y )
 {
-  const unsigned bits = eg_bits( ( ( x << j.costScale ) - j.predHor ) >> j.imvShift ) + eg_bits( ( ( y << j.costScale ) - j.predVer ) >> j.imvShift );
-  const double   c    = j.lambda * ( double ) bits;   // fp64 multiply, truncation (RdCost.h:314)
+  const unsigned bits = mvr::mv_bits( x, y, j.predHor, j.predVer, j.costScale, j.imvShift );
+  const double   c    = j.lambda * ( double ) bits;   // RdCost::getCost (mvr::rate), truncated to 32 bits when narrow
   return j.narrow ? ( unsigned long long ) ( unsigned ) c : ( unsigned long long ) c;   // bits <= 126: c < 2^31 when narrow
 }
 
-__device__ __forceinline__ void clip_mv( const MeJob &j, int &hor, int &ver )
+__device__ __forceinline__ void clip_mv( const MeJob &j, int &hor, int &ver )   // clipMvInPic (Mv.cpp:56-74) with the limits of the job
 {
   hor = min( j.horMax, max( j.horMin, hor ) );
   ver = min( j.verMax, max( j.verMin, ver ) );
 }
 __device__ __forceinline__ int div_pow2( int v, int i ) { return ( v + ( 1 << ( i - 1 ) ) - ( v >= 0 ? 1 : 0 ) ) >> i; }
-__device__ __forceinline__ int prec_down( int v, int rs ) { const int o = 1 << ( rs - 1 ); return v >= 0 ? ( v + o - 1 ) >> rs : ( v + o ) >> rs; }
 
 __device__ __forceinline__ Range search_range( const MeJob &j, int predHor, int predVer, int range )
 {
@@ -972,9 +952,9 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
     unsigned bits = mj.bits;
     if( fu.amvpDout )      // xEstimateMvPredAMVP (:3088-3128): the first candidate with the smallest template cost; every lane derives it, the job's first lane stores it
     {
-      const unsigned long long c0 = fu.amvpDout[2 * ( long ) jobIdx] + mg::rate( mj.motionLambda, mj.mvpIdxBits[0] );
-      const unsigned long long c1 = mj.numAmvpCand > 1 ? fu.amvpDout[2 * ( long ) jobIdx + 1] + mg::rate( mj.motionLambda, mj.mvpIdxBits[1] ) : ~0ull;
-      mvpIdx = c0 > c1 ? 1 : 0;
+      const unsigned long long c0 = mvr::amvp_cost( fu.amvpDout[2 * ( long ) jobIdx], mj.motionLambda, mj.mvpIdxBits[0] );
+      const unsigned long long c1 = mj.numAmvpCand > 1 ? mvr::amvp_cost( fu.amvpDout[2 * ( long ) jobIdx + 1], mj.motionLambda, mj.mvpIdxBits[1] ) : ~0ull;
+      mvpIdx = mvr::amvp_pick( c0, c1 );
       predH = mvpIdx ? mj.amvpCand[1][0] : mj.amvpCand[0][0]; predV = mvpIdx ? mj.amvpCand[1][1] : mj.amvpCand[0][1];
       if( fu.addIdxBits ) bits += mvpIdx ? mj.mvpIdxBits[1] : mj.mvpIdxBits[0];
       if( lane == 0 && ( WPJ == 1 || wv == 0 ) )
@@ -1037,18 +1017,18 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
   j.predVer   = jp->predVer;
   j.costScale = 2;   // m_pcRdCost->setCostScale(2) for the integer search (InterSearch.cpp:3374)
   j.lambda    = jp->motionLambda;
-  j.horMax    = ( pic.picW + 8 - jp->puX - 1 ) << 4;
-  j.horMin    = ( -pic.ctuSize - 8 - jp->puX + 1 ) << 4;
-  j.verMax    = ( pic.picH + 8 - jp->puY - 1 ) << 4;
-  j.verMin    = ( -pic.ctuSize - 8 - jp->puY + 1 ) << 4;
+  j.horMax    = MVR_CLIP_MAX( pic.picW, jp->puX );
+  j.horMin    = MVR_CLIP_MIN( pic.ctuSize, jp->puX );
+  j.verMax    = MVR_CLIP_MAX( pic.picH, jp->puY );
+  j.verMin    = MVR_CLIP_MIN( pic.ctuSize, jp->puY );
   j.seg        = ( j.w & 7 ) == 0 ? 8 : 4;
   j.segsPerRow = j.seg == 8 ? j.w >> 3 : j.w >> 2;
   j.items      = j.segsPerRow * ( ( j.h + ( 1 << j.ss ) - 1 ) >> j.ss );
   j.lpc        = 1;
   while( j.lpc < 64 && ( j.lpc << 1 ) <= j.items ) j.lpc <<= 1;
   j.bias       = jp->signedSamples ? 0x80008000u : 0u;
-  j.lpcShift   = floor_log2_u( ( unsigned ) j.lpc );
-  j.sprShift   = ( j.segsPerRow & ( j.segsPerRow - 1 ) ) == 0 ? floor_log2_u( ( unsigned ) j.segsPerRow ) : -1;
+  j.lpcShift   = mvr::floor_log2_u( ( unsigned ) j.lpc );
+  j.sprShift   = ( j.segsPerRow & ( j.segsPerRow - 1 ) ) == 0 ? mvr::floor_log2_u( ( unsigned ) j.segsPerRow ) : -1;
   j.narrow     = j.lambda >= 0.0 && j.lambda * 126.0 < 2147483648.0;
   j.tiny       = j.narrow && ( double ) ( j.w * j.h ) * ( j.bias ? 65535.0 : ( double ) ( ( 1 << pic.bitDepth ) - 1 ) ) + j.lambda * 126.0 < 67108864.0;
 
@@ -1088,8 +1068,8 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
   // start vector (:3675-3687)
   int mx = jp->mvHor, my = jp->mvVer;
   clip_mv( j, mx, my );
-  mx = div_pow2( prec_down( mx, 2 ), 2 );
-  my = div_pow2( prec_down( my, 2 ), 2 );
+  mx = div_pow2( mvr::prec_down( mx, 2 ), 2 );
+  my = div_pow2( mvr::prec_down( my, 2 ), 2 );
   if( !jp->hasIntMv2Nx2NPred )
   {
     // Start candidates in ONE round: rcMv is always accepted first (best = max), so the zero-vector test condition
@@ -1103,7 +1083,7 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
     {
       int ex = extra[i][0], ey = extra[i][1];
       clip_mv( j, ex, ey );
-      PUSH( prec_down( ex, 4 ), prec_down( ey, 4 ), 0, 0 );
+      PUSH( mvr::prec_down( ex, 4 ), mvr::prec_down( ey, 4 ), 0, 0 );
     }
     tz_round<WPJ>( j, s, pts, n, co, true );
     if( numExtra > 14 )   // 15th candidate: the list holds 16 points
@@ -1113,7 +1093,7 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
         int n = 0;
         int ex = extra[14][0], ey = extra[14][1];
         clip_mv( j, ex, ey );
-        PUSH( prec_down( ex, 4 ), prec_down( ey, 4 ), 0, 0 );
+        PUSH( mvr::prec_down( ex, 4 ), mvr::prec_down( ey, 4 ), 0, 0 );
         m = n;
       }
       tz_round<WPJ>( j, s, pts, m, co, false );
@@ -1134,8 +1114,8 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
     }
     int ix = jp->intMv2Nx2NPredHor << 4, iy = jp->intMv2Nx2NPredVer << 4;
     clip_mv( j, ix, iy );
-    ix = div_pow2( prec_down( ix, 2 ), 2 );
-    iy = div_pow2( prec_down( iy, 2 ), 2 );
+    ix = div_pow2( mvr::prec_down( ix, 2 ), 2 );
+    iy = div_pow2( mvr::prec_down( iy, 2 ), 2 );
     if( ( mx != ix || my != iy ) && ( ix != s.bestX || iy != s.bestY ) )
     {
       int n = 0;
@@ -1149,7 +1129,7 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
     {
       int ex = extra[i][0], ey = extra[i][1];
       clip_mv( j, ex, ey );
-      PUSH( prec_down( ex, 4 ), prec_down( ey, 4 ), 0, 0 );
+      PUSH( mvr::prec_down( ex, 4 ), mvr::prec_down( ey, 4 ), 0, 0 );
     }
     tz_round<WPJ>( j, s, pts, n, co, false );
   }
@@ -1390,9 +1370,9 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( VTMHIP
   if( fu.amvpDout )      // xEstimateMvPredAMVP (:3088-3128): the first candidate with the smallest template cost
   {
     unsigned bits = mj.bits;
-    const unsigned long long c0 = fu.amvpDout[2 * ( long ) jobIdx] + mg::rate( mj.motionLambda, mj.mvpIdxBits[0] );
-    const unsigned long long c1 = mj.numAmvpCand > 1 ? fu.amvpDout[2 * ( long ) jobIdx + 1] + mg::rate( mj.motionLambda, mj.mvpIdxBits[1] ) : ~0ull;
-    mvpIdx = c0 > c1 ? 1 : 0;
+    const unsigned long long c0 = mvr::amvp_cost( fu.amvpDout[2 * ( long ) jobIdx], mj.motionLambda, mj.mvpIdxBits[0] );
+    const unsigned long long c1 = mj.numAmvpCand > 1 ? mvr::amvp_cost( fu.amvpDout[2 * ( long ) jobIdx + 1], mj.motionLambda, mj.mvpIdxBits[1] ) : ~0ull;
+    mvpIdx = mvr::amvp_pick( c0, c1 );
     predH = mvpIdx ? mj.amvpCand[1][0] : mj.amvpCand[0][0]; predV = mvpIdx ? mj.amvpCand[1][1] : mj.amvpCand[0][1];
     if( fu.addIdxBits ) bits += mvpIdx ? mj.mvpIdxBits[1] : mj.mvpIdxBits[0];
     // (every lane has read the row's fields above before lane 0 of the row rewrites them: the loads' results are consumed -- c0 / c1 / predH -- before the stores issue in program order)
@@ -1408,8 +1388,8 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( VTMHIP
   MeJob j;
   j.org = orgBase + tj.orgOff; j.ref = refBase + tj.refOff; j.orgStride = tj.orgStride; j.refStride = tj.refStride;
   j.w = tj.width; j.h = tj.height; j.ss = tj.subShift; j.imvShift = ( unsigned ) tj.imvShift; j.predHor = tj.predHor; j.predVer = tj.predVer; j.costScale = 2; j.lambda = tj.motionLambda;
-  j.horMax = ( pic.picW + 8 - tj.puX - 1 ) << 4; j.horMin = ( -pic.ctuSize - 8 - tj.puX + 1 ) << 4;
-  j.verMax = ( pic.picH + 8 - tj.puY - 1 ) << 4; j.verMin = ( -pic.ctuSize - 8 - tj.puY + 1 ) << 4;
+  j.horMax = MVR_CLIP_MAX( pic.picW, tj.puX ); j.horMin = MVR_CLIP_MIN( pic.ctuSize, tj.puX );
+  j.verMax = MVR_CLIP_MAX( pic.picH, tj.puY ); j.verMin = MVR_CLIP_MIN( pic.ctuSize, tj.puY );
   j.seg = 8; j.segsPerRow = SPR; j.items = SPR * ( ( j.h + ( 1 << SS ) - 1 ) >> SS ); j.bias = 0;
   j.narrow = j.lambda >= 0.0 && j.lambda * 126.0 < 2147483648.0;
   j.tiny   = j.narrow && ( double ) ( j.w * j.h ) * ( double ) ( ( 1 << pic.bitDepth ) - 1 ) + j.lambda * 126.0 < 67108864.0;
@@ -1429,8 +1409,8 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( VTMHIP
   // one is skipped); entry 14 follows in a round of its own (it is the last of the list either way, and a round's minimum is the first STRICT one, so the split changes nothing)
   int mx = tj.mvHor, my = tj.mvVer;
   clip_mv( j, mx, my );
-  mx = div_pow2( prec_down( mx, 2 ), 2 );
-  my = div_pow2( prec_down( my, 2 ), 2 );
+  mx = div_pow2( mvr::prec_down( mx, 2 ), 2 );
+  my = div_pow2( mvr::prec_down( my, 2 ), 2 );
   const int m = mg::num_extra( mj );
   int  cx = slot == 0 ? mx : 0, cy = slot == 0 ? my : 0, cnr = 0, cdist = 0;
   bool cv = slot == 0 || ( slot == 1 && !fast && ( mx != 0 || my != 0 ) );
@@ -1446,7 +1426,7 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( VTMHIP
       if( k < slot && oh == eh && ov == ev ) efirst = false;
     }
     clip_mv( j, eh, ev );
-    eh = prec_down( eh, 4 ); ev = prec_down( ev, 4 );
+    eh = mvr::prec_down( eh, 4 ); ev = mvr::prec_down( ev, 4 );
     e15 = m > 14 && row_read( efirst ? 1 : 0, lane, 14 ) != 0;      // entry 14 (lane 14 of the row): the second round
     // entries 0 .. 13 move two lanes up
     const int  sh = row_read( eh, lane, ( slot + 14 ) & 15 ), sv = row_read( ev, lane, ( slot + 14 ) & 15 );
@@ -1669,7 +1649,7 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( VTMHIP
       // m_uniMvList entry 14, on the row's first lane
       int ex = mj.extraStart[14][0], ey = mj.extraStart[14][1];
       clip_mv( j, ex, ey );
-      cx = prec_down( ex, 4 ); cy = prec_down( ey, 4 ); cnr = 0; cdist = 0; cv = slot == 0;
+      cx = mvr::prec_down( ex, 4 ); cy = mvr::prec_down( ey, 4 ); cnr = 0; cdist = 0; cv = slot == 0;
     }
     else
     {
@@ -1732,18 +1712,18 @@ __global__ __launch_bounds__( WPJ == 1 ? 256 : 64 * WPJ ) void full_search_kerne
   j.orgStride = jp->orgStride; j.refStride = jp->refStride;
   j.w = jp->width; j.h = jp->height; j.ss = jp->subShift; j.imvShift = jp->imvShift;
   j.predHor = jp->predHor; j.predVer = jp->predVer; j.costScale = 2; j.lambda = jp->motionLambda;
-  j.horMax = ( pic.picW + 8 - jp->puX - 1 ) << 4;
-  j.horMin = ( -pic.ctuSize - 8 - jp->puX + 1 ) << 4;
-  j.verMax = ( pic.picH + 8 - jp->puY - 1 ) << 4;
-  j.verMin = ( -pic.ctuSize - 8 - jp->puY + 1 ) << 4;
+  j.horMax = MVR_CLIP_MAX( pic.picW, jp->puX );
+  j.horMin = MVR_CLIP_MIN( pic.ctuSize, jp->puX );
+  j.verMax = MVR_CLIP_MAX( pic.picH, jp->puY );
+  j.verMin = MVR_CLIP_MIN( pic.ctuSize, jp->puY );
   j.seg        = ( j.w & 7 ) == 0 ? 8 : 4;
   j.segsPerRow = j.seg == 8 ? j.w >> 3 : j.w >> 2;
   j.items      = j.segsPerRow * ( ( j.h + ( 1 << j.ss ) - 1 ) >> j.ss );
   j.lpc        = 1;
   while( j.lpc < 64 && ( j.lpc << 1 ) <= j.items ) j.lpc <<= 1;
   j.bias       = jp->signedSamples ? 0x80008000u : 0u;
-  j.lpcShift   = floor_log2_u( ( unsigned ) j.lpc );
-  j.sprShift   = ( j.segsPerRow & ( j.segsPerRow - 1 ) ) == 0 ? floor_log2_u( ( unsigned ) j.segsPerRow ) : -1;
+  j.lpcShift   = mvr::floor_log2_u( ( unsigned ) j.lpc );
+  j.sprShift   = ( j.segsPerRow & ( j.segsPerRow - 1 ) ) == 0 ? mvr::floor_log2_u( ( unsigned ) j.segsPerRow ) : -1;
   j.narrow     = j.lambda >= 0.0 && j.lambda * 126.0 < 2147483648.0;
   j.tiny       = false;
 
@@ -1794,7 +1774,7 @@ __global__ __launch_bounds__( WPJ == 1 ? 256 : 64 * WPJ ) void full_search_kerne
       const int pos = __popcll( keep & ( ( 1ull << lane ) - 1ull ) );
       int ch = eh, cv = ev;
       clip_mv( j, ch, cv );
-      pts[pos] = make_int4( mg::prec_down( ch, 4 ), mg::prec_down( cv, 4 ), 0, 0 );
+      pts[pos] = make_int4( mvr::prec_down( ch, 4 ), mvr::prec_down( cv, 4 ), 0, 0 );
       st[pos][0] = eh; st[pos][1] = ev;
     }
     job_sync<WPJ>();
@@ -1854,8 +1834,8 @@ __global__ __launch_bounds__( ( FullSq<W, H>::THREADS ) ) void full_search_sq_ke
   MeJob j;   // per-lane view of job `jl` (set below); only the fields mv_cost / search_range read
   auto  view = [&]( const vtmhip_full_job &q ) {
     j.ss = q.subShift; j.imvShift = q.imvShift; j.predHor = q.predHor; j.predVer = q.predVer; j.costScale = 2; j.lambda = q.motionLambda;
-    j.horMax = ( pic.picW + 8 - q.puX - 1 ) << 4; j.horMin = ( -pic.ctuSize - 8 - q.puX + 1 ) << 4;
-    j.verMax = ( pic.picH + 8 - q.puY - 1 ) << 4; j.verMin = ( -pic.ctuSize - 8 - q.puY + 1 ) << 4;
+    j.horMax = MVR_CLIP_MAX( pic.picW, q.puX ); j.horMin = MVR_CLIP_MIN( pic.ctuSize, q.puX );
+    j.verMax = MVR_CLIP_MAX( pic.picH, q.puY ); j.verMin = MVR_CLIP_MIN( pic.ctuSize, q.puY );
     j.narrow = j.lambda >= 0.0 && j.lambda * 126.0 < 2147483648.0; j.tiny = false;
   };
   if( tid < nj )

@@ -12,6 +12,7 @@
 //   final     rate re-weighting (:3478-3484) or the AMVR selection loop (:4208-4262), fp64 exactly as the reference
 #include "ctx.hpp"
 #include "mest_glue.hpp"
+#include "mv_rules.hpp"
 #include "dist_block.hpp"
 #include "bucket.hpp"
 
@@ -56,7 +57,7 @@ __global__ __launch_bounds__( 256 ) void mest_pattern_kernel( const int16_t *__r
     const int      bcw = bcw_weight( j );
     if( bcw )      // removeWeightHighFreq (Buffer.h:417-460)
     {
-      const int nrm = ( ( 1 << 16 ) + ( bcw > 0 ? ( bcw >> 1 ) : -( bcw >> 1 ) ) ) / bcw, w0 = nrm << 3, w1 = ( 8 - bcw ) * nrm;
+      const int nrm = mvr::bcw_normaliser( bcw ), w0 = mvr::bcw_w0( nrm ), w1 = mvr::bcw_w1( bcw, nrm );
       for( int i = threadIdx.x; i < w * h; i += 256 )
       {
         const int y = i / w, x = i - y * w;
@@ -115,7 +116,7 @@ __global__ __launch_bounds__( 256 ) void mest_prepare_kernel( vtmhip_pic_params 
         if( e >= 0 && !extra_is_first( j, e ) ) continue;
         int th = e < 0 ? j.mvHor : j.extraStart[e][0], tv = e < 0 ? j.mvVer : j.extraStart[e][1];
         clip_mv( pic, j, th, tv );
-        sad_job( d[k], slot, sst, j, prec_down( th, 4 ), prec_down( tv, 4 ), ss, VTMHIP_DIST_SAD );
+        sad_job( d[k], slot, sst, j, mvr::prec_down( th, 4 ), mvr::prec_down( tv, 4 ), ss, VTMHIP_DIST_SAD );
         k++;
       }
     }
@@ -128,8 +129,8 @@ __global__ __launch_bounds__( 256 ) void mest_bi_start_kernel( vtmhip_pic_params
   if( i >= n ) return;
   const vtmhip_me_job &j = jobs[i];
   if( !j.bi ) return;
-  const unsigned is = imv_shift( j.imv );
-  const int      ph = prec_down( j.mvPredHor, 2 ), pv = prec_down( j.mvPredVer, 2 );
+  const unsigned is = mvr::imv_shift( j.imv );
+  const int      ph = mvr::prec_down( j.mvPredHor, 2 ), pv = mvr::prec_down( j.mvPredVer, 2 );
   unsigned long long best = 0;
   int                bestH = j.mvHor, bestV = j.mvVer;
   if( wk.needDist )      // needDist == 0: the caller promised empty m_uniMvList lists -- rcMv is the only candidate and wins whatever its cost
@@ -140,8 +141,8 @@ __global__ __launch_bounds__( 256 ) void mest_bi_start_kernel( vtmhip_pic_params
       if( e >= 0 && !extra_is_first( j, e ) ) continue;
       int th = e < 0 ? j.mvHor : j.extraStart[e][0], tv = e < 0 ? j.mvVer : j.extraStart[e][1];
       clip_mv( pic, j, th, tv );
-      th = prec_down( th, 4 ); tv = prec_down( tv, 4 );
-      const unsigned long long c = wk.dout[( long ) i * REFINE_SLOTS + k] + rate( j.motionLambda, mv_bits( th, tv, ph, pv, 2, is ) );
+      th = mvr::prec_down( th, 4 ); tv = mvr::prec_down( tv, 4 );
+      const unsigned long long c = wk.dout[( long ) i * REFINE_SLOTS + k] + mvr::rate( j.motionLambda, mvr::mv_bits( th, tv, ph, pv, 2, is ) );
       if( k == 0 || c < best ) { best = c; if( e >= 0 ) { bestH = j.extraStart[e][0]; bestV = j.extraStart[e][1]; } }
       k++;
     }
@@ -154,9 +155,9 @@ __device__ __forceinline__ void refine_test_mv( const vtmhip_me_job &j, int intX
 {
   const int px = pos == 0 ? 0 : ( pos <= 3 ? -1 : pos <= 5 ? 0 : 1 );
   const int py = pos == 0 ? 0 : ( pos <= 3 ? pos - 2 : pos == 4 ? -1 : pos == 5 ? 1 : pos - 7 );
-  const int sh = amvr_shift( j.imv );
-  const int bh = prec_down( ( intX << 4 ) - j.amvpCand[c][0], sh ) << sh;   // cBaseMvd, roundTransPrecInternal2Amvr
-  const int bv = prec_down( ( intY << 4 ) - j.amvpCand[c][1], sh ) << sh;
+  const int sh = mvr::amvr_shift( j.imv );
+  const int bh = mvr::prec_down( ( intX << 4 ) - j.amvpCand[c][0], sh ) << sh;   // cBaseMvd, roundTransPrecInternal2Amvr
+  const int bv = mvr::prec_down( ( intY << 4 ) - j.amvpCand[c][1], sh ) << sh;
   th = ( px << sh ) + bh + j.amvpCand[c][0];
   tv = ( py << sh ) + bv + j.amvpCand[c][1];
 }
@@ -193,8 +194,7 @@ __global__ __launch_bounds__( 256 ) void mest_final_kernel( vtmhip_me_cfg cfg, c
   if( i >= n ) return;
   const vtmhip_me_job   &j = jobs[i];
   const vtmhip_me_result r = wk.ires[i];
-  const int              bcw = bcw_weight( j );
-  const double           fWeight = j.bi ? ( bcw ? fabs( ( double ) bcw / 8.0 ) : 0.5 ) : 1.0;    // xGetMEDistortionWeight (:7666-7676): |getBcwWeight| / g_BcwWeightBase, 0.5 for BCW_DEFAULT
+  const double           fWeight = mvr::me_dist_weight( j.bi, bcw_weight( j ), 0 );
   const double           lam = j.motionLambda;
   vtmhip_me_out o;
   o.intX = r.mvX; o.intY = r.mvY; o.intDist = r.dist;
@@ -202,7 +202,7 @@ __global__ __launch_bounds__( 256 ) void mest_final_kernel( vtmhip_me_cfg cfg, c
   if( j.imv == 0 || j.imv == 3 ) make_out_frac( j, r.mvX, r.mvY, r.dist, wk.fres[i], o );
   else
   {
-    const int sh = amvr_shift( j.imv );
+    const int sh = mvr::amvr_shift( j.imv );
     bits -= j.mvpIdxBits[j.mvpIdx & 1];
     unsigned long long bestDist = ~0ull, satd = 0;
     int                bestH = r.mvX << 4, bestV = r.mvY << 4, bestBits = 0, bestIdx = j.mvpIdx;
@@ -218,15 +218,15 @@ __global__ __launch_bounds__( 256 ) void mest_final_kernel( vtmhip_me_cfg cfg, c
         if( c == 0 || th != t0h || tv != t0v ) dist = satd = ( unsigned long long ) ( ( double ) wk.dout[( long ) i * REFINE_SLOTS + pos * 2 + c] * fWeight );
         else dist = satd;
         const int mvBits = ( int ) j.mvpIdxBits[c]
-                         + ( int ) mv_bits( prec_down( th, sh ), prec_down( tv, sh ), prec_down( j.amvpCand[c][0], sh ), prec_down( j.amvpCand[c][1], sh ), 0, 0 );
-        dist += rate( lam, ( unsigned ) mvBits );
+                         + ( int ) mvr::mv_bits( mvr::prec_down( th, sh ), mvr::prec_down( tv, sh ), mvr::prec_down( j.amvpCand[c][0], sh ), mvr::prec_down( j.amvpCand[c][1], sh ), 0, 0 );
+        dist += mvr::rate( lam, ( unsigned ) mvBits );
         if( dist < bestDist ) { bestDist = dist; bestH = th; bestV = tv; bestIdx = c; bestBits = mvBits; }
       }
     }
     o.mvHor = bestH; o.mvVer = bestV; o.mvpIdx = bestIdx; o.mvPredHor = j.amvpCand[bestIdx][0]; o.mvPredVer = j.amvpCand[bestIdx][1];
     bits += ( unsigned ) bestBits;
     o.bits = bits;
-    o.cost = bestDist - rate( lam, ( unsigned ) bestBits ) + rate( lam, bits );
+    o.cost = bestDist - mvr::rate( lam, ( unsigned ) bestBits ) + mvr::rate( lam, bits );
   }
   out[i] = o;
 }
@@ -269,9 +269,8 @@ __global__ __launch_bounds__( 576 ) void mest_amvr_kernel( vtmhip_pic_params pic
   if( pos != 0 ) return;
   // the selection (:4208-4262): lane k = (position k / 2, candidate k & 1) prices its test vector; the first strict minimum in the reference's evaluation order = the
   // lexicographic minimum of (cost, k)
-  const int      bcw = bcw_weight( j );
-  const double   fWeight = j.bi ? ( bcw ? fabs( ( double ) bcw / 8.0 ) : 0.5 ) : 1.0, lam = j.motionLambda;
-  const int      sh = amvr_shift( j.imv ), nc = min( ( int ) j.numAmvpCand, 2 );
+  const double   fWeight = mvr::me_dist_weight( j.bi, bcw_weight( j ), 0 ), lam = j.motionLambda;
+  const int      sh = mvr::amvr_shift( j.imv ), nc = min( ( int ) j.numAmvpCand, 2 );
   const int      p = lane >> 1, c = lane & 1;
   unsigned long long cost = ~0ull;
   int                th = 0, tv = 0, mvBits = 0;
@@ -282,8 +281,8 @@ __global__ __launch_bounds__( 576 ) void mest_amvr_kernel( vtmhip_pic_params pic
     refine_test_mv( j, r.mvX, r.mvY, p, c, th, tv );
     const bool own = c == 0 || th != t0h || tv != t0v;
     const unsigned long long d = ( unsigned long long ) ( ( double ) sDist[p * 2 + ( own ? c : 0 )] * fWeight );
-    mvBits = ( int ) j.mvpIdxBits[c] + ( int ) mv_bits( prec_down( th, sh ), prec_down( tv, sh ), prec_down( j.amvpCand[c][0], sh ), prec_down( j.amvpCand[c][1], sh ), 0, 0 );
-    cost = d + rate( lam, ( unsigned ) mvBits );
+    mvBits = ( int ) j.mvpIdxBits[c] + ( int ) mvr::mv_bits( mvr::prec_down( th, sh ), mvr::prec_down( tv, sh ), mvr::prec_down( j.amvpCand[c][0], sh ), mvr::prec_down( j.amvpCand[c][1], sh ), 0, 0 );
+    cost = d + mvr::rate( lam, ( unsigned ) mvBits );
   }
   unsigned long long bc = cost;
   unsigned           bk = ( unsigned ) lane;
@@ -300,7 +299,7 @@ __global__ __launch_bounds__( 576 ) void mest_amvr_kernel( vtmhip_pic_params pic
   o.mvHor = th; o.mvVer = tv; o.mvpIdx = c; o.mvPredHor = j.amvpCand[c][0]; o.mvPredVer = j.amvpCand[c][1];
   const unsigned bits = j.bits - j.mvpIdxBits[j.mvpIdx & 1] + ( unsigned ) mvBits;
   o.bits = bits;
-  o.cost = cost - rate( lam, ( unsigned ) mvBits ) + rate( lam, bits );
+  o.cost = cost - mvr::rate( lam, ( unsigned ) mvBits ) + mvr::rate( lam, bits );
   out[i] = o;
 }
 

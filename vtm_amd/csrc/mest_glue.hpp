@@ -4,36 +4,22 @@
 //     xMotionEstimation rows themselves in a prologue (a record in LDS, built by one lane of the job's workgroup) and frac_search_* writes the row's final result in its
 //     epilogue -- the one-thread-per-row launches between the searches (amvp_select, mest_prepare, mest_mid, mest_final: 232-byte records moved at HBM speed, and a launch each on
 //     the dependent chain of a level / of a CU-level call) disappear for uniform batches.
-// One source for both, so that the fused and the stand-alone forms cannot drift apart.
+// One source for both, so that the fused and the stand-alone forms cannot drift apart; the motion-vector rules themselves are in mv_rules.hpp.
 #pragma once
 #include "ctx.hpp"
+#include "mv_rules.hpp"
 
 namespace mg
 {
 
-__device__ __forceinline__ unsigned eg_bits( int v )
+__device__ __forceinline__ void clip_mv( const vtmhip_pic_params &pic, const vtmhip_me_job &j, int &hor, int &ver )   // clipMvInPic (Mv.cpp:56-74)
 {
-  // xGetExpGolombNumberOfBits (RdCost.h:301-313): its `while( t > 128 ) { len += 14; t >>= 7; }` only splits floorLog2( t ) = 7 + floorLog2( t >> 7 ),
-  // so the length is 1 + 2 * floorLog2( t ) for every t >= 1 -- no loop
-  const unsigned t = ( v <= 0 ) ? ( ( unsigned ) ( -v ) << 1 ) + 1 : ( unsigned ) ( v << 1 );
-  return 1u + ( ( unsigned ) ( 31 - __clz( ( int ) t ) ) << 1 );
-}
-__device__ __forceinline__ unsigned mv_bits( int x, int y, int predHor, int predVer, int costScale, unsigned imvShift )
-{
-  return eg_bits( ( ( x << costScale ) - predHor ) >> imvShift ) + eg_bits( ( ( y << costScale ) - predVer ) >> imvShift );
-}
-__device__ __forceinline__ unsigned long long rate( double lambda, unsigned bits ) { return ( unsigned long long ) ( lambda * bits ); }   // RdCost::getCost
-__device__ __forceinline__ int prec_down( int v, int rs ) { const int o = 1 << ( rs - 1 ); return v >= 0 ? ( v + o - 1 ) >> rs : ( v + o ) >> rs; }   // Mv::changePrecision
-__device__ __forceinline__ int amvr_shift( int imv ) { return imv == 0 ? 2 : imv == 1 ? 4 : imv == 2 ? 6 : 3; }   // Mv::m_amvrPrecision vs INTERNAL
-__device__ __forceinline__ void clip_mv( const vtmhip_pic_params &pic, const vtmhip_me_job &j, int &hor, int &ver )   // clipMvInPic
-{
-  const int horMax = ( pic.picW + 8 - j.puX - 1 ) << 4, horMin = ( -pic.ctuSize - 8 - j.puX + 1 ) << 4;
-  const int verMax = ( pic.picH + 8 - j.puY - 1 ) << 4, verMin = ( -pic.ctuSize - 8 - j.puY + 1 ) << 4;
+  const int horMax = MVR_CLIP_MAX( pic.picW, j.puX ), horMin = MVR_CLIP_MIN( pic.ctuSize, j.puX );
+  const int verMax = MVR_CLIP_MAX( pic.picH, j.puY ), verMin = MVR_CLIP_MIN( pic.ctuSize, j.puY );
   hor = min( horMax, max( horMin, hor ) );
   ver = min( verMax, max( verMin, ver ) );
 }
 __device__ __forceinline__ int sub_shift( const vtmhip_me_cfg &cfg, int w, int h ) { return cfg.fastInterSearchMode13 && h > 8 && w <= 64 ? 1 : 0; }   // RdCost.cpp:289-323, mode 2
-__device__ __forceinline__ unsigned imv_shift( int imv ) { return imv == 3 ? 1u : ( unsigned ) imv << 1; }
 // CU-level BCW weight of the searched list of a bi job (0: the default pair); the default weight (4 of 8) is normalised to 0
 __device__ __forceinline__ int bcw_weight( const vtmhip_me_job &j ) { const int w = j.bi ? VTMHIP_MEJ_BCW_WEIGHT( j.flags ) : 0; return w == 4 ? 0 : w; }
 
@@ -46,30 +32,14 @@ __device__ __forceinline__ bool extra_is_first( const vtmhip_me_job &j, int i )
 }
 __device__ __forceinline__ int num_extra( const vtmhip_me_job &j ) { return min( 15, max( 0, j.numExtraStart ) ); }
 
-// xEstimateMvPredAMVP's selection (:3088-3128): the first candidate with the smallest template cost; in place
-__device__ __forceinline__ void amvp_select( vtmhip_me_job &j, const unsigned long long *dout2, int addIdxBits, unsigned long long *distBiP )
-{
-  unsigned long long best = ~0ull;
-  int                bestIdx = 0;
-  for( int c = 0; c < j.numAmvpCand && c < 2; c++ )
-  {
-    const unsigned long long cost = dout2[c] + rate( j.motionLambda, j.mvpIdxBits[c] );
-    if( best > cost ) { best = cost; bestIdx = c; }
-  }
-  j.mvPredHor = bestIdx ? j.amvpCand[1][0] : j.amvpCand[0][0]; j.mvPredVer = bestIdx ? j.amvpCand[1][1] : j.amvpCand[0][1];
-  j.mvpIdx    = ( uint8_t ) bestIdx;
-  if( addIdxBits ) j.bits += bestIdx ? j.mvpIdxBits[1] : j.mvpIdxBits[0];
-  if( distBiP ) *distBiP = best;
-}
-
 // the xTZSearch job of a uni row (:3434-3447); `slot` / `slotStride`: where the search pattern (the original block) sits.  _scalars: everything but the start-candidate list
 // (predH / predV: the row's predictor -- j.mvPredHor / mvPredVer, or the AMVP selection a fused prologue has just made)
 __device__ __forceinline__ void make_tz_job_scalars( const vtmhip_me_cfg &cfg, const vtmhip_me_job &j, long slot, int slotStride, int predH, int predV, vtmhip_tz_job &t )
 {
   t.orgOff = slot; t.refOff = j.refOff; t.orgStride = slotStride; t.refStride = j.refStride;
-  t.puX = j.puX; t.puY = j.puY; t.width = j.width; t.height = j.height; t.subShift = ( int16_t ) sub_shift( cfg, j.width, j.height ); t.imvShift = ( uint8_t ) imv_shift( j.imv );
+  t.puX = j.puX; t.puY = j.puY; t.width = j.width; t.height = j.height; t.subShift = ( int16_t ) sub_shift( cfg, j.width, j.height ); t.imvShift = ( uint8_t ) mvr::imv_shift( j.imv );
   t.signedSamples = 0;
-  t.predHor = prec_down( predH, 2 ); t.predVer = prec_down( predV, 2 ); t.motionLambda = j.motionLambda;
+  t.predHor = mvr::prec_down( predH, 2 ); t.predVer = mvr::prec_down( predV, 2 ); t.motionLambda = j.motionLambda;
   const bool cached = ( j.flags & VTMHIP_MEJ_CACHED_INT_MV ) != 0;   // block-vector cache hit (:3360-3368): rcMv = the cached vector, xTZSearch with bFastSettings (:3434-3441)
   t.mvHor = cached ? j.mvHor : predH; t.mvVer = cached ? j.mvVer : predV;   // else rcMv = rcMvPred (:3446)
   t.searchRange = j.searchRange;
@@ -91,8 +61,8 @@ __device__ __forceinline__ void make_full_job( const vtmhip_me_cfg &cfg, const v
 {
   f.orgOff = slot; f.refOff = j.refOff; f.orgStride = slotStride; f.refStride = j.refStride;
   f.puX = j.puX; f.puY = j.puY; f.width = j.width; f.height = j.height; f.subShift = ( int16_t ) sub_shift( cfg, j.width, j.height );
-  f.imvShift = ( uint8_t ) imv_shift( j.imv ); f.signedSamples = 1;
-  f.predHor = prec_down( j.mvPredHor, 2 ); f.predVer = prec_down( j.mvPredVer, 2 ); f.motionLambda = j.motionLambda; f.centerHor = centerHor; f.centerVer = centerVer;
+  f.imvShift = ( uint8_t ) mvr::imv_shift( j.imv ); f.signedSamples = 1;
+  f.predHor = mvr::prec_down( j.mvPredHor, 2 ); f.predVer = mvr::prec_down( j.mvPredVer, 2 ); f.motionLambda = j.motionLambda; f.centerHor = centerHor; f.centerVer = centerVer;
   f.searchRange = cfg.bipredSearchRange; f.pad = 0;
 }
 
@@ -101,21 +71,20 @@ __device__ __forceinline__ void make_frac_job( int useHadME, int bitDepth, const
 {
   q.orgOff = slot; q.refOff = j.refOff; q.orgStride = slotStride; q.refStride = j.refStride; q.width = j.width; q.height = j.height;
   q.intX = ( int16_t ) intX; q.intY = ( int16_t ) intY;
-  q.predHor = prec_down( j.mvPredHor, 2 ); q.predVer = prec_down( j.mvPredVer, 2 ); q.motionLambda = j.motionLambda;
+  q.predHor = mvr::prec_down( j.mvPredHor, 2 ); q.predVer = mvr::prec_down( j.mvPredVer, 2 ); q.motionLambda = j.motionLambda;
   q.useHad = ( uint8_t ) useHadME; q.useAltHpelIf = j.imv == 3; q.imvShift = j.imv == 3; q.bitDepth = ( uint8_t ) bitDepth; q.wideOrg = bcw_weight( j ) != 0;
 }
 
 // the rate re-weighting after the fractional search (:3476-3485): the row's result
 __device__ __forceinline__ void make_out_frac( const vtmhip_me_job &j, int intX, int intY, unsigned long long intDist, const vtmhip_frac_result &f, vtmhip_me_out &o )
 {
-  const int    bcw = bcw_weight( j );
-  const double fWeight = j.bi ? ( bcw ? fabs( ( double ) bcw / 8.0 ) : 0.5 ) : 1.0;    // xGetMEDistortionWeight (:7666-7676): |getBcwWeight| / g_BcwWeightBase, 0.5 for BCW_DEFAULT
+  const double fWeight = mvr::me_dist_weight( j.bi, bcw_weight( j ), 0 );
   const double lam = j.motionLambda;
   o.intX = intX; o.intY = intY; o.intDist = intDist;
   const int      qx = ( intX << 2 ) + ( f.halfX << 1 ) + f.qterX, qy = ( intY << 2 ) + ( f.halfY << 1 ) + f.qterY;
-  const unsigned mvBits = mv_bits( qx, qy, prec_down( j.mvPredHor, 2 ), prec_down( j.mvPredVer, 2 ), 0, imv_shift( j.imv ) );
+  const unsigned mvBits = mvr::mv_bits( qx, qy, mvr::prec_down( j.mvPredHor, 2 ), mvr::prec_down( j.mvPredVer, 2 ), 0, mvr::imv_shift( j.imv ) );
   const unsigned bits = j.bits + mvBits;
-  o.cost = ( unsigned long long ) ( floor( fWeight * ( ( double ) f.cost - ( double ) rate( lam, mvBits ) ) ) + ( double ) rate( lam, bits ) );   // :3483
+  o.cost = ( unsigned long long ) ( floor( fWeight * ( ( double ) f.cost - ( double ) mvr::rate( lam, mvBits ) ) ) + ( double ) mvr::rate( lam, bits ) );   // :3483
   o.mvHor = qx << 2; o.mvVer = qy << 2; o.mvPredHor = j.mvPredHor; o.mvPredVer = j.mvPredVer; o.mvpIdx = j.mvpIdx; o.bits = bits;
 }
 

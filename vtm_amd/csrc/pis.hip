@@ -5,25 +5,10 @@
 // Heavy work stays in the library's kernels (motion_comp_kernel, dist_uniform_kernel, the searches behind vtmhip_xMotionEstimation_batch_dev);
 // here one thread per row / PU turns one stage's results into the next stage's job records, fp64 exactly where the reference uses it.
 #include "ctx.hpp"
+#include "mv_rules.hpp"
 
 namespace
 {
-
-__device__ __forceinline__ unsigned eg_bits( int v )   // RdCost::xGetExpGolombNumberOfBits (RdCost.h:301-313), closed form (see mest.hip)
-{
-  const unsigned t = ( v <= 0 ) ? ( ( unsigned ) ( -v ) << 1 ) + 1 : ( unsigned ) ( v << 1 );
-  return 1u + ( ( unsigned ) ( 31 - __clz( ( int ) t ) ) << 1 );
-}
-__device__ __forceinline__ unsigned long long rate( double lambda, unsigned bits ) { return ( unsigned long long ) ( lambda * bits ); }   // RdCost::getCost
-__device__ __forceinline__ int prec_down( int v, int rs ) { const int o = 1 << ( rs - 1 ); return v >= 0 ? ( v + o - 1 ) >> rs : ( v + o ) >> rs; }   // Mv::changePrecision
-__device__ __forceinline__ int amvr_shift( int imv ) { return imv == 0 ? 2 : imv == 1 ? 4 : imv == 2 ? 6 : 3; }
-__device__ __forceinline__ void clip_mv( const vtmhip_pic_params &pic, const vtmhip_me_job &j, int &hor, int &ver )   // clipMvInPic (Mv.cpp:56-74)
-{
-  const int horMax = ( pic.picW + 8 - j.puX - 1 ) << 4, horMin = ( -pic.ctuSize - 8 - j.puX + 1 ) << 4;
-  const int verMax = ( pic.picH + 8 - j.puY - 1 ) << 4, verMin = ( -pic.ctuSize - 8 - j.puY + 1 ) << 4;
-  hor = min( horMax, max( horMin, hor ) );
-  ver = min( verMax, max( verMin, ver ) );
-}
 
 // ---- xEstimateMvPredAMVP ---------------------------------------------------------------------------------------------------------
 struct AmvpWork
@@ -40,8 +25,8 @@ __global__ __launch_bounds__( 256 ) void amvp_select_kernel( vtmhip_me_job *__re
   int                bestIdx = 0;
   for( int c = 0; c < j.numAmvpCand && c < 2; c++ )
   {
-    const unsigned long long cost = wk.dout[2 * i + c] + rate( j.motionLambda, j.mvpIdxBits[c] );
-    if( best > cost ) { best = cost; bestIdx = c; }
+    const unsigned long long cost = mvr::amvp_cost( wk.dout[2 * i + c], j.motionLambda, j.mvpIdxBits[c] );
+    if( mvr::amvp_pick( best, cost ) ) { best = cost; bestIdx = c; }
   }
   j.mvPredHor = j.amvpCand[bestIdx][0]; j.mvPredVer = j.amvpCand[bestIdx][1];
   j.mvpIdx    = ( uint8_t ) bestIdx;
@@ -58,15 +43,15 @@ __device__ __forceinline__ void check_best_mvp( const vtmhip_me_job &j, vtmhip_p
 {
   if( j.imv > 0 && j.imv < 3 ) return;
   if( j.numAmvpCand < 2 ) return;
-  const int sh = amvr_shift( j.imv );
-  const int mh = prec_down( r.mvHor, sh ), mv = prec_down( r.mvVer, sh );
+  const int sh = mvr::amvr_shift( j.imv );
+  const int mh = mvr::prec_down( r.mvHor, sh ), mv = mvr::prec_down( r.mvVer, sh );
   int       bestIdx  = r.mvpIdx;
-  const int orgBits  = ( int ) ( eg_bits( mh - prec_down( r.mvPredHor, sh ) ) + eg_bits( mv - prec_down( r.mvPredVer, sh ) ) + j.mvpIdxBits[r.mvpIdx & 1] );
+  const int orgBits  = ( int ) ( mvr::eg_bits( mh - mvr::prec_down( r.mvPredHor, sh ) ) + mvr::eg_bits( mv - mvr::prec_down( r.mvPredVer, sh ) ) + j.mvpIdxBits[r.mvpIdx & 1] );
   int       bestBits = orgBits;
   for( int c = 0; c < 2; c++ )
   {
     if( c == r.mvpIdx ) continue;
-    const int b = ( int ) ( eg_bits( mh - prec_down( j.amvpCand[c][0], sh ) ) + eg_bits( mv - prec_down( j.amvpCand[c][1], sh ) ) + j.mvpIdxBits[c] );
+    const int b = ( int ) ( mvr::eg_bits( mh - mvr::prec_down( j.amvpCand[c][0], sh ) ) + mvr::eg_bits( mv - mvr::prec_down( j.amvpCand[c][1], sh ) ) + j.mvpIdxBits[c] );
     if( b < bestBits ) { bestBits = b; bestIdx = c; }
   }
   if( bestIdx != r.mvpIdx )
@@ -75,7 +60,7 @@ __device__ __forceinline__ void check_best_mvp( const vtmhip_me_job &j, vtmhip_p
     r.mvpIdx    = bestIdx;
     const unsigned orgAll = r.bits;
     r.bits = orgAll - ( unsigned ) orgBits + ( unsigned ) bestBits;
-    r.cost = ( r.cost - rate( j.motionLambda, orgAll ) ) + rate( j.motionLambda, r.bits );
+    r.cost = ( r.cost - mvr::rate( j.motionLambda, orgAll ) ) + mvr::rate( j.motionLambda, r.bits );
   }
 }
 
@@ -192,10 +177,10 @@ __global__ __launch_bounds__( 256 ) void pis_uni_select_kernel( vtmhip_pis_level
         // FastMEForGenBLowDelay (:2391-2404): the same picture sits in list 0 -- its vector, and its cost with the rate part re-priced against this row's predictor
         // (getBitsOfVectorWithPredictor at cost scale 0: the raw difference shifted by imvShift + MV_FRACTIONAL_BITS_DIFF)
         const vtmhip_pis_row &r0 = L.uniRows[uni_row( L, 0, from0, pu )];      // written by this thread (after xCheckBestMVP: uiCostTempL0 / uiBitsTempL0 of :2423-2427)
-        const int sh = ( j.imv == 3 ? 1 : ( int ) j.imv << 1 ) + 2;
+        const int sh = ( int ) mvr::imv_shift( j.imv ) + 2;
         r.mvHor = r0.mvHor; r.mvVer = r0.mvVer; r.mvPredHor = j.mvPredHor; r.mvPredVer = j.mvPredVer; r.mvpIdx = j.mvpIdx;
-        r.bits = j.bits + eg_bits( ( r.mvHor - j.mvPredHor ) >> sh ) + eg_bits( ( r.mvVer - j.mvPredVer ) >> sh );
-        r.cost = r0.cost - rate( j.motionLambda, r0.bits ) + rate( j.motionLambda, r.bits );
+        r.bits = j.bits + mvr::eg_bits( ( r.mvHor - j.mvPredHor ) >> sh ) + mvr::eg_bits( ( r.mvVer - j.mvPredVer ) >> sh );
+        r.cost = r0.cost - mvr::rate( j.motionLambda, r0.bits ) + mvr::rate( j.motionLambda, r.bits );
         vtmhip_me_out c;       // the row's "search result" for the caller (m_uniMotions stores vector and cost before xCheckBestMVP)
         c.mvHor = r.mvHor; c.mvVer = r.mvVer; c.mvPredHor = r.mvPredHor; c.mvPredVer = r.mvPredVer; c.mvpIdx = r.mvpIdx; c.bits = r.bits; c.cost = r.cost;
         c.intX = c.intY = 0; c.intDist = 0;
@@ -206,10 +191,10 @@ __global__ __launch_bounds__( 256 ) void pis_uni_select_kernel( vtmhip_pis_level
         // xReadBufferedUniMv (:7677-7697): vector and distortion of the default-weight pass (m_uniMotions), the rate re-priced against this call's predictor -- both in the
         // AMVR precision (changeTransPrecInternal2Amvr), cost scale 0
         const vtmhip_me_out g = L.uniOut[row];
-        const int sh = amvr_shift( j.imv );
+        const int sh = mvr::amvr_shift( j.imv );
         r.mvHor = g.mvHor; r.mvVer = g.mvVer; r.mvPredHor = j.mvPredHor; r.mvPredVer = j.mvPredVer; r.mvpIdx = j.mvpIdx;
-        r.bits = j.bits + eg_bits( prec_down( r.mvHor, sh ) - prec_down( j.mvPredHor, sh ) ) + eg_bits( prec_down( r.mvVer, sh ) - prec_down( j.mvPredVer, sh ) );
-        r.cost = g.cost + rate( j.motionLambda, r.bits );
+        r.bits = j.bits + mvr::eg_bits( mvr::prec_down( r.mvHor, sh ) - mvr::prec_down( j.mvPredHor, sh ) ) + mvr::eg_bits( mvr::prec_down( r.mvVer, sh ) - mvr::prec_down( j.mvPredVer, sh ) );
+        r.cost = g.cost + mvr::rate( j.motionLambda, r.bits );
         vtmhip_me_out c;
         c.mvHor = r.mvHor; c.mvVer = r.mvVer; c.mvPredHor = r.mvPredHor; c.mvPredVer = r.mvPredVer; c.mvpIdx = r.mvpIdx; c.bits = r.bits; c.cost = r.cost;
         c.intX = c.intY = 0; c.intDist = 0;
@@ -280,8 +265,8 @@ __global__ __launch_bounds__( 256 ) void pis_bi_jobs_kernel( vtmhip_pis_level L 
     if( L.picW )      // clipMv of motionCompensation (the PU's own record keeps the unclipped vector)
     {
       const vtmhip_me_job &u0 = L.uniJobs[uni_row( L, 0, 0, pu )];
-      ph = min( ( L.picW + 8 - u0.puX - 1 ) << 4, max( ( -L.ctuSize - 8 - u0.puX + 1 ) << 4, ph ) );
-      pv = min( ( L.picH + 8 - u0.puY - 1 ) << 4, max( ( -L.ctuSize - 8 - u0.puY + 1 ) << 4, pv ) );
+      ph = mvr::mv_clip_axis( ph, L.picW, L.ctuSize, u0.puX );
+      pv = mvr::mv_clip_axis( pv, L.picH, L.ctuSize, u0.puY );
     }
     const int64_t off = ( ot ? L.refPlaneOff[1][otherRef] : L.refPlaneOff[0][otherRef] ) + L.pos[pu];
     if( ot ) { po.refOff[1] = off; po.mv[1][0] = ph; po.mv[1][1] = pv; }

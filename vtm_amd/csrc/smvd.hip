@@ -10,6 +10,7 @@
 #include "ctx.hpp"
 #include "had.hpp"
 #include "mc_block.hpp"
+#include "mv_rules.hpp"
 #include <cstdlib>
 
 namespace
@@ -18,12 +19,6 @@ namespace
 __constant__ int8_t c_diamond[8][2] = { { 0, 2 }, { 1, 1 }, { 2, 0 }, { 1, -1 }, { 0, -2 }, { -1, -1 }, { -2, 0 }, { -1, 1 } };
 __constant__ int8_t c_cross[4][2]   = { { 0, 1 }, { 1, 0 }, { 0, -1 }, { -1, 0 } };
 
-__device__ __forceinline__ int      prec_dn( int v, int rs ) { const int o = 1 << ( rs - 1 ); return v >= 0 ? ( v + o - 1 ) >> rs : ( v + o ) >> rs; }   // Mv.h:183-197
-__device__ __forceinline__ unsigned eg_bits( int v )   // RdCost::xGetExpGolombNumberOfBits (RdCost.h:301-315)
-{
-  const unsigned t = ( v <= 0 ) ? ( ( unsigned ) ( -v ) << 1 ) + 1 : ( unsigned ) ( v << 1 );
-  return 1u + ( ( unsigned ) ( 31 - __clz( ( int ) t ) ) << 1 );
-}
 
 struct SmvdCtx   // workgroup-uniform view of one job
 {
@@ -82,8 +77,8 @@ __device__ __forceinline__ void make_pattern( const SmvdCtx &c, int mvHor, int m
 {
   PatternOut po;
   po.p = c.sPat; po.w = c.w; po.org = c.org; po.os = c.orgStride; po.cmax = ( 1 << c.bd ) - 1; po.clip = c.clip; po.bcw = c.bcw != 4;
-  const int normalizer = po.bcw ? ( ( 1 << 16 ) + ( c.bcw > 0 ? ( c.bcw >> 1 ) : -( c.bcw >> 1 ) ) ) / c.bcw : 0;
-  po.w0 = normalizer * 8; po.w1 = ( 8 - c.bcw ) * normalizer;
+  const int normalizer = po.bcw ? mvr::bcw_normaliser( c.bcw ) : 0;
+  po.w0 = normalizer * 8; po.w1 = ( 8 - c.bcw ) * normalizer;   // mvr::bcw_w0 / bcw_w1, written out: the shift form changes this file's code
   predict<THREADS>( c, 0, mvHor, mvVer, po );
 }
 
@@ -148,15 +143,15 @@ __device__ __forceinline__ unsigned long long symmetric_cost( const SmvdCtx &c, 
 
 __device__ __forceinline__ unsigned mv_bits( const SmvdCtx &c, const int mv[2], const int pred[2] )
 {
-  return eg_bits( prec_dn( mv[0], c.amvrShift ) - prec_dn( pred[0], c.amvrShift ) ) + eg_bits( prec_dn( mv[1], c.amvrShift ) - prec_dn( pred[1], c.amvrShift ) );
+  return mvr::eg_bits( mvr::prec_down( mv[0], c.amvrShift ) - mvr::prec_down( pred[0], c.amvrShift ) ) + mvr::eg_bits( mvr::prec_down( mv[1], c.amvrShift ) - mvr::prec_down( pred[1], c.amvrShift ) );
 }
-__device__ __forceinline__ unsigned long long rate( const SmvdCtx &c, unsigned bits ) { return ( unsigned long long ) ( c.lam * bits ); }   // RdCost::getCost
+__device__ __forceinline__ unsigned long long rate( const SmvdCtx &c, unsigned bits ) { return mvr::rate( c.lam, bits ); }
 
 template<int THREADS>
 __device__ unsigned long long refine( const SmvdCtx &c, const int predCur[2], const int predTar[2], int mvCur[2], int mvTar[2], unsigned long long minCost, int pattern,
                                       unsigned maxRounds )
 {
-  const int stepShift = 2 + ( c.imv == 3 ? 1 : ( c.imv << 1 ) );
+  const int stepShift = 2 + ( int ) mvr::imv_shift( c.imv );
   const int rounding = pattern == 0 ? 4 : 8, mask = rounding - 1;
   int       start = 0, end = pattern == 0 ? 3 : 7;
   for( unsigned round = 0; round < maxRounds; round++ )
@@ -226,11 +221,11 @@ __global__ __launch_bounds__( THREADS ) void smvd_kernel( vtmhip_pic_params pic,
   c.org = orgBase + j.orgOff; c.orgStride = j.orgStride; c.refBase = refBase;
   c.refOff[0] = j.refOff[0]; c.refOff[1] = j.refOff[1]; c.refStride[0] = j.refStride[0]; c.refStride[1] = j.refStride[1];
   c.bd = pic.bitDepth; c.imv = j.imv; c.bcw = j.bcwWeightTar ? j.bcwWeightTar : 4;
-  c.amvrShift = c.imv == 0 ? 2 : c.imv == 1 ? 4 : c.imv == 2 ? 6 : 3;
-  c.horMax = ( pic.picW + 8 - j.puX - 1 ) << 4; c.horMin = ( -pic.ctuSize - 8 - j.puX + 1 ) << 4;
-  c.verMax = ( pic.picH + 8 - j.puY - 1 ) << 4; c.verMin = ( -pic.ctuSize - 8 - j.puY + 1 ) << 4;
+  c.amvrShift = mvr::amvr_shift( c.imv );
+  c.horMax = MVR_CLIP_MAX( pic.picW, j.puX ); c.horMin = MVR_CLIP_MIN( pic.ctuSize, j.puX );
+  c.verMax = MVR_CLIP_MAX( pic.picH, j.puY ); c.verMin = MVR_CLIP_MIN( pic.ctuSize, j.puY );
   c.satd = j.useSatd != 0; c.clip = j.clipBiPred != 0;
-  c.lam = j.motionLambda; c.fWeight = c.bcw != 4 ? fabs( ( double ) c.bcw / 8.0 ) : 0.5;   // xGetMEDistortionWeight
+  c.lam = j.motionLambda; c.fWeight = mvr::me_dist_weight( true, c.bcw, 4 );
   c.idxBits[0] = j.mvpIdxBits[0]; c.idxBits[1] = j.mvpIdxBits[1];
   c.sPat = sMem; c.sB = sMem + c.w * c.h; c.sTmp = c.sB + c.w * c.h; c.sRed = sRed;
 
@@ -275,7 +270,7 @@ __global__ __launch_bounds__( THREADS ) void smvd_kernel( vtmhip_pic_params pic,
       if( s >= j.numFixed )
       {
         if( nc >= 5 ) break;
-        if( c.imv ) { v[0] = prec_dn( v[0], c.amvrShift ) * ( 1 << c.amvrShift ); v[1] = prec_dn( v[1], c.amvrShift ) * ( 1 << c.amvrShift ); }   // roundTransPrecInternal2Amvr
+        if( c.imv ) { v[0] = mvr::prec_down( v[0], c.amvrShift ) * ( 1 << c.amvrShift ); v[1] = mvr::prec_down( v[1], c.amvrShift ) * ( 1 << c.amvrShift ); }   // roundTransPrecInternal2Amvr
       }
       bool dup = false;
       for( int q = 0; q < nc; q++ ) dup |= seen[q][0] == v[0] && seen[q][1] == v[1];
@@ -573,23 +568,23 @@ __global__ __launch_bounds__( NW ? 64 * NW : 64 ) void smvd_tile_kernel( vtmhip_
   TileJob t;
   t.orgStride = j.orgStride; t.strideA = j.refStride[0]; t.strideB = j.refStride[1];
   t.org = orgBase + j.orgOff; t.refA = refBase + j.refOff[0]; t.refB = refBase + j.refOff[1];
-  t.horMax = ( pic.picW + 8 - j.puX - 1 ) << 4; t.horMin = ( -pic.ctuSize - 8 - j.puX + 1 ) << 4;
-  t.verMax = ( pic.picH + 8 - j.puY - 1 ) << 4; t.verMin = ( -pic.ctuSize - 8 - j.puY + 1 ) << 4;
+  t.horMax = MVR_CLIP_MAX( pic.picW, j.puX ); t.horMin = MVR_CLIP_MIN( pic.ctuSize, j.puX );
+  t.verMax = MVR_CLIP_MAX( pic.picH, j.puY ); t.verMin = MVR_CLIP_MIN( pic.ctuSize, j.puY );
   const int bcw = j.bcwWeightTar ? j.bcwWeightTar : 4;
-  const int normalizer = bcw != 4 ? ( ( 1 << 16 ) + ( bcw > 0 ? ( bcw >> 1 ) : -( bcw >> 1 ) ) ) / bcw : 0;
-  t.w0 = normalizer * 8; t.w1 = ( 8 - bcw ) * normalizer;
+  const int normalizer = bcw != 4 ? mvr::bcw_normaliser( bcw ) : 0;
+  t.w0 = normalizer * 8; t.w1 = ( 8 - bcw ) * normalizer;   // (as in make_pattern)
   t.clip = j.clipBiPred != 0; t.alt = j.imv == 3; t.satd = j.useSatd != 0; t.wide = bcw < 0 && !t.clip;
   {
     const int bd = pic.bitDepth, headRoom = max( 2, 14 - bd );
     t.f.shH = 6 - headRoom; t.f.offH = -( 8192 << t.f.shH ); t.f.shV = 6 + headRoom; t.f.offV = ( 1 << ( t.f.shV - 1 ) ) + ( 8192 << 6 ); t.f.cmax = ( 1 << bd ) - 1;
   }
-  const int    imv = j.imv, amvrShift = imv == 0 ? 2 : imv == 1 ? 4 : imv == 2 ? 6 : 3, stepShift = 2 + ( imv == 3 ? 1 : ( imv << 1 ) );
-  const double lam = j.motionLambda, fWeight = bcw != 4 ? fabs( ( double ) bcw / 8.0 ) : 0.5;
+  const int    imv = j.imv, amvrShift = mvr::amvr_shift( imv ), stepShift = 2 + ( int ) mvr::imv_shift( imv );
+  const double lam = j.motionLambda, fWeight = mvr::me_dist_weight( true, bcw, 4 );
   const unsigned idxBits0 = j.mvpIdxBits[0], idxBits1 = j.mvpIdxBits[1];
   auto idx_bits = [&]( int i ) { return i ? idxBits1 : idxBits0; };
-  auto rate = [&]( unsigned bits ) { return ( unsigned long long ) ( lam * bits ); };
+  auto rate = [&]( unsigned bits ) { return mvr::rate( lam, bits ); };
   auto mvbits = [&]( int mx, int my, int px, int py )
-  { return eg_bits( prec_dn( mx, amvrShift ) - prec_dn( px, amvrShift ) ) + eg_bits( prec_dn( my, amvrShift ) - prec_dn( py, amvrShift ) ); };
+  { return mvr::eg_bits( mvr::prec_down( mx, amvrShift ) - mvr::prec_down( px, amvrShift ) ) + mvr::eg_bits( mvr::prec_down( my, amvrShift ) - mvr::prec_down( py, amvrShift ) ); };
 
   // AMVP lists
   int cnd[2][2][2], num0 = min( 2, max( 1, ( int ) j.numCand[0] ) ), num1 = min( 2, max( 1, ( int ) j.numCand[1] ) );   // AMVP lists hold one or two candidates
@@ -612,7 +607,7 @@ __global__ __launch_bounds__( NW ? 64 * NW : 64 ) void smvd_tile_kernel( vtmhip_
   auto start_vec = [&]( int s, int c )
   {
     int v = j.starts[s][c];
-    if( s >= numFixed && imv ) v = prec_dn( v, amvrShift ) * ( 1 << amvrShift );   // roundTransPrecInternal2Amvr
+    if( s >= numFixed && imv ) v = mvr::prec_down( v, amvrShift ) * ( 1 << amvrShift );   // roundTransPrecInternal2Amvr
     return v;
   };
   if( phase == PH_INIT )
