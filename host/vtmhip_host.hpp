@@ -7,8 +7,8 @@
 //   vtmhip::fastFwdTrans / fastInvTrans tables      CommonLib/TrQuant.cpp:69-81, TrQuant.h:53-54
 //
 // Errors: the reference THROWs an Exception (TypeDef.h:1065-1081); here vtmhip::Exception (std::runtime_error) carries
-// the C ABI status text.  What the device path does not cover (applyWeight, useMR, step != 1 -- the same guards as
-// x86/RdCostX86.h:213,344,2157) throws "unsupported": inside VTM the trampoline falls back to the scalar function instead.
+// the C ABI status text.  What the device path does not cover (useMR, step != 1 -- the same guards as x86/RdCostX86.h:213,344,2157 -- and applyWeight
+// unless RdCost::setDeviceWeightedPrediction( true )) throws "unsupported": inside VTM the trampoline falls back to the scalar function instead.
 #pragma once
 #include <cstdint>
 #include <limits>
@@ -60,6 +60,14 @@ enum DFunc
   DF_TOTAL_FUNCTIONS
 };
 
+struct WPScalingParam   // Slice.h:2206-2222: the slice-header fields and the derived ones WeightPrediction::getWpScaling fills in
+{
+  bool     bPresentFlag = false;
+  uint32_t uiLog2WeightDenom = 0;
+  int      iWeight = 0, iOffset = 0;
+  int      w = 0, o = 0, offset = 0, shift = 0, round = 0;
+};
+
 class DistParam;
 typedef Distortion ( *FpDistFunc )( const DistParam & );
 
@@ -78,6 +86,7 @@ public:
   int         maskStride = 0, stepX = 0, maskStride2 = 0;
   CPelBuf     orgLuma;              // WCG_EXT (RdCost.h:73, 93-94): the co-located luma original a chroma DF_SSE_WTD block is weighted by
   int         cShiftX = 0, cShiftY = 0;
+  const WPScalingParam *wpCur = nullptr;   // RdCost.h:85: the [MAX_NUM_COMPONENT] parameters of the searched reference (InterSearch::setWpScalingDistParam)
 };
 
 inline int floorLog2( unsigned v ) { int r = -1; while( v ) { v >>= 1; r++; } return r; }
@@ -91,24 +100,57 @@ class RdCost
   int    m_predHor = 0, m_predVer = 0;
   ChromaFormat m_cf = CHROMA_420;   // RdCost::m_cf (set by RdCost::setChromaFormat)
 
+  static bool &deviceWP() { static bool on = false; return on; }
+  // applyWeight (RdCost.cpp:495, 532, ..., 2821, 3090-3374): RdCostWeightPrediction::xGetSADw / xGetHADsw / xGetSSEw on the device
+  static vtmhip_wp_param wpParam( const DistParam &p )
+  {
+    if( p.compID >= MAX_NUM_COMPONENT || !p.wpCur ) throw Exception( "Invalid component" );   // RdCostWeightPrediction.cpp:70 CHECK (and a missing wpCur)
+    const WPScalingParam &wp = p.wpCur[p.compID];
+    return vtmhip_wp_param{ wp.w, wp.offset, wp.shift, wp.round };
+  }
+  static Distortion xGetSADw( const DistParam &p )
+  {
+    const vtmhip_wp_param wp = wpParam( p ); uint64_t d = 0;   // subShift is ignored, as by the reference
+    check( vtmhip_xGetSADw( context(), p.org.buf, p.org.stride, p.cur.buf, p.cur.stride, p.org.width, p.org.height, &wp, p.bitDepth, p.isBiPred,
+                            p.maximumDistortionForEarlyExit, &d ), "xGetSADw" );
+    return d;
+  }
+  static Distortion xGetHADsw( const DistParam &p )
+  {
+    if( p.step != 1 ) throw Exception( "unsupported on the device path: applyWeight with step != 1 (keep the scalar function)" );
+    const vtmhip_wp_param wp = wpParam( p ); uint64_t d = 0;
+    check( vtmhip_xGetHADsw( context(), p.org.buf, p.org.stride, p.cur.buf, p.cur.stride, p.org.width, p.org.height, &wp, p.bitDepth, p.isBiPred, &d ), "xGetHADsw" );
+    return d;
+  }
+  static Distortion xGetSSEw( const DistParam &p )
+  {
+    if( p.subShift != 0 ) throw Exception( "Subshift not supported" );   // RdCostWeightPrediction.cpp:255 CHECK
+    const vtmhip_wp_param wp = wpParam( p ); uint64_t d = 0;
+    check( vtmhip_xGetSSEw( context(), p.org.buf, p.org.stride, p.cur.buf, p.cur.stride, p.org.width, p.org.height, &wp, p.bitDepth, p.isBiPred, &d ), "xGetSSEw" );
+    return d;
+  }
+
   static void guard( const DistParam &p )
   {
     if( p.applyWeight || p.useMR || p.step != 1 ) throw Exception( "unsupported on the device path: applyWeight / useMR / step != 1 (keep the scalar function)" );
   }
   static Distortion xGetSAD( const DistParam &p )
   {
+    if( p.applyWeight && deviceWP() ) return xGetSADw( p );
     guard( p ); uint64_t d = 0;
     check( vtmhip_xGetSAD( context(), p.org.buf, p.org.stride, p.cur.buf, p.cur.stride, p.org.width, p.org.height, p.subShift, &d ), "xGetSAD" );
     return d;
   }
   static Distortion xGetHADs( const DistParam &p )
   {
+    if( p.applyWeight && deviceWP() ) return xGetHADsw( p );
     guard( p ); uint64_t d = 0;
     check( vtmhip_xGetHADs( context(), p.org.buf, p.org.stride, p.cur.buf, p.cur.stride, p.org.width, p.org.height, &d ), "xGetHADs" );
     return d;
   }
   static Distortion xGetSSE( const DistParam &p )
   {
+    if( p.applyWeight && deviceWP() ) return xGetSSEw( p );
     guard( p ); uint64_t d = 0;
     check( vtmhip_xGetSSE( context(), p.org.buf, p.org.stride, p.cur.buf, p.cur.stride, p.org.width, p.org.height, &d ), "xGetSSE" );
     return d;
@@ -117,6 +159,7 @@ class RdCost
   // DF_SSE*_WTD (RdCost.cpp:3088-3463): the weight tables come from vtmhip_set_luma_level_weights; applyWeight is RdCostWeightPrediction::xGetSSEw (:3095-3098)
   static Distortion xGetSSE_WTD( const DistParam &p )
   {
+    if( p.applyWeight && deviceWP() ) return xGetSSEw( p );
     if( p.applyWeight ) throw Exception( "unsupported on the device path: applyWeight (keep the scalar function)" );
     uint64_t d = 0;
     check( vtmhip_xGetSSE_WTD( context(), p.org.buf, p.org.stride, p.cur.buf, p.cur.stride, p.org.width, p.org.height, p.compID, p.orgLuma.buf, p.orgLuma.stride,
@@ -135,6 +178,8 @@ class RdCost
 public:
   RdCost() { init(); }
   static FpDistFunc distFuncAt( int i ) { return table()[i]; }
+  // opt-in (off by default): route applyWeight of the SAD / HAD / SSE / SSE_WTD slots to vtmhip_xGetSADw / xGetHADsw / xGetSSEw instead of refusing it
+  static void setDeviceWeightedPrediction( bool on ) { deviceWP() = on; }
 
   void init()   // RdCost::init (RdCost.cpp:125-217) + the "initRdCostHIP" installer of INTEGRATION.md
   {

@@ -49,7 +49,7 @@ enum
   VTMHIP_E_NODEVICE    = -2,   /* no HIP device / device index out of range */
   VTMHIP_E_HIP         = -3,   /* a HIP runtime call failed; see vtmhip_last_error() */
   VTMHIP_E_NOMEM       = -4,
-  VTMHIP_E_UNSUPPORTED = -5    /* caller must keep its CPU path (applyWeight, useMR, step != 1, explicit scaling lists, ...) */
+  VTMHIP_E_UNSUPPORTED = -5    /* caller must keep its CPU path (useMR, step != 1, explicit scaling lists, ...; applyWeight: the vtmhip_xGet*w entries) */
 };
 
 enum { VTMHIP_DIST_SAD = 0, VTMHIP_DIST_SATD = 1, VTMHIP_DIST_SSE = 2 };
@@ -228,8 +228,8 @@ int vtmhip_intra_cand_cost_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase,
  *   dist  += (uint64_t) (int64_t) mse                                                        (DISTORTION_PRECISION_ADJUSTMENT = 0, FULL_NBIT)
  * Sample contract: org, cur and orgLuma in [0, 2^bitDepth), bitDepth <= 12 (the reference CHECKs org >= 0; |d| < 2^12 keeps d * d < 2^24).
  * The tables are the host's (RdCost::m_reshapeLumaLevelToWeightPLUT, m_chromaWeight, m_signalType; EncGOP.cpp:228-234, 1810-1853); the chroma
- * m_distortionWeight scaling of RdCost::getDistPart (:411-455) stays with the caller, as for DF_SSE.  applyWeight (RdCostWeightPrediction::xGetSSEw)
- * stays on the host: the trampoline falls back to the scalar function. */
+ * m_distortionWeight scaling of RdCost::getDistPart (:411-455) stays with the caller, as for DF_SSE.  applyWeight (RdCostWeightPrediction::xGetSSEw) is
+ * not this entry: vtmhip_xGetSSEw below. */
 
 /* The weight tables of a context: lut[1 << lumaBD] = m_reshapeLumaLevelToWeightPLUT, converted here to the reference's fixed point (int64_t)( w * 65536.0 );
  * every converted weight (and chromaWeight's) must lie in [0, 2^31) or the call fails.  invLut: the reshaper's inverse LUT (Reshape::getInvLUT(), 1 << lumaBD
@@ -262,6 +262,79 @@ typedef struct
  * fails only on what the host can see (no table set, null pointers). */
 int vtmhip_sse_wtd_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_curBase, const int16_t *d_orgLumaBase, const vtmhip_wtd_job *d_jobs,
                               int n, uint64_t *d_dist );
+
+/* ---- explicit weighted prediction (WeightedPredP / WeightedPredB): the distortion and sample ops of a weighted-prediction slice ------------------------
+ * Distortion: with DistParam::applyWeight every SAD / HAD / SSE / SSE_WTD slot hands off to RdCostWeightPrediction::xGetSADw / xGetHADsw / xGetSSEw
+ * (CommonLib/RdCost.cpp:495, 532, ..., 2821, 3090-3374; CommonLib/RdCostWeightPrediction.cpp:56-640), with the U0040_... = 1 branches (TypeDef.h:164).
+ * Motion estimation sets the flag and DistParam::wpCur in InterSearch::setWpScalingDistParam (EncoderLib/InterSearch.cpp:6057-6098, called at :3377).
+ * vtmhip_wp_param = the derived fields w, offset, shift, round of the block's component's WPScalingParam (Slice.h:2206-2222).  Per sample, q = ((w * cur +
+ * round) >> shift) + offset (arithmetic shift), Pel(v) = v truncated to int16, clip(v) = min(max(v, 0), 2^bitDepth - 1):
+ *   SADw  w == 1 << shift: offset == 0: |org - cur|;  bi: |org - (cur + offset)| (int, no clip, no Pel);  uni: |org - clip(cur + offset)|
+ *         otherwise:       bi: |org - Pel(q)|;  uni: |org - clip(q)|
+ *         after each row, if maxDist < sum the running sum is returned (the early exit: a PREFIX of the rows, not the whole block); subShift is ignored
+ *         (every row is read), so the entries take none
+ *   SSEw  residual = Pel(org - pred), pred = bi ? Pel(q) : clip(q);  sum += residual^2 (uint64); no early exit.  A nonzero subShift is the reference's CHECK.
+ *   HADsw diff = org - Pel(q) (never clipped, uni or bi; TCoeff).  W % 8 == 0 and H % 8 == 0: 8x8 Hadamard tiles, each (s + 2) >> 2 (no 8x16 / 16x8 tiles
+ *         and no DC adjustment, unlike xGetHADs); else W % 4 == 0 and H % 4 == 0: 4x4 tiles, (s + 1) >> 1; else 2x2 tiles, not normalised, in the reference's
+ *         row walk: the y += 2 loop advances org / cur by ONE row, so step k reads rows k and k + 1 (:624-633).  step is 1 (step != 1 stays on the host).
+ *   DISTORTION_PRECISION_ADJUSTMENT is 0 (FULL_NBIT, TypeDef.h:225-237): no final shift.
+ * Sample contract: bitDepth 8..12; w in [-256, 256], shift 0..8, offset and round in [-32768, 32767] (the reference derives |w| <= 255, shift <= 8); HAD
+ * blocks on the 2x2 path have even W and H (odd ones read outside the block in the reference); width / height 1..128.  Anything else is VTMHIP_E_INVALID
+ * (pointer entries) or VTMHIP_WP_INVALID_DIST (batched). */
+typedef struct
+{
+  int32_t w, offset, shift, round;   /* WPScalingParam::w / offset / shift / round of one component */
+} vtmhip_wp_param;
+
+/* DistParam::distFunc of the SAD / HAD / SSE (and SSE_WTD) slots under applyWeight (host pointers, like vtmhip_xGetSAD).  wp: &DistParam::wpCur[compID];
+ * isBiPred: DistParam::isBiPred; maxDist: DistParam::maximumDistortionForEarlyExit (SADw only). */
+int vtmhip_xGetSADw( vtmhip_ctx *ctx, const int16_t *org, int orgStride, const int16_t *cur, int curStride, int width, int height, const vtmhip_wp_param *wp,
+                     int bitDepth, int isBiPred, uint64_t maxDist, uint64_t *dist );
+int vtmhip_xGetSSEw( vtmhip_ctx *ctx, const int16_t *org, int orgStride, const int16_t *cur, int curStride, int width, int height, const vtmhip_wp_param *wp,
+                     int bitDepth, int isBiPred, uint64_t *dist );
+int vtmhip_xGetHADsw( vtmhip_ctx *ctx, const int16_t *org, int orgStride, const int16_t *cur, int curStride, int width, int height, const vtmhip_wp_param *wp,
+                      int bitDepth, int isBiPred, uint64_t *dist );
+
+#define VTMHIP_WP_INVALID_DIST UINT64_MAX   /* d_dist of a job the kernel rejected (see vtmhip_wp_dist_batch_dev) */
+typedef struct
+{
+  int64_t         orgOff, curOff;          /* samples inside d_orgBase / d_curBase */
+  int32_t         orgStride, curStride;
+  int16_t         width, height;           /* 1..128 */
+  uint8_t         kind;                    /* VTMHIP_DIST_SAD (xGetSADw), VTMHIP_DIST_SATD (xGetHADsw), VTMHIP_DIST_SSE (xGetSSEw) */
+  uint8_t         bitDepth, isBiPred, pad;
+  vtmhip_wp_param wp;
+  uint64_t        maxDist;                 /* SAD only: maximumDistortionForEarlyExit (UINT64_MAX: no early exit) */
+} vtmhip_wp_dist_job;
+
+/* n weighted distortions in one launch; d_dist[i] = the distFunc value.  Small blocks share a wave.  The jobs are device-resident, so a job outside the
+ * sample contract above (or with an unknown kind / isBiPred > 1) gets d_dist = VTMHIP_WP_INVALID_DIST and is not read; the call itself fails only on what
+ * the host can see (null pointers, n < 0). */
+int vtmhip_wp_dist_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_curBase, const vtmhip_wp_dist_job *d_jobs, int n, uint64_t *d_dist );
+
+/* Sample ops: WeightPrediction::addWeightUni / addWeightBi (CommonLib/WeightPrediction.cpp:46-64, 157-226, 288-392), called from
+ * InterPrediction::motionCompensation (InterPrediction.cpp:633, 639) and the bi-pred ME target preparation (InterSearch.cpp:3261, 3286).  Inputs are the
+ * 14-bit intermediates vtmhip_mc_batch_dev writes with bi = 1 (a weighted-prediction PU is two launches).  With shiftNum = IF_INTERNAL_FRAC_BITS(bd) =
+ * max(2, 14 - bd) (JVET_R0351_HIGH_BIT_DEPTH_SUPPORT = 1, TypeDef.h:59; InterpolationFilter.h:54) and P' = P + 8192 (IF_INTERNAL_OFFS):
+ *   bi (weightBidir):   s = shift + shiftNum;  dst = clip( (w0 * P0' + w1 * P1' + (1 << (s - 1)) + (offset << (s - 1))) >> s )   (bRoundLuma = true)
+ *   uni, w0 != 1 << shift (weightUnidir):                     s = shift + shiftNum;  dst = clip( ((w0 * P0' + (1 << (s - 1))) >> s) + offset )
+ *   uni, w0 == 1 << shift (noWeightUnidir / noWeightOffsetUnidir):  dst = clip( ((P0' + (1 << (shiftNum - 1))) >> shiftNum) + offset )
+ * The job carries the WPScalingParam fields as WeightPrediction::getWpScaling leaves them (:77-155), with o = iOffset << (bitDepth - 8) (1 with high-precision
+ * offsets):  uni: w0 = iWeight, offset = o, shift = log2Denom, round = log2Denom >= 1 ? 1 << (log2Denom - 1) : 0;  bi: w0 = iWeight of list 0, w1 = iWeight
+ * of list 1, offset = o0 + o1, shift = log2Denom + 1, round = 1 << log2Denom.  The ops derive their own rounding from shift, so `round` is not read (as in
+ * the reference).  Sample contract as above (w0 / w1 in [-256, 256], shift 0..8, offset in [-32768, 32767], bitDepth 8..12, width / height 1..128); a job
+ * outside it leaves its dst block untouched. */
+enum { VTMHIP_WP_UNI = 0, VTMHIP_WP_BI = 1 };
+typedef struct
+{
+  int64_t src0Off, src1Off, dstOff;        /* samples inside d_src0Base / d_src1Base / d_dstBase (src1: VTMHIP_WP_BI only) */
+  int32_t src0Stride, src1Stride, dstStride;
+  int16_t width, height;
+  uint8_t bitDepth, mode, pad0, pad1;      /* mode: VTMHIP_WP_UNI / VTMHIP_WP_BI */
+  int32_t w0, w1, offset, shift, round;
+} vtmhip_wp_pred_job;
+
+int vtmhip_wp_pred_batch_dev( vtmhip_ctx *ctx, const int16_t *d_src0Base, const int16_t *d_src1Base, int16_t *d_dstBase, const vtmhip_wp_pred_job *d_jobs, int n );
 
 /* SATD 8x8 block-grid micro-benchmark: every 8-aligned 8x8 block of the W x H org picture against the
  * reference picture displaced by (dx,dy) in [-r,r]^2.  d_ref must carry >= r samples of valid margin on every side.

@@ -44,6 +44,8 @@ int vtmhip_struct_size( int which )
   case 31: return ( int ) sizeof( vtmhip_smvd_job );
   case 32: return ( int ) sizeof( vtmhip_pis_pu_in );
   case 33: return ( int ) sizeof( vtmhip_wtd_job );
+  case 34: return ( int ) sizeof( vtmhip_wp_dist_job );
+  case 35: return ( int ) sizeof( vtmhip_wp_pred_job );
   default: return -1;
   }
 }

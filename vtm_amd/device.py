@@ -9,7 +9,7 @@ import numpy as np
 
 from . import lib as _lib
 from .lib import (AffineJob, DistJob, FracJob, FracResult, FullJob, IfJob, McJob, MeResult, PelOpJob, PicParams, QuantJob,   # noqa: F401
-                  TrJob, TuJob, TuResult, TzJob, VtmHipError, WtdJob)
+                  TrJob, TuJob, TuResult, TzJob, VtmHipError, WpDistJob, WpParam, WpPredJob, WtdJob)
 
 
 class DevBuf:
@@ -140,6 +140,32 @@ class Context:
     def sse_wtd_batch(self, d_org, d_cur, d_org_luma, d_jobs, n, d_out):
         """n WtdJob evaluations; d_out[i] = the raw distFunc value (WTD_INVALID_DIST for a rejected job)."""
         self._check(self.L.vtmhip_sse_wtd_batch_dev(self.h, d_org, d_cur, d_org_luma, d_jobs, n, d_out))
+
+    def _wp_dist(self, fn, org, org_stride, cur, cur_stride, w, h, wp, bit_depth, is_bi, *max_dist):
+        d = C.c_uint64()
+        p = WpParam(*(int(v) for v in wp))
+        self._check(fn(self.h, org.ctypes.data, org_stride, cur.ctypes.data, cur_stride, w, h, C.byref(p), bit_depth, int(is_bi), *max_dist, C.byref(d)))
+        return d.value
+
+    def xGetSADw(self, org, org_stride, cur, cur_stride, w, h, wp, bit_depth, is_bi, max_dist=(1 << 64) - 1):
+        """RdCostWeightPrediction::xGetSADw on host arrays; wp = (w, offset, shift, round) of the component, max_dist the early-exit bound."""
+        return self._wp_dist(self.L.vtmhip_xGetSADw, org, org_stride, cur, cur_stride, w, h, wp, bit_depth, is_bi, max_dist)
+
+    def xGetSSEw(self, org, org_stride, cur, cur_stride, w, h, wp, bit_depth, is_bi):
+        """RdCostWeightPrediction::xGetSSEw on host arrays."""
+        return self._wp_dist(self.L.vtmhip_xGetSSEw, org, org_stride, cur, cur_stride, w, h, wp, bit_depth, is_bi)
+
+    def xGetHADsw(self, org, org_stride, cur, cur_stride, w, h, wp, bit_depth, is_bi):
+        """RdCostWeightPrediction::xGetHADsw (step 1) on host arrays."""
+        return self._wp_dist(self.L.vtmhip_xGetHADsw, org, org_stride, cur, cur_stride, w, h, wp, bit_depth, is_bi)
+
+    def wp_dist_batch(self, d_org, d_cur, d_jobs, n, d_out):
+        """n WpDistJob evaluations; d_out[i] = the distFunc value (WP_INVALID_DIST for a rejected job)."""
+        self._check(self.L.vtmhip_wp_dist_batch_dev(self.h, d_org, d_cur, d_jobs, n, d_out))
+
+    def wp_pred_batch(self, d_src0, d_src1, d_dst, d_jobs, n):
+        """n WpPredJob sample ops (addWeightUni / addWeightBi) on 14-bit intermediates."""
+        self._check(self.L.vtmhip_wp_pred_batch_dev(self.h, d_src0, d_src1, d_dst, d_jobs, n))
 
     def xGetSADwMask(self, org, org_stride, cur, cur_stride, w, h, mask, mask_off, mask_stride, step_x, mask_stride2, sub_shift=0):
         """DF_SAD_WITH_MASK on host arrays; `mask` is a 1-D int16 array, mask_off the index of DistParam::mask inside it."""

@@ -11,6 +11,8 @@ OK, E_INVALID, E_NODEVICE, E_HIP, E_NOMEM, E_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 DIST_SAD, DIST_SATD, DIST_SSE = 0, 1, 2
 WTD_INV_RESHAPE_CUR = 1           # vtmhip_wtd_job.flags
 WTD_INVALID_DIST = (1 << 64) - 1  # d_dist of a rejected vtmhip_wtd_job
+WP_INVALID_DIST = (1 << 64) - 1   # d_dist of a rejected vtmhip_wp_dist_job
+WP_UNI, WP_BI = 0, 1              # vtmhip_wp_pred_job.mode
 DCT2, DCT8, DST7 = 0, 1, 2
 
 
@@ -243,9 +245,27 @@ class WtdJob(C.Structure):
                 ("cShiftY", C.c_uint8), ("flags", C.c_uint8), ("pad", C.c_int32)]
 
 
+class WpParam(C.Structure):
+    _fields_ = [("w", C.c_int32), ("offset", C.c_int32), ("shift", C.c_int32), ("round", C.c_int32)]
+
+
+class WpDistJob(C.Structure):
+    _fields_ = [("orgOff", C.c_int64), ("curOff", C.c_int64), ("orgStride", C.c_int32), ("curStride", C.c_int32), ("width", C.c_int16),
+                ("height", C.c_int16), ("kind", C.c_uint8), ("bitDepth", C.c_uint8), ("isBiPred", C.c_uint8), ("pad", C.c_uint8), ("wp", WpParam),
+                ("maxDist", C.c_uint64)]
+
+
+class WpPredJob(C.Structure):
+    _fields_ = [("src0Off", C.c_int64), ("src1Off", C.c_int64), ("dstOff", C.c_int64), ("src0Stride", C.c_int32), ("src1Stride", C.c_int32),
+                ("dstStride", C.c_int32), ("width", C.c_int16), ("height", C.c_int16), ("bitDepth", C.c_uint8), ("mode", C.c_uint8),
+                ("pad0", C.c_uint8), ("pad1", C.c_uint8), ("w0", C.c_int32), ("w1", C.c_int32), ("offset", C.c_int32), ("shift", C.c_int32),
+                ("round", C.c_int32)]
+
+
 _STRUCTS = [DistJob, TzJob, MeResult, PicParams, IfJob, FracJob, FracResult, TrJob, QuantJob, FullJob, McJob, PelOpJob,
             TuJob, TuResult, AffineJob, MeCfg, MeJob, MeOut, PredJob, MaskedSadJob, GeoBlendJob, DmvrJob, LfnstJob,
-            PisRow, PisPu, PisLevel, AffineMeJob, AffineMeOut, LfnstTuJob, PisLevelRun, PisBuffers, SmvdJob, PisPuIn, WtdJob]   # order of vtmhip_struct_size(which)
+            PisRow, PisPu, PisLevel, AffineMeJob, AffineMeOut, LfnstTuJob, PisLevelRun, PisBuffers, SmvdJob, PisPuIn, WtdJob,
+            WpDistJob, WpPredJob]   # order of vtmhip_struct_size(which)
 
 # every symbol include/vtmhip.h declares (tests/test_abi.py checks the exports against the header text)
 _PROTOS = {
@@ -294,6 +314,14 @@ _PROTOS = {
     "vtmhip_xGetSSE_WTD": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(C.c_uint64)]),
     "vtmhip_sse_wtd_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "vtmhip_xGetSADw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(WpParam), C.c_int, C.c_int,
+                                  C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vtmhip_xGetSSEw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(WpParam), C.c_int, C.c_int,
+                                  C.POINTER(C.c_uint64)]),
+    "vtmhip_xGetHADsw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(WpParam), C.c_int, C.c_int,
+                                   C.POINTER(C.c_uint64)]),
+    "vtmhip_wp_dist_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "vtmhip_wp_pred_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "vtmhip_filterHor": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                    C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vtmhip_filterVer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
