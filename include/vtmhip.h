@@ -700,7 +700,7 @@ typedef struct
   int32_t dstStride;        /* xIT: residual stride */
   int16_t width, height;    /* 1..64 (MAX_TB_SIZEY) */
   uint8_t typeHor, typeVer; /* VTMHIP_DCT2 / DCT8 / DST7 as TrQuant::getTrTypes chose them */
-  uint8_t bitDepth, pad;
+  uint8_t bitDepth, pad;    /* bitDepth: 8..12, the library's sample contract (not checked per job); xT takes residuals within +-(2^bitDepth - 1) */
 } vtmhip_tr_job;
 
 /* TrQuant::xT (TrQuant.cpp:776-851) for n TUs.  d_sumAbs (may be NULL): sum |coef| per TU (MTS pre-selection, :986-990). */
@@ -714,8 +714,9 @@ typedef struct
 {
   int64_t srcOff, dstOff;   /* W x H contiguous TCoeff blocks */
   int16_t width, height;
-  int16_t qpPer, qpRem;     /* QpParam::per / rem (Quant.cpp:65-104) */
-  uint8_t bitDepth, isIRAP, isTransformSkip, pad;
+  int16_t qpPer, qpRem;     /* QpParam::per / rem (Quant.cpp:65-104): base QP = QP + 6 * (bitDepth - 8), 0 .. 63 + 6 * (bitDepth - 8); for transform skip the
+                               caller applies QpParam's floor of 4 on the base QP */
+  uint8_t bitDepth, isIRAP, isTransformSkip, pad;   /* bitDepth: 8..12, the library's sample contract (not checked per job) */
   int32_t pad2;
 } vtmhip_quant_job;
 
@@ -734,8 +735,8 @@ typedef struct
   int64_t outOff;           /* W x H contiguous block inside d_levelsBase / d_recBase (when those are given) */
   int32_t resiStride;
   int16_t width, height;    /* 2..64 */
-  int16_t qpPer, qpRem;
-  uint8_t typeHor, typeVer, bitDepth, isIRAP;
+  int16_t qpPer, qpRem;     /* as vtmhip_quant_job */
+  uint8_t typeHor, typeVer, bitDepth, isIRAP;   /* bitDepth: 8..12, the library's sample contract (not checked per job); residuals within +-(2^bitDepth - 1) */
   int32_t pad;
 } vtmhip_tu_job;
 

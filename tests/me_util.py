@@ -158,7 +158,8 @@ def other_pred(scene, j):
     m = scene.margin
     plane = scene.ref_buf.reshape(-1, scene.ref_stride)
     blk = plane[m + j["y"] + dy:m + j["y"] + dy + j["h"], m + j["x"] + dx:m + j["x"] + dx + j["w"]].astype(np.int32)
-    return np.ascontiguousarray(np.clip(blk + rng.integers(-6, 7, blk.shape), 0, 1023).astype(np.int16))
+    top = (1 << j.get("bd", getattr(scene, "bd", 10))) - 1
+    return np.ascontiguousarray(np.clip(blk + rng.integers(-6, 7, blk.shape), 0, top).astype(np.int16))
 
 
 def oracle_mest_job(scene, j, keep):
@@ -188,8 +189,9 @@ def oracle_mest_job(scene, j, keep):
     return t
 
 
-def random_affine_jobs(scene, n, seed=5, sizes=(16, 32, 64, 128)):
-    """Affine ME jobs on a scene: control-point vectors = a small rotation / zoom around a translation, predictors near them."""
+def random_affine_jobs(scene, n, seed=5, sizes=(16, 32, 64, 128), bit_depth=10):
+    """Affine ME jobs on a scene: control-point vectors = a small rotation / zoom around a translation, predictors near them.  Jobs of a picture
+    at another depth than 10 bits carry it ("bd"): the other list's prediction is clipped to it."""
     rng = np.random.default_rng(seed)
     jobs = []
     while len(jobs) < n:
@@ -216,20 +218,22 @@ def random_affine_jobs(scene, n, seed=5, sizes=(16, 32, 64, 128)):
                          inter_dir=int(rng.choice([1, 2, 3])), prof=int(rng.integers(0, 4) != 0), prof_large=int(rng.integers(0, 2)), prof_bi=int(rng.integers(0, 2)),
                          bits=int(rng.integers(4, 14)), lam=float(rng.uniform(2, 30)), hevc_scale=float(rng.choice([0.5, 1.0, 4.0])),
                          other_seed=int(rng.integers(0, 1 << 30))))
+        if bit_depth != 10:
+            jobs[-1]["bd"] = bit_depth
     return jobs
 
 
-def affine_pred_struct(scene, j):
+def affine_pred_struct(scene, j, bit_depth=10):
     p = ol.AffinePred()
     p.ref = scene.ref_buf.ctypes.data + 2 * (scene.ref_off + j["y"] * scene.ref_stride + j["x"])
-    p.refStride, p.w, p.h, p.puX, p.puY, p.picW, p.picH, p.ctuSize, p.bitDepth = scene.ref_stride, j["w"], j["h"], j["x"], j["y"], scene.W, scene.H, 128, 10
+    p.refStride, p.w, p.h, p.puX, p.puY, p.picW, p.picH, p.ctuSize, p.bitDepth = scene.ref_stride, j["w"], j["h"], j["x"], j["y"], scene.W, scene.H, 128, bit_depth
     p.sixParam, p.interDir, p.profAllowed, p.profNeedsLargeGrad, p.profIsBi = j["six"], j["inter_dir"], j["prof"], j["prof_large"], j["prof_bi"]
     return p
 
 
-def affine_me_struct(scene, j, keep):
+def affine_me_struct(scene, j, keep, bit_depth=10):
     t = ol.AffineMeJob()
-    t.pred = affine_pred_struct(scene, j)
+    t.pred = affine_pred_struct(scene, j, bit_depth)
     t.org, t.orgStride = scene.cur.ctypes.data + 2 * (j["y"] * scene.W + j["x"]), scene.W
     if j["bi"]:
         o = other_pred(scene, j)
@@ -241,6 +245,29 @@ def affine_me_struct(scene, j, keep):
         t.mv[i][0], t.mv[i][1] = j["mv"][i]
     t.bits, t.motionLambda = j["bits"], j["lam"]
     return t
+
+
+def to_bit_depth(f, bd):
+    """A 10-bit picture of the generator at `bd` bits.  Below 10 bits the low bits go; above, the top bits are repeated into the new low ones and the
+    result is stretched by 5/4 about mid-grey and clipped, so that bright and dark areas sit at exactly 0 and 2^bd - 1 and edges span the whole range."""
+    f = f.astype(np.int32)
+    if bd <= 10:
+        return np.ascontiguousarray((f >> (10 - bd)).astype(np.int16))
+    v = (f << (bd - 10)) | (f >> (20 - bd))
+    mid = 1 << (bd - 1)
+    return np.ascontiguousarray(np.clip((v - mid) * 5 // 4 + mid, 0, (1 << bd) - 1).astype(np.int16))
+
+
+class DeepScene(Scene):
+    """`Scene` at another sample depth (to_bit_depth of the same two frames)."""
+
+    def __init__(self, w=416, h=240, hard=True, bit_depth=10, margin=160):
+        fr = (synth.gen_frames_hard if hard else synth.gen_frames)(w, h, 3)
+        self.bd = bit_depth
+        self.W, self.H = w, h
+        self.cur = to_bit_depth(fr[2], bit_depth)
+        self.ref_buf, self.ref_off, self.ref_stride = synth.extend_plane(to_bit_depth(fr[0], bit_depth), margin)
+        self.margin = margin
 
 
 # ---- SMVD (symmetric MVD search of predInterSearch) -------------------------------------------------------------------------------

@@ -119,6 +119,15 @@ def i16(a):
     return np.ascontiguousarray(a, dtype=np.int16)
 
 
+def basis_sign_block(w, h, th, tv, rh, rv, amp):
+    """A w x h residual of +-amp whose signs follow row rh of the horizontal and row rv of the vertical transform matrix (vo_tr_matrix types): both
+    passes of the forward transform add |basis| * amp, so coefficient (rv, rh) and the intermediates behind it reach their largest magnitude."""
+    mh, mv = np.zeros((w, w), np.int16), np.zeros((h, h), np.int16)
+    assert oracle().vo_tr_matrix(th, w, P(mh)) == 0 and oracle().vo_tr_matrix(tv, h, P(mv)) == 0
+    sh, sv = np.where(mh[rh] < 0, -1, 1), np.where(mv[rv] < 0, -1, 1)
+    return np.ascontiguousarray((np.outer(sv, sh) * amp).astype(np.int16))
+
+
 def o_dist(kind, org, cur, w, h, sub_shift=0, org_off=0, cur_off=0):
     """kind 0 SAD / 1 SATD / 2 SSE on 2-D int16 arrays (stride = row length)."""
     L = oracle()

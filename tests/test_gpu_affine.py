@@ -40,11 +40,11 @@ def hip_jobs(scene, jobs, others, hevc):
     return arr, poff
 
 
-def oracle_results(scene, jobs, L):
+def oracle_results(scene, jobs, L, bd=10):
     exp, hevc, preds = [], [], []
     for j in jobs:
         keep = []
-        t = me_util.affine_me_struct(scene, j, keep)
+        t = me_util.affine_me_struct(scene, j, keep, bd)
         t.hevcCost = 1 << 62
         r0 = ol.AffineMeResult()
         L.vo_affine_motion_estimation(C.byref(t), C.byref(r0))
@@ -53,7 +53,7 @@ def oracle_results(scene, jobs, L):
         L.vo_affine_motion_estimation(C.byref(t), C.byref(r))
         hevc.append(t.hevcCost)
         exp.append(([tuple(v) for v in r.mv][:3 if j["six"] else 2], r.bits, r.cost, r.iterations, r.refinements))
-        p = me_util.affine_pred_struct(scene, j)
+        p = me_util.affine_pred_struct(scene, j, bd)
         mv = ((C.c_int * 2) * 3)(*[(C.c_int * 2)(*v) for v in j["mv"]])
         a = np.zeros((j["h"], j["w"]), np.int16)
         L.vo_pred_affine_blk(C.byref(p), mv, 0, ol.P(a), j["w"])
@@ -61,10 +61,12 @@ def oracle_results(scene, jobs, L):
     return exp, hevc, preds
 
 
-def run_device(ctx, scene, jobs, hevc):
+def run_device(ctx, scene, jobs, hevc, bd=10, table=None):
     others = np.zeros(max(1, sum(j["w"] * j["h"] for j in jobs if j["bi"])), np.int16)
     arr, npred = hip_jobs(scene, jobs, others, hevc)
-    pic = PicParams(scene.W, scene.H, 128, 10, 0)
+    if table is not None:
+        table.append(arr)
+    pic = PicParams(scene.W, scene.H, 128, bd, 0)
     d_cur, d_ref, d_oth = ctx.to_device(scene.cur), ctx.to_device(scene.ref_buf), ctx.to_device(others)
     d_jobs = ctx.to_device(np.frombuffer(arr, np.uint8))
     d_res = ctx.alloc(C.sizeof(AffineMeOut) * len(jobs))
@@ -81,17 +83,30 @@ def run_device(ctx, scene, jobs, hevc):
     return got, preds
 
 
+def wide_path_jobs(arr, bd):
+    """Jobs of a table that the 32-bit distortion variants of the estimation kernel take (affine_me_kernel<*, false>): every job of a picture deeper than
+    10 bits, and the jobs under BCW weight -2."""
+    return sum(1 for t in arr if bd > 10 or (t.bi and t.bcwWeight < 0))
+
+
 @pytest.mark.parametrize("hard", [False, True])
-def test_affine_me_matches_oracle(ctx, hard):
+def test_affine_me_matches_oracle(ctx, hard, bd=10):
+    """xPredAffineBlk and xAffineMotionEstimation on 8-, 10- and 12-bit pictures (me_util.to_bit_depth: the 12-bit ones have flat areas at 0 and 4095);
+    at 12 bits every job runs the 32-bit distortion variant, and the jobs that measure with the Hadamard transform are the ones where it differs."""
     L = ol.oracle()
-    scene = me_util.Scene(416, 240, hard=hard)
-    jobs = me_util.random_affine_jobs(scene, 300, seed=41 + hard)
-    exp, hevc, exp_pred = oracle_results(scene, jobs, L)
-    got, preds = run_device(ctx, scene, jobs, hevc)
+    scene = me_util.Scene(416, 240, hard=hard) if bd == 10 else me_util.DeepScene(416, 240, hard=hard, bit_depth=bd)
+    n = 300 if bd == 10 else 150
+    jobs = me_util.random_affine_jobs(scene, n, seed=41 + hard if bd == 10 else 41 + hard + bd, bit_depth=bd)
+    exp, hevc, exp_pred = oracle_results(scene, jobs, L, bd)
+    table = []
+    got, preds = run_device(ctx, scene, jobs, hevc, bd, table)
     for k, j in enumerate(jobs):
         assert np.array_equal(preds[k], exp_pred[k]), ("xPredAffineBlk", k, j)
         assert got[k] == exp[k], ("xAffineMotionEstimation", k, j, got[k], exp[k])
-    assert sum(e[3] for e in exp) > 300 and sum(e[4] for e in exp) > 2000
+    f = n / 300
+    assert sum(e[3] for e in exp) > 300 * f and sum(e[4] for e in exp) > 2000 * f
+    if bd > 10:
+        assert wide_path_jobs(table[0], bd) == n and sum(t.useSatd for t in table[0]) > n // 2
 
 
 def test_affine_me_matches_golden_from_reference(ctx):
@@ -106,3 +121,10 @@ def test_affine_me_matches_golden_from_reference(ctx):
         assert [list(v) for v in got[k][0]] == z["mv"][k][:n].tolist() and got[k][1] == int(z["bits"][k]) and got[k][2] == int(z["cost"][k]), ("golden ME", k, j)
         assert np.array_equal(preds[k].reshape(-1), z["pred"][off:off + j["w"] * j["h"]]), ("golden prediction", k)
         off += j["w"] * j["h"]
+
+
+@pytest.mark.parametrize("bd", [8, 12])
+@pytest.mark.parametrize("hard", [False, True])
+def test_affine_me_matches_oracle_8_12bit(ctx, hard, bd):
+    """test_affine_me_matches_oracle at 8 and 12 bits."""
+    test_affine_me_matches_oracle(ctx, hard, bd)

@@ -13,11 +13,12 @@ pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def test_mc_luma_matches_oracle(ctx):
+def test_mc_luma_matches_oracle(ctx, bd=10):
+    """vtmhip_mc_luma_batch_dev vs vo_mc_luma on 8-, 10- and 12-bit pictures (me_util.to_bit_depth: the 12-bit one has flat areas at 0 and 4095)."""
     L = ol.oracle()
-    scene = me_util.Scene(416, 240, hard=True)
-    rng = np.random.default_rng(51)
-    n = 600
+    scene = me_util.Scene(416, 240, hard=True) if bd == 10 else me_util.DeepScene(416, 240, hard=True, bit_depth=bd)
+    rng = np.random.default_rng(51 if bd == 10 else 51 + bd)
+    n = 600 if bd == 10 else 300
     jobs = (McJob * n)()
     dst_stride = 136
     exp = np.zeros((n * 128, dst_stride), np.int16)
@@ -38,9 +39,9 @@ def test_mc_luma_matches_oracle(ctx):
         j = jobs[k]
         j.refOff = scene.ref_off + y * scene.ref_stride + x
         j.dstOff, j.refStride, j.dstStride, j.width, j.height = k * 128 * dst_stride, scene.ref_stride, dst_stride, w, h
-        j.mvHor, j.mvVer, j.bi, j.bitDepth, j.useAltHpelIf = mvh, mvv, bi, 10, alt
+        j.mvHor, j.mvVer, j.bi, j.bitDepth, j.useAltHpelIf = mvh, mvv, bi, bd, alt
         e = np.zeros((h, dst_stride), np.int16)
-        L.vo_mc_luma(C.c_void_p(scene.ref_buf.ctypes.data + 2 * j.refOff), scene.ref_stride, w, h, mvh, mvv, int(bi), 10, int(alt), ol.P(e), dst_stride)
+        L.vo_mc_luma(C.c_void_p(scene.ref_buf.ctypes.data + 2 * j.refOff), scene.ref_stride, w, h, mvh, mvv, int(bi), bd, int(alt), ol.P(e), dst_stride)
         exp[k * 128:k * 128 + h, :w] = e[:, :w]
         meta.append((w, h, mvh, mvv, bi, alt))
     d_ref = ctx.to_device(scene.ref_buf)
@@ -49,7 +50,7 @@ def test_mc_luma_matches_oracle(ctx):
     ctx.mc_luma_batch(d_ref.ptr, d_dst.ptr, d_jobs.ptr, n, 128, 128)
     got = d_dst.to_host().reshape(n * 128, dst_stride)
     for k, (w, h, *_rest) in enumerate(meta):
-        assert np.array_equal(got[k * 128:k * 128 + h, :w], exp[k * 128:k * 128 + h, :w]), (k, meta[k])
+        assert np.array_equal(got[k * 128:k * 128 + h, :w], exp[k * 128:k * 128 + h, :w]), (k, meta[k], bd)
 
 
 def test_pel_ops_match_reference_golden(ctx):
@@ -141,15 +142,15 @@ def test_affine_gradient_matches_reference_golden(ctx):
                 assert np.array_equal(eq[q], z["eq_%d_%d" % (k, six)]), (k, six, q)
 
 
-def test_motion_compensation_fused_matches_oracle(ctx):
+def test_motion_compensation_fused_matches_oracle(ctx, bd=10):
     """vtmhip_motion_compensation_batch_dev: uni / bi (two 14-bit predictions + addAvg) for luma and 4:2:0 chroma blocks, prediction
     output plus the fused residual (org - pred) or removeHighFreq (2*org - pred) epilogue, against the oracle composition
-    vo_mc_block -> vo_add_avg -> subtract."""
+    vo_mc_block -> vo_add_avg -> subtract; 8-, 10- and 12-bit pictures."""
     from vtm_amd import synth
     from vtm_amd.lib import PredJob
     L = ol.oracle()
     W, H, m = 416, 240, 64
-    fr = synth.gen_frames(W, H, 3, chroma=True)
+    fr = [[me_util.to_bit_depth(p, bd) for p in f] for f in synth.gen_frames(W, H, 3, chroma=True)]
     (yb0, yo, ys), (ub0, uo, us) = synth.extend_plane(fr[0][0], m), synth.extend_plane(fr[0][1], m // 2)
     (yb1, _, _), (ub1, _, _) = synth.extend_plane(fr[1][0], m), synth.extend_plane(fr[1][1], m // 2)
     org_y, org_u = np.ascontiguousarray(fr[2][0]), np.ascontiguousarray(fr[2][1])
@@ -158,8 +159,8 @@ def test_motion_compensation_fused_matches_oracle(ctx):
     base = {(0, 0): 0, (0, 1): yb0.size, (1, 0): 2 * yb0.size, (1, 1): 2 * yb0.size + ub0.size}
     planes = {(0, 0): yb0, (0, 1): yb1, (1, 0): ub0, (1, 1): ub1}
     orgs = np.concatenate([org_y.reshape(-1), org_u.reshape(-1)])
-    rng = np.random.default_rng(91)
-    n = 500
+    rng = np.random.default_rng(91 if bd == 10 else 91 + bd)
+    n = 500 if bd == 10 else 250
     jobs = (PredJob * n)()
     exp_pred, exp_out, meta = [], [], []
     pos = 0
@@ -185,15 +186,15 @@ def test_motion_compensation_fused_matches_oracle(ctx):
             j.mv[l][0], j.mv[l][1] = mv[l]
         j.predOff = j.outOff = pos
         j.predStride = j.outStride = cw
-        j.width, j.height, j.mode, j.epilogue, j.bitDepth, j.useAltHpelIf, j.chroma = cw, ch, mode, epi, 10, alt, chroma
+        j.width, j.height, j.mode, j.epilogue, j.bitDepth, j.useAltHpelIf, j.chroma = cw, ch, mode, epi, bd, alt, chroma
         p = [np.zeros((ch, cw), np.int16), np.zeros((ch, cw), np.int16)]
         for l in ((0, 1) if mode == 2 else (mode,)):
             pl = planes[(chroma, l)]
             refp = pl.ctypes.data + 2 * (o0 + cy * st + cx)
-            L.vo_mc_block(1 if chroma else 0, C.c_void_p(refp), st, cw, ch, mv[l][0], mv[l][1], int(mode == 2), 10, alt, ol.P(p[l]), cw)
+            L.vo_mc_block(1 if chroma else 0, C.c_void_p(refp), st, cw, ch, mv[l][0], mv[l][1], int(mode == 2), bd, alt, ol.P(p[l]), cw)
         if mode == 2:
             pred = np.zeros((ch, cw), np.int16)
-            L.vo_add_avg(ol.P(p[0]), cw, ol.P(p[1]), cw, ol.P(pred), cw, cw, ch, 10)
+            L.vo_add_avg(ol.P(p[0]), cw, ol.P(p[1]), cw, ol.P(pred), cw, cw, ch, bd)
         else:
             pred = p[mode]
         ob = (org_u if chroma else org_y)[cy:cy + ch, cx:cx + cw].astype(np.int32)
@@ -210,8 +211,8 @@ def test_motion_compensation_fused_matches_oracle(ctx):
     at = 0
     for k, (cw, ch, chroma, mode, epi) in enumerate(meta):
         sl = slice(at, at + cw * ch)
-        assert np.array_equal(gp[sl], exp_pred[k]), ("pred", k, meta[k])
-        assert np.array_equal(go[sl], exp_out[k]), ("out", k, meta[k])
+        assert np.array_equal(gp[sl], exp_pred[k]), ("pred", k, meta[k], bd)
+        assert np.array_equal(go[sl], exp_out[k]), ("out", k, meta[k], bd)
         at += cw * ch
     # prediction-only and epilogue-only calls
     d_out2 = ctx.to_device(np.zeros(pos, np.int16))
@@ -268,13 +269,13 @@ def test_full_search_square_kernel_matches_oracle(ctx, size):
 
 def test_geo_blend_matches_oracle(ctx):
     """vtmhip_weightedGeoBlk / _batch_dev vs the oracle on synthetic weight planes: all four walk directions, chroma step 2, odd widths and unaligned
-    strides (scalar path of the kernel), 8- and 10-bit, a narrowed clip range."""
+    strides (scalar path of the kernel), 8-, 10- and 12-bit, a narrowed clip range."""
     from vtm_amd.lib import GeoBlendJob
     L = ol.oracle()
     rng = np.random.default_rng(911)
     M = 224
     plane = ol.i16(rng.integers(0, 9, (M, M))).reshape(-1)
-    for bd, clip in ((10, (0, 1023)), (8, (0, 255)), (10, (64, 940))):
+    for bd, clip in ((10, (0, 1023)), (8, (0, 255)), (10, (64, 940)), (12, (0, 4095))):
         n = 200
         jobs = (GeoBlendJob * n)()
         srcs, exp, pos, spos = [], [], 0, 0
@@ -308,175 +309,172 @@ def test_geo_blend_matches_oracle(ctx):
         assert np.array_equal(d_dst.to_host(np.int16), np.concatenate(exp)), bd
 
 
-def test_bdof_matches_oracle(ctx):
+def test_bdof_matches_oracle(ctx, bd=10):
     """vtmhip_bdof_batch_dev vs vo_bdof_pu: every PU size class the reference enables BDOF for, integer / half / mixed phases on either list,
-    8- and 10-bit, prediction and both fused epilogues."""
+    8-, 10- and 12-bit, prediction and both fused epilogues."""
     from vtm_amd import synth
     from vtm_amd.lib import PredJob
     L = ol.oracle()
     W, H, M = 256, 192, 48
     fr = list(synth.gen_frames(W, H, 3, seed=9))
-    rng = np.random.default_rng(1012)
-    for bd in (10, 8):
-        planes = [np.ascontiguousarray(np.pad((f >> (10 - bd)).astype(np.int16), M, mode="edge")) for f in (fr[0], fr[2])]
-        org = np.ascontiguousarray((fr[1] >> (10 - bd)).astype(np.int16))
-        S, plane_sz = planes[0].shape[1], planes[0].size
-        n = 150
-        jobs = (PredJob * n)()
-        exp_pred, exp_out, pos = [], [], 0
-        for k in range(n):
-            w, h = int(rng.choice([8, 16, 32, 64, 128])), int(rng.choice([8, 16, 32, 64, 128]))
-            if w * h < 128:
-                w = 16
-            x, y = int(rng.integers(0, (W - w) // 4 + 1)) * 4, int(rng.integers(0, (H - h) // 4 + 1)) * 4
-            mv = [int(v) for v in rng.integers(-500, 500, 4)]
-            if k % 5 == 0:
-                mv[k % 4] &= ~15
-            if k % 13 == 0:
-                mv = [v & ~15 for v in mv]
-            if k % 17 == 0:
-                mv = [(v & ~15) | 8 for v in mv]
-            e = np.zeros((h, w), np.int16)
-            at = [C.c_void_p(p.ctypes.data + 2 * ((y + M) * S + x + M)) for p in planes]
-            L.vo_bdof_pu(at[0], S, at[1], S, w, h, *mv, bd, ol.P(e), w)
-            j = jobs[k]
-            for l in range(2):
-                j.refOff[l], j.refStride[l] = l * plane_sz + (M + y) * S + M + x, S
-            j.mv[0][0], j.mv[0][1], j.mv[1][0], j.mv[1][1] = mv
-            j.orgOff, j.orgStride = y * W + x, W
-            j.predOff = j.outOff = pos
-            j.predStride = j.outStride = w
-            j.width, j.height, j.mode, j.bitDepth, j.epilogue = w, h, 2, bd, 1 + k % 2
-            o = org[y:y + h, x:x + w].astype(np.int32)
-            exp_pred.append(e.reshape(-1))
-            exp_out.append(((o if j.epilogue == 1 else 2 * o) - e).astype(np.int16).reshape(-1))
-            pos += w * h
-        d_ref = ctx.to_device(np.concatenate([p.reshape(-1) for p in planes]))
-        d_org, d_jobs = ctx.to_device(org.reshape(-1)), ctx.to_device(np.frombuffer(jobs, np.uint8))
-        d_pred, d_out = ctx.alloc(2 * pos), ctx.alloc(2 * pos)
-        ctx.bdof_batch(d_org.ptr, d_ref.ptr, d_pred.ptr, d_out.ptr, d_jobs.ptr, n, 128, 128)
-        assert np.array_equal(d_pred.to_host(np.int16), np.concatenate(exp_pred)), bd
-        assert np.array_equal(d_out.to_host(np.int16), np.concatenate(exp_out)), bd
-        d_pred2 = ctx.alloc(2 * pos)
-        ctx.bdof_batch(0, d_ref.ptr, d_pred2.ptr, 0, d_jobs.ptr, n, 128, 128)   # prediction only
-        assert np.array_equal(d_pred2.to_host(np.int16), np.concatenate(exp_pred)), bd
+    rng = np.random.default_rng(1012 if bd == 10 else 1012 + bd)
+    planes = [np.ascontiguousarray(np.pad(me_util.to_bit_depth(f, bd), M, mode="edge")) for f in (fr[0], fr[2])]
+    org = me_util.to_bit_depth(fr[1], bd)
+    S, plane_sz = planes[0].shape[1], planes[0].size
+    n = 150
+    jobs = (PredJob * n)()
+    exp_pred, exp_out, pos = [], [], 0
+    for k in range(n):
+        w, h = int(rng.choice([8, 16, 32, 64, 128])), int(rng.choice([8, 16, 32, 64, 128]))
+        if w * h < 128:
+            w = 16
+        x, y = int(rng.integers(0, (W - w) // 4 + 1)) * 4, int(rng.integers(0, (H - h) // 4 + 1)) * 4
+        mv = [int(v) for v in rng.integers(-500, 500, 4)]
+        if k % 5 == 0:
+            mv[k % 4] &= ~15
+        if k % 13 == 0:
+            mv = [v & ~15 for v in mv]
+        if k % 17 == 0:
+            mv = [(v & ~15) | 8 for v in mv]
+        e = np.zeros((h, w), np.int16)
+        at = [C.c_void_p(p.ctypes.data + 2 * ((y + M) * S + x + M)) for p in planes]
+        L.vo_bdof_pu(at[0], S, at[1], S, w, h, *mv, bd, ol.P(e), w)
+        j = jobs[k]
+        for l in range(2):
+            j.refOff[l], j.refStride[l] = l * plane_sz + (M + y) * S + M + x, S
+        j.mv[0][0], j.mv[0][1], j.mv[1][0], j.mv[1][1] = mv
+        j.orgOff, j.orgStride = y * W + x, W
+        j.predOff = j.outOff = pos
+        j.predStride = j.outStride = w
+        j.width, j.height, j.mode, j.bitDepth, j.epilogue = w, h, 2, bd, 1 + k % 2
+        o = org[y:y + h, x:x + w].astype(np.int32)
+        exp_pred.append(e.reshape(-1))
+        exp_out.append(((o if j.epilogue == 1 else 2 * o) - e).astype(np.int16).reshape(-1))
+        pos += w * h
+    d_ref = ctx.to_device(np.concatenate([p.reshape(-1) for p in planes]))
+    d_org, d_jobs = ctx.to_device(org.reshape(-1)), ctx.to_device(np.frombuffer(jobs, np.uint8))
+    d_pred, d_out = ctx.alloc(2 * pos), ctx.alloc(2 * pos)
+    ctx.bdof_batch(d_org.ptr, d_ref.ptr, d_pred.ptr, d_out.ptr, d_jobs.ptr, n, 128, 128)
+    assert np.array_equal(d_pred.to_host(np.int16), np.concatenate(exp_pred)), bd
+    assert np.array_equal(d_out.to_host(np.int16), np.concatenate(exp_out)), bd
+    d_pred2 = ctx.alloc(2 * pos)
+    ctx.bdof_batch(0, d_ref.ptr, d_pred2.ptr, 0, d_jobs.ptr, n, 128, 128)   # prediction only
+    assert np.array_equal(d_pred2.to_host(np.int16), np.concatenate(exp_pred)), bd
 
 
-def test_dmvr_matches_oracle(ctx):
+def test_dmvr_matches_oracle(ctx, bd=10):
     """vtmhip_dmvr_batch_dev vs vo_dmvr_pu: all PU size classes, with / without BDOF, vectors around the clip's motion, integer phases, far
-    out-of-picture vectors (clipMv), 8- and 10-bit, prediction + fused epilogues + vector differences."""
+    out-of-picture vectors (clipMv), 8-, 10- and 12-bit, prediction + fused epilogues + vector differences."""
     from vtm_amd import synth
     from vtm_amd.lib import DmvrJob, PicParams
     L = ol.oracle()
     W, H, M = 256, 192, 160
     fr = list(synth.gen_frames(W, H, 3, seed=9))
-    rng = np.random.default_rng(1015)
-    for bd in (10, 8):
-        planes = [np.ascontiguousarray(np.pad((f >> (10 - bd)).astype(np.int16), M, mode="edge")) for f in (fr[0], fr[2])]
-        org = np.ascontiguousarray((fr[1] >> (10 - bd)).astype(np.int16))
-        S, plane_sz = planes[0].shape[1], planes[0].size
-        o = [C.c_void_p(p.ctypes.data + 2 * (M * S + M)) for p in planes]
-        n, regions = 160, 64
-        jobs = (DmvrJob * n)()
-        exp_pred, exp_out, exp_mvd, pos = [], [], np.zeros((n, regions, 2), np.int32), 0
-        for k in range(n):
-            w, h = int(rng.choice([8, 16, 32, 64, 128])), int(rng.choice([8, 16, 32, 64, 128]))
-            if w * h < 128:
-                w = 16
-            x, y = int(rng.integers(0, (W - w) // 4 + 1)) * 4, int(rng.integers(0, (H - h) // 4 + 1)) * 4
-            base = np.array([48, 32]) + rng.integers(-40, 41, 2)
-            mv = [int(-base[0]), int(-base[1]), int(base[0] + rng.integers(-24, 25)), int(base[1] + rng.integers(-24, 25))]
-            if k % 9 == 0:
-                mv = [int(v) for v in rng.integers(-4000, 4000, 4)]
-            if k % 7 == 0:
-                mv[k % 4] &= ~15
-            if k % 11 == 0:
-                mv = [v & ~15 for v in mv]
-            bio = k % 2
-            nsub = (w // min(w, 16)) * (h // min(h, 16))
-            e, mvd = np.zeros((h, w), np.int16), np.zeros(2 * nsub, np.int32)
-            L.vo_dmvr_pu(o[0], o[1], S, W, H, 128, x, y, w, h, *mv, bd, bio, ol.P(e), w, C.c_void_p(mvd.ctypes.data))
-            exp_mvd[k, :nsub] = mvd.reshape(-1, 2)
-            j = jobs[k]
-            for l in range(2):
-                j.refOff[l], j.refStride[l] = l * plane_sz + (M + y) * S + M + x, S
-            j.mv[0][0], j.mv[0][1], j.mv[1][0], j.mv[1][1] = mv
-            j.orgOff, j.orgStride, j.puX, j.puY = y * W + x, W, x, y
-            j.predOff = j.outOff = pos
-            j.predStride = j.outStride = w
-            j.width, j.height, j.bitDepth, j.bioApplied, j.epilogue = w, h, bd, bio, 1 + k % 2
-            ob = org[y:y + h, x:x + w].astype(np.int32)
-            exp_pred.append(e.reshape(-1))
-            exp_out.append(((ob if j.epilogue == 1 else 2 * ob) - e).astype(np.int16).reshape(-1))
-            pos += w * h
-        assert np.count_nonzero(exp_mvd) > 300
-        pic = PicParams(W, H, 128, bd, 0)
-        d_ref = ctx.to_device(np.concatenate([p.reshape(-1) for p in planes]))
-        d_org, d_jobs = ctx.to_device(org.reshape(-1)), ctx.to_device(np.frombuffer(jobs, np.uint8))
-        d_pred, d_out, d_mvd = ctx.alloc(2 * pos), ctx.alloc(2 * pos), ctx.alloc(4 * exp_mvd.size)
-        ctx.dmvr_batch(pic, d_org.ptr, d_ref.ptr, d_pred.ptr, d_out.ptr, d_jobs.ptr, n, 128, 128, d_mvd.ptr)
-        got_mvd = d_mvd.to_host(np.int32).reshape(n, regions, 2)
-        for k in range(n):
-            nsub = (jobs[k].width // min(jobs[k].width, 16)) * (jobs[k].height // min(jobs[k].height, 16))
-            assert np.array_equal(got_mvd[k, :nsub], exp_mvd[k, :nsub]), (bd, k)
-        assert np.array_equal(d_pred.to_host(np.int16), np.concatenate(exp_pred)), bd
-        assert np.array_equal(d_out.to_host(np.int16), np.concatenate(exp_out)), bd
+    rng = np.random.default_rng(1015 if bd == 10 else 1015 + bd)
+    planes = [np.ascontiguousarray(np.pad(me_util.to_bit_depth(f, bd), M, mode="edge")) for f in (fr[0], fr[2])]
+    org = me_util.to_bit_depth(fr[1], bd)
+    S, plane_sz = planes[0].shape[1], planes[0].size
+    o = [C.c_void_p(p.ctypes.data + 2 * (M * S + M)) for p in planes]
+    n, regions = 160, 64
+    jobs = (DmvrJob * n)()
+    exp_pred, exp_out, exp_mvd, pos = [], [], np.zeros((n, regions, 2), np.int32), 0
+    for k in range(n):
+        w, h = int(rng.choice([8, 16, 32, 64, 128])), int(rng.choice([8, 16, 32, 64, 128]))
+        if w * h < 128:
+            w = 16
+        x, y = int(rng.integers(0, (W - w) // 4 + 1)) * 4, int(rng.integers(0, (H - h) // 4 + 1)) * 4
+        base = np.array([48, 32]) + rng.integers(-40, 41, 2)
+        mv = [int(-base[0]), int(-base[1]), int(base[0] + rng.integers(-24, 25)), int(base[1] + rng.integers(-24, 25))]
+        if k % 9 == 0:
+            mv = [int(v) for v in rng.integers(-4000, 4000, 4)]
+        if k % 7 == 0:
+            mv[k % 4] &= ~15
+        if k % 11 == 0:
+            mv = [v & ~15 for v in mv]
+        bio = k % 2
+        nsub = (w // min(w, 16)) * (h // min(h, 16))
+        e, mvd = np.zeros((h, w), np.int16), np.zeros(2 * nsub, np.int32)
+        L.vo_dmvr_pu(o[0], o[1], S, W, H, 128, x, y, w, h, *mv, bd, bio, ol.P(e), w, C.c_void_p(mvd.ctypes.data))
+        exp_mvd[k, :nsub] = mvd.reshape(-1, 2)
+        j = jobs[k]
+        for l in range(2):
+            j.refOff[l], j.refStride[l] = l * plane_sz + (M + y) * S + M + x, S
+        j.mv[0][0], j.mv[0][1], j.mv[1][0], j.mv[1][1] = mv
+        j.orgOff, j.orgStride, j.puX, j.puY = y * W + x, W, x, y
+        j.predOff = j.outOff = pos
+        j.predStride = j.outStride = w
+        j.width, j.height, j.bitDepth, j.bioApplied, j.epilogue = w, h, bd, bio, 1 + k % 2
+        ob = org[y:y + h, x:x + w].astype(np.int32)
+        exp_pred.append(e.reshape(-1))
+        exp_out.append(((ob if j.epilogue == 1 else 2 * ob) - e).astype(np.int16).reshape(-1))
+        pos += w * h
+    assert np.count_nonzero(exp_mvd) > 300, bd
+    pic = PicParams(W, H, 128, bd, 0)
+    d_ref = ctx.to_device(np.concatenate([p.reshape(-1) for p in planes]))
+    d_org, d_jobs = ctx.to_device(org.reshape(-1)), ctx.to_device(np.frombuffer(jobs, np.uint8))
+    d_pred, d_out, d_mvd = ctx.alloc(2 * pos), ctx.alloc(2 * pos), ctx.alloc(4 * exp_mvd.size)
+    ctx.dmvr_batch(pic, d_org.ptr, d_ref.ptr, d_pred.ptr, d_out.ptr, d_jobs.ptr, n, 128, 128, d_mvd.ptr)
+    got_mvd = d_mvd.to_host(np.int32).reshape(n, regions, 2)
+    for k in range(n):
+        nsub = (jobs[k].width // min(jobs[k].width, 16)) * (jobs[k].height // min(jobs[k].height, 16))
+        assert np.array_equal(got_mvd[k, :nsub], exp_mvd[k, :nsub]), (bd, k)
+    assert np.array_equal(d_pred.to_host(np.int16), np.concatenate(exp_pred)), bd
+    assert np.array_equal(d_out.to_host(np.int16), np.concatenate(exp_out)), bd
 
 
-def test_dmvr_chroma_matches_oracle(ctx):
-    """vtmhip_dmvr_chroma_batch_dev vs vo_dmvr_chroma on vector differences taken from vo_dmvr_pu: moved and unmoved sub-PUs, clipped vectors, 8- and
-    10-bit, both fused epilogues."""
+def test_dmvr_chroma_matches_oracle(ctx, bd=10):
+    """vtmhip_dmvr_chroma_batch_dev vs vo_dmvr_chroma on vector differences taken from vo_dmvr_pu: moved and unmoved sub-PUs, clipped vectors, 8-,
+    10- and 12-bit, both fused epilogues."""
     from vtm_amd import synth
     from vtm_amd.lib import DmvrJob, PicParams
     L = ol.oracle()
     W, H, M = 256, 192, 160
     fr = list(synth.gen_frames(W, H, 3, seed=9, chroma=True))
-    rng = np.random.default_rng(1017)
-    for bd in (10, 8):
-        P = [[np.ascontiguousarray(np.pad((f[c] >> (10 - bd)).astype(np.int16), M if c == 0 else M // 2, mode="edge")) for c in range(3)] for f in (fr[0], fr[2])]
-        orgc = np.ascontiguousarray((fr[1][1] >> (10 - bd)).astype(np.int16))
-        SY, SC, csz = P[0][0].shape[1], P[0][1].shape[1], P[0][1].size
-        oy = [C.c_void_p(P[l][0].ctypes.data + 2 * (M * SY + M)) for l in range(2)]
-        n, regions = 120, 64
-        jobs = (DmvrJob * n)()
-        mvd_all = np.zeros((n, regions, 2), np.int32)
-        exp_pred, exp_out, pos = [], [], 0
-        for k in range(n):
-            w, h = int(rng.choice([8, 16, 32, 64, 128])), int(rng.choice([8, 16, 32, 64, 128]))
-            if w * h < 128:
-                w = 16
-            x, y = int(rng.integers(0, (W - w) // 8 + 1)) * 8, int(rng.integers(0, (H - h) // 8 + 1)) * 8
-            base = np.array([48, 32]) + rng.integers(-40, 41, 2)
-            mv = [int(-base[0]), int(-base[1]), int(base[0] + rng.integers(-24, 25)), int(base[1] + rng.integers(-24, 25))]
-            if k % 9 == 0:
-                mv = [int(v) for v in rng.integers(-4000, 4000, 4)]
-            comp = 1 + k % 2
-            nsub = (w // min(w, 16)) * (h // min(h, 16))
-            lum, mvd = np.zeros((h, w), np.int16), np.zeros(2 * nsub, np.int32)
-            L.vo_dmvr_pu(oy[0], oy[1], SY, W, H, 128, x, y, w, h, *mv, bd, 0, ol.P(lum), w, C.c_void_p(mvd.ctypes.data))
-            mvd_all[k, :nsub] = mvd.reshape(-1, 2)
-            oc = [C.c_void_p(P[l][comp].ctypes.data + 2 * ((M // 2) * SC + M // 2)) for l in range(2)]
-            e = np.zeros((h // 2, w // 2), np.int16)
-            L.vo_dmvr_chroma(oc[0], oc[1], SC, W, H, 128, x, y, w, h, *mv, C.c_void_p(mvd.ctypes.data), bd, ol.P(e), w // 2)
-            j = jobs[k]
-            for l in range(2):
-                j.refOff[l], j.refStride[l] = (2 * l + comp - 1) * csz + (M // 2 + y // 2) * SC + M // 2 + x // 2, SC
-            j.mv[0][0], j.mv[0][1], j.mv[1][0], j.mv[1][1] = mv
-            j.orgOff, j.orgStride, j.puX, j.puY, j.mvdRow = (y // 2) * (W // 2) + x // 2, W // 2, x, y, k
-            j.predOff = j.outOff = pos
-            j.predStride = j.outStride = w // 2
-            j.width, j.height, j.bitDepth, j.epilogue = w, h, bd, 1 + (k // 2) % 2
-            ob = orgc[y // 2:(y + h) // 2, x // 2:(x + w) // 2].astype(np.int32)
-            exp_pred.append(e.reshape(-1))
-            exp_out.append(((ob if j.epilogue == 1 else 2 * ob) - e).astype(np.int16).reshape(-1))
-            pos += w * h // 4
-        pic = PicParams(W, H, 128, bd, 0)
-        d_ref = ctx.to_device(np.concatenate([P[l][c].reshape(-1) for l in range(2) for c in (1, 2)]))
-        d_org, d_jobs, d_mvd = ctx.to_device(orgc.reshape(-1)), ctx.to_device(np.frombuffer(jobs, np.uint8)), ctx.to_device(mvd_all.reshape(-1))
-        d_pred, d_out = ctx.alloc(2 * pos), ctx.alloc(2 * pos)
-        ctx.dmvr_chroma_batch(pic, d_org.ptr, d_ref.ptr, d_pred.ptr, d_out.ptr, d_jobs.ptr, n, 128, 128, d_mvd.ptr)
-        assert np.array_equal(d_pred.to_host(np.int16), np.concatenate(exp_pred)), bd
-        assert np.array_equal(d_out.to_host(np.int16), np.concatenate(exp_out)), bd
+    rng = np.random.default_rng(1017 if bd == 10 else 1017 + bd)
+    P = [[np.ascontiguousarray(np.pad(me_util.to_bit_depth(f[c], bd), M if c == 0 else M // 2, mode="edge")) for c in range(3)] for f in (fr[0], fr[2])]
+    orgc = me_util.to_bit_depth(fr[1][1], bd)
+    SY, SC, csz = P[0][0].shape[1], P[0][1].shape[1], P[0][1].size
+    oy = [C.c_void_p(P[l][0].ctypes.data + 2 * (M * SY + M)) for l in range(2)]
+    n, regions = 120, 64
+    jobs = (DmvrJob * n)()
+    mvd_all = np.zeros((n, regions, 2), np.int32)
+    exp_pred, exp_out, pos = [], [], 0
+    for k in range(n):
+        w, h = int(rng.choice([8, 16, 32, 64, 128])), int(rng.choice([8, 16, 32, 64, 128]))
+        if w * h < 128:
+            w = 16
+        x, y = int(rng.integers(0, (W - w) // 8 + 1)) * 8, int(rng.integers(0, (H - h) // 8 + 1)) * 8
+        base = np.array([48, 32]) + rng.integers(-40, 41, 2)
+        mv = [int(-base[0]), int(-base[1]), int(base[0] + rng.integers(-24, 25)), int(base[1] + rng.integers(-24, 25))]
+        if k % 9 == 0:
+            mv = [int(v) for v in rng.integers(-4000, 4000, 4)]
+        comp = 1 + k % 2
+        nsub = (w // min(w, 16)) * (h // min(h, 16))
+        lum, mvd = np.zeros((h, w), np.int16), np.zeros(2 * nsub, np.int32)
+        L.vo_dmvr_pu(oy[0], oy[1], SY, W, H, 128, x, y, w, h, *mv, bd, 0, ol.P(lum), w, C.c_void_p(mvd.ctypes.data))
+        mvd_all[k, :nsub] = mvd.reshape(-1, 2)
+        oc = [C.c_void_p(P[l][comp].ctypes.data + 2 * ((M // 2) * SC + M // 2)) for l in range(2)]
+        e = np.zeros((h // 2, w // 2), np.int16)
+        L.vo_dmvr_chroma(oc[0], oc[1], SC, W, H, 128, x, y, w, h, *mv, C.c_void_p(mvd.ctypes.data), bd, ol.P(e), w // 2)
+        j = jobs[k]
+        for l in range(2):
+            j.refOff[l], j.refStride[l] = (2 * l + comp - 1) * csz + (M // 2 + y // 2) * SC + M // 2 + x // 2, SC
+        j.mv[0][0], j.mv[0][1], j.mv[1][0], j.mv[1][1] = mv
+        j.orgOff, j.orgStride, j.puX, j.puY, j.mvdRow = (y // 2) * (W // 2) + x // 2, W // 2, x, y, k
+        j.predOff = j.outOff = pos
+        j.predStride = j.outStride = w // 2
+        j.width, j.height, j.bitDepth, j.epilogue = w, h, bd, 1 + (k // 2) % 2
+        ob = orgc[y // 2:(y + h) // 2, x // 2:(x + w) // 2].astype(np.int32)
+        exp_pred.append(e.reshape(-1))
+        exp_out.append(((ob if j.epilogue == 1 else 2 * ob) - e).astype(np.int16).reshape(-1))
+        pos += w * h // 4
+    pic = PicParams(W, H, 128, bd, 0)
+    d_ref = ctx.to_device(np.concatenate([P[l][c].reshape(-1) for l in range(2) for c in (1, 2)]))
+    d_org, d_jobs, d_mvd = ctx.to_device(orgc.reshape(-1)), ctx.to_device(np.frombuffer(jobs, np.uint8)), ctx.to_device(mvd_all.reshape(-1))
+    d_pred, d_out = ctx.alloc(2 * pos), ctx.alloc(2 * pos)
+    ctx.dmvr_chroma_batch(pic, d_org.ptr, d_ref.ptr, d_pred.ptr, d_out.ptr, d_jobs.ptr, n, 128, 128, d_mvd.ptr)
+    assert np.array_equal(d_pred.to_host(np.int16), np.concatenate(exp_pred)), bd
+    assert np.array_equal(d_out.to_host(np.int16), np.concatenate(exp_out)), bd
 
 
 def test_prediction_entry_points_empty_and_invalid(ctx):
@@ -500,10 +498,11 @@ def test_prediction_entry_points_empty_and_invalid(ctx):
             bad()
 
 
-def test_bcw_ops_match_oracle(ctx):
-    """vtmhip_remove_weight_high_freq_batch_dev / vtmhip_add_weighted_avg_batch_dev vs the oracle: the five BCW weights (and their list-0 complements)."""
+def test_bcw_ops_match_oracle(ctx, deep=False):
+    """vtmhip_remove_weight_high_freq_batch_dev / vtmhip_add_weighted_avg_batch_dev vs the oracle: the five BCW weights (and their list-0 complements);
+    8- and 10-bit jobs, or (deep) 8- and 12-bit jobs with a third of the 14-bit inputs at the two ends of their range."""
     L = ol.oracle()
-    rng = np.random.default_rng(1019)
+    rng = np.random.default_rng(1119 if deep else 1019)
     n = 120
     jobs = (PelOpJob * n)()
     A, B, E0, E1, pos = [], [], [], [], 0
@@ -511,12 +510,14 @@ def test_bcw_ops_match_oracle(ctx):
         w, h = int(rng.choice([4, 8, 16, 32, 64, 128])), int(rng.choice([4, 8, 16, 32, 64]))
         bw = [-2, 3, 4, 5, 10][k % 5]
         lw = bw if k % 2 else 8 - bw
-        bd = 8 if k % 7 == 0 else 10
+        bd = 8 if k % 7 == 0 else (12 if deep else 10)
         hi = 8192 + ((1 << bd) - 1) * (1 << (14 - bd))
         a, b = ol.i16(rng.integers(0, 1 << bd, (h, w))), ol.i16(rng.integers(0, 1 << bd, (h, w)))
         e0 = a.copy()
         L.vo_remove_weight_high_freq(ol.P(e0), w, ol.P(b), w, w, h, lw)
         a14, b14 = ol.i16(rng.integers(-8192, hi, (h, w))), ol.i16(rng.integers(-8192, hi, (h, w)))
+        if deep:
+            a14[rng.random((h, w)) < 0.33], b14[rng.random((h, w)) < 0.33] = hi, -8192
         e1 = np.zeros((h, w), np.int16)
         L.vo_add_weighted_avg(ol.P(a14), w, ol.P(b14), w, ol.P(e1), w, w, h, bd, lw)
         j = jobs[k]
@@ -596,3 +597,38 @@ def test_merge_candidate_satd_batch(ctx):
             ctx.merge_cand_satd_batch(pic, d_org.ptr, d_ref.ptr, d_pred.ptr, d_p.ptr, n_each, d_b.ptr, n_each, d_d.ptr, n_each, d_mvd.ptr, w, h, d_dist.ptr, uniform=uniform)
             assert d_dist.to_host(np.uint64).tolist() == exp, (w, h, uniform)
             assert np.array_equal(d_pred.to_host(np.int16), np.concatenate(preds)), (w, h, uniform)
+
+
+@pytest.mark.parametrize("bd", [8, 12])
+def test_mc_luma_matches_oracle_8_12bit(ctx, bd):
+    """test_mc_luma_matches_oracle at 8 and 12 bits."""
+    test_mc_luma_matches_oracle(ctx, bd)
+
+
+@pytest.mark.parametrize("bd", [8, 12])
+def test_motion_compensation_fused_matches_oracle_8_12bit(ctx, bd):
+    """test_motion_compensation_fused_matches_oracle at 8 and 12 bits."""
+    test_motion_compensation_fused_matches_oracle(ctx, bd)
+
+
+@pytest.mark.parametrize("bd", [8, 12])
+def test_bdof_matches_oracle_8_12bit(ctx, bd):
+    """test_bdof_matches_oracle at 8 and 12 bits."""
+    test_bdof_matches_oracle(ctx, bd)
+
+
+@pytest.mark.parametrize("bd", [8, 12])
+def test_dmvr_matches_oracle_8_12bit(ctx, bd):
+    """test_dmvr_matches_oracle at 8 and 12 bits."""
+    test_dmvr_matches_oracle(ctx, bd)
+
+
+@pytest.mark.parametrize("bd", [8, 12])
+def test_dmvr_chroma_matches_oracle_8_12bit(ctx, bd):
+    """test_dmvr_chroma_matches_oracle at 8 and 12 bits."""
+    test_dmvr_chroma_matches_oracle(ctx, bd)
+
+
+def test_bcw_ops_match_oracle_12bit(ctx):
+    """test_bcw_ops_match_oracle with 8- and 12-bit jobs."""
+    test_bcw_ops_match_oracle(ctx, True)

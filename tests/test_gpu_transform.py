@@ -60,7 +60,7 @@ def _tu_list():
     return tus
 
 
-@pytest.mark.parametrize("bd", [10, 8])
+@pytest.mark.parametrize("bd", [10, 8, 12])
 def test_xT_xIT_batch_matches_oracle(ctx, bd):
     L = ol.oracle()
     rng = np.random.default_rng(32 + bd)
@@ -75,6 +75,8 @@ def test_xT_xIT_batch_matches_oracle(ctx, bd):
         blk = rng.integers(-amp + 1, amp, (h, w)).astype(np.int16)
         if k % 7 == 0:
             blk[:] = amp - 1 if k % 14 == 0 else -(amp - 1)   # dc extremes
+        elif bd == 12 and k % 7 == 3 and w > 1 and h > 1:      # signs along a basis row: the largest first-pass values of that row
+            blk = ol.basis_sign_block(w, h, th, tv, int(rng.integers(0, min(w, 32))), int(rng.integers(0, min(h, 32))), amp - 1)
         resi[k * 64:k * 64 + h, 3:3 + w] = blk
         j = jobs[k]
         j.srcOff, j.dstOff, j.srcStride, j.dstStride = k * 64 * stride + 3, k * 4096, stride, stride
@@ -98,6 +100,8 @@ def test_xT_xIT_batch_matches_oracle(ctx, bd):
     exp_resi = np.zeros((n * 64, stride), np.int16)
     for k, (w, h, th, tv) in enumerate(tus):
         c = (exp_coef[k, :w * h] // 3) * 3
+        if bd == 12 and k % 5 == 0:     # dequantised coefficients at the int16 limits
+            c = np.where(np.arange(w * h) % 3 == 0, np.where(c < 0, -32768, 32767), c)
         c2 = c.reshape(h, w).copy()
         sw, sh = _skip(th, w), _skip(tv, h)
         if sw:
@@ -178,12 +182,75 @@ def test_quant_dequant_batch_matches_oracle(ctx):
         assert sm[k] == exp_sum[k], ("absSum", cases[k])
 
 
+def qp_sweep(bd):
+    """Every QP of the depth, -6 (bd - 8) .. 63, as qpPer / qpRem of the base QP (QP + 6 (bd - 8), Quant.cpp:65-104)."""
+    off = 6 * (bd - 8)
+    return [((qp + off) // 6, (qp + off) % 6) for qp in range(-off, 64)]
+
+
+@pytest.mark.parametrize("bd", [8, 10, 12])
+def test_quant_dequant_full_qp_range_matches_oracle(ctx, bd):
+    """vtmhip_quant_batch_dev / vtmhip_dequant_batch_dev at every QP of the depth (qpPer 0 .. 14 at 12 bits), every size, plain and transform skip:
+    negative transform shifts (64-sample sides at 10 bits, 32 x 32 and up at 12), the dequant left-shift-and-clip path at high qpPer, levels and
+    dequantised values at the int16 limits (a quarter of the coefficients at the int16 limits, the lowest QPs)."""
+    L = ol.oracle()
+    rng = np.random.default_rng(141 + bd)
+    sizes = [(w, h) for w in (4, 8, 16, 32, 64) for h in (4, 8, 16, 32, 64)]
+    cases = [(w, h, per, rem, (i + per + ts) & 1, ts) for (per, rem) in qp_sweep(bd) for i, (w, h) in enumerate(sizes) for ts in (0, 1)
+             if not (ts and max(w, h) > 32)]
+    n = len(cases)
+    coef = np.zeros((n, 4096), np.int32)
+    jobs = (QuantJob * n)()
+    exp_q, exp_du, exp_dq = (np.zeros((n, 4096), np.int32) for _ in range(3))
+    exp_sum = np.zeros(n, np.int32)
+    for k, (w, h, per, rem, irap, ts) in enumerate(cases):
+        if ts:
+            c = rng.integers(-(1 << bd) + 1, 1 << bd, w * h).astype(np.int32)
+            c[rng.random(w * h) < 0.25] = (1 << bd) - 1
+        else:
+            c = rng.integers(-32768, 32768, w * h).astype(np.int32)
+            c[rng.random(w * h) < 0.4] //= 64
+            ext = rng.random(w * h) < 0.25
+            c[ext] = np.where(rng.random(int(ext.sum())) < 0.5, -32768, 32767)
+        coef[k, :w * h] = c
+        j = jobs[k]
+        j.srcOff, j.dstOff, j.width, j.height, j.qpPer, j.qpRem = k * 4096, k * 4096, w, h, per, rem
+        j.bitDepth, j.isIRAP, j.isTransformSkip = bd, irap, ts
+        s = C.c_int32()
+        L.vo_quant(ol.P(np.ascontiguousarray(c)), w, h, bd, per, rem, irap, ts, ol.P(exp_q[k]), ol.P(exp_du[k]), C.byref(s))
+        exp_sum[k] = s.value
+        L.vo_dequant(ol.P(exp_q[k]), w, h, bd, per, rem, ts, ol.P(exp_dq[k]))
+    assert exp_dq.max() == 32767 and exp_dq.min() == -32768 and (bd < 12 or np.abs(exp_q).max() == 32768)
+    d_coef = ctx.to_device(coef)
+    d_q, d_du, d_dq = (ctx.to_device(np.zeros((n, 4096), np.int32)) for _ in range(3))
+    d_jobs = ctx.to_device(np.frombuffer(jobs, np.uint8))
+    d_sum = ctx.alloc(4 * n, np.int32)
+    ctx.quant_batch(d_coef.ptr, d_q.ptr, d_du.ptr, d_jobs.ptr, n, d_sum.ptr)
+    ctx.dequant_batch(d_q.ptr, d_dq.ptr, d_jobs.ptr, n)
+    q, du, dq = (d.to_host().reshape(n, 4096) for d in (d_q, d_du, d_dq))
+    sm = d_sum.to_host()
+    for k, (w, h, *_r) in enumerate(cases):
+        assert np.array_equal(q[k, :w * h], exp_q[k, :w * h]), ("q", cases[k])
+        assert np.array_equal(du[k, :w * h], exp_du[k, :w * h]), ("deltaU", cases[k])
+        assert np.array_equal(dq[k, :w * h], exp_dq[k, :w * h]), ("dequant", cases[k])
+        assert sm[k] == exp_sum[k], ("absSum", cases[k])
+
+
+def _tu_block(rng, bd, w, h, th, tv, amp):
+    """A residual block for the chain tests at 8 / 12 bits: random of amplitude `amp`, or (one in four) +-(2^bd - 1) with signs along a basis row."""
+    if rng.random() < 0.25:
+        return ol.basis_sign_block(w, h, th, tv, int(rng.integers(0, min(w, 32))), int(rng.integers(0, min(h, 32))), (1 << bd) - 1)
+    return rng.integers(-amp, amp + 1, (h, w)).astype(np.int16)
+
+
 @pytest.mark.parametrize("big,uniform", [(False, False), (True, False), (False, True), (True, True)])
-def test_tu_chain_matches_oracle(ctx, big, uniform):
-    """Fused xT -> quant -> dequant -> xIT -> SSE (one launch) vs the oracle's separate steps; all 2-D sizes and type pairs."""
+def test_tu_chain_matches_oracle(ctx, big, uniform, bd=10):
+    """Fused xT -> quant -> dequant -> xIT -> SSE (one launch) vs the oracle's separate steps; all 2-D sizes and type pairs.  At 8 and 12 bits the QP
+    runs over the whole range of the depth and a quarter of the residuals are full-scale basis-row sign patterns (the int16 first-pass limit)."""
     from vtm_amd.lib import TuJob, TuResult
     L = ol.oracle()
-    rng = np.random.default_rng(77 + big)
+    rng = np.random.default_rng(77 + big if bd == 10 else 77 + big + 2 * bd)
+    sweep = qp_sweep(bd)
     tus = [t for t in _tu_list() if t[0] > 1 and t[1] > 1 and ((t[0] * t[1] > 256) == big)]
     n = len(tus)
     stride = 72
@@ -191,22 +258,27 @@ def test_tu_chain_matches_oracle(ctx, big, uniform):
     jobs = (TuJob * n)()
     exp, exp_lv, exp_rec = [], np.zeros((n, 4096), np.int32), np.zeros((n, 4096), np.int16)
     for k, (w, h, th, tv) in enumerate(tus):
-        amp = int(rng.choice([8, 60, 400, 1023]))
-        blk = rng.integers(-amp, amp + 1, (h, w)).astype(np.int16)
+        if bd == 10:
+            amp = int(rng.choice([8, 60, 400, 1023]))
+            blk = rng.integers(-amp, amp + 1, (h, w)).astype(np.int16)
+            qp = int(rng.choice([22, 27, 32, 37])) + 12
+            per, rem = qp // 6, qp % 6
+        else:
+            blk = _tu_block(rng, bd, w, h, th, tv, int(rng.choice([8, 60, 400, (1 << bd) - 1])))
+            per, rem = sweep[int(rng.integers(0, len(sweep)))]
         resi[k * 64:k * 64 + h, 4:4 + w] = blk
-        qp = int(rng.choice([22, 27, 32, 37])) + 12
         irap = int(rng.integers(0, 2))
         j = jobs[k]
         j.resiOff, j.outOff, j.resiStride, j.width, j.height = k * 64 * stride + 4, k * 4096, stride, w, h
-        j.qpPer, j.qpRem, j.typeHor, j.typeVer, j.bitDepth, j.isIRAP = qp // 6, qp % 6, th, tv, 10, irap
+        j.qpPer, j.qpRem, j.typeHor, j.typeVer, j.bitDepth, j.isIRAP = per, rem, th, tv, bd, irap
         coef, qc, dq = np.zeros(w * h, np.int32), np.zeros(w * h, np.int32), np.zeros(w * h, np.int32)
         blk_c = np.ascontiguousarray(blk)
-        assert L.vo_fwd_2d(ol.P(blk_c), w, w, h, 10, th, tv, ol.P(coef)) == 0
+        assert L.vo_fwd_2d(ol.P(blk_c), w, w, h, bd, th, tv, ol.P(coef)) == 0
         s = C.c_int32()
-        L.vo_quant(ol.P(coef), w, h, 10, j.qpPer, j.qpRem, irap, 0, ol.P(qc), None, C.byref(s))
-        L.vo_dequant(ol.P(qc), w, h, 10, j.qpPer, j.qpRem, 0, ol.P(dq))
+        L.vo_quant(ol.P(coef), w, h, bd, j.qpPer, j.qpRem, irap, 0, ol.P(qc), None, C.byref(s))
+        L.vo_dequant(ol.P(qc), w, h, bd, j.qpPer, j.qpRem, 0, ol.P(dq))
         rec = np.zeros((h, w), np.int16)
-        assert L.vo_inv_2d(ol.P(dq), w, h, 10, th, tv, ol.P(rec), w) == 0
+        assert L.vo_inv_2d(ol.P(dq), w, h, bd, th, tv, ol.P(rec), w) == 0
         exp.append((ol.o_dist(2, blk_c, rec, w, h), int(np.abs(coef.astype(np.int64)).sum()), s.value))
         exp_lv[k, :w * h], exp_rec[k, :w * h] = qc, rec.reshape(-1)
     d_resi = ctx.to_device(resi)
@@ -232,30 +304,35 @@ def test_tu_chain_matches_oracle(ctx, big, uniform):
     got = [(r.sse, r.sumAbs, r.absSum) for r in res]
     lv, rc = d_lv.to_host().reshape(n, 4096), d_rec.to_host().reshape(n, 4096)
     for k, (w, h, th, tv) in enumerate(tus):
-        assert got[k] == exp[k], (tus[k], got[k], exp[k])
+        assert got[k] == exp[k], (tus[k], bd, jobs[k].qpPer, got[k], exp[k])
         assert np.array_equal(lv[k, :w * h], exp_lv[k, :w * h]) and np.array_equal(rc[k, :w * h], exp_rec[k, :w * h]), tus[k]
 
 
 @pytest.mark.parametrize("size", [(8, 8), (16, 16), (32, 32), (64, 64), (32, 8), (8, 32), (16, 64)])
-def test_xT_uniform_batch_matches_oracle(ctx, size):
-    """vtmhip_xT_uniform_batch_dev: forward transforms of the MTS candidates of one TU size (TuJob table), coefficients and sum|coef|."""
+def test_xT_uniform_batch_matches_oracle(ctx, size, bd=10):
+    """vtmhip_xT_uniform_batch_dev: forward transforms of the MTS candidates of one TU size (TuJob table), coefficients and sum|coef|; residuals of
+    +-(2^bd - 1), at 12 bits every fourth block a basis-row sign pattern of full amplitude."""
     from vtm_amd.lib import TuJob, TuResult
     L = ol.oracle()
     w, h = size
-    rng = np.random.default_rng(700 + w + h)
+    rng = np.random.default_rng(700 + w + h if bd == 10 else 700 + w + h + 1000 * bd)
     cands = [(0, 0)] if max(w, h) > 32 else [(0, 0), (2, 2), (1, 2), (2, 1), (1, 1)]
     nblk = 37
     n = nblk * len(cands)
     stride = w + 6
-    resi = rng.integers(-1023, 1024, (nblk, h, stride)).astype(np.int16)
+    resi = rng.integers(-(1 << bd) + 1, 1 << bd, (nblk, h, stride)).astype(np.int16)
+    if bd == 12:
+        for b in range(0, nblk, 4):
+            th, tv = cands[(b // 4) % len(cands)]
+            resi[b, :, :w] = ol.basis_sign_block(w, h, th, tv, int(rng.integers(0, min(w, 32))), int(rng.integers(0, min(h, 32))), (1 << bd) - 1)
     jobs = (TuJob * n)()
     exp = np.zeros((n, h * w), np.int32)
     for k in range(n):
         b, (th, tv) = k % nblk, cands[k // nblk]
         j = jobs[k]
         j.resiOff, j.outOff, j.resiStride, j.width, j.height = b * h * stride, k * w * h, stride, w, h
-        j.typeHor, j.typeVer, j.bitDepth, j.qpPer, j.qpRem = th, tv, 10, 7, 2
-        assert L.vo_fwd_2d(C.c_void_p(resi.ctypes.data + 2 * j.resiOff), stride, w, h, 10, th, tv, ol.P(exp[k])) == 0
+        j.typeHor, j.typeVer, j.bitDepth, j.qpPer, j.qpRem = th, tv, bd, 7, 2
+        assert L.vo_fwd_2d(C.c_void_p(resi.ctypes.data + 2 * j.resiOff), stride, w, h, bd, th, tv, ol.P(exp[k])) == 0
     d_resi, d_jobs = ctx.to_device(resi), ctx.to_device(np.frombuffer(jobs, np.uint8))
     d_coef, d_res = ctx.alloc(4 * n * w * h), ctx.alloc(C.sizeof(TuResult) * n)
     ctx.xT_uniform_batch(d_resi.ptr, d_jobs.ptr, n, w, h, d_coef.ptr, d_res.ptr)
@@ -266,28 +343,37 @@ def test_xT_uniform_batch_matches_oracle(ctx, size):
 
 
 @pytest.mark.parametrize("uniform", [False, True])
-def test_transform_skip_candidate_of_the_fused_chain(ctx, uniform):
+def test_transform_skip_candidate_of_the_fused_chain(ctx, uniform, bd=10):
     """The MTS_SKIP candidate (TuJob.typeHor == 3): xTransformSkip -> Quant::quant(TS) -> dequant(TS) -> xITransformSkip -> SSE, mixed with
-    DCT2 jobs in the generic launch and alone in the uniform one; sumAbs = sum |residual| (vtmhip_mts_select2 scales it)."""
+    DCT2 jobs in the generic launch and alone in the uniform one; sumAbs = sum |residual| (vtmhip_mts_select2 scales it).  At 8 and 12 bits: residuals
+    up to +-(2^bd - 1) and the whole QP range of the depth."""
     from vtm_amd.lib import TuJob, TuResult
     L = ol.oracle()
-    rng = np.random.default_rng(991 + uniform)
+    rng = np.random.default_rng(991 + uniform if bd == 10 else 991 + uniform + 2 * bd)
+    sweep = qp_sweep(bd)
     shapes = [(4, 4), (8, 8), (16, 16), (32, 32), (8, 4), (4, 16), (32, 8), (16, 32)]
     for (w, h) in shapes:
         n = 24
         stride = w + 5
-        resi = rng.integers(-700, 701, (n, h, stride)).astype(np.int16)
+        amp = 700 if bd == 10 else (1 << bd) - 1
+        resi = rng.integers(-amp, amp + 1, (n, h, stride)).astype(np.int16)
         resi[rng.random(resi.shape) < 0.5] //= 40
+        if bd != 10:
+            resi[rng.random(resi.shape) < 0.1] = amp
         jobs = (TuJob * n)()
         exp = []
         exp_lv, exp_rec = np.zeros((n, w * h), np.int32), np.zeros((n, w * h), np.int16)
         for k in range(n):
             ts = uniform or (k % 2 == 0)
-            qp = int(rng.choice([22, 27, 32, 37])) + 12
+            if bd == 10:
+                qp = int(rng.choice([22, 27, 32, 37])) + 12
+                per, rem = qp // 6, qp % 6
+            else:
+                per, rem = sweep[int(rng.integers(0, len(sweep)))]
             irap = int(rng.integers(0, 2))
             j = jobs[k]
             j.resiOff, j.outOff, j.resiStride, j.width, j.height = k * h * stride, k * w * h, stride, w, h
-            j.qpPer, j.qpRem, j.bitDepth, j.isIRAP = qp // 6, qp % 6, 10, irap
+            j.qpPer, j.qpRem, j.bitDepth, j.isIRAP = per, rem, bd, irap
             j.typeHor = j.typeVer = 3 if ts else 0
             blk = np.ascontiguousarray(resi[k, :, :w])
             coef, qc, dq = np.zeros(w * h, np.int32), np.zeros(w * h, np.int32), np.zeros(w * h, np.int32)
@@ -295,14 +381,14 @@ def test_transform_skip_candidate_of_the_fused_chain(ctx, uniform):
             rec = np.zeros((h, w), np.int16)
             if ts:
                 coef[:] = blk.reshape(-1)
-                L.vo_quant(ol.P(coef), w, h, 10, j.qpPer, j.qpRem, irap, 1, ol.P(qc), None, C.byref(s))
-                L.vo_dequant(ol.P(qc), w, h, 10, j.qpPer, j.qpRem, 1, ol.P(dq))
+                L.vo_quant(ol.P(coef), w, h, bd, j.qpPer, j.qpRem, irap, 1, ol.P(qc), None, C.byref(s))
+                L.vo_dequant(ol.P(qc), w, h, bd, j.qpPer, j.qpRem, 1, ol.P(dq))
                 rec[:] = dq.reshape(h, w).astype(np.int16)   # xITransformSkip: Pel( coefficient )
             else:
-                assert L.vo_fwd_2d(ol.P(blk), w, w, h, 10, 0, 0, ol.P(coef)) == 0
-                L.vo_quant(ol.P(coef), w, h, 10, j.qpPer, j.qpRem, irap, 0, ol.P(qc), None, C.byref(s))
-                L.vo_dequant(ol.P(qc), w, h, 10, j.qpPer, j.qpRem, 0, ol.P(dq))
-                assert L.vo_inv_2d(ol.P(dq), w, h, 10, 0, 0, ol.P(rec), w) == 0
+                assert L.vo_fwd_2d(ol.P(blk), w, w, h, bd, 0, 0, ol.P(coef)) == 0
+                L.vo_quant(ol.P(coef), w, h, bd, j.qpPer, j.qpRem, irap, 0, ol.P(qc), None, C.byref(s))
+                L.vo_dequant(ol.P(qc), w, h, bd, j.qpPer, j.qpRem, 0, ol.P(dq))
+                assert L.vo_inv_2d(ol.P(dq), w, h, bd, 0, 0, ol.P(rec), w) == 0
             exp.append((ol.o_dist(2, blk, rec, w, h), int(np.abs(coef.astype(np.int64)).sum()), s.value))
             exp_lv[k], exp_rec[k] = qc, rec.reshape(-1)
         d_resi, d_jobs = ctx.to_device(resi), ctx.to_device(np.frombuffer(jobs, np.uint8))
@@ -313,7 +399,7 @@ def test_transform_skip_candidate_of_the_fused_chain(ctx, uniform):
         else:
             ctx.tu_chain_batch(d_resi.ptr, d_jobs.ptr, n, w, h, d_res.ptr, d_lv.ptr, d_rec.ptr)
         res = (TuResult * n).from_buffer_copy(d_res.to_host(np.uint8).tobytes())
-        assert [(r.sse, r.sumAbs, r.absSum) for r in res] == exp, (w, h)
+        assert [(r.sse, r.sumAbs, r.absSum) for r in res] == exp, (w, h, bd)
         assert np.array_equal(d_lv.to_host().reshape(n, w * h), exp_lv) and np.array_equal(d_rec.to_host().reshape(n, w * h), exp_rec), (w, h)
 
 
@@ -405,14 +491,15 @@ def test_mixed_tu_batch_is_bucketed_by_shape(ctx):
     assert not bad, [(jobs[k].width, jobs[k].height, jobs[k].typeHor, got[k], exp[k]) for k in bad[:6]]
 
 
-def test_mts_select_batch_matches_oracle(ctx):
+def test_mts_select_batch_matches_oracle(ctx, bd=10):
     """vtmhip_mts_select_batch_dev (the pre-selection of TrQuant::transformNxN( trModes, maxCand ) for every TU of a level, from the sum |coef| of its candidates)
     vs vo_mts_select (pinned against the real member in tests/test_oracle_vs_ref.py): candidate lists with and without the transform-skip entry, every TU
     shape class of the threshold table, maxCand 0 .. 4, costs that tie with the threshold."""
     from vtm_amd.lib import TuResult
     L = ol.oracle()
-    rng = np.random.default_rng(4711)
-    for it in range(24):
+    rng = np.random.default_rng(4711 if bd == 10 else 4711 + bd)
+    pruned_all = 0
+    for it in range(24 if bd == 10 else 12):
         w, h = int(rng.choice([4, 8, 16, 32])), int(rng.choice([4, 8, 16, 32]))
         modes = [0] + ([1] if it % 3 else []) + [2, 3, 4, 5][:int(rng.integers(0, 5))]
         max_cand = int(rng.integers(0, 5))
@@ -428,14 +515,44 @@ def test_mts_select_batch_matches_oracle(ctx):
         res["sumAbs"] = sums.reshape(-1)
         d_res = ctx.to_device(res.view(np.uint8))
         d_test = ctx.alloc(nc * ntu)
-        ctx.mts_select_batch(d_res.ptr, ntu, modes, w, h, 10, max_cand, d_test.ptr)
+        ctx.mts_select_batch(d_res.ptr, ntu, modes, w, h, bd, max_cand, d_test.ptr)
         got = d_test.to_host(np.uint8).reshape(nc, ntu)
         marr = np.array(modes, np.uint8)
         pruned = 0
         for t in range(0, ntu, 7):
             col = np.ascontiguousarray(sums[:, t])
             exp = np.zeros(nc, np.uint8)
-            L.vo_mts_select(ol.P(col), ol.P(marr), nc, w, h, 10, 15, max_cand, ol.P(exp))
+            L.vo_mts_select(ol.P(col), ol.P(marr), nc, w, h, bd, 15, max_cand, ol.P(exp))
             assert list(got[:, t]) == list(exp), (w, h, modes, max_cand, list(col), list(got[:, t]), list(exp))
             pruned += int(nc - exp.sum())
-        assert nc == 1 or pruned > 0
+        # the sums are drawn for 10 bits: at other depths the transform-skip scale moves the threshold, and a single list may keep all its candidates
+        assert nc == 1 or pruned > 0 or bd != 10
+        pruned_all += pruned
+    assert pruned_all > 0
+
+
+@pytest.mark.parametrize("bd", [8, 12])
+@pytest.mark.parametrize("big,uniform", [(False, False), (True, False), (False, True), (True, True)])
+def test_tu_chain_matches_oracle_8_12bit(ctx, big, uniform, bd):
+    """test_tu_chain_matches_oracle at 8 and 12 bits."""
+    test_tu_chain_matches_oracle(ctx, big, uniform, bd)
+
+
+@pytest.mark.parametrize("bd", [8, 12])
+@pytest.mark.parametrize("size", [(8, 8), (16, 16), (32, 32), (64, 64), (32, 8), (8, 32), (16, 64)])
+def test_xT_uniform_batch_matches_oracle_8_12bit(ctx, size, bd):
+    """test_xT_uniform_batch_matches_oracle at 8 and 12 bits."""
+    test_xT_uniform_batch_matches_oracle(ctx, size, bd)
+
+
+@pytest.mark.parametrize("bd", [8, 12])
+@pytest.mark.parametrize("uniform", [False, True])
+def test_transform_skip_candidate_of_the_fused_chain_8_12bit(ctx, uniform, bd):
+    """test_transform_skip_candidate_of_the_fused_chain at 8 and 12 bits."""
+    test_transform_skip_candidate_of_the_fused_chain(ctx, uniform, bd)
+
+
+@pytest.mark.parametrize("bd", [8, 12])
+def test_mts_select_batch_matches_oracle_8_12bit(ctx, bd):
+    """test_mts_select_batch_matches_oracle at 8 and 12 bits."""
+    test_mts_select_batch_matches_oracle(ctx, bd)
