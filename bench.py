@@ -22,7 +22,9 @@ every rank inside every step (RCCL broadcast over xGMI, double-buffered) and eve
 STRONG scaling: `value` = pictures/s of the whole job.
 
 Prints ONE JSON line (rank 0).  `value` = pictures/s of the stages above -- NOT a full encode (the CU recursion, CABAC and DepQuant are host work
-the path does not contain).  Extra keys: satd_gblocks_per_s (SURVEY.md 8d SATD-8x8 grid micro-benchmark, 81 displacements), roofline, cpu_baseline.
+the path does not contain).  A plain run does only what `value` needs: set-up, warm-up, the timed steps, --dump-outputs.  --full adds the measurements
+that take runs of their own, after the timed steps: stages_ms and kernels (an event-instrumented pass), satd_gblocks_per_s (SURVEY.md 8d SATD-8x8 grid
+micro-benchmark, 81 displacements), integer_search, roofline, pcie, cpu_baseline.
 """
 import argparse
 import json
@@ -61,6 +63,8 @@ def parse():
                     "(ASR search ranges 192 / 384); default 2,4,.. (--refs of them: search range 96)")
     ap.add_argument("--transform-skip", action="store_true", help="add the MTS_SKIP candidate to the TU chains")
     ap.add_argument("--shard", choices=["ctu", "row"], default="ctu", help="--gpus N: raster-scan CTU ranges (balanced) or whole CTU rows")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure what `value` does not need: per-stage and per-kernel times, the SATD "
+                    "micro-benchmark, the SAD-candidate statistics, the rooflines, the PCIe upload and the CPU baseline (the last two with one GPU only)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline sample (rank 0, N=1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-encoder-level", action="store_true", help="skip cpu_baseline.encoder_level (the real reference encoder, plain vs predInterSearch on the device, on a small clip: ~40 s)")
@@ -483,73 +487,73 @@ def main():
         dt = float(t.item())
     dumped = dump_outputs(result_arrays(last[0]), a.dump_outputs) if a.dump_outputs and rank == 0 else None
 
-    # ---- per-stage and per-kernel time: a separate, event-instrumented pass after the timed region ---------------------------------
-    # stage_ms: events between the steps of the serial order; kernel times: HIP events around every launch of the main kernels, recorded by the
-    # library on the stream the kernel is launched on (vtmhip_kernel_timing)
-    stage_acc, reps = {}, 3
-    ctx.kernel_timing(True)
-    for _ in range(reps):
-        fme.run(cur.data_ptr(), dpb.data_ptr(), timing=True)
-        torch.cuda.synchronize()
-        for k2, v in fme.stage_ms().items():
-            stage_acc[k2] = stage_acc.get(k2, 0.0) + v / reps
-    kern = {}
-    for k in KERNELS:
-        ms, n = ctx.kernel_timing_read(k)
-        if n:
-            kern[k] = {"ms_per_step": ms / reps, "launches_per_step": n // reps}
-    ctx.kernel_timing(False)
+    kern, sad_cands = {}, None      # --full only (the roofline and integer_search keys are formed from them)
+    if a.full:
+        # ---- per-stage and per-kernel time: a separate, event-instrumented pass after the timed region ---------------------------------
+        # stage_ms: events between the steps of the serial order; kernel times: HIP events around every launch of the main kernels, recorded by the
+        # library on the stream the kernel is launched on (vtmhip_kernel_timing)
+        stage_acc, reps = {}, 3
+        ctx.kernel_timing(True)
+        for _ in range(reps):
+            fme.run(cur.data_ptr(), dpb.data_ptr(), timing=True)
+            torch.cuda.synchronize()
+            for k2, v in fme.stage_ms().items():
+                stage_acc[k2] = stage_acc.get(k2, 0.0) + v / reps
+        for k in KERNELS:
+            ms, n = ctx.kernel_timing_read(k)
+            if n:
+                kern[k] = {"ms_per_step": ms / reps, "launches_per_step": n // reps}
+        ctx.kernel_timing(False)
 
-    # ---- SATD 8x8 grid micro-benchmark (extra key; outside the timed steps): each rank takes its band of 8-sample block rows ---------------
-    rows8 = H // 8
-    r0, r1 = (rows8 * rank) // world, (rows8 * (rank + 1)) // world
-    nb = (W // 8) * (r1 - r0)
-    satd_out = torch.empty(max(1, nb) * 81, dtype=torch.int32, device=dev)
-    ref0_ptr = dpb.data_ptr() + 2 * (refs[0][0][0] + r0 * 8 * refs[0][0][1])
-    cur_ptr = cur.data_ptr() + 2 * r0 * 8 * W
-    # ONE number: 2 warm-up launches, then SATD_REPS launches back to back between two events on the launch stream (torch's current stream IS the context's stream here); the
-    # per-launch event bracket of vtmhip_kernel_timing is NOT used for this kernel (it added ~80 us to a 144 us launch in round 3 and gave the line two different rates)
-    SATD_REPS = 20
+        # ---- SATD 8x8 grid micro-benchmark (extra key; outside the timed steps): each rank takes its band of 8-sample block rows ---------------
+        rows8 = H // 8
+        r0, r1 = (rows8 * rank) // world, (rows8 * (rank + 1)) // world
+        nb = (W // 8) * (r1 - r0)
+        satd_out = torch.empty(max(1, nb) * 81, dtype=torch.int32, device=dev)
+        ref0_ptr = dpb.data_ptr() + 2 * (refs[0][0][0] + r0 * 8 * refs[0][0][1])
+        cur_ptr = cur.data_ptr() + 2 * r0 * 8 * W
+        # ONE number: 2 warm-up launches, then SATD_REPS launches back to back between two events on the launch stream (torch's current stream IS the context's stream here); the
+        # per-launch event bracket of vtmhip_kernel_timing is NOT used for this kernel (it added ~80 us to a 144 us launch in round 3 and gave the line two different rates)
+        SATD_REPS = 20
 
-    def satd_rate(c_ptr, c_stride, r_ptr, r_stride, w, h, out_ptr):
-        for _ in range(2):
-            ctx.satd8_grid(c_ptr, c_stride, r_ptr, r_stride, w, h, 4, out_ptr)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(SATD_REPS):
-            ctx.satd8_grid(c_ptr, c_stride, r_ptr, r_stride, w, h, 4, out_ptr)
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / SATD_REPS
+        def satd_rate(c_ptr, c_stride, r_ptr, r_stride, w, h, out_ptr):
+            for _ in range(2):
+                ctx.satd8_grid(c_ptr, c_stride, r_ptr, r_stride, w, h, 4, out_ptr)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(SATD_REPS):
+                ctx.satd8_grid(c_ptr, c_stride, r_ptr, r_stride, w, h, 4, out_ptr)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / SATD_REPS
 
-    satd_ms = satd_rate(cur_ptr, W, ref0_ptr, refs[0][0][1], W, (r1 - r0) * 8, satd_out.data_ptr())
-    # the other two picture sizes SURVEY.md 8(d) lists for this micro-benchmark (rank 0, N = 1 only; uniform random 10-bit samples: the kernel's arithmetic path -- packed
-    # 16-bit levels for samples inside [0, 1023] -- is the one the synthetic picture takes)
-    satd_sizes = {}
-    if world == 1 and not a.no_cpu_baseline:
-        for (sw, sh) in ((1920, 1080), (7680, 4320)):
-            if (sw, sh) == (W, H):
-                continue
-            g = torch.Generator(device=dev)
-            g.manual_seed(sw)
-            sc = torch.randint(0, 1024, (sh, sw), dtype=torch.int16, device=dev, generator=g)
-            sr_ = torch.randint(0, 1024, (sh + 16, sw + 16), dtype=torch.int16, device=dev, generator=g)
-            so = torch.empty((sw // 8) * (sh // 8) * 81, dtype=torch.int32, device=dev)
-            ms_ = satd_rate(sc.data_ptr(), sw, sr_.data_ptr() + 2 * (8 * (sw + 16) + 8), sw + 16, sw, (sh // 8) * 8, so.data_ptr())
-            satd_sizes["%dx%d" % (sw, sh)] = {"pairs_per_launch": (sw // 8) * (sh // 8) * 81, "ms_per_launch": ms_, "gblocks_per_s": (sw // 8) * (sh // 8) * 81 / ms_ / 1e6}
-            del sc, sr_, so
-    satd_g = torch.tensor([nb * 81 / satd_ms / 1e6], dtype=torch.float64, device=dev)
-    if use_dist:
-        dist.all_reduce(satd_g)
+        satd_ms = satd_rate(cur_ptr, W, ref0_ptr, refs[0][0][1], W, (r1 - r0) * 8, satd_out.data_ptr())
+        # the other two picture sizes SURVEY.md 8(d) lists for this micro-benchmark (rank 0, N = 1 only; uniform random 10-bit samples: the kernel's arithmetic path -- packed
+        # 16-bit levels for samples inside [0, 1023] -- is the one the synthetic picture takes)
+        satd_sizes = {}
+        if world == 1 and not a.no_cpu_baseline:
+            for (sw, sh) in ((1920, 1080), (7680, 4320)):
+                if (sw, sh) == (W, H):
+                    continue
+                g = torch.Generator(device=dev)
+                g.manual_seed(sw)
+                sc = torch.randint(0, 1024, (sh, sw), dtype=torch.int16, device=dev, generator=g)
+                sr_ = torch.randint(0, 1024, (sh + 16, sw + 16), dtype=torch.int16, device=dev, generator=g)
+                so = torch.empty((sw // 8) * (sh // 8) * 81, dtype=torch.int32, device=dev)
+                ms_ = satd_rate(sc.data_ptr(), sw, sr_.data_ptr() + 2 * (8 * (sw + 16) + 8), sw + 16, sw, (sh // 8) * 8, so.data_ptr())
+                satd_sizes["%dx%d" % (sw, sh)] = {"pairs_per_launch": (sw // 8) * (sh // 8) * 81, "ms_per_launch": ms_, "gblocks_per_s": (sw // 8) * (sh // 8) * 81 / ms_ / 1e6}
+                del sc, sr_, so
+        satd_g = torch.tensor([nb * 81 / satd_ms / 1e6], dtype=torch.float64, device=dev)
+        if use_dist:
+            dist.all_reduce(satd_g)
 
-    # SAD candidates of the integer searches (SURVEY.md 8d prices one at 4 * W * H >> subShift algorithmic bytes): counted after the timed region by running the levels' uni
-    # searches once more through the public TZ call (the kernel keeps the count per search) -- rank 0, one GPU
-    sad_cands = None
-    if rank == 0 and world == 1 and sim <= 1:
-        try:
-            sad_cands = fme.sad_candidates(cur.data_ptr(), dpb.data_ptr())
-        except Exception as e:      # a statistic: never fails the line
-            print("sad_candidates:", e, file=sys.stderr)
+        # SAD candidates of the integer searches (SURVEY.md 8d prices one at 4 * W * H >> subShift algorithmic bytes): counted after the timed region by running the levels' uni
+        # searches once more through the public TZ call (the kernel keeps the count per search) -- rank 0, one GPU
+        if rank == 0 and world == 1 and sim <= 1:
+            try:
+                sad_cands = fme.sad_candidates(cur.data_ptr(), dpb.data_ptr())
+            except Exception as e:      # a statistic: never fails the line
+                print("sad_candidates:", e, file=sys.stderr)
     if rank == 0:
         wc = fme.work_counts()
         # ---- roofline of the dominant kernel: vector-ALU ISSUE (these kernels are integer / packed-16-bit instruction streams; their HBM traffic is
@@ -618,9 +622,10 @@ def main():
                                 + (", replayed from a hipGraph" if use_graph else ""),
                        "parallelism": ("1 GPU" if world == 1 else "one picture, CTUs sharded over %d GPUs (%s): bands %s; the planes of the newest reference picture (Y, Cb, Cr) broadcast from rank 0 and the results gathered to rank 0 every step"
                                        % (world, "raster-scan CTU ranges" if a.shard == "ctu" else "whole CTU rows", [b[1] - b[0] for b in bands]))},
-            "satd_gblocks_per_s": float(satd_g.item()),
-            "stages_ms": stage_acc, "kernels": kern, "workload_key": wkey,
         }
+        if a.full:
+            out.update({"satd_gblocks_per_s": float(satd_g.item()), "stages_ms": stage_acc, "kernels": kern})
+        out["workload_key"] = wkey
         if dumped:
             out["dump_outputs"] = dumped
         if sad_cands:
@@ -642,13 +647,14 @@ def main():
                 r = issue_roofline(k, kern[k]["ms_per_step"], kern[k]["launches_per_step"])
                 r.pop("note", None)
                 out["roofline_next"].append(r)
-        r = issue_roofline("satd8_grid_kernel", satd_ms, 1, in_step=False)      # the same 20 back-to-back launches as satd_gblocks_per_s: one rate per line
-        r["pairs_per_s_G"] = nb * 81 / satd_ms / 1e6
-        r["pairs_per_launch"] = nb * 81
-        out["satd_roofline"] = r
-        satd_sizes["%dx%d" % (W, H)] = {"pairs_per_launch": nb * 81, "ms_per_launch": satd_ms, "gblocks_per_s": nb * 81 / satd_ms / 1e6}
-        out["satd_grid_sizes"] = satd_sizes
-        if world == 1:
+        if a.full:
+            r = issue_roofline("satd8_grid_kernel", satd_ms, 1, in_step=False)      # the same 20 back-to-back launches as satd_gblocks_per_s: one rate per line
+            r["pairs_per_s_G"] = nb * 81 / satd_ms / 1e6
+            r["pairs_per_launch"] = nb * 81
+            out["satd_roofline"] = r
+            satd_sizes["%dx%d" % (W, H)] = {"pairs_per_launch": nb * 81, "ms_per_launch": satd_ms, "gblocks_per_s": nb * 81 / satd_ms / 1e6}
+            out["satd_grid_sizes"] = satd_sizes
+        if a.full and world == 1:
             # what a host encoder would add per picture if the inputs were NOT resident: the original picture and the picture reconstructed last (the other
             # reference pictures are already on the device) from pinned host memory, measured here, not overlapped -- never part of `value`
             n_up = int(cur.numel() + newest[1])
@@ -666,7 +672,7 @@ def main():
             out["pcie"] = {"h2d_bytes_per_picture": 2 * n_up, "h2d_ms_per_picture": up_ms, "h2d_GBps": 2 * n_up / up_ms / 1e6,
                            "pictures_per_s_if_not_overlapped": 1000.0 / (1e3 * dt / a.steps + up_ms)}
             del host, stage
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(fme, cur_np, dpb_np, refs, sr, W, H, lam, qp, a.cpu_seconds, pocs=poc_arg, chroma=ch_cpu, affine=a.affine, low_delay=a.config == "ldp", smvd=smvd)
             if not a.no_encoder_level:
                 try:

@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 TAG=$1
 shift
-EXTRA="$@"
+EXTRA="--full $@"      # --full on every pass: summarize_profiles.py counts the 3 passes of the per-stage timing among the picture passes
 python bench.py $EXTRA > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || (tail -30 gpurun_out/bench_$TAG.err; exit 1)
 cat gpurun_out/bench_$TAG.json | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print({k:d[k] for k in ('value','ms_per_step','satd_gblocks_per_s')}); print(d['stages_ms']); print(d['kernels']); print(d.get('roofline')); print(d.get('cpu_baseline'))"
