@@ -1112,6 +1112,11 @@ int vtmhip_pis_run_picture( vtmhip_ctx *ctx, const vtmhip_pis_level_run *levels,
 int vtmhip_predInterSearch_batch_dev( vtmhip_ctx *ctx, const vtmhip_pis_level_run *L, const vtmhip_pis_buffers *buf );
 /* 1 when a batch of width x height blocks may promise cfg.uniformSquare (the tiled kernels know the shape) */
 int vtmhip_is_uniform_shape( int width, int height );
+/* Row-band form of the integer search kernel (tz_search_kernel: a thread keeps K segments of the block for the whole search, a round loads all its candidates at once): the K
+ * (1, 2 or 4) a fused uniform launch of width x height blocks at this row sub-sampling shift and pic.wavesPerJob runs with, 0 when the launch keeps the by-candidate kernel
+ * (4-sample segments, widths 12 / 24 / 48, a block that K * 64 * wavesPerJob threads do not cover exactly).  Job-table calls (vtmhip_tz_search_batch_dev) always keep that
+ * kernel; so does every launch when VTMHIP_TZ_BANDS=0 is set in the environment. */
+int vtmhip_tz_band_items( int width, int height, int subShift, int wavesPerJob );
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ for l in sys.stdin:
     if 'LDS Size' in l and cur:
         name = subprocess.run(['c++filt', cur], capture_output=True, text=True).stdout.strip()
         name = re.sub(r'\(anonymous namespace\)::', '', name); name = re.sub(r'\(.*', '', name); name = re.sub(r'^void ', '', name)
-        print('%-48s VGPRs %3s  spilled %3s  scratch %4s B  waves/SIMD %s  SGPRs %3s  static LDS %6s B' % (name[:48], d.get('VGPRs'), d.get('VGPRs Spill'), d.get('ScratchSize'), d.get('Occupancy'), d.get('TotalSGPRs'), d.get('LDS Size')))
+        print('%-48s VGPRs %3s  spilled %3s  scratch %4s B  waves/SIMD %s  SGPRs %3s  spilled %3s  static LDS %6s B' % (name[:48], d.get('VGPRs'), d.get('VGPRs Spill'), d.get('ScratchSize'), d.get('Occupancy'), d.get('TotalSGPRs'), d.get('SGPRs Spill'), d.get('LDS Size')))
         cur = None
 "
 done

@@ -299,6 +299,10 @@ struct Coop
   bool                leader;    // the single thread that writes the candidate list
   unsigned long long *redCost;   // [wpj] cross-wave arg-min exchange (LDS)
   unsigned           *redIdx;
+  // row-band kernels (K > 0) only
+  int4               *ptsBase;   // [2][16] candidate lists: a round's list sits in the half the last round did not use
+  unsigned           *part;      // [2][16][4 * wpj] partial SADs of a round's candidates, by round parity
+  int16_t            *orgLds;    // where an in-kernel raster scan stages the original block
 };
 
 template<int WPJ>
@@ -451,14 +455,164 @@ __device__ __forceinline__ void eval_candidates( const MeJob &j, const int4 *pts
   bestIdx  = uni( bestIdx );
 }
 
-// evaluate the n (<= 16) candidates whose (x, y, nr, dist) sit in pts[] and replay the accept rule
-template<int WPJ>
-__device__ __forceinline__ void tz_round( const MeJob &j, TzState &s, const int4 *pts, int n, const Coop &co, bool touchMeta )
+// ---- row bands -----------------------------------------------------------------------------------------------------------------------
+// The other decomposition of a list round, for launches whose block shape is known on the host (vtmhip_tz_band_items).  Instead of dealing the round's CANDIDATES to the
+// waves, a thread owns K fixed segments of the block for the whole search: items t, t + T, .. of the T = 64 * WPJ threads (the 256 items of a wave of a 128x128 search are a
+// band of 16 rows).  Its K original segments stay in registers, XORed with the sign bias, so a round fetches the reference only: the loads of ALL its candidates for the
+// thread's items, BAND_LOADS of them in flight, one partial SAD per candidate.  A row-wide DPP sum leaves four row totals per wave and candidate; they meet in LDS
+// (part[parity][candidate][4 * WPJ]) and after ONE barrier every wave forms the same (cost, index) minimum itself -- lane c adds the partials of candidate c.  The sums are
+// exact integers: totals, costs and the accepted point are those of eval_candidates.  The candidate lists alternate between two halves of pts[] like the partials do, so a
+// round needs two workgroup barriers (list written / partials written) and none before the next list is written.
+constexpr int BAND_LOADS = 8;
+
+template<int K> struct Band
 {
+  unsigned o[K > 0 ? K : 1][4];   // the thread's original segments
+  unsigned offB, stepB;           // byte offset of its first segment from a candidate's top-left reference sample; segment m lies m * stepB further
+};
+
+template<int K>
+__device__ __forceinline__ void band_load_org( const MeJob &j, Band<K> &bd, int tid, int threads )
+{
+  // threads is a multiple of segsPerRow (both powers of two, threads >= 64 > 16): a thread's segments share one column and lie threads / segsPerRow rows apart
+  const int  r = tid >> j.sprShift, x = ( tid & ( j.segsPerRow - 1 ) ) << 3;
+  const long os = ( long ) j.orgStride << j.ss;
+  const int  cs = j.refStride << j.ss, rows = threads >> j.sprShift;
+#pragma unroll
+  for( int m = 0; m < K; m++ )
+  {
+    const Pel8 a = *reinterpret_cast<const Pel8 *>( j.org + ( r + m * rows ) * os + x );
+#pragma unroll
+    for( int k = 0; k < 4; k++ ) bd.o[m][k] = a.v[k] ^ j.bias;
+  }
+  bd.offB  = ( unsigned ) ( r * cs + x ) * 2u;
+  bd.stepB = ( unsigned ) ( rows * cs ) * 2u;
+}
+
+// the thread's partial SADs of the round's n candidates, summed over the 16 lanes of its DPP row; lane (16 row + c) returns the row total of candidate c
+// (px, py: lane c holds candidate c's position)
+template<int K, bool SGN>
+__device__ __forceinline__ unsigned band_partials( const MeJob &j, const Band<K> &bd, int px, int py, int n, int lane )
+{
+  // candidates whose loads are in flight together.  Four segments per thread: one candidate -- eight loads with the extra dword of the aligned form do not fit 128 registers.
+  // (Eight loads WITHOUT that form, odd candidates fetched by 2-byte aligned loads, measured the same: 0.558 against 0.564 ms per launch of the 128x128 level, 0.596 by
+  // candidates.  That level moves 32 KB per candidate through the CU's vector memory path and is bound by it, not by the number of loads in flight: DESIGN.md 4.2)
+  constexpr int  CH = K == 4 ? 1 : BAND_LOADS / K;
+  const bool   evenStride = !( ( j.refStride << j.ss ) & 1 );
+  const size_t stepB = uni( bd.stepB );
+  const int    slot = lane & 15;
+  unsigned     mine = 0;
+  for( int c0 = 0; c0 < n; c0 += CH )
+  {
+    Pel8     b[CH][K];
+    unsigned e[CH][K];
+    bool     odd[CH];
+#pragma unroll
+    for( int q = 0; q < CH; q++ )
+    {
+      odd[q] = false;
+      if( c0 + q < n )      // (uniform)
+      {
+        const int16_t *cp = j.ref + ( long ) __builtin_amdgcn_readlane( py, c0 + q ) * j.refStride + __builtin_amdgcn_readlane( px, c0 + q );
+        // a candidate at an odd sample offset (every lane's address has its parity when the row step is even): the dword-aligned form of ld8
+        odd[q] = evenStride && ( reinterpret_cast<uintptr_t>( cp ) & 2 ) != 0;
+        const char *cb = reinterpret_cast<const char *>( cp ) - ( odd[q] ? 2 : 0 );
+#pragma unroll
+        for( int m = 0; m < K; m++ ) b[q][m] = *reinterpret_cast<const Pel8 *>( cb + m * stepB + bd.offB );
+        if( odd[q] )
+        {
+#pragma unroll
+          for( int m = 0; m < K; m++ ) e[q][m] = *reinterpret_cast<const unsigned *>( cb + m * stepB + 16 + bd.offB );
+        }
+      }
+    }
+#pragma unroll
+    for( int q = 0; q < CH; q++ )
+      if( c0 + q < n )
+      {
+        if( odd[q] )
+        {
+#pragma unroll
+          for( int m = 0; m < K; m++ )
+          {
+            Pel8 &v = b[q][m];
+            v.v[0] = __builtin_amdgcn_alignbit( v.v[1], v.v[0], 16 ); v.v[1] = __builtin_amdgcn_alignbit( v.v[2], v.v[1], 16 );
+            v.v[2] = __builtin_amdgcn_alignbit( v.v[3], v.v[2], 16 ); v.v[3] = __builtin_amdgcn_alignbit( e[q][m], v.v[3], 16 );
+          }
+        }
+        unsigned s = 0;
+#pragma unroll
+        for( int m = 0; m < K; m++ )
+#pragma unroll
+          for( int k = 0; k < 4; k++ ) s = sad2( bd.o[m][k], bx<SGN>( b[q][m].v[k], j.bias ), s );
+        s += dpp_u32<DPP_XOR1>( s );
+        s += dpp_u32<DPP_XOR2>( s );
+        s += dpp_u32<DPP_HALF_MIRROR>( s );
+        s += dpp_u32<DPP_MIRROR>( s );      // every lane of the row holds the row's total
+        mine = slot == c0 + q ? s : mine;
+      }
+  }
+  return mine;
+}
+
+// a list round of n (1 .. 16) candidates in pts[]: the first strict minimum in list order as (cost, index), the same in every wave
+template<int WPJ, int K>
+__device__ __forceinline__ void band_round( const MeJob &j, const Band<K> &bd, const int4 *pts, int n, const Coop &co, unsigned long long &bestCost, unsigned &bestIdx )
+{
+  const int lane = co.lane;
+  unsigned *part = co.part + ( pts == co.ptsBase ? 0 : 16 * 4 * WPJ );
+  const int4     p    = pts[lane & 15];      // lane c (and c + 16, ..): candidate c; entries from n on are stale and unused
+  const unsigned mine = j.bias ? band_partials<K, true>( j, bd, p.x, p.y, n, lane ) : band_partials<K, false>( j, bd, p.x, p.y, n, lane );
+  if( ( lane & 15 ) < n ) part[( lane & 15 ) * ( 4 * WPJ ) + co.wave * 4 + ( lane >> 4 )] = mine;
+  job_sync<WPJ>();
+  // candidate c's 4 * WPJ partials: from four waves on, the four DPP rows add a quarter each (lane 16 g + c) and the quarters meet by two cross-row steps
+  constexpr int G = WPJ >= 4 ? 4 : 1;
+  unsigned      tot = 0;
+  {
+    const uint4 *pp = reinterpret_cast<const uint4 *>( part + ( G == 4 ? lane & 15 : min( lane, 15 ) ) * ( 4 * WPJ ) ) + ( G == 4 ? ( lane >> 4 ) * ( WPJ / 4 ) : 0 );
+#pragma unroll
+    for( int w = 0; w < WPJ / G; w++ ) { const uint4 t = pp[w]; tot += t.x + t.y + t.z + t.w; }
+    if( G == 4 ) { tot += __shfl_xor( tot, 16, 64 ); tot += __shfl_xor( tot, 32, 64 ); }
+  }
+  const bool valid = lane < n;
+  bestCost = ~0ull;
+  bestIdx  = valid ? ( unsigned ) lane : 0xffffffffu;
+  if( valid ) bestCost = ( ( unsigned long long ) tot << j.ss ) + mv_cost( j, p.x, p.y );
+  if( j.narrow )      // (the keys of eval_candidates)
+  {
+    unsigned cm, km;
+    if( j.tiny )
+    {
+      const unsigned m = wave_min_u32( valid ? ( ( unsigned ) bestCost << 6 ) | bestIdx : 0xffffffffu );
+      cm = m == 0xffffffffu ? 0xffffffffu : m >> 6;
+      km = m == 0xffffffffu ? 0xffffffffu : m & 63u;
+    }
+    else
+    {
+      const unsigned c32 = valid ? ( unsigned ) bestCost : 0xffffffffu;
+      cm = wave_min_u32( c32 );
+      km = wave_min_u32( c32 == cm ? bestIdx : 0xffffffffu );
+    }
+    bestCost = km == 0xffffffffu ? ~0ull : ( unsigned long long ) uni( cm );
+    bestIdx  = uni( km );
+    return;
+  }
+  wave_argmin( bestCost, bestIdx );
+  bestCost = uni( bestCost );
+  bestIdx  = uni( bestIdx );
+}
+
+// evaluate the n (<= 16) candidates whose (x, y, nr, dist) sit in pts[] and replay the accept rule
+// (K > 0, row bands: pts moves on to the other half of the list buffer)
+template<int WPJ, int K>
+__device__ __forceinline__ void tz_round( const MeJob &j, const Band<K> &bd, TzState &s, int4 *&pts, int n, const Coop &co, bool touchMeta )
+{
+  if( K > 0 && n == 0 ) return;      // (uniform over the job: nothing was written, nobody meets)
   job_sync<WPJ>();   // pts[] was written by the job's leader thread
   unsigned long long cost;
   unsigned           idx;
-  eval_candidates<false, WPJ>( j, pts, n, 0, 0, 1, 1, co, cost, idx );
+  if constexpr( K > 0 ) band_round<WPJ, K>( j, bd, pts, n, co, cost, idx );
+  else eval_candidates<false, WPJ>( j, pts, n, 0, 0, 1, 1, co, cost, idx );
   s.nEval += ( unsigned ) n;
   if( n > 0 && cost < s.bestSad )
   {
@@ -473,7 +627,8 @@ __device__ __forceinline__ void tz_round( const MeJob &j, TzState &s, const int4
       s.pointNr   = uni( p.z );
     }
   }
-  job_sync<WPJ>();   // everyone has read pts[] before the next round overwrites it
+  if constexpr( K > 0 ) pts = co.ptsBase + ( pts == co.ptsBase ? 16 : 0 );   // the next list goes to the other half: two barriers lie between two uses of a half
+  else job_sync<WPJ>();   // everyone has read pts[] before the next round overwrites it
 }
 
 #define PUSH( X, Y, NR, D ) do { if( co.leader ) pts[n] = make_int4( ( X ), ( Y ), ( NR ), ( D ) ); n++; } while( 0 )
@@ -558,16 +713,16 @@ __device__ int diamond_points( const Range &sr, int sx, int sy, int d, bool corn
   return n;
 }
 
-template<int WPJ>
-__device__ __forceinline__ void tz_diamond( const MeJob &j, TzState &s, int sx, int sy, int d, bool corners, int4 *pts, const Coop &co )
+template<int WPJ, int K>
+__device__ __forceinline__ void tz_diamond( const MeJob &j, const Band<K> &bd, TzState &s, int sx, int sy, int d, bool corners, int4 *&pts, const Coop &co )
 {
   const int n = diamond_points( s.sr, sx, sy, d, corners, pts, co );
   s.bestRound += 1;
-  tz_round<WPJ>( j, s, pts, n, co, true );
+  tz_round<WPJ, K>( j, bd, s, pts, n, co, true );
 }
 
-template<int WPJ>
-__device__ __forceinline__ void tz_two_point( const MeJob &j, TzState &s, int4 *pts, const Coop &co )
+template<int WPJ, int K>
+__device__ __forceinline__ void tz_two_point( const MeJob &j, const Band<K> &bd, TzState &s, int4 *&pts, const Coop &co )
 {
   // untested neighbours of the best point, by the point number of the dist-1 round (xTZ2PointSearch :426-446);
   // packed as 2-bit fields (value + 1) per point number 0..8
@@ -581,7 +736,7 @@ __device__ __forceinline__ void tz_two_point( const MeJob &j, TzState &s, int4 *
   int       n  = 0;
   if( x1 >= s.sr.left && x1 <= s.sr.right && y1 >= s.sr.top && y1 <= s.sr.bottom ) PUSH( x1, y1, 0, 2 );
   if( x2 >= s.sr.left && x2 <= s.sr.right && y2 >= s.sr.top && y2 <= s.sr.bottom ) PUSH( x2, y2, 0, 2 );
-  tz_round<WPJ>( j, s, pts, n, co, true );
+  tz_round<WPJ, K>( j, bd, s, pts, n, co, true );
 }
 
 // Raster scan when a whole wave shares one candidate (lpc == 64, 8-sample segments, power-of-two row length): the lane's IPL
@@ -646,7 +801,7 @@ __device__ __forceinline__ void raster_resident_org( const MeJob &j, int total, 
 }
 
 // raster scan (xTZSearch :3888-3899 / adaptive :3883-3903): candidate k = (row k / nx, column k % nx) in row-major order
-template<int WPJ>
+template<int WPJ, int K>
 __device__ __forceinline__ void tz_raster( const MeJob &j, TzState &s, const Range &r, int stepXY, const Coop &co )
 {
   const int nx = r.right >= r.left ? ( r.right - r.left ) / stepXY + 1 : 0;
@@ -661,6 +816,13 @@ __device__ __forceinline__ void tz_raster( const MeJob &j, TzState &s, const Ran
   if( false ) {}
   else if( WPJ >= 4 && fits && ipl == 4 ) raster_resident_org<4, WPJ>( j, total, r.left, r.top, nx, stepXY, co, cost, idx );
   else if( WPJ >= 2 && fits && ipl == 1 ) raster_resident_org<1, WPJ>( j, total, r.left, r.top, nx, stepXY, co, cost, idx );
+  else if( K > 0 && WPJ >= 2 && total > 0 )
+  {
+    // a row-band search keeps no LDS copy of the original block; this scan reads one per candidate, so it is staged here, where a scan is actually reached
+    MeJob js = j;
+    stage_org<WPJ, ( WPJ >= 4 ? ORG_LDS_CAP : ORG_LDS_CAP2 )>( js, co.orgLds, co.lane + 64 * co.wave );
+    eval_candidates<true, WPJ>( js, nullptr, total, r.left, r.top, nx, stepXY, co, cost, idx );
+  }
   else eval_candidates<true, WPJ>( j, nullptr, total, r.left, r.top, nx > 0 ? nx : 1, stepXY, co, cost, idx );
   s.nEval += ( unsigned ) total;
   if( total > 0 && cost < s.bestSad )
@@ -917,7 +1079,7 @@ __global__ __launch_bounds__( 256 ) void tz_raster_cols_kernel( vtmhip_pic_param
 }
 
 // WPJ = 1: 256 threads = 4 independent jobs.  WPJ > 1: 64 * WPJ threads = 1 job.
-template<int WPJ>
+template<int WPJ, int K>
 __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, const int16_t *__restrict__ orgBase, const int16_t *__restrict__ refBase,
                                                const vtmhip_tz_job *__restrict__ jobs, int numJobs, vtmhip_me_result *__restrict__ results, int mode, TzSaved *__restrict__ saved,
                                                int *__restrict__ list, int totCap, const MeFuse &fu, int blockIdxX, int gridDimX )
@@ -925,7 +1087,8 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
   // mode 0: the whole search.  Split launches: mode 1 stops at the raster decision of jobs tz_raster_cols_kernel can take (state -> saved[], job
   // index -> list[]; every other job runs to the end here); mode 2 resumes the listed jobs after the scan.
   constexpr int JOBS_PER_BLOCK = WPJ == 1 ? 4 : 1;
-  __shared__ int4               sPts[JOBS_PER_BLOCK][16];   // 15 m_uniMvList candidates / 16 diamond points at most
+  __shared__ int4               sPts[JOBS_PER_BLOCK][K > 0 ? 32 : 16];   // 15 m_uniMvList candidates / 16 diamond points at most (row bands: two lists, used in turn)
+  __shared__ __attribute__( ( aligned( 16 ) ) ) unsigned sPart[K > 0 ? JOBS_PER_BLOCK * 2 * 16 * 4 * WPJ : 1];   // row bands: [job][parity][candidate][4 * WPJ] row totals
   __shared__ unsigned long long sRedCost[WPJ];
   __shared__ unsigned           sRedIdx[WPJ];
   __shared__ __attribute__( ( aligned( 16 ) ) ) int16_t sOrgLds[WPJ >= 4 ? ORG_LDS_CAP : WPJ == 2 ? ORG_LDS_CAP2 : 8];
@@ -1003,6 +1166,7 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
   Coop                 co;
   co.lane = lane; co.wave = WPJ == 1 ? 0 : wv; co.wpj = WPJ; co.leader = ( lane == 0 && co.wave == 0 );
   co.redCost = sRedCost; co.redIdx = sRedIdx;
+  co.ptsBase = pts; co.part = sPart + ( WPJ == 1 ? wv : 0 ) * ( 2 * 16 * 4 * WPJ ); co.orgLds = sOrgLds;
 
   MeJob j;
   j.org       = orgBase + jp->orgOff;
@@ -1053,7 +1217,16 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
     }
     j.resOff = ( int ) ( r * ( ( long ) j.refStride << j.ss ) + x );
   }
-  stage_org<WPJ, ( WPJ >= 4 ? ORG_LDS_CAP : ORG_LDS_CAP2 )>( j, sOrgLds, ( int ) threadIdx.x );
+  Band<K> bd;
+  if constexpr( K > 0 )
+  {
+    // the launch promised this shape (vtmhip_tz_band_items): never true.  Uniform over the job, before any barrier of the search
+    if( j.seg != 8 || j.sprShift < 0 || j.items != K * 64 * WPJ ) return;
+    j.orgLds = nullptr;
+    if( K == 1 && WPJ == 1 ) { bd.o[0][0] = j.orgSeg[0]; bd.o[0][1] = j.orgSeg[1]; bd.o[0][2] = j.orgSeg[2]; bd.o[0][3] = j.orgSeg[3]; bd.offB = ( unsigned ) j.resOff * 2u; bd.stepB = 0; }
+    else band_load_org<K>( j, bd, WPJ == 1 ? lane : ( int ) threadIdx.x, 64 * WPJ );
+  }
+  else stage_org<WPJ, ( WPJ >= 4 ? ORG_LDS_CAP : ORG_LDS_CAP2 )>( j, sOrgLds, ( int ) threadIdx.x );
 
   const bool ext = jp->extendedSettings != 0, fast = jp->fastSettings != 0, firstStop = jp->firstSearchStop != 0;
   const int  iRaster = fast ? 8 : 5, searchRange = jp->searchRange;
@@ -1085,7 +1258,7 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
       clip_mv( j, ex, ey );
       PUSH( mvr::prec_down( ex, 4 ), mvr::prec_down( ey, 4 ), 0, 0 );
     }
-    tz_round<WPJ>( j, s, pts, n, co, true );
+    tz_round<WPJ, K>( j, bd, s, pts, n, co, true );
     if( numExtra > 14 )   // 15th candidate: the list holds 16 points
     {
       int m = 0;
@@ -1096,7 +1269,7 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
         PUSH( mvr::prec_down( ex, 4 ), mvr::prec_down( ey, 4 ), 0, 0 );
         m = n;
       }
-      tz_round<WPJ>( j, s, pts, m, co, false );
+      tz_round<WPJ, K>( j, bd, s, pts, m, co, false );
     }
   }
   else
@@ -1104,13 +1277,13 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
     {
       int n = 0;
       PUSH( mx, my, 0, 0 );
-      tz_round<WPJ>( j, s, pts, n, co, true );
+      tz_round<WPJ, K>( j, bd, s, pts, n, co, true );
     }
     if( !fast && ( mx != 0 || my != 0 ) && ( s.bestX != 0 || s.bestY != 0 ) )
     {
       int n = 0;
       PUSH( 0, 0, 0, 0 );
-      tz_round<WPJ>( j, s, pts, n, co, true );
+      tz_round<WPJ, K>( j, bd, s, pts, n, co, true );
     }
     int ix = jp->intMv2Nx2NPredHor << 4, iy = jp->intMv2Nx2NPredVer << 4;
     clip_mv( j, ix, iy );
@@ -1120,7 +1293,7 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
     {
       int n = 0;
       PUSH( ix, iy, 0, 0 );
-      tz_round<WPJ>( j, s, pts, n, co, true );
+      tz_round<WPJ, K>( j, bd, s, pts, n, co, true );
     }
     // m_uniMvList start candidates (:3725-3762): one parallel round, same first-strict-minimum semantics
     int       n  = 0;
@@ -1131,7 +1304,7 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
       clip_mv( j, ex, ey );
       PUSH( mvr::prec_down( ex, 4 ), mvr::prec_down( ey, 4 ), 0, 0 );
     }
-    tz_round<WPJ>( j, s, pts, n, co, false );
+    tz_round<WPJ, K>( j, bd, s, pts, n, co, false );
   }
 
   s.sr = search_range( j, s.bestX << 4, s.bestY << 4, searchRange >> ( fast ? 1 : 0 ) );
@@ -1141,17 +1314,17 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
 
   for( int d = 1; d <= searchRange; d *= 2 )
   {
-    tz_diamond<WPJ>( j, s, startX, startY, d, ext, pts, co );
+    tz_diamond<WPJ, K>( j, bd, s, startX, startY, d, ext, pts, co );
     if( firstStop && s.bestRound >= 3 ) break;
   }
   if( ext && !bestCandidateZero )
   {
-    for( int d = 1; d <= ( searchRange >> 1 ); d *= 2 ) tz_diamond<WPJ>( j, s, 0, 0, d, false, pts, co );
+    for( int d = 1; d <= ( searchRange >> 1 ); d *= 2 ) tz_diamond<WPJ, K>( j, bd, s, 0, 0, d, false, pts, co );
   }
   if( s.bestDist == 1 )
   {
     s.bestDist = 0;
-    tz_two_point<WPJ>( j, s, pts, co );
+    tz_two_point<WPJ, K>( j, bd, s, pts, co );
   }
   if( ext )
   {
@@ -1163,7 +1336,7 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
       lsr.left /= 2; lsr.right /= 2; lsr.top /= 2; lsr.bottom /= 2;
     }
     s.bestDist = ( unsigned ) win;
-    tz_raster<WPJ>( j, s, lsr, win, co );
+    tz_raster<WPJ, K>( j, s, lsr, win, co );
   }
   else if( ( int ) s.bestDist >= iRaster )
   {
@@ -1190,7 +1363,7 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
       }
       return;   // wave-uniform (WPJ == 1) / block-uniform: the search continues in the mode-2 launch
     }
-    tz_raster<WPJ>( j, s, s.sr, iRaster, co );
+    tz_raster<WPJ, K>( j, s, s.sr, iRaster, co );
   }
   }   // mode != 2
   else
@@ -1218,13 +1391,13 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
     s.pointNr  = 0;
     for( int d = 1; d < searchRange + 1; d *= 2 )
     {
-      tz_diamond<WPJ>( j, s, startX, startY, d, ext, pts, co );
+      tz_diamond<WPJ, K>( j, bd, s, startX, startY, d, ext, pts, co );
       if( fast && s.bestRound >= 2 ) break;
     }
     if( s.bestDist == 1 )
     {
       s.bestDist = 0;
-      if( s.pointNr != 0 ) tz_two_point<WPJ>( j, s, pts, co );
+      if( s.pointNr != 0 ) tz_two_point<WPJ, K>( j, bd, s, pts, co );
     }
   }
 
@@ -1238,8 +1411,9 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
   }
 }
 
-template<int WPJ>
-__global__ __launch_bounds__( WPJ == 1 ? 256 : 64 * WPJ ) __attribute__( ( amdgpu_waves_per_eu( WPJ == 2 || WPJ == 4 || WPJ == 8 ? 4 : 1 ) ) )      // two / four / eight waves per search sit at 129 .. 131 VGPRs: a register or two over the four-waves-per-SIMD budget
+// K: 0 = the candidates of a round are dealt to the waves (any shape); 1 / 2 / 4 = row bands, K segments per thread (vtmhip_tz_band_items)
+template<int WPJ, int K = 0>
+__global__ __launch_bounds__( WPJ == 1 ? 256 : 64 * WPJ ) __attribute__( ( amdgpu_waves_per_eu( WPJ == 2 || WPJ == 4 || WPJ == 8 || ( K > 0 && WPJ > 1 ) ? 4 : 1 ) ) )      // two / four / eight waves per search sit at 129 .. 131 VGPRs: a register or two over the four-waves-per-SIMD budget
 void tz_search_kernel( vtmhip_pic_params pic, const int16_t *__restrict__ orgBase, const int16_t *__restrict__ refBase, const vtmhip_tz_job *__restrict__ jobs, int numJobs,
                        vtmhip_me_result *__restrict__ results, int mode, TzSaved *__restrict__ saved, int *__restrict__ list, int totCap, MeFuse fu )
 {
@@ -1249,10 +1423,10 @@ void tz_search_kernel( vtmhip_pic_params pic, const int16_t *__restrict__ orgBas
     // 130 000 workgroups that leave at once -- 50 us of a launch for nothing.  A bounded grid walks the list instead (the waves of a workgroup are independent searches here)
     const int listed = uni( list[0] );
     for( int b = ( int ) blockIdx.x; b * 4 < listed; b += ( int ) gridDim.x )
-      tz_search_one<WPJ>( pic, orgBase, refBase, jobs, numJobs, results, mode, saved, list, totCap, fu, b, ( int ) gridDim.x );
+      tz_search_one<WPJ, K>( pic, orgBase, refBase, jobs, numJobs, results, mode, saved, list, totCap, fu, b, ( int ) gridDim.x );
     return;
   }
-  tz_search_one<WPJ>( pic, orgBase, refBase, jobs, numJobs, results, mode, saved, list, totCap, fu, ( int ) blockIdx.x, ( int ) gridDim.x );
+  tz_search_one<WPJ, K>( pic, orgBase, refBase, jobs, numJobs, results, mode, saved, list, totCap, fu, ( int ) blockIdx.x, ( int ) gridDim.x );
 }
 
 
@@ -1951,6 +2125,23 @@ __global__ __launch_bounds__( ( FullSq<W, H>::THREADS ) ) void full_search_sq_ke
 
 }   // namespace
 
+// The row-band form of tz_search_kernel: the segments per thread (1, 2 or 4) a launch of this shape runs with, 0 when it keeps the by-candidate kernel.  Takes 8-sample
+// segments, a power-of-two row length and a block that K * 64 * wavesPerJob threads cover exactly
+extern "C" int vtmhip_tz_band_items( int width, int height, int subShift, int wavesPerJob )
+{
+  const int wpj = wavesPerJob <= 1 ? 1 : wavesPerJob;
+  if( wpj != 1 && wpj != 2 && wpj != 4 && wpj != 8 && wpj != 16 ) return 0;
+  if( width < 8 || ( width & 7 ) || height < 1 || subShift < 0 || subShift > 1 ) return 0;
+  const int spr = width >> 3, threads = 64 * wpj;
+  if( ( spr & ( spr - 1 ) ) || spr > 64 ) return 0;
+  const int items = spr * ( ( height + ( 1 << subShift ) - 1 ) >> subShift );
+  if( items % threads ) return 0;
+  const int k = items / threads;
+  if( wpj == 1 && k != 1 ) return 0;      // a single wave keeps one segment per lane (32x32 with row sub-sampling), sixteen waves at most two: the register budget
+  if( wpj == 16 && k == 4 ) return 0;
+  return k == 1 || k == 2 || k == 4 ? k : 0;
+}
+
 extern "C" int vtmhip_tz_search_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase,
                                            const vtmhip_tz_job *d_jobs, int n, vtmhip_me_result *d_results )
 {
@@ -2007,9 +2198,18 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
     if( totBytes ) VTMHIP_HIP( ctx, hipMemsetAsync( d_list, 0, ( size_t ) ( ( char * ) d_tot - ( char * ) d_list ) + totBytes, ctx->stream ) );
     else VTMHIP_HIP( ctx, hipMemsetAsync( d_list, 0, sizeof( int ), ctx->stream ) );
   }
-#define VTMHIP_TZ_LAUNCH( W, GRID, MODE ) \
-  hipLaunchKernelGGL( tz_search_kernel<W>, dim3( GRID ), dim3( W == 1 ? 256 : 64 * W ), 0, ctx->stream, *pic, d_orgBase, d_refBase, d_jobs, n, d_results, MODE, d_saved, d_list, totCap, \
+#define VTMHIP_TZ_LAUNCH_K( W, KK, GRID, MODE ) \
+  hipLaunchKernelGGL( ( tz_search_kernel<W, KK> ), dim3( GRID ), dim3( W == 1 ? 256 : 64 * W ), 0, ctx->stream, *pic, d_orgBase, d_refBase, d_jobs, n, d_results, MODE, d_saved, d_list, totCap, \
                       ( MODE ) == 2 ? fuNone : fuFirst )
+  // bandK (vtmhip_tz_band_items of the launch's shape, 0 without VTMHIP_TZ_BANDS or for job tables): the row-band instantiation
+#define VTMHIP_TZ_LAUNCH( W, GRID, MODE )                               \
+  switch( bandK )                                                       \
+  {                                                                     \
+  case 1: VTMHIP_TZ_LAUNCH_K( W, 1, GRID, MODE ); break;                \
+  case 2: VTMHIP_TZ_LAUNCH_K( W, ( W == 1 ? 0 : 2 ), GRID, MODE ); break; \
+  case 4: VTMHIP_TZ_LAUNCH_K( W, ( W == 1 || W == 16 ? 0 : 4 ), GRID, MODE ); break; \
+  default: VTMHIP_TZ_LAUNCH_K( W, 0, GRID, MODE ); break;               \
+  }
 #define VTMHIP_TZ_SWITCH( MODE )                                    \
   switch( wpj )                                                     \
   {                                                                 \
@@ -2025,6 +2225,10 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
   static const bool groupOn = !( getenv( "VTMHIP_TZ_GROUP" ) && atoi( getenv( "VTMHIP_TZ_GROUP" ) ) == 0 );
   static const int  groupItems = getenv( "VTMHIP_TZ_GROUP_ITEMS" ) ? atoi( getenv( "VTMHIP_TZ_GROUP_ITEMS" ) ) : 32;
   int grpItems = 0, grpSs = 0;
+  // Row bands (VTMHIP_TZ_BANDS=0: off): the fused uniform rows whose shape vtmhip_tz_band_items accepts.  Job tables, mixed batches and the resume launch of a tz_group_kernel
+  // level keep the by-candidate kernel
+  static const bool bandsOn = !( getenv( "VTMHIP_TZ_BANDS" ) && atoi( getenv( "VTMHIP_TZ_BANDS" ) ) == 0 );
+  int bandK = 0;
   if( groupOn && fuse && fuse->me && !fuse->cfg.extendedSettings && ( wpj == 0 || wpj == 1 ) && ( uniformW == 8 || uniformW == 16 || uniformW == 32 ) && uniformH >= 8 )
   {
     const int ss = fuse->cfg.fastInterSearchMode13 && uniformH > 8 && uniformW <= 64 ? 1 : 0;      // mg::sub_shift
@@ -2053,6 +2257,8 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
   }
   else
   { VTMHIP_TIME_KERNEL( ctx, "tz_search_kernel" );
+    if( bandsOn && fuse && fuse->me && uniformW > 0 && uniformH > 0 )
+      bandK = vtmhip_tz_band_items( uniformW, uniformH, fuse->cfg.fastInterSearchMode13 && uniformH > 8 && uniformW <= 64 ? 1 : 0 /* mg::sub_shift */, wpj );
     VTMHIP_TZ_SWITCH( split ? 1 : 0 )
   }
   if( split )
@@ -2069,6 +2275,7 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
   }
 #undef VTMHIP_TZ_SWITCH
 #undef VTMHIP_TZ_LAUNCH
+#undef VTMHIP_TZ_LAUNCH_K
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
 }

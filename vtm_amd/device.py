@@ -281,6 +281,10 @@ class Context:
     def is_uniform_shape(self, w, h):
         return bool(self.L.vtmhip_is_uniform_shape(w, h))
 
+    def tz_band_items(self, w, h, sub_shift, waves_per_job):
+        """segments per thread of the row-band integer search kernel for a fused uniform launch of this shape; 0: the by-candidate kernel"""
+        return int(self.L.vtmhip_tz_band_items(w, h, sub_shift, waves_per_job))
+
     def affine_motion_estimation_batch(self, pic, d_org, d_ref, d_other, d_jobs, n, max_w, max_h, d_results, bcw=False):
         """InterSearch::xAffineMotionEstimation per AffineMeJob (one workgroup per job); bcw: the batch may hold bi jobs under a CU-level BCW weight of -2 (32-bit variant beside)"""
         f = self.L.vtmhip_xAffineMotionEstimation_bcw_batch_dev if bcw else self.L.vtmhip_xAffineMotionEstimation_batch_dev

@@ -389,6 +389,7 @@ _PROTOS = {
     "vtmhip_pis_stage": (C.c_int, [C.c_void_p, C.POINTER(PisLevel), C.c_int]),
     "vtmhip_predInterSearch_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(PisLevelRun), C.POINTER(PisBuffers)]),
     "vtmhip_is_uniform_shape": (C.c_int, [C.c_int, C.c_int]),
+    "vtmhip_tz_band_items": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "vtmhip_tz_search_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(PicParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_void_p]),
 }
