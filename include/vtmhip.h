@@ -358,7 +358,7 @@ typedef struct
 {
   int32_t picW, picH;   /* pps.getPicWidth/HeightInLumaSamples: clipMv / xClipMv limits */
   int32_t ctuSize;      /* sps.getMaxCUWidth() */
-  int32_t bitDepth;
+  int32_t bitDepth;     /* sps.getBitDepth( CHANNEL_TYPE_LUMA ): 8 .. 12 (the library's sample contract); every entry that takes these parameters returns VTMHIP_E_INVALID outside it */
   int32_t wavesPerJob;  /* tuning hint for this batch: 0/1 = one wave per search; 2, 4, 8, 16 = waves that split each candidate list (large PUs) */
   int32_t maxSearchRange; /* tuning hint: the largest searchRange of the batch's TZ jobs (m_aaiAdaptSR: up to 384 with ASR).  The raster scan of xTZSearch (:3888-3899) is run by a
                              column-walking kernel whose per-scan totals live in LDS: 0 (or <= 96) sizes it for the 39 x 39 points of SearchRange 96; a larger value for

@@ -23,7 +23,51 @@ class Scene:
         self.margin = margin
 
 
-def random_tz_jobs(scene, n, seed=5, ranges=(64, 96, 192, 384, 8), allow_ext=True, sizes=None):
+def motion_lambda(qp, bd):
+    """The reference's motion lambda of a slice QP (LambdaFromQpEnable, DepQuant; EncSlice.cpp:699-786, RdCost.cpp:79-84): sqrt( 0.57 * 2^((QP + 6 * (bd - 8) - 12) / 3) *
+    2^(0.25 / 3) ).  QP 63: 281 / 1 125 / 4 501 at 8 / 10 / 12 bits; 10-bit QP 32: 31.3."""
+    return (0.57 * 2.0 ** ((qp + 6 * (bd - 8) - 12) / 3.0) * 2.0 ** (0.25 / 3.0)) ** 0.5
+
+
+REAL_QPS = (22, 32, 33, 51, 63)      # 12-bit 128x128: QP 32 / 33 = lambda 125.3 / 140.7, either side of the one-word key's limit (130.03)
+EDGE = [6e5, 2e7, 3e9]               # beyond the one-word key for every shape; the last two beyond the 32-bit keys (lambda * 126 >= 2^31)
+
+
+def real_lambdas(bd):
+    return [motion_lambda(q, bd) for q in REAL_QPS]
+
+
+def key_class(w, h, bd, lam, signed=0):
+    """Which arg-min key the integer-search kernels pick for a job (MeJob::narrow / MeJob::tiny): "tiny" = distortion + rate < 2^26 whatever the candidate (one 32-bit
+    (cost << 6 | index) key), "narrow" = rate < 2^31 (two-word 32-bit keys), "wide" = the 64-bit arg-min.  Only for coverage floors: never for an expected value."""
+    if not (lam >= 0.0 and lam * 126.0 < 2147483648.0):
+        return "wide"
+    top = 65535.0 if signed else float((1 << bd) - 1)
+    return "tiny" if float(w * h) * top + lam * 126.0 < 67108864.0 else "narrow"
+
+
+def key_classes(jobs, bd):
+    out = {"tiny": 0, "narrow": 0, "wide": 0}
+    for j in jobs:
+        out[key_class(j["w"], j["h"], bd, j["lam"], j.get("signed", 0))] += 1
+    return out
+
+
+def random_tz_jobs(scene, n, seed=5, ranges=(64, 96, 192, 384, 8), allow_ext=True, sizes=None, lams=None):
+    """lams: the jobs' motion lambdas are drawn from this list (a generator of its own: independent of the jobs' periodic flags) instead of uniform(1, 40); the other
+    fields stay what they are without it."""
+    jobs = _random_tz_jobs(scene, n, seed, ranges, allow_ext, sizes)
+    return draw_lambdas(jobs, lams, seed) if lams else jobs
+
+
+def draw_lambdas(jobs, lams, seed):
+    pick = np.random.default_rng(seed + 77000).integers(0, len(lams), len(jobs))
+    for j, i in zip(jobs, pick):
+        j["lam"] = float(lams[int(i)])
+    return jobs
+
+
+def _random_tz_jobs(scene, n, seed, ranges, allow_ext, sizes):
     rng = np.random.default_rng(seed)
     jobs = []
     trial = 0
@@ -55,7 +99,7 @@ def oracle_ctx(scene, j, org_block):
     c.orgStride = org_block.shape[1]
     c.ref = scene.ref_buf.ctypes.data + 2 * (scene.ref_off + j["y"] * scene.ref_stride + j["x"])
     c.refStride = scene.ref_stride
-    c.w, c.h, c.subShift, c.bitDepth, c.imvShift = j["w"], j["h"], j["subShift"], 10, 0
+    c.w, c.h, c.subShift, c.bitDepth, c.imvShift = j["w"], j["h"], j["subShift"], getattr(scene, "bd", 10), 0
     c.mv = ol.MvCost(j["lam"], j["predHor"], j["predVer"], 2)
     c.picW, c.picH, c.puX, c.puY, c.ctuSize = scene.W, scene.H, j["x"], j["y"], 128
     return c
@@ -115,9 +159,46 @@ def _round_amvr(v, imv):
     return (((v + o - 1) >> rs) if v >= 0 else ((v + o) >> rs)) << rs
 
 
-def random_mest_jobs(scene, n, seed=17, sizes=None):
+def random_mest_jobs(scene, n, seed=17, sizes=None, lams=None, bcws=None):
     """(PU, list, refIdx) jobs of InterSearch::xMotionEstimation: uni / bi, every cu.imv mode, AMVP candidates rounded to the AMVR
-    precision as the encoder's AMVP lists are, m_uniMvList entries with duplicates."""
+    precision as the encoder's AMVP lists are, m_uniMvList entries with duplicates.  lams: motion lambdas drawn from this list instead of uniform(1, 40); bcws: the bi
+    rows' CU-level BCW weights cycle over this list (0: the default pair)."""
+    jobs = _random_mest_jobs(scene, n, seed, sizes)
+    if lams:
+        draw_lambdas(jobs, lams, seed)
+    if bcws:
+        for k, j in enumerate(j for j in jobs if j["bi"]):
+            j["bcw"] = int(bcws[k % len(bcws)])
+    return jobs
+
+
+def uniform_mest_rows(jobs, imv=0, bi=None):
+    """The jobs as rows of a uniform batch: one AMVR mode (candidates on its grid), optionally all uni / all bi."""
+    for j in jobs:
+        j["imv"] = imv
+        if bi is not None:
+            j["bi"] = bi
+        j["cands"] = [[_round_amvr(v, imv) for v in c] for c in j["cands"]]
+        j["mvPred"] = tuple(j["cands"][j["mvpIdx"]])
+    return jobs
+
+
+def run_oracle_mest(scene, jobs, cfgv):
+    """vo_motion_estimation per job: ([result key], [(intX, intY, intDist)])"""
+    L = ol.oracle()
+    cfg = ol.MestCfg(*cfgv)
+    exp, exp_int = [], []
+    for j in jobs:
+        keep = []
+        t = oracle_mest_job(scene, j, keep)
+        r = ol.MestResult()
+        L.vo_motion_estimation(C.byref(cfg), C.byref(t), C.byref(r))
+        exp.append(r.key())
+        exp_int.append((r.intX, r.intY, r.intDist))
+    return exp, exp_int
+
+
+def _random_mest_jobs(scene, n, seed, sizes):
     rng = np.random.default_rng(seed)
     jobs = []
     t = 0
@@ -173,7 +254,7 @@ def oracle_mest_job(scene, j, keep):
         o = other_pred(scene, j)
         keep.append(o)
         t.otherPred, t.otherStride = o.ctypes.data, j["w"]
-    t.w, t.h, t.puX, t.puY, t.picW, t.picH, t.ctuSize, t.bitDepth = j["w"], j["h"], j["x"], j["y"], scene.W, scene.H, 128, 10
+    t.w, t.h, t.puX, t.puY, t.picW, t.picH, t.ctuSize, t.bitDepth = j["w"], j["h"], j["x"], j["y"], scene.W, scene.H, 128, getattr(scene, "bd", 10)
     t.bi, t.imv, t.mvpIdx, t.numAmvpCand = j["bi"], j["imv"], j["mvpIdx"], j["numCand"]
     t.mvPredHor, t.mvPredVer = j["mvPred"]
     t.mvHor, t.mvVer = j["mv"]
@@ -268,6 +349,56 @@ class DeepScene(Scene):
         self.cur = to_bit_depth(fr[2], bit_depth)
         self.ref_buf, self.ref_off, self.ref_stride = synth.extend_plane(to_bit_depth(fr[0], bit_depth), margin)
         self.margin = margin
+
+
+def make_signed(scene, seed=17, span=None):
+    """Turns the scene's original into a bi-pred search target 2*org - other with `other` in 0 .. span - 1 (default: the whole range of the depth): -(2^bd - 1) .. 2 * (2^bd - 1)"""
+    bd = getattr(scene, "bd", 10)
+    other = np.random.default_rng(seed).integers(0, span or (1 << bd), scene.cur.shape)
+    scene.cur = np.ascontiguousarray((2 * scene.cur.astype(np.int32) - other).astype(np.int16))
+    scene.signed = 1
+    return scene
+
+
+class SaturatedScene(Scene):
+    """A picture pair whose block SADs sit at about w * h * (2^bd - 1) -- what natural pictures never reach: original = bright field (max - noise 0..3) with dark 8x8
+    specks (0 .. 63), reference = dark field (noise 0..3) with bright specks (max - 0 .. 63), w * h / 512 specks per plane, so that candidates still differ.  signed: the
+    original becomes 2*org - other with other in 0..7: the full positive excursion of a bi-pred target of the depth."""
+
+    def __init__(self, w=416, h=240, bit_depth=10, seed=1, signed=False, margin=160):
+        rng = np.random.default_rng(seed)
+        top = (1 << bit_depth) - 1
+        cur = top - rng.integers(0, 4, (h, w))
+        ref = rng.integers(0, 4, (h, w))
+        for plane, bright in ((cur, False), (ref, True)):
+            for _ in range(w * h // 512):
+                x, y = int(rng.integers(0, w - 7)), int(rng.integers(0, h - 7))
+                a = rng.integers(0, 64, (8, 8))
+                plane[y:y + 8, x:x + 8] = top - a if bright else a
+        self.bd, self.W, self.H, self.margin = bit_depth, w, h, margin
+        self.cur = np.ascontiguousarray(cur.astype(np.int16))
+        self.ref_buf, self.ref_off, self.ref_stride = synth.extend_plane(np.ascontiguousarray(ref.astype(np.int16)), margin)
+        if signed:
+            make_signed(self, seed + 1, span=8)
+
+
+BIG = ([128, 128, 64], [128, 128, 64])      # random_*_jobs sizes: 128x128 / 128x64 / 64x128 (and 64x64): the shapes whose distortion alone approaches 2^26 at 12 bits
+
+
+def near_key_limit(jobs, exp_cost, exp_dist, bd, signed):
+    """Floors of a 12-bit saturated-scene test, from the expected results alone: unsigned, the jobs classed "tiny" that end with 2^25 <= cost < 2^26 (the one-word key
+    within a factor of two of its limit); signed, the jobs whose distortion alone is >= 2^26."""
+    if signed:
+        return sum(1 for d in exp_dist if d >= 1 << 26)
+    return sum(1 for j, c in zip(jobs, exp_cost) if key_class(j["w"], j["h"], bd, j["lam"], 0) == "tiny" and (1 << 25) <= c < (1 << 26))
+
+
+def simd_had4_split(j, cfgv, bd):
+    """The one class of xMotionEstimation jobs left out of the saturated-scene comparisons against the REAL member: bi rows of width 4 under the BCW weight -2 with the
+    Hadamard cost at bitDepth <= 10.  Their target -4 * org + 5 * pred differs from the reference block by up to 5 * (2^bd - 1), and the reference's x86 4x4 / 4x8 / 4x16
+    Hadamards for bitDepth <= 10 (16-bit lanes) leave their range there: its scalar xCalcHADs4x4 -- which the oracle equals on every such block -- and its SIMD build return
+    different sums (tests/test_oracle_vs_ref.py::test_width4_hadamard_of_a_weight_m2_target_scalar_is_the_arbiter).  Natural scenes never reach it; nothing wider is left out."""
+    return bool(j["bi"] and j["w"] == 4 and j.get("bcw", 0) == -2 and cfgv[1] and bd <= 10)
 
 
 # ---- SMVD (symmetric MVD search of predInterSearch) -------------------------------------------------------------------------------

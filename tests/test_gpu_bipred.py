@@ -73,12 +73,12 @@ def test_pel_ops_match_reference_golden(ctx):
 
 
 @pytest.mark.parametrize("wpj", [0, 2, 4, 8, 16])
-def test_full_search_matches_oracle(ctx, wpj):
+def test_full_search_matches_oracle(ctx, wpj, bd=10):
     """xSetSearchRange + xPatternSearch around the current vector on the unclipped bi-pred target 2*org - pred."""
     L = ol.oracle()
-    scene = me_util.Scene(416, 240, hard=True)
+    scene = me_util.Scene(416, 240, hard=True) if bd == 10 else me_util.DeepScene(416, 240, hard=True, bit_depth=bd)
     rng = np.random.default_rng(61)
-    tgt = np.ascontiguousarray((2 * scene.cur.astype(np.int32) - rng.integers(0, 1024, scene.cur.shape)).astype(np.int16))
+    tgt = np.ascontiguousarray((2 * scene.cur.astype(np.int32) - rng.integers(0, 1 << bd, scene.cur.shape)).astype(np.int16))
     n = 500
     jobs = (FullJob * n)()
     exp = []
@@ -93,6 +93,8 @@ def test_full_search_matches_oracle(ctx, wpj):
         sr = int(rng.choice([4, 4, 4, 2, 7]))
         jd = dict(w=w, h=h, x=x, y=y, subShift=1 if (h > 8 and w <= 64) else 0, lam=float(rng.uniform(1, 40)),
                   predHor=int(rng.integers(-64, 64)), predVer=int(rng.integers(-64, 64)))
+        if bd != 10:      # the motion lambdas of QP 22 .. 63 at the depth
+            jd["lam"] = me_util.real_lambdas(bd)[k % 5]
         org = np.ascontiguousarray(tgt[y:y + h, x:x + w])
         c = me_util.oracle_ctx(scene, jd, org)
         rg = ol.Range()
@@ -109,7 +111,7 @@ def test_full_search_matches_oracle(ctx, wpj):
     d_org, d_ref = ctx.to_device(tgt), ctx.to_device(scene.ref_buf)
     d_jobs = ctx.to_device(np.frombuffer(jobs, np.uint8))
     d_res = ctx.alloc(32 * n)
-    ctx.full_search_batch(PicParams(416, 240, 128, 10, wpj), d_org.ptr, d_ref.ptr, d_jobs.ptr, n, d_res.ptr)
+    ctx.full_search_batch(PicParams(416, 240, 128, bd, wpj), d_org.ptr, d_ref.ptr, d_jobs.ptr, n, d_res.ptr)
     res = (MeResult * n).from_buffer_copy(d_res.to_host(np.uint8).tobytes())
     got = [(r.mvX, r.mvY, r.cost, r.dist, r.nEval) for r in res]
     bad = [k for k in range(n) if got[k] != exp[k]]
@@ -220,14 +222,27 @@ def test_motion_compensation_fused_matches_oracle(ctx, bd=10):
     assert np.array_equal(d_out2.to_host(np.int16), go)
 
 
+@pytest.mark.parametrize("bd", [8, 12])
+@pytest.mark.parametrize("wpj", [0, 4])
+def test_full_search_matches_oracle_8_12bit(ctx, wpj, bd):
+    """test_full_search_matches_oracle on an 8- / 12-bit picture: the signed pattern spans -(2^bd - 1) .. 2 * (2^bd - 1)"""
+    test_full_search_matches_oracle(ctx, wpj, bd)
+
+
+@pytest.mark.parametrize("bd", [8, 12])
+@pytest.mark.parametrize("size", [8, 32, 64])
+def test_full_search_square_kernel_matches_oracle_8_12bit(ctx, size, bd):
+    test_full_search_square_kernel_matches_oracle(ctx, size, bd)
+
+
 @pytest.mark.parametrize("size", [8, 16, 32, 64])
-def test_full_search_square_kernel_matches_oracle(ctx, size):
+def test_full_search_square_kernel_matches_oracle(ctx, size, bd=10):
     """vtmhip_full_search_square_batch_dev (one lane per candidate over an LDS window): uniform S x S jobs, +-4 and smaller / clipped
     ranges, picture-corner positions, signed bi-pred targets and plain pictures."""
     L = ol.oracle()
-    scene = me_util.Scene(416, 240, hard=True)
+    scene = me_util.Scene(416, 240, hard=True) if bd == 10 else me_util.DeepScene(416, 240, hard=True, bit_depth=bd)
     rng = np.random.default_rng(62 + size)
-    tgt = np.ascontiguousarray((2 * scene.cur.astype(np.int32) - rng.integers(0, 1024, scene.cur.shape)).astype(np.int16))
+    tgt = np.ascontiguousarray((2 * scene.cur.astype(np.int32) - rng.integers(0, 1 << bd, scene.cur.shape)).astype(np.int16))
     for signed, plane in ((1, tgt), (0, scene.cur)):
         n = 700 if size <= 16 else 250
         jobs = (FullJob * n)()
@@ -244,6 +259,8 @@ def test_full_search_square_kernel_matches_oracle(ctx, size):
             sr = int(rng.choice([4, 4, 4, 2, 1, 0, 3]))
             jd = dict(w=w, h=h, x=x, y=y, subShift=1 if (h > 8 and w <= 64) else 0, lam=float(rng.uniform(1, 40)),
                       predHor=int(rng.integers(-64, 64)), predVer=int(rng.integers(-64, 64)))
+            if bd != 10:
+                jd["lam"] = me_util.real_lambdas(bd)[k % 5]
             org = np.ascontiguousarray(plane[y:y + h, x:x + w])
             c = me_util.oracle_ctx(scene, jd, org)
             rg = ol.Range()
@@ -260,7 +277,7 @@ def test_full_search_square_kernel_matches_oracle(ctx, size):
         d_org, d_ref = ctx.to_device(plane), ctx.to_device(scene.ref_buf)
         d_jobs = ctx.to_device(np.frombuffer(jobs, np.uint8))
         d_res = ctx.alloc(32 * n)
-        ctx.full_search_batch(PicParams(416, 240, 128, 10, 0), d_org.ptr, d_ref.ptr, d_jobs.ptr, n, d_res.ptr, square=size)
+        ctx.full_search_batch(PicParams(416, 240, 128, bd, 0), d_org.ptr, d_ref.ptr, d_jobs.ptr, n, d_res.ptr, square=size)
         res = (MeResult * n).from_buffer_copy(d_res.to_host(np.uint8).tobytes())
         got = [(r.mvX, r.mvY, r.cost, r.dist, r.nEval) for r in res]
         bad = [k for k in range(n) if got[k] != exp[k]]

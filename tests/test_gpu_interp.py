@@ -286,3 +286,55 @@ def test_frac_search_tiled_rect_path(ctx, w, h, use_had, signed, bd):
     got = [(r.halfX, r.halfY, r.qterX, r.qterY, r.cost) for r in res]
     bad = [k for k in range(n) if got[k] != exp[k]]
     assert not bad, [(got[k], exp[k]) for k in bad[:5]]
+
+
+def _tiled_case_at_depth(ctx, w, h, use_had, signed, bd):
+    """The tiled (uniform-shape) fractional search on a picture that really has `bd` bits, under the motion lambdas of QP 22 .. 63 at that depth; signed: the target is
+    2*org - pred with pred over the whole range of the depth (-(2^bd - 1) .. 2 * (2^bd - 1): what a bi row of xMotionEstimation hands over)."""
+    L = ol.oracle()
+    scene = me_util.DeepScene(416, 240, hard=True, bit_depth=bd)
+    rng = np.random.default_rng(2000 + 64 * w + h + bd)
+    if signed:
+        me_util.make_signed(scene, 3000 + w + h + bd)
+        assert scene.cur.min() < -(1 << (bd - 1)) and scene.cur.max() > (1 << bd)
+    lams = me_util.real_lambdas(bd)
+    n = max(12, 9000 // (w * h))
+    arr = (FracJob * n)()
+    exp = []
+    for k in range(n):
+        x = int(rng.integers(0, (416 - w) // 4 + 1)) * 4
+        y = int(rng.integers(0, (240 - h) // 4 + 1)) * 4
+        j = dict(w=w, h=h, x=x, y=y, subShift=0, lam=float(lams[k % 5]), predHor=int(rng.integers(-64, 64)), predVer=int(rng.integers(-64, 64)))
+        ix, iy = int(rng.integers(-12, 12)), int(rng.integers(-12, 12))
+        org = np.ascontiguousarray(scene.cur[y:y + h, x:x + w])
+        c = me_util.oracle_ctx(scene, j, org)
+        assert c.bitDepth == bd
+        fr = ol.FracResult()
+        L.vo_frac_search(C.byref(c), ix, iy, use_had, 0, C.byref(fr))
+        exp.append((fr.halfX, fr.halfY, fr.qterX, fr.qterY, fr.cost))
+        t = arr[k]
+        t.orgOff, t.refOff = y * 416 + x, scene.ref_off + y * scene.ref_stride + x
+        t.orgStride, t.refStride, t.width, t.height = 416, scene.ref_stride, w, h
+        t.intX, t.intY, t.predHor, t.predVer, t.motionLambda = ix, iy, j["predHor"], j["predVer"], j["lam"]
+        t.useHad, t.useAltHpelIf, t.imvShift, t.bitDepth = use_had, 0, 0, bd
+    d_cur, d_ref = ctx.to_device(scene.cur), ctx.to_device(scene.ref_buf)
+    d_jobs = ctx.to_device(np.frombuffer(arr, np.uint8))
+    d_res = ctx.alloc(16 * n)
+    ctx.frac_search_batch(d_cur.ptr, d_ref.ptr, d_jobs.ptr, n, w, h, d_res.ptr, uniform_square=True)
+    res = (FracResult * n).from_buffer_copy(d_res.to_host(np.uint8).tobytes())
+    got = [(r.halfX, r.halfY, r.qterX, r.qterY, r.cost) for r in res]
+    bad = [k for k in range(n) if got[k] != exp[k]]
+    assert not bad, (len(bad), n, [(got[k], exp[k]) for k in bad[:5]])
+
+
+@pytest.mark.parametrize("w,h", [(16, 8), (8, 32), (64, 16), (16, 64), (64, 32), (32, 64)])
+@pytest.mark.parametrize("use_had", [1, 0])
+def test_frac_search_tiled_rect_path_on_a_12bit_picture(ctx, w, h, use_had):
+    _tiled_case_at_depth(ctx, w, h, use_had, 0, 12)
+
+
+@pytest.mark.parametrize("bd", [8, 12])
+@pytest.mark.parametrize("use_had", [1, 0])
+@pytest.mark.parametrize("w,h", [(8, 8), (16, 16), (32, 32), (64, 64), (128, 128), (64, 16), (16, 64)])
+def test_frac_search_tiled_paths_signed_target_of_the_depth(ctx, w, h, use_had, bd):
+    _tiled_case_at_depth(ctx, w, h, use_had, 1, bd)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import cpu_pis
+import me_util
 import oracle_lib as ol
 from vtm_amd import pipeline, synth
 from vtm_amd.pipeline import FrameHotPath
@@ -14,11 +15,13 @@ from vtm_amd.pipeline import FrameHotPath
 pytestmark = pytest.mark.gpu
 
 
-def make_scene(torch, dev, W, H, pocs0, pocs1, cur_poc, hard=True, chroma=False):
+def make_scene(torch, dev, W, H, pocs0, pocs1, cur_poc, hard=True, chroma=False, bd=10):
     """-> (cur_np, dpb_np, refs, sr, cur, dpb[, chroma_dev, chroma_cpu]): with chroma=True the original buffer is Y | Cb | Cr, every reference picture's
     extended Cb / Cr planes follow its luma plane in the reference buffer, and the two dicts are FrameHotPath's / cpu_pis.run_pu's `chroma` arguments"""
     nfr = max(pocs0 + pocs1 + [cur_poc]) + 1
     frames = (synth.gen_frames_hard if hard else synth.gen_frames)(W, H, nfr, chroma=chroma)
+    if bd != 10:      # the generator's 10-bit planes at another depth
+        frames = [tuple(me_util.to_bit_depth(p, bd) for p in f) if chroma else me_util.to_bit_depth(f, bd) for f in frames]
     planes, refs, acc = [], ([], []), 0
     refs_c = ([], [])
     cache = {}
@@ -54,20 +57,21 @@ def make_scene(torch, dev, W, H, pocs0, pocs1, cur_poc, hard=True, chroma=False)
     return y, dpb_np, refs, sr, torch.from_numpy(cur_all).to(dev), torch.from_numpy(dpb_np).to(dev), ch_dev, ch_cpu
 
 
-def check(hp, cur_np, dpb_np, refs, sr, W, H, lam, qp, R, per_level=24, min_checked=60, pocs=None, chroma=None, stats=None, affine=False, low_delay=False, smvd=None):
+def check(hp, cur_np, dpb_np, refs, sr, W, H, lam, qp, R, per_level=24, min_checked=60, pocs=None, chroma=None, stats=None, affine=False, low_delay=False, smvd=None, bd=10):
     snaps = hp.snapshot()
     nref = hp.nref
     checked = 0
     dirs = set()
+    qp_off = 6 * (bd - 8)      # QpParam: base QP = QP + 6 * (bitDepth - 8)
     if chroma is not None:
-        cqp = pipeline.chroma_qp(qp) + 12
+        cqp = pipeline.chroma_qp(qp) + qp_off
         chroma = dict(chroma, qp_per=cqp // 6, qp_rem=cqp % 6)
     for li, lvl in enumerate(snaps):
         parent = snaps[lvl["parent_level"]] if lvl["parent_level"] >= 0 else None
         s, npu = lvl["size"], lvl["npu"]
         for i in range(0, npu, max(1, npu // per_level)):
             out = cpu_pis.run_pu(cur_np, dpb_np.ctypes.data, refs, sr, W, H, s, int(lvl["xs"][i]), int(lvl["ys"][i]), cpu_pis.cands_of(lvl, nref, i), lam,
-                                 (qp + 12) // 6, (qp + 12) % 6, lvl["cands"], ref=R, pocs=pocs, chroma=chroma, affine=affine, low_delay=low_delay, smvd=smvd)
+                                 (qp + qp_off) // 6, (qp + qp_off) % 6, lvl["cands"], ref=R, bd=bd, pocs=pocs, chroma=chroma, affine=affine, low_delay=low_delay, smvd=smvd)
             cpu_pis.compare_with_device(lvl, parent, nref, i, out)
             if stats is not None and "smvd" in out:
                 stats["smvd"] = stats.get("smvd", 0) + 1
@@ -140,6 +144,34 @@ def test_frame_hot_path_with_bdof_and_chroma(use_ref, name, pocs0, pocs1, cur, q
     if pocs1:
         assert stats["bio"] >= 5, stats         # BDOF really ran on some of the checked PUs
     assert stats["chroma_nz"] >= 5, stats        # and chroma TUs with non-zero levels were compared
+    ctx.close()
+
+
+@pytest.mark.parametrize("use_ref", [False, True])
+@pytest.mark.parametrize("bd,qp", [(8, 32), (12, 32), (12, 37), (10, 32)])
+def test_frame_hot_path_at_the_depths_lambda(use_ref, bd, qp):
+    """The driver (RA 1 + 1, chroma, BDOF) on 8- / 10- / 12-bit pictures under the motion lambda the reference derives from the slice QP at that depth instead of the other
+    tests' 8.0: 10-bit QP 32 = 31.3 (the benchmark's point); 12-bit QP 32 / 37 = 125.3 / 223.3, either side of 130.03, where the 128x128 integer search leaves its
+    one-word arg-min key; 8-bit QP 32 = 7.8 -- every sampled PU against the CPU chain through the oracle and through the reference's own members."""
+    torch = pytest.importorskip("torch")
+    from vtm_amd.device import Context
+    if use_ref and not ol.have_ref():
+        pytest.skip("oracle/_ref/libvtmref.so not present")
+    W, H = 256, 128
+    dev = torch.device("cuda", 0)
+    pocs0, pocs1, cur = [0], [4], 2
+    cur_np, dpb_np, refs, sr, cur_d, dpb, ch_dev, ch_cpu = make_scene(torch, dev, W, H, pocs0, pocs1, cur, chroma=True, bd=bd)
+    assert 0 <= int(cur_np.min()) and int(cur_np.max()) < (1 << bd) and (bd <= 10 or int(cur_np.max()) > 1023)
+    ctx = Context(0)
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    lam = me_util.motion_lambda(qp, bd)
+    pocs = (cur, pocs0, pocs1)
+    hp = FrameHotPath(ctx, torch, dev, W, H, W, refs, sr, motion_lambda=lam, qp=qp, bit_depth=bd, pocs=pocs, chroma=ch_dev)
+    hp.run(cur_d.data_ptr(), dpb.data_ptr())
+    torch.cuda.synchronize()
+    stats = {}
+    dirs = check(hp, cur_np, dpb_np, refs, sr, W, H, lam, qp, ol.ref() if use_ref else None, per_level=20, min_checked=50, pocs=pocs, chroma=ch_cpu, stats=stats, bd=bd)
+    print("depth:", bd, qp, round(lam, 1), sorted(dirs), stats)
     ctx.close()
 
 

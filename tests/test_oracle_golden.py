@@ -324,3 +324,16 @@ def test_oracle_members_on_real_encoder_records(name, min_rows, min_cached):
             cached += hd.rowCached[row]
     print(name, "rows", rows, "cached", cached)
     assert rows >= min_rows and cached >= min_cached, (rows, cached)
+
+
+@pytest.mark.parametrize("sat", [0, 1])
+@pytest.mark.parametrize("bd", [8, 12])
+def test_motion_search_8_12bit_golden(oracle, bd, sat):
+    """xTZSearch and xMotionEstimation at 8 / 12 bits on a natural and a saturated scene under the lambdas of QP 22 .. 63, recorded from the real members
+    (tests/golden/gen_me_depth_golden.py): the oracle without the reference."""
+    from test_gpu_me_depth_golden import load
+    scene, jobs, exp, _ = load("tz", bd, sat)
+    assert [g[:4] for g in me_util.run_oracle_tz(scene, jobs)] == exp
+    scene, jobs, exp, cfgv = load("mest", bd, sat)
+    got, got_int = me_util.run_oracle_mest(scene, jobs, cfgv)
+    assert [g + ((0, 0) if j["bi"] else i[:2]) for g, i, j in zip(got, got_int, jobs)] == exp

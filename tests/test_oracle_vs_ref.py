@@ -904,3 +904,175 @@ def test_mts_preselection_equals_reference_transformNxN_8_12bit(oracle, reflib, 
 def test_affine_prediction_and_me_equal_reference_members_8_12bit(oracle, reflib, bd):
     """test_affine_prediction_and_me_equal_reference_members at 8 and 12 bits."""
     test_affine_prediction_and_me_equal_reference_members(oracle, reflib, bd)
+
+
+# ---- the motion-search members at 8 / 12 bits, the reference's lambdas up to QP 63, lambdas beyond the device's 32-bit keys, and a saturated scene ---------------------------
+def _tz_ref_equals_oracle(reflib, scene, jobs):
+    exp = []
+    for j in jobs:
+        org = np.ascontiguousarray(scene.cur[j["y"]:j["y"] + j["h"], j["x"]:j["x"] + j["w"]])
+        c, t, r = me_util.oracle_ctx(scene, j, org), me_util.oracle_tz_job(j), ol.MeResult()
+        reflib.ref_tz_search(C.byref(c), C.byref(t), C.byref(r))
+        exp.append((r.mvX, r.mvY, r.cost, r.dist))
+    got = [g[:4] for g in me_util.run_oracle_tz(scene, jobs)]
+    bad = [k for k in range(len(jobs)) if got[k] != exp[k]]
+    assert not bad, (len(bad), [(jobs[k], got[k], exp[k]) for k in bad[:3]])
+    return exp
+
+
+@pytest.mark.parametrize("signed", [0, 1])
+@pytest.mark.parametrize("bd", [8, 12])
+def test_tz_search_equals_reference_xTZSearch_8_12bit(oracle, reflib, bd, signed):
+    """xTZSearch on 8- and 12-bit pictures, plain and 2*org - pred targets, motion lambdas of QP 22 .. 63 at the depth and 6e5 / 2e7 / 3e9."""
+    scene = me_util.DeepScene(416, 240, hard=True, bit_depth=bd)
+    if signed:
+        me_util.make_signed(scene, 40 + bd)
+    jobs = me_util.random_tz_jobs(scene, 300, seed=211 + bd + signed, lams=me_util.real_lambdas(bd) + me_util.EDGE)
+    for j in jobs:
+        j["signed"] = signed
+    cls = me_util.key_classes(jobs, bd)
+    assert min(cls.values()) >= 20, cls
+    _tz_ref_equals_oracle(reflib, scene, jobs)
+
+
+@pytest.mark.parametrize("signed", [0, 1])
+@pytest.mark.parametrize("bd", [8, 10, 12])
+def test_tz_search_equals_reference_xTZSearch_saturated_scene(oracle, reflib, bd, signed):
+    """Block SADs of about w * h * (2^bd - 1); over a third of the jobs 128x128 / 128x64 / 64x128 / 64x64.  At 12 bits the expected costs reach the limit of the device's
+    one-word key (unsigned) and leave it (signed)."""
+    scene = me_util.SaturatedScene(416, 240, bd, seed=60 + bd, signed=bool(signed))
+    jobs = (me_util.random_tz_jobs(scene, 200, seed=221 + bd + signed, lams=me_util.real_lambdas(bd) + me_util.EDGE) +
+            me_util.random_tz_jobs(scene, 150, seed=231 + bd + signed, sizes=me_util.BIG, lams=me_util.real_lambdas(bd)))
+    for j in jobs:
+        j["signed"] = signed
+    assert sum(1 for j in jobs if j["w"] * j["h"] >= 128 * 64) * 3 >= len(jobs)
+    cls = me_util.key_classes(jobs, bd)
+    assert min(cls.values()) >= 20, cls
+    exp = _tz_ref_equals_oracle(reflib, scene, jobs)
+    if bd == 12:
+        assert me_util.near_key_limit(jobs, [e[2] for e in exp], [e[3] for e in exp], bd, signed) >= 10
+
+
+@pytest.mark.parametrize("saturated", [0, 1])
+@pytest.mark.parametrize("bd", [8, 12])
+def test_frac_and_full_search_equal_reference_8_12bit(oracle, reflib, bd, saturated):
+    """xPatternSearchFracDIF and xPatternSearch at 8 / 12 bits: SAD and Hadamard, plain and signed (2*org - pred over the depth's whole range) targets, a natural and a
+    saturated scene, lambdas of QP 22 .. 63."""
+    scene = me_util.SaturatedScene(416, 240, bd, seed=70 + bd) if saturated else me_util.DeepScene(416, 240, hard=True, bit_depth=bd)
+    rng = np.random.default_rng(240 + bd + saturated)
+    lams = me_util.real_lambdas(bd)
+    seen = set()
+    for trial in range(200):
+        w = int(rng.choice([8, 16, 32, 64, 128, 4, 16, 8, 32, 64]))
+        h = int(rng.choice([8, 16, 32, 64, 128, 8, 4, 16]))
+        if w == 4 and h == 4:
+            continue
+        x = int(rng.integers(0, (416 - w) // 4 + 1)) * 4
+        y = int(rng.integers(0, (240 - h) // 4 + 1)) * 4
+        org = np.ascontiguousarray(scene.cur[y:y + h, x:x + w])
+        signed = trial % 3 == 0
+        if signed:   # bi-pred ME target: other prediction over the whole range (natural scene) or dark (saturated: the full positive excursion)
+            org = (2 * org.astype(np.int32) - rng.integers(0, 8 if saturated else 1 << bd, org.shape)).astype(np.int16)
+        j = dict(w=w, h=h, x=x, y=y, subShift=0, lam=float(lams[trial % 5]), predHor=int(rng.integers(-64, 64)), predVer=int(rng.integers(-64, 64)))
+        c = me_util.oracle_ctx(scene, j, org)
+        assert c.bitDepth == bd
+        ix, iy, had = int(rng.integers(-12, 12)), int(rng.integers(-12, 12)), int(trial % 4 != 0)
+        seen.add((signed, had))
+        a, b = ol.FracResult(), ol.FracResult()
+        oracle.vo_frac_search(C.byref(c), ix, iy, had, 0, C.byref(a))
+        reflib.ref_frac_search(C.byref(c), ix, iy, had, 0, C.byref(b))
+        assert (a.halfX, a.halfY, a.qterX, a.qterY, a.cost) == (b.halfX, b.halfY, b.qterX, b.qterY, b.cost), (trial, w, h, signed, had)
+        sr, out = ol.Range(), (C.c_int * 4)()
+        oracle.vo_set_search_range(C.byref(c), ix * 16, iy * 16, 4, C.byref(sr))
+        reflib.ref_set_search_range(C.byref(c), ix * 16, iy * 16, 4, out)
+        assert list(out) == [sr.left, sr.right, sr.top, sr.bottom]
+        c.subShift = 1 if (h > 8 and w <= 64) else 0
+        m, r = ol.MeResult(), ol.MeResult()
+        oracle.vo_full_search(C.byref(c), C.byref(sr), C.byref(m))
+        reflib.ref_full_search(C.byref(c), out, C.byref(r))
+        assert (m.mvX, m.mvY, m.cost, m.dist) == (r.mvX, r.mvY, r.cost, r.dist), (trial, w, h, signed)
+    assert len(seen) == 4
+
+
+@pytest.mark.parametrize("bd", [8, 12])
+@pytest.mark.parametrize("use_had,fen,ext,first_stop", [(1, 1, 0, 1), (0, 1, 0, 0), (1, 0, 1, 1)])
+def test_motion_estimation_equals_reference_xMotionEstimation_8_12bit(oracle, reflib, use_had, fen, ext, first_stop, bd):
+    """Whole xMotionEstimation at 8 / 12 bits under the lambdas of QP 22 .. 63; the bi rows under the default pair and the BCW weights -2 / 3 / 5 / 10 in turn."""
+    scene = me_util.DeepScene(416, 240, hard=True, bit_depth=bd)
+    cfg = ol.MestCfg(4, use_had, fen, ext, first_stop)
+    jobs = me_util.random_mest_jobs(scene, 200, seed=310 + use_had * 4 + fen * 2 + ext + bd, lams=me_util.real_lambdas(bd), bcws=(0, -2, 3, 5, 10))
+    seen, weights = set(), set()
+    for j in jobs:
+        keep = []
+        t = me_util.oracle_mest_job(scene, j, keep)
+        assert t.bitDepth == bd
+        a, b = ol.MestResult(), ol.MestResult()
+        oracle.vo_motion_estimation(C.byref(cfg), C.byref(t), C.byref(a))
+        reflib.ref_motion_estimation(C.byref(cfg), C.byref(t), C.byref(b))
+        assert a.key() == b.key(), (j, a.key(), b.key())
+        if not j["bi"]:
+            assert (a.intX, a.intY) == (b.intX, b.intY)
+        seen.add((j["bi"], j["imv"]))
+        weights.add(j.get("bcw", 0))
+    assert len(seen) == 8 and weights == {0, -2, 3, 5, 10}
+
+
+@pytest.mark.parametrize("bd", [8, 12])
+def test_smvd_members_equal_reference_8_12bit_real_lambdas(oracle, reflib, bd):
+    """xGetSymmetricCost / xSymmetricMotionEstimation / symmvdCheckBestMvp at 8 / 12 bits under the lambdas of QP 22 .. 63 at the depth."""
+    scene = me_util.SmvdScene(416, 240, hard=True, bit_depth=bd)
+    jobs = me_util.draw_lambdas(me_util.random_smvd_jobs(scene, 120, seed=19 + bd), me_util.real_lambdas(bd), 19 + bd)
+    moved = 0
+    for k, j in enumerate(jobs):
+        a, b = me_util.smvd_member_results(scene, j, oracle, "vo_"), me_util.smvd_member_results(scene, j, reflib, "ref_")
+        assert a == b, (k, j, a, b)
+        moved += a[1][0] != tuple(j["starts"][0])
+    assert moved > 20, moved
+
+
+@pytest.mark.parametrize("bd", [8, 10, 12])
+def test_width4_hadamard_of_a_weight_m2_target_scalar_is_the_arbiter(oracle, reflib, bd):
+    """4-wide SATD of a saturated bi-pred target under the BCW weight -2 (-4 * org + 5 * pred, up to 5 * (2^bd - 1) from the reference block): the oracle equals the
+    reference's scalar xGetHADs on every block.  The reference's own SIMD table entry (16-bit lanes for bitDepth <= 10) does not equal its scalar form there -- 433 / 2 181
+    of 4 000 blocks at 8 / 10 bits when this was written -- which is why me_util.simd_had4_split leaves that class out of the saturated-scene xMotionEstimation pins;
+    at 12 bits (32-bit SIMD path) the three agree."""
+    rng = np.random.default_rng(40 + bd)
+    top = (1 << bd) - 1
+    split = 0
+    for t in range(1500):
+        w, h = 4, int(rng.choice([4, 8, 16]))
+        org, pred, ref = top - rng.integers(0, 4, (h, w)), rng.integers(0, 4, (h, w)), rng.integers(0, 4, (h, w))
+        m = rng.integers(0, 2, (h, w)) * (t % 2)                 # specks: dark in the original, bright in the other list's prediction
+        org, pred = np.where(m, rng.integers(0, 64, (h, w)), org), np.where(m, top - rng.integers(0, 64, (h, w)), pred)
+        ref = np.where(rng.integers(0, 2, (h, w)) * (t % 3 == 0), top - rng.integers(0, 64, (h, w)), ref)
+        tgt, cur = ol.i16(-4 * org + 5 * pred), ol.i16(ref)
+        scalar, simd, mine = ol.r_dist(1, 0, tgt, cur, w, h, bd), ol.r_dist(1, 1, tgt, cur, w, h, bd), ol.o_dist(1, tgt, cur, w, h)
+        assert mine == scalar, (t, h, mine, scalar, simd)
+        split += simd != scalar
+    assert bd <= 10 or split == 0
+    print("width-4 Hadamard, weight -2 target, %d bits: SIMD != scalar on %d of 1500 blocks" % (bd, split))
+
+
+@pytest.mark.parametrize("bd", [8, 10, 12])
+@pytest.mark.parametrize("use_had,fen,ext,first_stop", [(1, 1, 0, 1), (0, 1, 0, 0)])
+def test_motion_estimation_equals_reference_xMotionEstimation_saturated_scene(oracle, reflib, use_had, fen, ext, first_stop, bd):
+    """Whole xMotionEstimation on the saturated scene: every shape + a list of 4-wide blocks, bi rows under the default pair and the BCW weights -2 / 3 / 5 / 10; only
+    the class of me_util.simd_had4_split (where the reference's own two builds disagree) is left out."""
+    scene = me_util.SaturatedScene(416, 240, bd, seed=60 + bd)
+    cfgv = (4, use_had, fen, ext, first_stop)
+    cfg = ol.MestCfg(*cfgv)
+    lams = me_util.real_lambdas(bd)
+    jobs = (me_util.random_mest_jobs(scene, 200, seed=330 + bd + use_had, lams=lams, bcws=(0, -2, 3, 5, 10)) +
+            me_util.random_mest_jobs(scene, 100, seed=340 + bd + use_had, sizes=([4], [8, 16, 32, 64, 128]), lams=lams, bcws=(-2, 3, -2, 10)))
+    left_out = [j for j in jobs if me_util.simd_had4_split(j, cfgv, bd)]
+    jobs = [j for j in jobs if not me_util.simd_had4_split(j, cfgv, bd)]
+    assert all(j["w"] == 4 and j["bcw"] == -2 for j in left_out) and (len(left_out) > 0) == bool(use_had and bd <= 10)
+    for j in jobs:
+        keep = []
+        t = me_util.oracle_mest_job(scene, j, keep)
+        a, b = ol.MestResult(), ol.MestResult()
+        oracle.vo_motion_estimation(C.byref(cfg), C.byref(t), C.byref(a))
+        reflib.ref_motion_estimation(C.byref(cfg), C.byref(t), C.byref(b))
+        assert a.key() == b.key(), (j, a.key(), b.key())
+    assert sum(1 for j in jobs if j["bi"] and j["w"] == 4 and j.get("bcw", 0) in (3, 10)) >= 10      # 4-wide weighted rows outside the class stay in
+    assert sum(1 for j in jobs if j["bi"] and j.get("bcw", 0) == -2) >= (10 if bd == 12 or not use_had else 5)

@@ -2160,6 +2160,7 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
   MeFuse fuNone; memset( &fuNone, 0, sizeof( fuNone ) );
   const MeFuse fuFirst = fuse ? *fuse : fuNone;      // the first launch (mode 0 / 1) builds the records; the resume launch (mode 2) reads the stored ones
   VTMHIP_REQUIRE( ctx, pic->picW > 0 && pic->picH > 0 && pic->ctuSize > 0, "picture parameters" );
+  VTMHIP_REQUIRE( ctx, pic->bitDepth >= 8 && pic->bitDepth <= 12, "bit depth out of range" );      // (MeJob::tiny is derived from it)
   // wavesPerJob: tuning hint for the whole batch (0 / 1: a wave per search -- small blocks, short candidate lists;
   // 2..16: that many waves split every candidate list -- large blocks, raster scans)
   const int wpj = pic->wavesPerJob;
@@ -2300,6 +2301,7 @@ int vtmhip_internal_full_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, 
   VTMHIP_REQUIRE( ctx, pic && n >= 0, "pic / n" );
   if( n == 0 ) return VTMHIP_OK;
   VTMHIP_REQUIRE( ctx, d_orgBase && d_refBase && ( d_jobs || fuse ) && d_results, "null pointer" );
+  VTMHIP_REQUIRE( ctx, pic->bitDepth >= 8 && pic->bitDepth <= 12, "bit depth out of range" );
   FullFuse fu; memset( &fu, 0, sizeof( fu ) );
   if( fuse ) fu = *fuse;
   if( width && height && ( !fuse || ( fuse->noStart && fuse->bipredSearchRange <= 4 ) ) )

@@ -346,6 +346,7 @@ extern "C" int vtmhip_xMotionEstimation_batch_dev( vtmhip_ctx *ctx, const vtmhip
   VTMHIP_REQUIRE( ctx, n >= 0, "n" );
   if( n == 0 ) return VTMHIP_OK;
   VTMHIP_REQUIRE( ctx, pic && cfg && d_orgBase && d_refBase && d_jobs && d_results, "null pointer" );
+  VTMHIP_REQUIRE( ctx, pic->bitDepth >= 8 && pic->bitDepth <= 12, "bit depth out of range" );      // (the fractional jobs' shifts and offsets, the integer search's keys)
   // mixed shapes, enough jobs to fill launches per class: bucket by shape (VTMHIP_MEST_BUCKET=0 keeps the one-wave-per-PU chain for the whole batch)
   static const bool bucket = !( getenv( "VTMHIP_MEST_BUCKET" ) && atoi( getenv( "VTMHIP_MEST_BUCKET" ) ) == 0 );
   if( bucket && !cfg->uniformSquare && n >= 64 && bucket_allowed( ctx ) )   // (not under hipGraph capture: the bucketing synchronises the stream once)
@@ -363,6 +364,7 @@ int mest_run( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const vtmhip_me_cfg
   VTMHIP_REQUIRE( ctx, n >= 0, "n" );
   if( n == 0 ) return VTMHIP_OK;
   VTMHIP_REQUIRE( ctx, pic && cfg && d_orgBase && d_refBase && d_jobs && d_results, "null pointer" );
+  VTMHIP_REQUIRE( ctx, pic->bitDepth >= 8 && pic->bitDepth <= 12, "bit depth out of range" );
   VTMHIP_REQUIRE( ctx, maxWidth >= 4 && maxWidth <= 128 && maxHeight >= 4 && maxHeight <= 128, "maxWidth / maxHeight" );
   VTMHIP_REQUIRE( ctx, cfg->uniformImv >= -1 && cfg->uniformImv <= 3, "uniformImv" );
   VTMHIP_REQUIRE( ctx, cfg->bipredSearchRange >= 0 && cfg->bipredSearchRange <= 64, "bipredSearchRange" );
