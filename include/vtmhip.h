@@ -772,6 +772,87 @@ int vtmhip_mts_select_batch_dev( vtmhip_ctx *ctx, const vtmhip_tu_result *d_resu
 int vtmhip_xT_uniform_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int width, int height, int32_t *d_coefBase,
                                  vtmhip_tu_result *d_results );
 
+/* ---- joint Cb-Cr residual coding (JCCR / ICT): TrQuant::m_fwdICT[-3..3] / m_invICT[-3..3] and the joint chroma candidate ---------------
+ * (CommonLib/TrQuant.cpp:86-157 fwdTransformCbCr / invTransformCbCr, :619-687 fwdTransformICT / invTransformICT / selectICTCandidates;
+ * g_ictModes Rom.cpp:527; TU::getICTMode UnitTools.cpp:3825; callers InterSearch.cpp:6813-7032 and IntraSearch::xRecurIntraChromaCodingQT.)
+ *   mode = g_ictModes[signFlag][cbfMask] = { { 0, 3, 1, 2 }, { 0, -3, -1, -2 } };  s = mode < 0 ? -1 : 1;  `/` truncates toward zero, Pel() wraps to
+ *   int16, `>>` is arithmetic:
+ *     +-1: c = Pel( (4 cb + s 2 cr) / 5 )                      d1 += (cb - c)^2 + (cr - ((s c) >> 1))^2      inverse: cr = (s cb) >> 1
+ *     +-2: c = Pel( (cb + s cr) / 2 )                          d1 += (cb - c)^2 + (cr - s c)^2               inverse: cr = cb;  -2: cr = cb == -32768 ? 32767 : -cb
+ *     +-3: c = Pel( (4 cr + s 2 cb) / 5 ), stored in the Cr block  d1 += (cb - ((s c) >> 1))^2 + (cr - c)^2  inverse: cb = (s cr) >> 1
+ *       0: no joint residual; d1 = sum cb^2, d2 = sum cr^2
+ *   The coded component is Cb for cbfMask 2 and 3 and Cr for cbfMask 1.  Sums are int64.
+ * Sample range: the entries take ANY int16 residual (the Pel wrap is part of the rule).  Encoder residuals lie within +-(2^bitDepth - 1), which makes a joint
+ * residual of modes +-1 / +-3 reach 6 (2^bitDepth - 1) / 5 (1227 at 10 bits, 4914 at 12) -- outside the +-(2^bitDepth - 1) vtmhip_tu_job documents for xT.  The
+ * joint chain holds for it on all three launch paths, and for every int16 joint residual: the generic and the one-lane kernels accumulate in 32 bits as the
+ * reference does; the register-blocked kernel's packed first pass multiplies int16 pairs into a 32-bit accumulator (|sum| <= 64 * 32768 * 90 < 2^31) and its
+ * output stays below sum|m| * 32768 >> (log2 N + bitDepth - 9) <= 2^22, inside the 24-bit multiplies of the second pass.
+ * Out of scope: LMCS chroma residual scaling around the ICT (scaleSignal, InterSearch.cpp:6838-6842, 6978-6982), ACT, the picture-level sign decision
+ * (EncSlice::setJointCbCrModes: the caller passes signFlag), the CABAC estimate, the level-order picture driver, a host C++ mirror. */
+
+/* (*m_fwdICT[mode])( resCb, resCr, resC1, resC2 ) on host pointers, staged like vtmhip_xGetSAD; mode -3 .. 3, width / height 1 .. 64.  The joint residual goes
+ * to c1 (modes +-1, +-2) or c2 (modes +-3); the other block -- both for mode 0 -- is not written and may be NULL.  dist = { d1, d2 }. */
+int vtmhip_fwdTransformCbCr( vtmhip_ctx *ctx, int mode, const int16_t *cb, int cbStride, const int16_t *cr, int crStride, int16_t *c1, int c1Stride,
+                             int16_t *c2, int c2Stride, int width, int height, int64_t dist[2] );
+/* (*m_invICT[mode])( resCb, resCr ), in place on host pointers */
+int vtmhip_invTransformCbCr( vtmhip_ctx *ctx, int mode, int16_t *cb, int cbStride, int16_t *cr, int crStride, int width, int height );
+
+typedef struct
+{
+  int64_t cbOff, crOff;         /* the Cb / Cr residual blocks inside d_resiBase */
+  int64_t outOff;               /* the joint residual of cbfMask m (W x H contiguous) goes to d_jointBase + outOff + (m - 1) * W * H */
+  int32_t cbStride, crStride;
+  int16_t width, height;        /* 1 .. 64 */
+  uint8_t signFlag;             /* picHeader.getJointCbCrSignFlag() */
+  uint8_t maskBits;             /* bit m (m = 1 .. 3) set: write the joint residual of cbfMask m */
+  uint8_t pad0, pad1;
+} vtmhip_ict_job;
+
+/* TrQuant::fwdTransformICT for cbfMask 0 .. 3 of n (Cb, Cr) pairs -- the loop of selectICTCandidates (:648-658): d_dist[i][m] = { d1, d2 } of cbfMask m
+ * (int64 [n][4][2]) and the requested joint residual planes.  d_jointBase may be NULL when no job asks for a plane. */
+int vtmhip_ict_fwd_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_ict_job *d_jobs, int n, int16_t *d_jointBase, int64_t *d_dist );
+
+/* TrQuant::selectICTCandidates' decision from the four distance pairs (host arithmetic, no device): an inter CU tests { 3 }; an intra CU the best cbfMask whose
+ * d1 beats min( d1[0], d2[0] ) and the runner-up within 9 / 8 of it (3 / 2 when no mask won), integer arithmetic as :660-686.  masks: the cbfMasks to test in
+ * the reference's order, *numMasks of them (0 .. 2). */
+int vtmhip_ict_select( const int64_t dist[4][2], int isIntra, int masks[2], int *numMasks );
+
+typedef struct
+{
+  int64_t cbOff, crOff;     /* the ORIGINAL Cb / Cr residual blocks inside d_resiBase (one stride: both come from the same residual buffer) */
+  int64_t outOff;           /* W x H contiguous block inside d_levelsBase / d_recCbBase / d_recCrBase (where those are given) */
+  int32_t resiStride;
+  int16_t width, height;    /* 2..64 */
+  int16_t qpPer, qpRem;     /* QpParam( tu, codeCompId ).per / rem (Quant.cpp:112-125: the JOINT_CbCr offsets and table when |mode| == 2); the device does not derive it */
+  uint8_t typeHor;          /* VTMHIP_DCT2 (DCT2 / DCT2) or VTMHIP_TRSKIP (both sides <= 32; qpPer / qpRem = per( true ) / rem( true )) */
+  uint8_t bitDepth;         /* 8..12 */
+  uint8_t isIRAP;
+  uint8_t cbfMask;          /* tu.jointCbCr: 1 .. 3 */
+  uint8_t signFlag;         /* picHeader.getJointCbCrSignFlag() */
+  uint8_t pad[7];
+} vtmhip_jccr_job;
+
+typedef struct
+{
+  uint64_t sseCb, sseCr;    /* getDistPart( DF_SSE ) of the ORIGINAL Cb / Cr residual against the block the inverse ICT rebuilt (InterSearch.cpp:6910-6998) */
+  int64_t  fwdDist;         /* d1 of the job's mode (the forward ICT's own distance) */
+  int32_t  sumAbs;          /* sum |coef| of the joint residual after xT (transform skip: sum |joint residual|) */
+  int32_t  absSum;          /* uiAbsSum of Quant::quant on the coded component */
+} vtmhip_jccr_result;
+
+/* The joint chroma candidate of xEstimateInterResidualQT, one launch, nothing through global memory in between: per job load Cb and Cr once, forward ICT of the
+ * job's mode, xT -> Quant::quant -> Quant::dequant -> xIT (or the transform-skip copies) on the joint residual with the arithmetic of vtmhip_tu_chain_batch_dev,
+ * inverse ICT, both SSEs.  Zero levels need no special case (they reconstruct zero and the inverse ICT of zero is zero).  d_levelsBase (levels of the coded
+ * component), d_recCbBase and d_recCrBase may be NULL.  uniformSize as in vtmhip_tu_chain_batch_dev: every job exactly maxWidth x maxHeight with VTMHIP_DCT2 ->
+ * one lane per pair (4x4, 8x4, 4x8) or the register-blocked kernel (power-of-two sides >= 8); 0: any mix, sides 2..64, on the generic LDS kernel.
+ * The job table is read back (n * 48 bytes, one stream synchronisation) and checked on the host before anything is launched: a cbfMask outside 1 .. 3, a
+ * typeHor other than the two above, transform skip on a side > 32, a size outside 2 .. maxWidth / maxHeight or (uniformSize) a job of another shape or with
+ * transform skip return VTMHIP_E_INVALID and launch nothing.  n == 0 is VTMHIP_OK. */
+int vtmhip_jccr_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
+                                 int32_t *d_levelsBase, int16_t *d_recCbBase, int16_t *d_recCrBase, vtmhip_jccr_result *d_results );
+
+int vtmhip_jccr_struct_size( int which );   /* sizeof() of 0 vtmhip_ict_job, 1 vtmhip_jccr_job, 2 vtmhip_jccr_result; -1 otherwise (vtmhip_struct_size keeps its list) */
+
 /* ---- affine ME gradients: AffineGradientSearch::m_HorizontalSobelFilter / m_VerticalSobelFilter / m_EqualCoeffComputer -----------
  * (AffineGradientSearch.h:50-54, AffineGradientSearch.cpp:62-170; caller xAffineMotionEstimation, InterSearch.cpp:5340-5775) */
 typedef struct

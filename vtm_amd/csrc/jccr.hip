@@ -1,0 +1,898 @@
+// jccr.hip -- joint Cb-Cr residual coding (JCCR / ICT): the forward / inverse inter-component transform and the joint chroma candidate of the residual loop.
+//
+// Reference: CommonLib/TrQuant.cpp fwdTransformCbCr / invTransformCbCr :86-157 (the tables m_fwdICT / m_invICT[-3..3] :166-181), fwdTransformICT /
+// invTransformICT / selectICTCandidates :619-687; g_ictModes CommonLib/Rom.cpp:527; TU::getICTMode CommonLib/UnitTools.cpp:3825; the joint loop of
+// xEstimateInterResidualQT, EncoderLib/InterSearch.cpp:6813-7032 (forward ICT :6851, transformNxN on the coded component :6884-6890, invTransformNxN +
+// invTransformICT :6964-6975, DF_SSE of Cb and Cr against the original residuals :6984-6998).
+//
+// The chain kernels repeat the arithmetic of the single-component chain (transform.hip tu_chain_kernel / tu_chain_lane_kernel / tu_chain_uni_kernel, same
+// order of the integer operations) between a forward ICT at the load and an inverse ICT + two SSEs at the end; chroma joint candidates are DCT2 / DCT2 or
+// transform skip, so only the DCT-2 matrices are staged.  transform.hip itself is untouched.
+//
+// Headroom: a joint residual is a Pel, so every path takes the whole int16 range.  The generic and the lane kernel multiply and accumulate in 32 bits like the
+// reference.  The register-blocked kernel keeps the int16-packed first pass: v_dot2 of int16 pairs into a 32-bit accumulator is exact for |sum| <= N * 32768 *
+// 90 < 2^31 (N <= 64), and the pass's output is bounded by sum|m| * 32768 >> (log2 N + bitDepth - 9) <= 64 N * 2^15 >> (log2 N + bitDepth - 9) = 2^(30 - bitDepth)
+// <= 2^22 for bitDepth >= 8, inside the signed 24-bit operands of the second pass.  The residuals an encoder produces stay far below: 6 (2^bitDepth - 1) / 5.
+//
+// Out of scope: LMCS chroma residual scaling (scaleSignal), ACT, the picture-level sign decision (the caller passes signFlag), the CABAC estimate.
+#include "ctx.hpp"
+
+namespace
+{
+
+struct DctTabs { const int16_t *m[7]; };   // [log2 N] -> device pointer to the N x N forward DCT-2 matrix (row-major)
+
+__constant__ int c_jqScales[2][6]    = { { 26214, 23302, 20560, 18396, 16384, 14564 }, { 18396, 16384, 14564, 13107, 11651, 10280 } };   // g_quantScales, Rom.cpp:463-473
+__constant__ int c_jqInvScales[2][6] = { { 40, 45, 51, 57, 64, 72 }, { 57, 64, 72, 80, 90, 102 } };
+
+__device__ __forceinline__ int ilog2( int v ) { return 31 - __clz( v ); }
+__device__ __forceinline__ int zero_out( int n ) { return n > 32 ? n - 32 : 0; }   // DCT-2: the columns / rows past 32 (TrQuant.cpp:792-796)
+
+// ---- the ICT rules ---------------------------------------------------------------------------------------------------------------------------------
+__host__ __device__ __forceinline__ int ict_abs_mode( int cbfMask ) { return cbfMask == 1 ? 3 : cbfMask - 1; }   // |g_ictModes[.][cbfMask]|, cbfMask 1 .. 3
+
+// the joint residual of one sample: C++ division (toward zero), then the Pel wrap
+__device__ __forceinline__ int ict_fwd( int am, int s, int cb, int cr )
+{
+  const int v = am == 1 ? ( 4 * cb + s * 2 * cr ) / 5 : am == 2 ? ( cb + s * cr ) / 2 : ( 4 * cr + s * 2 * cb ) / 5;
+  return ( int ) ( int16_t ) v;
+}
+
+// the component the decoder derives from the coded one (v: a Pel)
+__device__ __forceinline__ int ict_inv( int am, int s, int v )
+{
+  if( am == 2 ) return s > 0 ? v : ( v == -32768 ? 32767 : -v );   // the non-normative clip of mode -2
+  return ( s * v ) >> 1;
+}
+
+__device__ __forceinline__ long long ict_dist( int am, int s, int cb, int cr, int c )
+{
+  const int       o  = am == 2 ? s * c : ( s * c ) >> 1;   // (the forward distance of mode -2 knows no clip: square( crx + c1 ))
+  const long long e0 = am == 3 ? cb - o : cb - c, e1 = am == 3 ? cr - c : cr - o;
+  return e0 * e0 + e1 * e1;
+}
+
+// one reconstructed sample v of the coded component: both rebuilt blocks and both squared errors against the original residuals
+__device__ __forceinline__ void jccr_finish( int am, int s, int v, int cb, int cr, int16_t *recCb, int16_t *recCr, long i, long long &sseCb, long long &sseCr )
+{
+  const int o = ict_inv( am, s, v ), rb = am == 3 ? o : v, rr = am == 3 ? v : o;
+  if( recCb ) recCb[i] = ( int16_t ) rb;
+  if( recCr ) recCr[i] = ( int16_t ) rr;
+  const int db = cb - rb, dr = cr - rr;
+  sseCb += ( long long ) ( unsigned long long ) ( ( unsigned ) db * ( unsigned ) db );
+  sseCr += ( long long ) ( unsigned long long ) ( ( unsigned ) dr * ( unsigned ) dr );
+}
+
+// ---- Quant::quant + Quant::dequant of one coefficient, flat scaling list (Quant.cpp:955-1038, 357-482), as tu_chain_kernel has them ---------------------
+struct QParams { long long add; int qBits, scale, iscale, rightShift, inMin, inMax; };
+
+__device__ __forceinline__ QParams q_params( const vtmhip_jccr_job &j, int lw, int lh, bool ts )
+{
+  const int needSqrt = ts ? 0 : ( lw + lh ) & 1;
+  const int trShift  = ts ? 0 : 15 - j.bitDepth - ( ( lw + lh ) >> 1 ) + ( needSqrt ? -1 : 0 );
+  QParams   p;
+  p.qBits      = 14 + j.qpPer + trShift;
+  p.add        = ( long long ) ( j.isIRAP ? 171 : 85 ) << ( p.qBits - 9 );
+  p.scale      = c_jqScales[needSqrt][j.qpRem];
+  p.iscale     = c_jqInvScales[needSqrt][j.qpRem];
+  p.rightShift = 6 - ( trShift + j.qpPer );
+  const int inBits = min( 16, 32 + p.rightShift - 7 );
+  p.inMin = -( 1 << ( inBits - 1 ) );
+  p.inMax = ( 1 << ( inBits - 1 ) ) - 1;
+  return p;
+}
+
+__device__ __forceinline__ int q_level( const QParams &p, int c, long long &absSum )
+{
+  const long long tt  = ( long long ) abs( c ) * p.scale;
+  const int       mag = ( int ) ( ( tt + p.add ) >> p.qBits );
+  absSum += mag;
+  return min( 32767, max( -32768, c < 0 ? -mag : mag ) );
+}
+
+__device__ __forceinline__ int q_dequant( const QParams &p, int q )
+{
+  const int qq = min( p.inMax, max( p.inMin, q ) );
+  int       v;
+  if( p.rightShift > 0 ) v = ( int ) ( ( unsigned ) ( qq * p.iscale ) + ( 1u << ( p.rightShift - 1 ) ) ) >> p.rightShift;
+  else v = ( int ) ( ( unsigned ) ( qq * p.iscale ) << ( -p.rightShift ) );
+  return min( 32767, max( -32768, v ) );
+}
+
+// ---- forward ICT of all four cbfMasks: one wave per (Cb, Cr) pair --------------------------------------------------------------------------------------
+__global__ __launch_bounds__( 256 ) void ict_fwd_kernel( const int16_t *__restrict__ resiBase, const vtmhip_ict_job *__restrict__ jobs, int n,
+                                                        int16_t *__restrict__ jointBase, long long *__restrict__ dist )
+{
+  const int lane = threadIdx.x & 63, job = blockIdx.x * 4 + ( threadIdx.x >> 6 );
+  if( job >= n ) return;
+  const vtmhip_ict_job j = jobs[job];
+  const int      w = j.width, h = j.height, s = j.signFlag ? -1 : 1;
+  const int16_t *cb = resiBase + j.cbOff, *cr = resiBase + j.crOff;
+  int16_t       *out = jointBase ? jointBase + j.outOff : nullptr;
+  long long      d[5] = { 0, 0, 0, 0, 0 };   // sum cb^2, sum cr^2, d1 of cbfMask 1, 2, 3
+  for( int i = lane; i < w * h; i += 64 )
+  {
+    const int y = i / w, x = i - y * w;
+    const int b = cb[( long ) y * j.cbStride + x], r = cr[( long ) y * j.crStride + x];
+    d[0] += ( long long ) b * b;
+    d[1] += ( long long ) r * r;
+#pragma unroll
+    for( int m = 1; m <= 3; m++ )
+    {
+      const int am = ict_abs_mode( m ), c = ict_fwd( am, s, b, r );
+      d[1 + m] += ict_dist( am, s, b, r, c );
+      if( out && ( ( j.maskBits >> m ) & 1 ) ) out[( long ) ( m - 1 ) * w * h + i] = ( int16_t ) c;
+    }
+  }
+#pragma unroll
+  for( int k = 0; k < 5; k++ ) d[k] = ( long long ) wave_reduce_add_u64( ( unsigned long long ) d[k] );
+  if( lane == 0 )
+  {
+    long long *o = dist + ( long ) job * 8;
+    o[0] = d[0]; o[1] = d[1];
+    o[2] = d[2]; o[3] = 0;
+    o[4] = d[3]; o[5] = 0;
+    o[6] = d[4]; o[7] = 0;
+  }
+}
+
+// inverse ICT in place on two contiguous blocks (the pointer entry)
+__global__ __launch_bounds__( 256 ) void ict_inv_kernel( int16_t *__restrict__ cb, int16_t *__restrict__ cr, int count, int am, int s )
+{
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if( i >= count ) return;
+  if( am == 3 ) cb[i] = ( int16_t ) ict_inv( am, s, cr[i] );
+  else cr[i] = ( int16_t ) ict_inv( am, s, cb[i] );
+}
+
+// ---- the joint chain, generic path: everything in LDS, TPT threads per pair (64: four independent pairs per workgroup, wave-level synchronisation only;
+// 256: one pair per workgroup) -- tu_chain_kernel between the two ICTs ---------------------------------------------------------------------------------
+template<int TPT>
+__device__ __forceinline__ void jc_sync()
+{
+  if( TPT <= 64 ) { __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" ); __builtin_amdgcn_wave_barrier(); }
+  else __syncthreads();
+}
+
+struct JccrSums { long long sumAbs, absSum, sseCb, sseCr, fwdDist; };
+
+__device__ __forceinline__ vtmhip_jccr_result jccr_result_of( const JccrSums &a )
+{
+  vtmhip_jccr_result r;
+  r.sseCb = ( uint64_t ) a.sseCb; r.sseCr = ( uint64_t ) a.sseCr; r.fwdDist = a.fwdDist; r.sumAbs = ( int32_t ) a.sumAbs; r.absSum = ( int32_t ) a.absSum;
+  return r;
+}
+
+// the five sums over the TPT threads of a pair (TPT > 64: across its waves through sRed)
+template<int TPT>
+__device__ __forceinline__ void jccr_reduce_store( JccrSums a, long long ( *sRed )[5], int sub, int t, bool live, vtmhip_jccr_result *out )
+{
+  long long v[5] = { a.sumAbs, a.absSum, a.sseCb, a.sseCr, a.fwdDist };
+  if( TPT <= 64 )
+  {
+#pragma unroll
+    for( int o = 32; o > 0; o >>= 1 )
+      if( o < TPT )
+      {
+#pragma unroll
+        for( int k = 0; k < 5; k++ ) v[k] += __shfl_xor( v[k], o, 64 );
+      }
+    if( t == 0 && live ) { const JccrSums r = { v[0], v[1], v[2], v[3], v[4] }; *out = jccr_result_of( r ); }
+    return;
+  }
+#pragma unroll
+  for( int k = 0; k < 5; k++ ) v[k] = ( long long ) wave_reduce_add_u64( ( unsigned long long ) v[k] );
+  __syncthreads();
+  if( ( threadIdx.x & 63 ) == 0 )
+  {
+#pragma unroll
+    for( int k = 0; k < 5; k++ ) sRed[threadIdx.x >> 6][k] = v[k];
+  }
+  __syncthreads();
+  constexpr int WPT = TPT > 64 ? TPT / 64 : 1;   // waves per pair
+  if( t == 0 && live )
+  {
+    long long r[5] = { 0, 0, 0, 0, 0 };
+    for( int q = 0; q < WPT; q++ )
+#pragma unroll
+      for( int k = 0; k < 5; k++ ) r[k] += sRed[sub * WPT + q][k];
+    const JccrSums rs = { r[0], r[1], r[2], r[3], r[4] };
+    *out = jccr_result_of( rs );
+  }
+}
+
+template<int TPT>
+__global__ __launch_bounds__( 256 ) void jccr_chain_kernel( const int16_t *__restrict__ resiBase, const vtmhip_jccr_job *__restrict__ jobs, int numJobs, DctTabs tabs,
+                                                           int *__restrict__ levelsBase, int16_t *__restrict__ recCbBase, int16_t *__restrict__ recCrBase,
+                                                           vtmhip_jccr_result *__restrict__ results, int maxW, int maxH )
+{
+  extern __shared__ __attribute__( ( aligned( 16 ) ) ) int ldsw[];
+  __shared__ long long sRed[4][5];
+  constexpr int TUS = 256 / TPT;
+  const int     sub = TPT == 64 ? ( int ) ( threadIdx.x >> 6 ) : 0, t = TPT == 64 ? ( int ) ( threadIdx.x & 63 ) : ( int ) threadIdx.x;
+  const int     jobIdx = blockIdx.x * TUS + sub;
+  if( jobIdx >= numJobs ) return;   // TPT == 64: whole waves leave; TPT == 256: grid == numJobs
+  const vtmhip_jccr_job j = jobs[jobIdx];
+  const int      w = j.width, h = j.height, bd = j.bitDepth;
+  const int      mx = maxW > maxH ? maxW : maxH;
+  const int      perTu = maxW * maxH + maxW * ( maxH + 1 ) + ( ( mx * mx + 1 ) >> 1 );   // ints
+  int           *blk = ldsw + sub * perTu;            // [h][w] joint residual -> coefficients -> dequantised coefficients
+  int           *tmp = blk + maxW * maxH;             // [w][h+1] / [w][h]
+  int16_t       *sM  = ( int16_t * ) ( tmp + maxW * ( maxH + 1 ) );
+  const int16_t *cbp = resiBase + j.cbOff, *crp = resiBase + j.crOff;
+  const int      am = ict_abs_mode( j.cbfMask ), s = j.signFlag ? -1 : 1;
+  int           *levels = levelsBase ? levelsBase + j.outOff : nullptr;
+  int16_t       *recCb = recCbBase ? recCbBase + j.outOff : nullptr, *recCr = recCrBase ? recCrBase + j.outOff : nullptr;
+  JccrSums       a = { 0, 0, 0, 0, 0 };
+  // load Cb and Cr once: the joint residual of the job's mode and its own distance
+  for( int i = t; i < w * h; i += TPT )
+  {
+    const int  y = i / w, x = i - y * w;
+    const long o = ( long ) y * j.resiStride + x;
+    const int  cb = cbp[o], cr = crp[o], c = ict_fwd( am, s, cb, cr );
+    a.fwdDist += ict_dist( am, s, cb, cr, c );
+    blk[i] = c;
+  }
+  const int  lw = ilog2( w ), lh = ilog2( h );
+  const bool ts = j.typeHor == VTMHIP_TRSKIP;
+  const int  skipW = ts ? 0 : zero_out( w ), skipH = ts ? 0 : zero_out( h );
+  jc_sync<TPT>();
+  if( ts )
+  {
+    // xTransformSkip / xITransformSkip are plain copies: quantise the joint residual itself, without transform shift or sqrt(2) compensation
+    const QParams qp = q_params( j, lw, lh, true );
+    for( int i = t; i < w * h; i += TPT )
+    {
+      const int c = blk[i];
+      a.sumAbs += abs( c );
+      const int q = q_level( qp, c, a.absSum );
+      if( levels ) levels[i] = q;
+      const int  y = i / w, x = i - y * w;
+      const long o = ( long ) y * j.resiStride + x;
+      jccr_finish( am, s, ( int ) ( int16_t ) q_dequant( qp, q ), cbp[o], crp[o], recCb, recCr, i, a.sseCb, a.sseCr );
+    }
+  }
+  else
+  {
+    // ---- forward: TrQuant::xT --------------------------------------------------------------------------------------------------------
+    {
+      const int s1 = lw + bd + 6 - 15, s2 = lh + 6;
+      const int16_t *m = tabs.m[lw];
+      for( int i = t; i < w * w; i += TPT ) { const int k = i / w, n = i - k * w; sM[n * w + k] = m[i]; }
+      jc_sync<TPT>();
+      {
+        const int rnd = s1 > 0 ? 1 << ( s1 - 1 ) : 0, kEff = w - skipW;
+        for( int o = t; o < h * w; o += TPT )
+        {
+          const int jj = o / w, k = o - jj * w;
+          int       v  = 0;
+          if( k < kEff )
+          {
+            unsigned sum = 0;
+            for( int n = 0; n < w; n++ ) sum += ( unsigned ) blk[jj * w + n] * ( unsigned ) ( int ) sM[n * w + k];
+            v = ( int ) ( sum + ( unsigned ) rnd ) >> s1;
+          }
+          tmp[k * ( h + 1 ) + jj] = v;
+        }
+      }
+      jc_sync<TPT>();
+      m = tabs.m[lh];
+      for( int i = t; i < h * h; i += TPT ) { const int k = i / h, n = i - k * h; sM[n * h + k] = m[i]; }
+      jc_sync<TPT>();
+      {
+        const int rnd = 1 << ( s2 - 1 ), kEff = h - skipH, jEff = w - skipW;
+        for( int o = t; o < w * h; o += TPT )
+        {
+          const int j2 = o / h, k2 = o - j2 * h;
+          int       v  = 0;
+          if( j2 < jEff && k2 < kEff )
+          {
+            unsigned sum = 0;
+            for( int n = 0; n < h; n++ ) sum += ( unsigned ) tmp[j2 * ( h + 1 ) + n] * ( unsigned ) ( int ) sM[n * h + k2];
+            v = ( int ) ( sum + ( unsigned ) rnd ) >> s2;
+          }
+          blk[k2 * w + j2] = v;
+          a.sumAbs += abs( v );
+        }
+      }
+      jc_sync<TPT>();
+    }
+    // ---- Quant::quant + Quant::dequant, in place ---------------------------------------------------------------------------------------
+    {
+      const QParams qp = q_params( j, lw, lh, false );
+      for( int i = t; i < w * h; i += TPT )
+      {
+        const int q = q_level( qp, blk[i], a.absSum );
+        if( levels ) levels[i] = q;
+        blk[i] = q_dequant( qp, q );
+      }
+      jc_sync<TPT>();
+    }
+    // ---- inverse: TrQuant::xIT, then the inverse ICT and the two SSEs ---------------------------------------------------------------------
+    {
+      const int s1 = 7, s2 = 20 - bd;
+      const int16_t *m = tabs.m[lh];
+      for( int i = t; i < h * h; i += TPT ) sM[i] = m[i];
+      jc_sync<TPT>();
+      {
+        const unsigned rnd = 1u << ( s1 - 1 );
+        const int      linesEff = w - skipW, cut = h - skipH;
+        for( int o = t; o < w * h; o += TPT )
+        {
+          const int i = o / h, jj = o - i * h;
+          int       v = 0;
+          if( i < linesEff )
+          {
+            unsigned sum = 0;
+            for( int k = 0; k < cut; k++ ) sum += ( unsigned ) blk[k * w + i] * ( unsigned ) ( int ) sM[k * h + jj];
+            v = min( 32767, max( -32768, ( int ) ( sum + rnd ) >> s1 ) );
+          }
+          tmp[i * h + jj] = v;
+        }
+      }
+      jc_sync<TPT>();
+      m = tabs.m[lw];
+      for( int i = t; i < w * w; i += TPT ) sM[i] = m[i];
+      jc_sync<TPT>();
+      {
+        const unsigned rnd = 1u << ( s2 - 1 );
+        const int      cut = w - skipW;
+        for( int o = t; o < w * h; o += TPT )
+        {
+          const int y = o / w, x = o - y * w;
+          unsigned  sum = 0;
+          for( int k = 0; k < cut; k++ ) sum += ( unsigned ) tmp[k * h + y] * ( unsigned ) ( int ) sM[k * w + x];
+          const int  v  = min( 32767, max( -32768, ( int ) ( sum + rnd ) >> s2 ) );
+          const long ro = ( long ) y * j.resiStride + x;   // the two original residuals again, from L2
+          jccr_finish( am, s, v, cbp[ro], crp[ro], recCb, recCr, o, a.sseCb, a.sseCr );
+        }
+      }
+    }
+  }
+  jccr_reduce_store<TPT>( a, sRed, sub, t, true, results + jobIdx );
+}
+
+// ---- uniform 4x4 / 8x4 / 4x8 batches: ONE LANE per pair, the joint block in registers (tu_chain_lane_kernel between the two ICTs) ----------------------
+template<int W, int H>
+__global__ __launch_bounds__( 256 ) void jccr_chain_lane_kernel( const int16_t *__restrict__ resiBase, const vtmhip_jccr_job *__restrict__ jobs, int numJobs, DctTabs tabs,
+                                                                int *__restrict__ levelsBase, int16_t *__restrict__ recCbBase, int16_t *__restrict__ recCrBase,
+                                                                vtmhip_jccr_result *__restrict__ results )
+{
+  constexpr int LW = W == 4 ? 2 : 3, LH = H == 4 ? 2 : 3, N = W * H;
+  __shared__ int16_t sMH[W * W], sMV[H * H];
+  for( int i = threadIdx.x; i < W * W; i += 256 ) sMH[i] = tabs.m[LW][i];
+  for( int i = threadIdx.x; i < H * H; i += 256 ) sMV[i] = tabs.m[LH][i];
+  __syncthreads();
+  const int jobIdx = blockIdx.x * 256 + threadIdx.x;
+  if( jobIdx >= numJobs ) return;
+  const vtmhip_jccr_job j = jobs[jobIdx];
+  const int      bd = j.bitDepth, am = ict_abs_mode( j.cbfMask ), s = j.signFlag ? -1 : 1;
+  const int16_t *cbp = resiBase + j.cbOff, *crp = resiBase + j.crOff;
+  int            r[N], b[N], t[N];
+  JccrSums       a = { 0, 0, 0, 0, 0 };
+  const bool     aligned = ( ( j.cbOff | j.crOff | j.resiStride ) & 3 ) == 0;   // 8-byte aligned rows: 4 samples per load
+  if( aligned )
+  {
+#pragma unroll
+    for( int y = 0; y < H; y++ )
+#pragma unroll
+      for( int x = 0; x < W; x += 4 )
+      {
+        const int2 vb = *reinterpret_cast<const int2 *>( cbp + ( long ) y * j.resiStride + x ), vr = *reinterpret_cast<const int2 *>( crp + ( long ) y * j.resiStride + x );
+        const int  cb4[4] = { ( int ) ( short ) vb.x, vb.x >> 16, ( int ) ( short ) vb.y, vb.y >> 16 }, cr4[4] = { ( int ) ( short ) vr.x, vr.x >> 16, ( int ) ( short ) vr.y, vr.y >> 16 };
+#pragma unroll
+        for( int q = 0; q < 4; q++ )
+        {
+          const int c = ict_fwd( am, s, cb4[q], cr4[q] );
+          a.fwdDist += ict_dist( am, s, cb4[q], cr4[q], c );
+          r[y * W + x + q] = c;
+        }
+      }
+  }
+  else
+  {
+#pragma unroll
+    for( int y = 0; y < H; y++ )
+#pragma unroll
+      for( int x = 0; x < W; x++ )
+      {
+        const int cb = cbp[( long ) y * j.resiStride + x], cr = crp[( long ) y * j.resiStride + x], c = ict_fwd( am, s, cb, cr );
+        a.fwdDist += ict_dist( am, s, cb, cr, c );
+        r[y * W + x] = c;
+      }
+  }
+  // forward: rows, then columns (TrQuant::xT; no zero-out at these sizes)
+  {
+    const int s1 = LW + bd + 6 - 15, s2 = LH + 6;
+    const int rnd1 = s1 > 0 ? 1 << ( s1 - 1 ) : 0, rnd2 = 1 << ( s2 - 1 );
+#pragma unroll
+    for( int y = 0; y < H; y++ )
+#pragma unroll
+      for( int k = 0; k < W; k++ )
+      {
+        unsigned sum = 0;
+#pragma unroll
+        for( int n = 0; n < W; n++ ) sum += ( unsigned ) r[y * W + n] * ( unsigned ) ( int ) sMH[k * W + n];
+        t[k * H + y] = ( int ) ( sum + ( unsigned ) rnd1 ) >> s1;
+      }
+#pragma unroll
+    for( int x = 0; x < W; x++ )
+#pragma unroll
+      for( int k = 0; k < H; k++ )
+      {
+        unsigned sum = 0;
+#pragma unroll
+        for( int n = 0; n < H; n++ ) sum += ( unsigned ) t[x * H + n] * ( unsigned ) ( int ) sMV[k * H + n];
+        const int v = ( int ) ( sum + ( unsigned ) rnd2 ) >> s2;
+        b[k * W + x] = v;
+        a.sumAbs += abs( v );
+      }
+  }
+  // Quant::quant + Quant::dequant
+  {
+    const QParams qp = q_params( j, LW, LH, false );
+    int          *levels = levelsBase ? levelsBase + j.outOff : nullptr;
+#pragma unroll
+    for( int i = 0; i < N; i++ )
+    {
+      const int q = q_level( qp, b[i], a.absSum );
+      if( levels ) levels[i] = q;
+      b[i] = q_dequant( qp, q );
+    }
+  }
+  // inverse: columns, then rows (TrQuant::xIT); the inverse ICT and both SSEs per sample, the original residuals read again (L2) instead of held in registers
+  {
+    const int      s2 = 20 - bd;
+    const unsigned rnd1 = 1u << 6, rnd2 = 1u << ( s2 - 1 );
+    int16_t       *recCb = recCbBase ? recCbBase + j.outOff : nullptr, *recCr = recCrBase ? recCrBase + j.outOff : nullptr;
+#pragma unroll
+    for( int x = 0; x < W; x++ )
+#pragma unroll
+      for( int y = 0; y < H; y++ )
+      {
+        unsigned sum = 0;
+#pragma unroll
+        for( int k = 0; k < H; k++ ) sum += ( unsigned ) b[k * W + x] * ( unsigned ) ( int ) sMV[k * H + y];
+        t[x * H + y] = min( 32767, max( -32768, ( int ) ( sum + rnd1 ) >> 7 ) );
+      }
+#pragma unroll
+    for( int y = 0; y < H; y++ )
+#pragma unroll
+      for( int x = 0; x < W; x++ )
+      {
+        unsigned sum = 0;
+#pragma unroll
+        for( int k = 0; k < W; k++ ) sum += ( unsigned ) t[k * H + y] * ( unsigned ) ( int ) sMH[k * W + x];
+        r[y * W + x] = min( 32767, max( -32768, ( int ) ( sum + rnd2 ) >> s2 ) );
+      }
+    if( aligned )
+    {
+#pragma unroll
+      for( int y = 0; y < H; y++ )
+#pragma unroll
+        for( int x = 0; x < W; x += 4 )
+        {
+          const int2 vb = *reinterpret_cast<const int2 *>( cbp + ( long ) y * j.resiStride + x ), vr = *reinterpret_cast<const int2 *>( crp + ( long ) y * j.resiStride + x );
+          const int  cb4[4] = { ( int ) ( short ) vb.x, vb.x >> 16, ( int ) ( short ) vb.y, vb.y >> 16 }, cr4[4] = { ( int ) ( short ) vr.x, vr.x >> 16, ( int ) ( short ) vr.y, vr.y >> 16 };
+#pragma unroll
+          for( int q = 0; q < 4; q++ ) jccr_finish( am, s, r[y * W + x + q], cb4[q], cr4[q], recCb, recCr, y * W + x + q, a.sseCb, a.sseCr );
+        }
+    }
+    else
+    {
+#pragma unroll
+      for( int y = 0; y < H; y++ )
+#pragma unroll
+        for( int x = 0; x < W; x++ )
+          jccr_finish( am, s, r[y * W + x], cbp[( long ) y * j.resiStride + x], crp[( long ) y * j.resiStride + x], recCb, recCr, y * W + x, a.sseCb, a.sseCr );
+    }
+  }
+  results[jobIdx] = jccr_result_of( a );
+}
+
+// ---- uniform batches with power-of-two sides >= 8: the register-blocked passes of tu_chain_uni_kernel (a lane owns a 2 x 8 block of outputs) ------------
+// rows x cols outputs (cols multiple of 8); rEff / cEff: outputs beyond them are zero (zero-out); inner: summation length.  32-bit A values below 2^23 in
+// magnitude (the header comment has the bound), matrix entries |m| <= 90: the 24-bit multiply is exact.
+template<int LPT, bool CLIP>
+__device__ __forceinline__ void jq_pass( const int *A, int aRowStride, int aColStride, const int16_t *B, int ldb, int inner, int rows, int cols, int rEff, int cEff,
+                                         int *out, int oRowStride, int oColStride, int shift, int t, long long *sumAbs )
+{
+  const int cb = cols >> 3, lcb = 31 - __clz( cb ), rnd = shift > 0 ? 1 << ( shift - 1 ) : 0;
+  for( int it = t; it < ( rows >> 1 ) * cb; it += LPT )
+  {
+    const int r = ( it >> lcb ) << 1, c0 = ( it & ( cb - 1 ) ) << 3;   // cb is a power of two
+    int       acc[2][8];
+#pragma unroll
+    for( int i = 0; i < 8; i++ ) acc[0][i] = acc[1][i] = rnd;
+    if( r < rEff && c0 < cEff )
+    {
+      const int *a0 = A + r * aRowStride, *a1 = a0 + aRowStride;
+      for( int n = 0; n < inner; n++ )
+      {
+        const int  av0 = a0[n * aColStride], av1 = a1[n * aColStride];
+        const int4 bv = *reinterpret_cast<const int4 *>( B + n * ldb + c0 );
+        const int  b[8] = { ( int ) ( short ) bv.x, bv.x >> 16, ( int ) ( short ) bv.y, bv.y >> 16, ( int ) ( short ) bv.z, bv.z >> 16, ( int ) ( short ) bv.w, bv.w >> 16 };
+#pragma unroll
+        for( int i = 0; i < 8; i++ ) { acc[0][i] += __mul24( av0, b[i] ); acc[1][i] += __mul24( av1, b[i] ); }
+      }
+    }
+#pragma unroll
+    for( int q = 0; q < 2; q++ )
+#pragma unroll
+      for( int i = 0; i < 8; i++ )
+      {
+        int v = ( r + q < rEff && c0 + i < cEff ) ? acc[q][i] >> shift : 0;
+        if( CLIP ) v = min( 32767, max( -32768, v ) );
+        out[( r + q ) * oRowStride + ( c0 + i ) * oColStride] = v;
+        if( sumAbs ) *sumAbs += abs( v );
+      }
+  }
+}
+
+// The same product for int16 A values with the summation index contiguous: v_dot2_i32_i16 takes two summation steps per instruction into a 32-bit
+// accumulator.  Bp: the matrix with rows n, n + 1 interleaved per column -- Bp[(n >> 1) * cols + c] = (B[n][c], B[n+1][c]).
+template<int LPT, bool CLIP, class OutT>
+__device__ __forceinline__ void jq_pass16( const int16_t *A, int aRowStride, const unsigned *Bp, int inner, int rows, int cols, int rEff, int cEff, OutT *out,
+                                           int oRowStride, int oColStride, int shift, int t )
+{
+  typedef short v2s __attribute__( ( ext_vector_type( 2 ) ) );
+  const int cb = cols >> 3, lcb = 31 - __clz( cb ), rnd = shift > 0 ? 1 << ( shift - 1 ) : 0;
+  for( int it = t; it < ( rows >> 1 ) * cb; it += LPT )
+  {
+    const int r = ( it >> lcb ) << 1, c0 = ( it & ( cb - 1 ) ) << 3;
+    int       acc[2][8];
+#pragma unroll
+    for( int i = 0; i < 8; i++ ) acc[0][i] = acc[1][i] = rnd;
+    if( r < rEff && c0 < cEff )
+    {
+      const unsigned *a0 = reinterpret_cast<const unsigned *>( A + r * aRowStride ), *a1 = reinterpret_cast<const unsigned *>( A + ( r + 1 ) * aRowStride );
+      for( int n2 = 0; n2 < ( inner >> 1 ); n2++ )
+      {
+        const unsigned av0 = a0[n2], av1 = a1[n2];
+        const uint4    b0 = *reinterpret_cast<const uint4 *>( Bp + n2 * cols + c0 ), b1 = *reinterpret_cast<const uint4 *>( Bp + n2 * cols + c0 + 4 );
+        const unsigned bw[8] = { b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w };
+        v2s va0, va1;
+        __builtin_memcpy( &va0, &av0, 4 );
+        __builtin_memcpy( &va1, &av1, 4 );
+#pragma unroll
+        for( int i = 0; i < 8; i++ )
+        {
+          v2s vb;
+          __builtin_memcpy( &vb, &bw[i], 4 );
+          acc[0][i] = __builtin_amdgcn_sdot2( va0, vb, acc[0][i], false );
+          acc[1][i] = __builtin_amdgcn_sdot2( va1, vb, acc[1][i], false );
+        }
+      }
+    }
+#pragma unroll
+    for( int q = 0; q < 2; q++ )
+#pragma unroll
+      for( int i = 0; i < 8; i++ )
+      {
+        int v = ( r + q < rEff && c0 + i < cEff ) ? acc[q][i] >> shift : 0;
+        if( CLIP ) v = min( 32767, max( -32768, v ) );
+        out[( r + q ) * oRowStride + ( c0 + i ) * oColStride] = ( OutT ) v;
+      }
+  }
+}
+
+template<int LPT>
+__global__ __launch_bounds__( 256 ) void jccr_chain_uni_kernel( const int16_t *__restrict__ resiBase, const vtmhip_jccr_job *__restrict__ jobs, int numJobs, DctTabs tabs,
+                                                               int *__restrict__ levelsBase, int16_t *__restrict__ recCbBase, int16_t *__restrict__ recCrBase,
+                                                               vtmhip_jccr_result *__restrict__ results, int w, int h )
+{
+  extern __shared__ __attribute__( ( aligned( 16 ) ) ) int ldsw[];
+  __shared__ long long sRed[4][5];
+  constexpr int TUS = 256 / LPT;
+  const int     sub = threadIdx.x / LPT, t = threadIdx.x - sub * LPT;
+  const int     perTu = w * h + w * ( h + 1 );   // ints: blk, tmp (the 16-bit joint residual lives in blk until the second forward pass overwrites it)
+  int16_t      *sMat = ( int16_t * ) ( ldsw + TUS * perTu );
+  const int     lw = ilog2( w ), lh = ilog2( h );
+  // width:  mW0 = M_W with rows k, k+1 interleaved (second inverse pass), mW1 = M_W^T with rows n, n+1 interleaved (first forward pass)
+  // height: mH0 = M_H with rows k, k+1 interleaved (first inverse pass),   mH1 = M_H^T plain (second forward pass: 32-bit input)
+  int16_t *mW0 = sMat, *mW1 = mW0 + w * w, *mH0 = mW1 + w * w, *mH1 = mH0 + h * h;
+  {
+    const int16_t *mw = tabs.m[lw], *mh = tabs.m[lh];
+    for( int i = threadIdx.x; i < w * w; i += 256 )
+    {
+      const int k = i >> lw, n = i & ( w - 1 );
+      mW0[( ( k >> 1 ) * w + n ) * 2 + ( k & 1 )] = mw[i];
+      mW1[( ( n >> 1 ) * w + k ) * 2 + ( n & 1 )] = mw[i];
+    }
+    for( int i = threadIdx.x; i < h * h; i += 256 )
+    {
+      const int k = i >> lh, n = i & ( h - 1 );
+      mH0[( ( k >> 1 ) * h + n ) * 2 + ( k & 1 )] = mh[i];
+      mH1[n * h + k]                              = mh[i];
+    }
+  }
+  __syncthreads();
+  const int  jobIdx = blockIdx.x * TUS + sub;
+  const bool live   = jobIdx < numJobs;   // dead groups (whole waves or idle lane groups) compute the last job again and write nothing: they only meet the barriers
+  const vtmhip_jccr_job j = jobs[live ? jobIdx : numJobs - 1];
+  const int      bd = j.bitDepth, am = ict_abs_mode( j.cbfMask ), s = j.signFlag ? -1 : 1;
+  int           *blk = ldsw + sub * perTu, *tmp = blk + w * h;
+  int16_t       *sR  = ( int16_t * ) blk;
+  const int16_t *cbp = resiBase + j.cbOff, *crp = resiBase + j.crOff;
+  JccrSums       a = { 0, 0, 0, 0, 0 };
+  for( int i = t; i < w * h; i += LPT )
+  {
+    const long o  = ( long ) ( i >> lw ) * j.resiStride + ( i & ( w - 1 ) );
+    const int  cb = cbp[o], cr = crp[o], c = ict_fwd( am, s, cb, cr );
+    a.fwdDist += ict_dist( am, s, cb, cr, c );
+    sR[i] = ( int16_t ) c;
+  }
+  int16_t *dq16 = reinterpret_cast<int16_t *>( tmp );   // dequantised coefficients [k][k2] (after the second forward pass has consumed tmp)
+  int16_t *t16  = reinterpret_cast<int16_t *>( blk );   // first inverse pass output [y][i] (after quantisation has consumed blk)
+  int     *rec32 = tmp;                                  // reconstructed joint residual [y][x]
+  const int skipW = zero_out( w ), skipH = zero_out( h );
+  jc_sync<LPT>();
+  // forward (TrQuant::xT): tmp[k][y] = sum_n sR[y][n] * MT_hor[n][k];  blk[k2][j2] = sum_n tmp[j2][n] * MT_ver[n][k2]
+  jq_pass16<LPT, false>( sR, w, reinterpret_cast<const unsigned *>( mW1 ), w, h, w, h, w - skipW, tmp, 1, h + 1, lw + bd + 6 - 15, t );
+  jc_sync<LPT>();
+  jq_pass<LPT, false>( tmp, h + 1, 1, mH1, h, h, w, h, w - skipW, h - skipH, blk, 1, w, lh + 6, t, &a.sumAbs );
+  jc_sync<LPT>();
+  {
+    const QParams qp = q_params( j, lw, lh, false );
+    int          *levels = ( levelsBase && live ) ? levelsBase + j.outOff : nullptr;
+    for( int i = t; i < w * h; i += LPT )
+    {
+      const int q = q_level( qp, blk[i], a.absSum );
+      if( levels ) levels[i] = q;
+      dq16[( ( i & ( w - 1 ) ) << lh ) + ( i >> lw )] = ( int16_t ) q_dequant( qp, q );   // transposed: the vertical index contiguous
+    }
+  }
+  jc_sync<LPT>();
+  // inverse (TrQuant::xIT): t16[y][i] = clip( sum_k dq[k][i] * M_ver[k][y] );  rec[y][x] = clip( sum_k t16[y][k] * M_hor[k][x] )
+  jq_pass16<LPT, true>( dq16, h, reinterpret_cast<const unsigned *>( mH0 ), h - skipH, w, h, w - skipW, h, t16, 1, w, 7, t );
+  jc_sync<LPT>();
+  jq_pass16<LPT, true>( t16, w, reinterpret_cast<const unsigned *>( mW0 ), w - skipW, h, w, h, w, rec32, w, 1, 20 - bd, t );
+  jc_sync<LPT>();
+  {
+    int16_t *recCb = ( recCbBase && live ) ? recCbBase + j.outOff : nullptr, *recCr = ( recCrBase && live ) ? recCrBase + j.outOff : nullptr;
+    for( int i = t; i < w * h; i += LPT )
+    {
+      const long o = ( long ) ( i >> lw ) * j.resiStride + ( i & ( w - 1 ) );   // the two original residuals again, from L2
+      jccr_finish( am, s, rec32[i], cbp[o], crp[o], recCb, recCr, i, a.sseCb, a.sseCr );
+    }
+  }
+  jccr_reduce_store<LPT>( a, sRed, sub, t, live, results + ( live ? jobIdx : 0 ) );
+}
+
+DctTabs tabs_of( const vtmhip_ctx *ctx )
+{
+  DctTabs t;
+  for( int l = 0; l < 7; l++ ) t.m[l] = ctx->trTab[VTMHIP_DCT2][l];
+  return t;
+}
+
+// The core matrices belong to the context and are filled by transform.hip's entries on their first use: run its smallest one once.
+int ensure_tables( vtmhip_ctx *ctx )
+{
+  if( ctx->trTabBuf ) return VTMHIP_OK;
+  const int32_t src[2] = { 0, 0 };
+  int32_t       dst[2];
+  return vtmhip_fastFwdTrans( ctx, VTMHIP_DCT2, 2, src, dst, 0, 1, 0, 0 );
+}
+
+bool pow2( int v ) { return v > 0 && ( v & ( v - 1 ) ) == 0; }
+
+template<int W, int H>
+int launch_lane( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int32_t *d_levelsBase, int16_t *d_recCbBase, int16_t *d_recCrBase,
+                 vtmhip_jccr_result *d_results )
+{
+  VTMHIP_TIME_KERNEL( ctx, "jccr_chain_lane_kernel" );
+  hipLaunchKernelGGL( ( jccr_chain_lane_kernel<W, H> ), dim3( ( n + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, d_resiBase, d_jobs, n, tabs_of( ctx ), d_levelsBase,
+                      d_recCbBase, d_recCrBase, d_results );
+  VTMHIP_LAUNCHED( ctx );
+  return VTMHIP_OK;
+}
+
+template<int LPT>
+int launch_uni( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int w, int h, int32_t *d_levelsBase, int16_t *d_recCbBase,
+                int16_t *d_recCrBase, vtmhip_jccr_result *d_results )
+{
+  constexpr int TUS = 256 / LPT;
+  const size_t  lds = TUS * ( ( size_t ) w * h + ( size_t ) w * ( h + 1 ) ) * sizeof( int ) + ( 2 * ( size_t ) w * w + 2 * ( size_t ) h * h ) * sizeof( int16_t );
+  if( lds > 64 * 1024 )   // 64x64 only: 64.3 KB
+    VTMHIP_HIP( ctx, hipFuncSetAttribute( reinterpret_cast<const void *>( jccr_chain_uni_kernel<LPT> ), hipFuncAttributeMaxDynamicSharedMemorySize, ( int ) lds ) );
+  VTMHIP_TIME_KERNEL( ctx, "jccr_chain_uni_kernel" );
+  hipLaunchKernelGGL( jccr_chain_uni_kernel<LPT>, dim3( ( n + TUS - 1 ) / TUS ), dim3( 256 ), lds, ctx->stream, d_resiBase, d_jobs, n, tabs_of( ctx ), d_levelsBase,
+                      d_recCbBase, d_recCrBase, d_results, w, h );
+  VTMHIP_LAUNCHED( ctx );
+  return VTMHIP_OK;
+}
+
+// host-pointer staging of the two pointer entries: both blocks compactly (stride = width) at the start of the pinned / device staging area
+void stage_pair( char *hp, const int16_t *cb, int cbStride, const int16_t *cr, int crStride, int w, int h )
+{
+  const size_t blk = ( size_t ) w * h * sizeof( int16_t );
+  for( int y = 0; y < h; y++ )
+  {
+    memcpy( hp + ( size_t ) y * w * 2, cb + ( ptrdiff_t ) y * cbStride, ( size_t ) w * 2 );
+    memcpy( hp + blk + ( size_t ) y * w * 2, cr + ( ptrdiff_t ) y * crStride, ( size_t ) w * 2 );
+  }
+}
+
+void unstage( int16_t *dst, int dstStride, const char *src, int w, int h )
+{
+  for( int y = 0; y < h; y++ ) memcpy( dst + ( ptrdiff_t ) y * dstStride, src + ( size_t ) y * w * 2, ( size_t ) w * 2 );
+}
+
+}   // namespace
+
+extern "C"
+{
+
+int vtmhip_jccr_struct_size( int which )
+{
+  switch( which )
+  {
+  case 0: return ( int ) sizeof( vtmhip_ict_job );
+  case 1: return ( int ) sizeof( vtmhip_jccr_job );
+  case 2: return ( int ) sizeof( vtmhip_jccr_result );
+  default: return -1;
+  }
+}
+
+int vtmhip_fwdTransformCbCr( vtmhip_ctx *ctx, int mode, const int16_t *cb, int cbStride, const int16_t *cr, int crStride, int16_t *c1, int c1Stride, int16_t *c2,
+                             int c2Stride, int width, int height, int64_t dist[2] )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  VTMHIP_REQUIRE( ctx, mode >= -3 && mode <= 3, "mode: -3 .. 3 (m_fwdICT has seven slots)" );
+  VTMHIP_REQUIRE( ctx, width >= 1 && width <= 64 && height >= 1 && height <= 64, "width / height: 1 .. 64" );
+  const int am = mode < 0 ? -mode : mode, cbfMask = am == 3 ? 1 : am == 0 ? 0 : am + 1;
+  int16_t  *joint = am == 3 ? c2 : c1;
+  const int jointStride = am == 3 ? c2Stride : c1Stride;
+  VTMHIP_REQUIRE( ctx, cb && cr && dist && ( am == 0 || joint ), "null pointer" );
+  const size_t blk = ( size_t ) width * height * sizeof( int16_t );
+  const size_t jobOff = ( 3 * blk + 63 ) & ~( size_t ) 63, outOff = jobOff + 64;   // [cb][cr][joint] job dist[4][2]
+  int st = vtmhip_internal_scratch( ctx, outOff + 64 );
+  if( st ) return st;
+  char *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
+  stage_pair( hp, cb, cbStride, cr, crStride, width, height );
+  vtmhip_ict_job j;
+  memset( &j, 0, sizeof( j ) );
+  j.cbOff = 0; j.crOff = ( int64_t ) width * height; j.cbStride = j.crStride = width;
+  j.outOff = ( int64_t ) ( 2 - ( cbfMask ? cbfMask - 1 : 0 ) ) * width * height;   // the requested plane lands right behind the two inputs
+  j.width = ( int16_t ) width; j.height = ( int16_t ) height; j.signFlag = mode < 0; j.maskBits = ( uint8_t ) ( cbfMask ? 1 << cbfMask : 0 );
+  memcpy( hp + jobOff, &j, sizeof( j ) );
+  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, outOff, hipMemcpyHostToDevice, ctx->stream ) );
+  hipLaunchKernelGGL( ict_fwd_kernel, dim3( 1 ), dim3( 256 ), 0, ctx->stream, ( const int16_t * ) dp, ( const vtmhip_ict_job * ) ( dp + jobOff ), 1, ( int16_t * ) dp,
+                      ( long long * ) ( dp + outOff ) );
+  VTMHIP_LAUNCHED( ctx );
+  VTMHIP_HIP( ctx, hipMemcpyAsync( hp + 2 * blk, dp + 2 * blk, blk, hipMemcpyDeviceToHost, ctx->stream ) );
+  VTMHIP_HIP( ctx, hipMemcpyAsync( hp + outOff, dp + outOff, 64, hipMemcpyDeviceToHost, ctx->stream ) );
+  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
+  memcpy( dist, hp + outOff + 16 * cbfMask, 16 );
+  if( am ) unstage( joint, jointStride, hp + 2 * blk, width, height );
+  return VTMHIP_OK;
+}
+
+int vtmhip_invTransformCbCr( vtmhip_ctx *ctx, int mode, int16_t *cb, int cbStride, int16_t *cr, int crStride, int width, int height )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  VTMHIP_REQUIRE( ctx, mode >= -3 && mode <= 3, "mode: -3 .. 3 (m_invICT has seven slots)" );
+  VTMHIP_REQUIRE( ctx, width >= 1 && width <= 64 && height >= 1 && height <= 64, "width / height: 1 .. 64" );
+  VTMHIP_REQUIRE( ctx, cb && cr, "null pointer" );
+  if( mode == 0 ) return VTMHIP_OK;   // invTransformCbCr<0> touches nothing
+  const size_t blk = ( size_t ) width * height * sizeof( int16_t );
+  int st = vtmhip_internal_scratch( ctx, 2 * blk );
+  if( st ) return st;
+  char *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
+  stage_pair( hp, cb, cbStride, cr, crStride, width, height );
+  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, 2 * blk, hipMemcpyHostToDevice, ctx->stream ) );
+  const int count = width * height;
+  hipLaunchKernelGGL( ict_inv_kernel, dim3( ( count + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ( int16_t * ) dp, ( int16_t * ) ( dp + blk ), count,
+                      mode < 0 ? -mode : mode, mode < 0 ? -1 : 1 );
+  VTMHIP_LAUNCHED( ctx );
+  VTMHIP_HIP( ctx, hipMemcpyAsync( hp, dp, 2 * blk, hipMemcpyDeviceToHost, ctx->stream ) );
+  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
+  if( mode == 3 || mode == -3 ) unstage( cb, cbStride, hp, width, height );
+  else unstage( cr, crStride, hp + blk, width, height );
+  return VTMHIP_OK;
+}
+
+int vtmhip_ict_fwd_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_ict_job *d_jobs, int n, int16_t *d_jointBase, int64_t *d_dist )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
+  if( n == 0 ) return VTMHIP_OK;
+  VTMHIP_REQUIRE( ctx, d_resiBase && d_jobs && d_dist, "null pointer" );
+  VTMHIP_TIME_KERNEL( ctx, "ict_fwd_kernel" );
+  hipLaunchKernelGGL( ict_fwd_kernel, dim3( ( n + 3 ) / 4 ), dim3( 256 ), 0, ctx->stream, d_resiBase, d_jobs, n, d_jointBase, ( long long * ) d_dist );
+  VTMHIP_LAUNCHED( ctx );
+  return VTMHIP_OK;
+}
+
+int vtmhip_ict_select( const int64_t dist[4][2], int isIntra, int masks[2], int *numMasks )
+{
+  if( !dist || !masks || !numMasks ) return VTMHIP_E_INVALID;
+  *numMasks = 0;
+  if( !isIntra ) { masks[( *numMasks )++] = 3; return VTMHIP_OK; }
+  int64_t minDist1 = dist[0][0] < dist[0][1] ? dist[0][0] : dist[0][1], minDist2 = INT64_MAX;
+  int     cbfMask1 = 0, cbfMask2 = 0;
+  for( int cbfMask = 1; cbfMask <= 3; cbfMask++ )
+  {
+    if( dist[cbfMask][0] < minDist1 )
+    {
+      cbfMask2 = cbfMask1; minDist2 = minDist1;
+      cbfMask1 = cbfMask;  minDist1 = dist[cbfMask1][0];
+    }
+    else if( dist[cbfMask][0] < minDist2 )
+    {
+      cbfMask2 = cbfMask; minDist2 = dist[cbfMask2][0];
+    }
+  }
+  if( cbfMask1 ) masks[( *numMasks )++] = cbfMask1;
+  if( cbfMask2 && ( ( minDist2 < ( 9 * minDist1 ) / 8 ) || ( !cbfMask1 && minDist2 < ( 3 * minDist1 ) / 2 ) ) ) masks[( *numMasks )++] = cbfMask2;
+  return VTMHIP_OK;
+}
+
+int vtmhip_jccr_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
+                                 int32_t *d_levelsBase, int16_t *d_recCbBase, int16_t *d_recCrBase, vtmhip_jccr_result *d_results )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
+  if( n == 0 ) return VTMHIP_OK;
+  VTMHIP_REQUIRE( ctx, d_resiBase && d_jobs && d_results, "null pointer" );
+  VTMHIP_REQUIRE( ctx, maxWidth >= 2 && maxWidth <= 64 && maxHeight >= 2 && maxHeight <= 64, "maxWidth / maxHeight: 2..64 (2-D transforms)" );
+  const bool lanePath = uniformSize && maxWidth * maxHeight <= 32 && maxWidth >= 4 && maxHeight >= 4;
+  const bool uniPath  = uniformSize && maxWidth >= 8 && maxHeight >= 8;
+  if( uniPath ) VTMHIP_REQUIRE( ctx, pow2( maxWidth ) && pow2( maxHeight ), "uniformSize: width / height must be powers of two (TU sizes are)" );
+  int st = ensure_tables( ctx );
+  if( st ) return st;
+  // the job table, checked on the host before anything is launched (the kernels index LDS and the core matrices by these fields)
+  {
+    const size_t bytes = ( size_t ) n * sizeof( vtmhip_jccr_job );
+    st = vtmhip_internal_scratch( ctx, bytes );
+    if( st ) return st;
+    VTMHIP_HIP( ctx, hipMemcpyAsync( ctx->pinned, d_jobs, bytes, hipMemcpyDeviceToHost, ctx->stream ) );
+    VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
+    const vtmhip_jccr_job *jobs = ( const vtmhip_jccr_job * ) ctx->pinned;
+    for( int i = 0; i < n; i++ )
+    {
+      const vtmhip_jccr_job &j = jobs[i];
+      const bool ts = j.typeHor == VTMHIP_TRSKIP;
+      VTMHIP_REQUIRE( ctx, j.cbfMask >= 1 && j.cbfMask <= 3, "cbfMask: 1 .. 3" );
+      VTMHIP_REQUIRE( ctx, ts || j.typeHor == VTMHIP_DCT2, "typeHor: VTMHIP_DCT2 or VTMHIP_TRSKIP" );
+      VTMHIP_REQUIRE( ctx, pow2( j.width ) && pow2( j.height ) && j.width >= 2 && j.height >= 2 && j.width <= maxWidth && j.height <= maxHeight,
+                      "width / height: powers of two, 2 .. maxWidth / maxHeight" );
+      VTMHIP_REQUIRE( ctx, !ts || ( j.width <= 32 && j.height <= 32 ), "transform skip: sides <= 32 (log2MaxTransformSkipBlockSize)" );
+      VTMHIP_REQUIRE( ctx, j.bitDepth >= 8 && j.bitDepth <= 12 && j.qpRem >= 0 && j.qpRem < 6 && j.qpPer >= 0, "bitDepth 8..12, qpRem 0..5, qpPer >= 0" );
+      VTMHIP_REQUIRE( ctx, !uniformSize || ( !ts && j.width == maxWidth && j.height == maxHeight ), "uniformSize: every job maxWidth x maxHeight with VTMHIP_DCT2" );
+    }
+  }
+  if( lanePath )
+  {
+    if( maxWidth == 4 && maxHeight == 4 ) return launch_lane<4, 4>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recCbBase, d_recCrBase, d_results );
+    if( maxWidth == 8 ) return launch_lane<8, 4>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recCbBase, d_recCrBase, d_results );
+    return launch_lane<4, 8>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recCbBase, d_recCrBase, d_results );
+  }
+  if( uniPath )
+  {
+    const int items = maxWidth * maxHeight / 16;   // one lane = 2 x 8 outputs of a transform pass
+#define VTMHIP_JCCR_UNI( LPT ) launch_uni<LPT>( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, d_levelsBase, d_recCbBase, d_recCrBase, d_results )
+    if( items <= 4 ) return VTMHIP_JCCR_UNI( 4 );
+    if( items <= 8 ) return VTMHIP_JCCR_UNI( 8 );
+    if( items <= 16 ) return VTMHIP_JCCR_UNI( 16 );
+    if( items <= 32 ) return VTMHIP_JCCR_UNI( 32 );
+    if( items <= 64 ) return VTMHIP_JCCR_UNI( 64 );
+    if( items <= 128 ) return VTMHIP_JCCR_UNI( 128 );
+    return VTMHIP_JCCR_UNI( 256 );
+#undef VTMHIP_JCCR_UNI
+  }
+  const int    mx    = maxWidth > maxHeight ? maxWidth : maxHeight;
+  const size_t perTu = ( size_t ) maxWidth * maxHeight + ( size_t ) maxWidth * ( maxHeight + 1 ) + ( ( mx * mx + 1 ) >> 1 );
+  VTMHIP_TIME_KERNEL( ctx, "jccr_chain_kernel" );
+  if( maxWidth * maxHeight <= 256 )
+    hipLaunchKernelGGL( jccr_chain_kernel<64>, dim3( ( n + 3 ) / 4 ), dim3( 256 ), 4 * perTu * sizeof( int ), ctx->stream, d_resiBase, d_jobs, n, tabs_of( ctx ), d_levelsBase,
+                        d_recCbBase, d_recCrBase, d_results, maxWidth, maxHeight );
+  else
+    hipLaunchKernelGGL( jccr_chain_kernel<256>, dim3( n ), dim3( 256 ), perTu * sizeof( int ), ctx->stream, d_resiBase, d_jobs, n, tabs_of( ctx ), d_levelsBase, d_recCbBase,
+                        d_recCrBase, d_results, maxWidth, maxHeight );
+  VTMHIP_LAUNCHED( ctx );
+  return VTMHIP_OK;
+}
+
+}   // extern "C"

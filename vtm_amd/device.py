@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib as _lib
-from .lib import (AffineJob, DistJob, FracJob, FracResult, FullJob, IfJob, McJob, MeResult, PelOpJob, PicParams, QuantJob,   # noqa: F401
+from .lib import (AffineJob, DistJob, FracJob, FracResult, FullJob, IctJob, IfJob, JccrJob, JccrResult, McJob, MeResult, PelOpJob, PicParams, QuantJob,   # noqa: F401
                   TrJob, TuJob, TuResult, TzJob, VtmHipError, WpDistJob, WpParam, WpPredJob, WtdJob)
 
 
@@ -218,6 +218,22 @@ class Context:
         self._check(self.L.vtmhip_fastInvTrans(self.h, ttype, n, src.ctypes.data, dst.ctypes.data, shift, line, skip1, skip2, cmin, cmax))
         return dst
 
+    def fwdTransformCbCr(self, mode, cb, cr):
+        """(*m_fwdICT[mode])(resCb, resCr, resC1, resC2) on two 2-D int16 host arrays (any row stride); returns (joint residual or None for mode 0, (d1, d2))."""
+        h, w = cb.shape
+        assert cr.shape == cb.shape and cb.strides[1] == 2 and cr.strides[1] == 2
+        joint = np.zeros((h, w), np.int16) if mode else None
+        jp = joint.ctypes.data if mode else None
+        d = (C.c_int64 * 2)()
+        self._check(self.L.vtmhip_fwdTransformCbCr(self.h, mode, cb.ctypes.data, cb.strides[0] // 2, cr.ctypes.data, cr.strides[0] // 2, jp, w, jp, w, w, h, d))
+        return joint, (d[0], d[1])
+
+    def invTransformCbCr(self, mode, cb, cr):
+        """(*m_invICT[mode])(resCb, resCr), in place on two 2-D int16 host arrays (any row stride)."""
+        h, w = cb.shape
+        assert cr.shape == cb.shape and cb.strides[1] == 2 and cr.strides[1] == 2
+        self._check(self.L.vtmhip_invTransformCbCr(self.h, mode, cb.ctypes.data, cb.strides[0] // 2, cr.ctypes.data, cr.strides[0] // 2, w, h))
+
     # ---- batched device calls (device pointers: DevBuf.ptr or tensor.data_ptr()) ---------------------------------
     def dist_batch(self, d_org, d_cur, d_jobs, n, d_out):
         self._check(self.L.vtmhip_dist_batch_dev(self.h, d_org, d_cur, d_jobs, n, d_out))
@@ -393,6 +409,14 @@ class Context:
         """transform-skip candidates (TuJob.typeHor == 3) of one TU size"""
         self._check(self.L.vtmhip_tu_ts_chain_batch_dev(self.h, d_resi, d_jobs, n, w, h, d_levels, d_rec, d_results))
 
+    def ict_fwd_batch(self, d_resi, d_jobs, n, d_dist, d_joint=None):
+        """forward ICT of cbfMask 0 .. 3 for n IctJob pairs: int64 d_dist[n][4][2] and the joint residual planes the jobs ask for"""
+        self._check(self.L.vtmhip_ict_fwd_batch_dev(self.h, d_resi, d_jobs, n, d_joint, d_dist))
+
+    def jccr_chain_batch(self, d_resi, d_jobs, n, max_w, max_h, d_results, d_levels=None, d_rec_cb=None, d_rec_cr=None, uniform=False):
+        """the joint Cb-Cr candidate of n JccrJob pairs: forward ICT -> xT -> quant -> dequant -> xIT -> inverse ICT -> SSE of Cb and of Cr (JccrResult)"""
+        self._check(self.L.vtmhip_jccr_chain_batch_dev(self.h, d_resi, d_jobs, n, max_w, max_h, int(uniform), d_levels, d_rec_cb, d_rec_cr, d_results))
+
     def affine_sobel_batch(self, d_pred, d_deriv, d_jobs, n):
         self._check(self.L.vtmhip_affine_sobel_batch_dev(self.h, d_pred, d_deriv, d_jobs, n))
 
@@ -406,3 +430,13 @@ class Context:
 def struct_array_to_numpy(arr):
     """ctypes array of Structures -> uint8 numpy view (for upload)."""
     return np.frombuffer(arr, dtype=np.uint8)
+
+
+def ict_select(dist, is_intra):
+    """TrQuant::selectICTCandidates' decision from the four (d1, d2) pairs: the cbfMasks to test (host only, no device)."""
+    d = (C.c_int64 * 8)(*[int(v) for pair in dist for v in pair])
+    masks, num = (C.c_int * 2)(), C.c_int()
+    st = _lib.load().vtmhip_ict_select(d, int(is_intra), masks, C.byref(num))
+    if st != _lib.OK:
+        raise VtmHipError(st)
+    return [masks[i] for i in range(num.value)]

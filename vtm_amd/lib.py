@@ -13,7 +13,8 @@ WTD_INV_RESHAPE_CUR = 1           # vtmhip_wtd_job.flags
 WTD_INVALID_DIST = (1 << 64) - 1  # d_dist of a rejected vtmhip_wtd_job
 WP_INVALID_DIST = (1 << 64) - 1   # d_dist of a rejected vtmhip_wp_dist_job
 WP_UNI, WP_BI = 0, 1              # vtmhip_wp_pred_job.mode
-DCT2, DCT8, DST7 = 0, 1, 2
+DCT2, DCT8, DST7, TRSKIP = 0, 1, 2, 3
+ICT_MODES = ((0, 3, 1, 2), (0, -3, -1, -2))   # g_ictModes[signFlag][cbfMask]
 
 
 class DistJob(C.Structure):
@@ -262,10 +263,26 @@ class WpPredJob(C.Structure):
                 ("round", C.c_int32)]
 
 
+class IctJob(C.Structure):
+    _fields_ = [("cbOff", C.c_int64), ("crOff", C.c_int64), ("outOff", C.c_int64), ("cbStride", C.c_int32), ("crStride", C.c_int32), ("width", C.c_int16),
+                ("height", C.c_int16), ("signFlag", C.c_uint8), ("maskBits", C.c_uint8), ("pad0", C.c_uint8), ("pad1", C.c_uint8)]
+
+
+class JccrJob(C.Structure):
+    _fields_ = [("cbOff", C.c_int64), ("crOff", C.c_int64), ("outOff", C.c_int64), ("resiStride", C.c_int32), ("width", C.c_int16), ("height", C.c_int16),
+                ("qpPer", C.c_int16), ("qpRem", C.c_int16), ("typeHor", C.c_uint8), ("bitDepth", C.c_uint8), ("isIRAP", C.c_uint8), ("cbfMask", C.c_uint8),
+                ("signFlag", C.c_uint8), ("pad", C.c_uint8 * 7)]
+
+
+class JccrResult(C.Structure):
+    _fields_ = [("sseCb", C.c_uint64), ("sseCr", C.c_uint64), ("fwdDist", C.c_int64), ("sumAbs", C.c_int32), ("absSum", C.c_int32)]
+
+
 _STRUCTS = [DistJob, TzJob, MeResult, PicParams, IfJob, FracJob, FracResult, TrJob, QuantJob, FullJob, McJob, PelOpJob,
             TuJob, TuResult, AffineJob, MeCfg, MeJob, MeOut, PredJob, MaskedSadJob, GeoBlendJob, DmvrJob, LfnstJob,
             PisRow, PisPu, PisLevel, AffineMeJob, AffineMeOut, LfnstTuJob, PisLevelRun, PisBuffers, SmvdJob, PisPuIn, WtdJob,
             WpDistJob, WpPredJob]   # order of vtmhip_struct_size(which)
+_JCCR_STRUCTS = [IctJob, JccrJob, JccrResult]   # order of vtmhip_jccr_struct_size(which)
 
 # every symbol include/vtmhip.h declares (tests/test_abi.py checks the exports against the header text)
 _PROTOS = {
@@ -322,6 +339,13 @@ _PROTOS = {
                                    C.POINTER(C.c_uint64)]),
     "vtmhip_wp_dist_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vtmhip_wp_pred_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "vtmhip_jccr_struct_size": (C.c_int, [C.c_int]),
+    "vtmhip_fwdTransformCbCr": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(C.c_int64)]),
+    "vtmhip_invTransformCbCr": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "vtmhip_ict_fwd_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "vtmhip_ict_select": (C.c_int, [C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vtmhip_jccr_chain_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtmhip_filterHor": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                    C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vtmhip_filterVer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
@@ -438,6 +462,10 @@ def load():
         if lib.vtmhip_struct_size(i) != C.sizeof(s):
             raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
                               % (s.__name__, C.sizeof(s), lib.vtmhip_struct_size(i)))
+    for i, s in enumerate(_JCCR_STRUCTS):
+        if lib.vtmhip_jccr_struct_size(i) != C.sizeof(s):
+            raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
+                              % (s.__name__, C.sizeof(s), lib.vtmhip_jccr_struct_size(i)))
     _lib = lib
     return lib
 
