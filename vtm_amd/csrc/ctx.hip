@@ -106,6 +106,7 @@ int vtmhip_destroy( vtmhip_ctx *ctx )
   if( ctx->trTabBuf ) ( void ) hipFree( ctx->trTabBuf );
   if( ctx->wtdFixed ) ( void ) hipFree( ctx->wtdFixed );
   if( ctx->wtdInv ) ( void ) hipFree( ctx->wtdInv );
+  if( ctx->lmcsFwd ) ( void ) hipFree( ctx->lmcsFwd );
   if( ctx->pinned ) ( void ) hipHostFree( ctx->pinned );
   for( auto &t : ctx->timed ) { ( void ) hipEventDestroy( t.start ); ( void ) hipEventDestroy( t.stop ); }
   for( hipEvent_t e : ctx->forkEvents ) ( void ) hipEventDestroy( e );

@@ -14,8 +14,13 @@
 // 90 < 2^31 (N <= 64), and the pass's output is bounded by sum|m| * 32768 >> (log2 N + bitDepth - 9) <= 64 N * 2^15 >> (log2 N + bitDepth - 9) = 2^(30 - bitDepth)
 // <= 2^22 for bitDepth >= 8, inside the signed 24-bit operands of the second pass.  The residuals an encoder produces stay far below: 6 (2^bitDepth - 1) / 5.
 //
-// Out of scope: LMCS chroma residual scaling (scaleSignal), ACT, the picture-level sign decision (the caller passes signFlag), the CABAC estimate.
+// CRS (template flag of the three chain kernels, vtmhip_jccr_chain_crs_batch_dev): LMCS chroma residual scaling around the joint candidate (InterSearch.cpp:6822-6823,
+// 6838-6842, 6977-6998) with lmcs.hpp's rules -- Cb and Cr go through fwd() before the forward ICT (fwdDist is the distance on the scaled pair), both rebuilt blocks
+// through inv() before the rec stores and the SSEs, which are taken against the unscaled residuals.  The job's adj is 0 for "leave this job alone".
+//
+// Out of scope: ACT, the picture-level sign decision (the caller passes signFlag), the CABAC estimate.
 #include "ctx.hpp"
+#include "lmcs.hpp"
 
 namespace
 {
@@ -53,14 +58,39 @@ __device__ __forceinline__ long long ict_dist( int am, int s, int cb, int cr, in
 }
 
 // one reconstructed sample v of the coded component: both rebuilt blocks and both squared errors against the original residuals
-__device__ __forceinline__ void jccr_finish( int am, int s, int v, int cb, int cr, int16_t *recCb, int16_t *recCr, long i, long long &sseCb, long long &sseCr )
+// (CRS: both go through the inverse scaling first; cb, cr are the UNSCALED residuals)
+template<bool CRS>
+__device__ __forceinline__ void jccr_finish( int am, int s, int v, int cb, int cr, int16_t *recCb, int16_t *recCr, long i, long long &sseCb, long long &sseCr, int adj,
+                                             int maxAbs )
 {
-  const int o = ict_inv( am, s, v ), rb = am == 3 ? o : v, rr = am == 3 ? v : o;
+  const int o = ict_inv( am, s, v );
+  int       rb = am == 3 ? o : v, rr = am == 3 ? v : o;
+  if( CRS && adj ) { rb = lmcs_inv( rb, adj, maxAbs ); rr = lmcs_inv( rr, adj, maxAbs ); }
   if( recCb ) recCb[i] = ( int16_t ) rb;
   if( recCr ) recCr[i] = ( int16_t ) rr;
   const int db = cb - rb, dr = cr - rr;
   sseCb += ( long long ) ( unsigned long long ) ( ( unsigned ) db * ( unsigned ) db );
   sseCr += ( long long ) ( unsigned long long ) ( ( unsigned ) dr * ( unsigned ) dr );
+}
+
+// CRS: the job's effective adj (0: not scaled), the clip bound and the reciprocal of the forward rule
+struct CrsParams { int adj, maxAbs; LmcsScale sc; };
+
+template<bool CRS>
+__device__ __forceinline__ CrsParams crs_params( const vtmhip_jccr_job &j, int w, int h )
+{
+  CrsParams p;
+  p.adj    = CRS ? lmcs_job_adj( j.chromaAdj, w, h ) : 0;
+  p.maxAbs = ( 1 << j.bitDepth ) - 1;
+  p.sc     = lmcs_scale_of( CRS && p.adj ? p.adj : 1 );
+  return p;
+}
+
+// the (Cb, Cr) pair as the forward ICT sees it
+template<bool CRS>
+__device__ __forceinline__ void crs_fwd_pair( const CrsParams &p, int &cb, int &cr )
+{
+  if( CRS && p.adj ) { cb = lmcs_fwd( cb, p.sc, p.maxAbs ); cr = lmcs_fwd( cr, p.sc, p.maxAbs ); }
 }
 
 // ---- Quant::quant + Quant::dequant of one coefficient, flat scaling list (Quant.cpp:955-1038, 357-482), as tu_chain_kernel has them ---------------------
@@ -201,7 +231,7 @@ __device__ __forceinline__ void jccr_reduce_store( JccrSums a, long long ( *sRed
   }
 }
 
-template<int TPT>
+template<int TPT, bool CRS>
 __global__ __launch_bounds__( 256 ) void jccr_chain_kernel( const int16_t *__restrict__ resiBase, const vtmhip_jccr_job *__restrict__ jobs, int numJobs, DctTabs tabs,
                                                            int *__restrict__ levelsBase, int16_t *__restrict__ recCbBase, int16_t *__restrict__ recCrBase,
                                                            vtmhip_jccr_result *__restrict__ results, int maxW, int maxH )
@@ -224,12 +254,15 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_kernel( const int16_t *__res
   int           *levels = levelsBase ? levelsBase + j.outOff : nullptr;
   int16_t       *recCb = recCbBase ? recCbBase + j.outOff : nullptr, *recCr = recCrBase ? recCrBase + j.outOff : nullptr;
   JccrSums       a = { 0, 0, 0, 0, 0 };
+  const CrsParams crs = crs_params<CRS>( j, w, h );
   // load Cb and Cr once: the joint residual of the job's mode and its own distance
   for( int i = t; i < w * h; i += TPT )
   {
     const int  y = i / w, x = i - y * w;
     const long o = ( long ) y * j.resiStride + x;
-    const int  cb = cbp[o], cr = crp[o], c = ict_fwd( am, s, cb, cr );
+    int        cb = cbp[o], cr = crp[o];
+    crs_fwd_pair<CRS>( crs, cb, cr );
+    const int  c = ict_fwd( am, s, cb, cr );
     a.fwdDist += ict_dist( am, s, cb, cr, c );
     blk[i] = c;
   }
@@ -249,7 +282,7 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_kernel( const int16_t *__res
       if( levels ) levels[i] = q;
       const int  y = i / w, x = i - y * w;
       const long o = ( long ) y * j.resiStride + x;
-      jccr_finish( am, s, ( int ) ( int16_t ) q_dequant( qp, q ), cbp[o], crp[o], recCb, recCr, i, a.sseCb, a.sseCr );
+      jccr_finish<CRS>( am, s, ( int ) ( int16_t ) q_dequant( qp, q ), cbp[o], crp[o], recCb, recCr, i, a.sseCb, a.sseCr, crs.adj, crs.maxAbs );
     }
   }
   else
@@ -344,7 +377,7 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_kernel( const int16_t *__res
           for( int k = 0; k < cut; k++ ) sum += ( unsigned ) tmp[k * h + y] * ( unsigned ) ( int ) sM[k * w + x];
           const int  v  = min( 32767, max( -32768, ( int ) ( sum + rnd ) >> s2 ) );
           const long ro = ( long ) y * j.resiStride + x;   // the two original residuals again, from L2
-          jccr_finish( am, s, v, cbp[ro], crp[ro], recCb, recCr, o, a.sseCb, a.sseCr );
+          jccr_finish<CRS>( am, s, v, cbp[ro], crp[ro], recCb, recCr, o, a.sseCb, a.sseCr, crs.adj, crs.maxAbs );
         }
       }
     }
@@ -353,7 +386,7 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_kernel( const int16_t *__res
 }
 
 // ---- uniform 4x4 / 8x4 / 4x8 batches: ONE LANE per pair, the joint block in registers (tu_chain_lane_kernel between the two ICTs) ----------------------
-template<int W, int H>
+template<int W, int H, bool CRS>
 __global__ __launch_bounds__( 256 ) void jccr_chain_lane_kernel( const int16_t *__restrict__ resiBase, const vtmhip_jccr_job *__restrict__ jobs, int numJobs, DctTabs tabs,
                                                                 int *__restrict__ levelsBase, int16_t *__restrict__ recCbBase, int16_t *__restrict__ recCrBase,
                                                                 vtmhip_jccr_result *__restrict__ results )
@@ -370,6 +403,7 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_lane_kernel( const int16_t *
   const int16_t *cbp = resiBase + j.cbOff, *crp = resiBase + j.crOff;
   int            r[N], b[N], t[N];
   JccrSums       a = { 0, 0, 0, 0, 0 };
+  const CrsParams crs = crs_params<CRS>( j, W, H );
   const bool     aligned = ( ( j.cbOff | j.crOff | j.resiStride ) & 3 ) == 0;   // 8-byte aligned rows: 4 samples per load
   if( aligned )
   {
@@ -379,10 +413,11 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_lane_kernel( const int16_t *
       for( int x = 0; x < W; x += 4 )
       {
         const int2 vb = *reinterpret_cast<const int2 *>( cbp + ( long ) y * j.resiStride + x ), vr = *reinterpret_cast<const int2 *>( crp + ( long ) y * j.resiStride + x );
-        const int  cb4[4] = { ( int ) ( short ) vb.x, vb.x >> 16, ( int ) ( short ) vb.y, vb.y >> 16 }, cr4[4] = { ( int ) ( short ) vr.x, vr.x >> 16, ( int ) ( short ) vr.y, vr.y >> 16 };
+        int        cb4[4] = { ( int ) ( short ) vb.x, vb.x >> 16, ( int ) ( short ) vb.y, vb.y >> 16 }, cr4[4] = { ( int ) ( short ) vr.x, vr.x >> 16, ( int ) ( short ) vr.y, vr.y >> 16 };
 #pragma unroll
         for( int q = 0; q < 4; q++ )
         {
+          crs_fwd_pair<CRS>( crs, cb4[q], cr4[q] );
           const int c = ict_fwd( am, s, cb4[q], cr4[q] );
           a.fwdDist += ict_dist( am, s, cb4[q], cr4[q], c );
           r[y * W + x + q] = c;
@@ -396,7 +431,9 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_lane_kernel( const int16_t *
 #pragma unroll
       for( int x = 0; x < W; x++ )
       {
-        const int cb = cbp[( long ) y * j.resiStride + x], cr = crp[( long ) y * j.resiStride + x], c = ict_fwd( am, s, cb, cr );
+        int cb = cbp[( long ) y * j.resiStride + x], cr = crp[( long ) y * j.resiStride + x];
+        crs_fwd_pair<CRS>( crs, cb, cr );
+        const int c = ict_fwd( am, s, cb, cr );
         a.fwdDist += ict_dist( am, s, cb, cr, c );
         r[y * W + x] = c;
       }
@@ -475,7 +512,7 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_lane_kernel( const int16_t *
           const int2 vb = *reinterpret_cast<const int2 *>( cbp + ( long ) y * j.resiStride + x ), vr = *reinterpret_cast<const int2 *>( crp + ( long ) y * j.resiStride + x );
           const int  cb4[4] = { ( int ) ( short ) vb.x, vb.x >> 16, ( int ) ( short ) vb.y, vb.y >> 16 }, cr4[4] = { ( int ) ( short ) vr.x, vr.x >> 16, ( int ) ( short ) vr.y, vr.y >> 16 };
 #pragma unroll
-          for( int q = 0; q < 4; q++ ) jccr_finish( am, s, r[y * W + x + q], cb4[q], cr4[q], recCb, recCr, y * W + x + q, a.sseCb, a.sseCr );
+          for( int q = 0; q < 4; q++ ) jccr_finish<CRS>( am, s, r[y * W + x + q], cb4[q], cr4[q], recCb, recCr, y * W + x + q, a.sseCb, a.sseCr, crs.adj, crs.maxAbs );
         }
     }
     else
@@ -484,7 +521,8 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_lane_kernel( const int16_t *
       for( int y = 0; y < H; y++ )
 #pragma unroll
         for( int x = 0; x < W; x++ )
-          jccr_finish( am, s, r[y * W + x], cbp[( long ) y * j.resiStride + x], crp[( long ) y * j.resiStride + x], recCb, recCr, y * W + x, a.sseCb, a.sseCr );
+          jccr_finish<CRS>( am, s, r[y * W + x], cbp[( long ) y * j.resiStride + x], crp[( long ) y * j.resiStride + x], recCb, recCr, y * W + x, a.sseCb, a.sseCr, crs.adj,
+                            crs.maxAbs );
     }
   }
   results[jobIdx] = jccr_result_of( a );
@@ -576,7 +614,7 @@ __device__ __forceinline__ void jq_pass16( const int16_t *A, int aRowStride, con
   }
 }
 
-template<int LPT>
+template<int LPT, bool CRS>
 __global__ __launch_bounds__( 256 ) void jccr_chain_uni_kernel( const int16_t *__restrict__ resiBase, const vtmhip_jccr_job *__restrict__ jobs, int numJobs, DctTabs tabs,
                                                                int *__restrict__ levelsBase, int16_t *__restrict__ recCbBase, int16_t *__restrict__ recCrBase,
                                                                vtmhip_jccr_result *__restrict__ results, int w, int h )
@@ -615,10 +653,13 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_uni_kernel( const int16_t *_
   int16_t       *sR  = ( int16_t * ) blk;
   const int16_t *cbp = resiBase + j.cbOff, *crp = resiBase + j.crOff;
   JccrSums       a = { 0, 0, 0, 0, 0 };
+  const CrsParams crs = crs_params<CRS>( j, w, h );
   for( int i = t; i < w * h; i += LPT )
   {
     const long o  = ( long ) ( i >> lw ) * j.resiStride + ( i & ( w - 1 ) );
-    const int  cb = cbp[o], cr = crp[o], c = ict_fwd( am, s, cb, cr );
+    int        cb = cbp[o], cr = crp[o];
+    crs_fwd_pair<CRS>( crs, cb, cr );
+    const int  c = ict_fwd( am, s, cb, cr );
     a.fwdDist += ict_dist( am, s, cb, cr, c );
     sR[i] = ( int16_t ) c;
   }
@@ -653,7 +694,7 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_uni_kernel( const int16_t *_
     for( int i = t; i < w * h; i += LPT )
     {
       const long o = ( long ) ( i >> lw ) * j.resiStride + ( i & ( w - 1 ) );   // the two original residuals again, from L2
-      jccr_finish( am, s, rec32[i], cbp[o], crp[o], recCb, recCr, i, a.sseCb, a.sseCr );
+      jccr_finish<CRS>( am, s, rec32[i], cbp[o], crp[o], recCb, recCr, i, a.sseCb, a.sseCr, crs.adj, crs.maxAbs );
     }
   }
   jccr_reduce_store<LPT>( a, sRed, sub, t, live, results + ( live ? jobIdx : 0 ) );
@@ -677,27 +718,27 @@ int ensure_tables( vtmhip_ctx *ctx )
 
 bool pow2( int v ) { return v > 0 && ( v & ( v - 1 ) ) == 0; }
 
-template<int W, int H>
+template<int W, int H, bool CRS>
 int launch_lane( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int32_t *d_levelsBase, int16_t *d_recCbBase, int16_t *d_recCrBase,
                  vtmhip_jccr_result *d_results )
 {
   VTMHIP_TIME_KERNEL( ctx, "jccr_chain_lane_kernel" );
-  hipLaunchKernelGGL( ( jccr_chain_lane_kernel<W, H> ), dim3( ( n + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, d_resiBase, d_jobs, n, tabs_of( ctx ), d_levelsBase,
+  hipLaunchKernelGGL( ( jccr_chain_lane_kernel<W, H, CRS> ), dim3( ( n + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, d_resiBase, d_jobs, n, tabs_of( ctx ), d_levelsBase,
                       d_recCbBase, d_recCrBase, d_results );
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
 }
 
-template<int LPT>
+template<int LPT, bool CRS>
 int launch_uni( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int w, int h, int32_t *d_levelsBase, int16_t *d_recCbBase,
                 int16_t *d_recCrBase, vtmhip_jccr_result *d_results )
 {
   constexpr int TUS = 256 / LPT;
   const size_t  lds = TUS * ( ( size_t ) w * h + ( size_t ) w * ( h + 1 ) ) * sizeof( int ) + ( 2 * ( size_t ) w * w + 2 * ( size_t ) h * h ) * sizeof( int16_t );
   if( lds > 64 * 1024 )   // 64x64 only: 64.3 KB
-    VTMHIP_HIP( ctx, hipFuncSetAttribute( reinterpret_cast<const void *>( jccr_chain_uni_kernel<LPT> ), hipFuncAttributeMaxDynamicSharedMemorySize, ( int ) lds ) );
+    VTMHIP_HIP( ctx, hipFuncSetAttribute( reinterpret_cast<const void *>( jccr_chain_uni_kernel<LPT, CRS> ), hipFuncAttributeMaxDynamicSharedMemorySize, ( int ) lds ) );
   VTMHIP_TIME_KERNEL( ctx, "jccr_chain_uni_kernel" );
-  hipLaunchKernelGGL( jccr_chain_uni_kernel<LPT>, dim3( ( n + TUS - 1 ) / TUS ), dim3( 256 ), lds, ctx->stream, d_resiBase, d_jobs, n, tabs_of( ctx ), d_levelsBase,
+  hipLaunchKernelGGL( ( jccr_chain_uni_kernel<LPT, CRS> ), dim3( ( n + TUS - 1 ) / TUS ), dim3( 256 ), lds, ctx->stream, d_resiBase, d_jobs, n, tabs_of( ctx ), d_levelsBase,
                       d_recCbBase, d_recCrBase, d_results, w, h );
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
@@ -717,6 +758,75 @@ void stage_pair( char *hp, const int16_t *cb, int cbStride, const int16_t *cr, i
 void unstage( int16_t *dst, int dstStride, const char *src, int w, int h )
 {
   for( int y = 0; y < h; y++ ) memcpy( dst + ( ptrdiff_t ) y * dstStride, src + ( size_t ) y * w * 2, ( size_t ) w * 2 );
+}
+
+// vtmhip_jccr_chain_batch_dev (CRS == false) and vtmhip_jccr_chain_crs_batch_dev: one dispatch, the same launch paths
+template<bool CRS>
+int jccr_chain_entry( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
+                      int32_t *d_levelsBase, int16_t *d_recCbBase, int16_t *d_recCrBase, vtmhip_jccr_result *d_results )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
+  if( n == 0 ) return VTMHIP_OK;
+  VTMHIP_REQUIRE( ctx, d_resiBase && d_jobs && d_results, "null pointer" );
+  VTMHIP_REQUIRE( ctx, maxWidth >= 2 && maxWidth <= 64 && maxHeight >= 2 && maxHeight <= 64, "maxWidth / maxHeight: 2..64 (2-D transforms)" );
+  const bool lanePath = uniformSize && maxWidth * maxHeight <= 32 && maxWidth >= 4 && maxHeight >= 4;
+  const bool uniPath  = uniformSize && maxWidth >= 8 && maxHeight >= 8;
+  if( uniPath ) VTMHIP_REQUIRE( ctx, pow2( maxWidth ) && pow2( maxHeight ), "uniformSize: width / height must be powers of two (TU sizes are)" );
+  int st = ensure_tables( ctx );
+  if( st ) return st;
+  // the job table, checked on the host before anything is launched (the kernels index LDS and the core matrices by these fields)
+  {
+    const size_t bytes = ( size_t ) n * sizeof( vtmhip_jccr_job );
+    st = vtmhip_internal_scratch( ctx, bytes );
+    if( st ) return st;
+    VTMHIP_HIP( ctx, hipMemcpyAsync( ctx->pinned, d_jobs, bytes, hipMemcpyDeviceToHost, ctx->stream ) );
+    VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
+    const vtmhip_jccr_job *jobs = ( const vtmhip_jccr_job * ) ctx->pinned;
+    for( int i = 0; i < n; i++ )
+    {
+      const vtmhip_jccr_job &j = jobs[i];
+      const bool ts = j.typeHor == VTMHIP_TRSKIP;
+      VTMHIP_REQUIRE( ctx, j.cbfMask >= 1 && j.cbfMask <= 3, "cbfMask: 1 .. 3" );
+      VTMHIP_REQUIRE( ctx, ts || j.typeHor == VTMHIP_DCT2, "typeHor: VTMHIP_DCT2 or VTMHIP_TRSKIP" );
+      VTMHIP_REQUIRE( ctx, pow2( j.width ) && pow2( j.height ) && j.width >= 2 && j.height >= 2 && j.width <= maxWidth && j.height <= maxHeight,
+                      "width / height: powers of two, 2 .. maxWidth / maxHeight" );
+      VTMHIP_REQUIRE( ctx, !ts || ( j.width <= 32 && j.height <= 32 ), "transform skip: sides <= 32 (log2MaxTransformSkipBlockSize)" );
+      VTMHIP_REQUIRE( ctx, j.bitDepth >= 8 && j.bitDepth <= 12 && j.qpRem >= 0 && j.qpRem < 6 && j.qpPer >= 0, "bitDepth 8..12, qpRem 0..5, qpPer >= 0" );
+      VTMHIP_REQUIRE( ctx, !CRS || j.chromaAdj <= 32767, "chromaAdj: 0 (no scaling) .. 32767" );
+      VTMHIP_REQUIRE( ctx, !uniformSize || ( !ts && j.width == maxWidth && j.height == maxHeight ), "uniformSize: every job maxWidth x maxHeight with VTMHIP_DCT2" );
+    }
+  }
+  if( lanePath )
+  {
+    if( maxWidth == 4 && maxHeight == 4 ) return launch_lane<4, 4, CRS>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recCbBase, d_recCrBase, d_results );
+    if( maxWidth == 8 ) return launch_lane<8, 4, CRS>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recCbBase, d_recCrBase, d_results );
+    return launch_lane<4, 8, CRS>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recCbBase, d_recCrBase, d_results );
+  }
+  if( uniPath )
+  {
+    const int items = maxWidth * maxHeight / 16;   // one lane = 2 x 8 outputs of a transform pass
+#define VTMHIP_JCCR_UNI( LPT ) launch_uni<LPT, CRS>( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, d_levelsBase, d_recCbBase, d_recCrBase, d_results )
+    if( items <= 4 ) return VTMHIP_JCCR_UNI( 4 );
+    if( items <= 8 ) return VTMHIP_JCCR_UNI( 8 );
+    if( items <= 16 ) return VTMHIP_JCCR_UNI( 16 );
+    if( items <= 32 ) return VTMHIP_JCCR_UNI( 32 );
+    if( items <= 64 ) return VTMHIP_JCCR_UNI( 64 );
+    if( items <= 128 ) return VTMHIP_JCCR_UNI( 128 );
+    return VTMHIP_JCCR_UNI( 256 );
+#undef VTMHIP_JCCR_UNI
+  }
+  const int    mx    = maxWidth > maxHeight ? maxWidth : maxHeight;
+  const size_t perTu = ( size_t ) maxWidth * maxHeight + ( size_t ) maxWidth * ( maxHeight + 1 ) + ( ( mx * mx + 1 ) >> 1 );
+  VTMHIP_TIME_KERNEL( ctx, "jccr_chain_kernel" );
+  if( maxWidth * maxHeight <= 256 )
+    hipLaunchKernelGGL( ( jccr_chain_kernel<64, CRS> ), dim3( ( n + 3 ) / 4 ), dim3( 256 ), 4 * perTu * sizeof( int ), ctx->stream, d_resiBase, d_jobs, n, tabs_of( ctx ), d_levelsBase,
+                        d_recCbBase, d_recCrBase, d_results, maxWidth, maxHeight );
+  else
+    hipLaunchKernelGGL( ( jccr_chain_kernel<256, CRS> ), dim3( n ), dim3( 256 ), perTu * sizeof( int ), ctx->stream, d_resiBase, d_jobs, n, tabs_of( ctx ), d_levelsBase, d_recCbBase,
+                        d_recCrBase, d_results, maxWidth, maxHeight );
+  VTMHIP_LAUNCHED( ctx );
+  return VTMHIP_OK;
 }
 
 }   // namespace
@@ -832,67 +942,13 @@ int vtmhip_ict_select( const int64_t dist[4][2], int isIntra, int masks[2], int 
 int vtmhip_jccr_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
                                  int32_t *d_levelsBase, int16_t *d_recCbBase, int16_t *d_recCrBase, vtmhip_jccr_result *d_results )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_resiBase && d_jobs && d_results, "null pointer" );
-  VTMHIP_REQUIRE( ctx, maxWidth >= 2 && maxWidth <= 64 && maxHeight >= 2 && maxHeight <= 64, "maxWidth / maxHeight: 2..64 (2-D transforms)" );
-  const bool lanePath = uniformSize && maxWidth * maxHeight <= 32 && maxWidth >= 4 && maxHeight >= 4;
-  const bool uniPath  = uniformSize && maxWidth >= 8 && maxHeight >= 8;
-  if( uniPath ) VTMHIP_REQUIRE( ctx, pow2( maxWidth ) && pow2( maxHeight ), "uniformSize: width / height must be powers of two (TU sizes are)" );
-  int st = ensure_tables( ctx );
-  if( st ) return st;
-  // the job table, checked on the host before anything is launched (the kernels index LDS and the core matrices by these fields)
-  {
-    const size_t bytes = ( size_t ) n * sizeof( vtmhip_jccr_job );
-    st = vtmhip_internal_scratch( ctx, bytes );
-    if( st ) return st;
-    VTMHIP_HIP( ctx, hipMemcpyAsync( ctx->pinned, d_jobs, bytes, hipMemcpyDeviceToHost, ctx->stream ) );
-    VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
-    const vtmhip_jccr_job *jobs = ( const vtmhip_jccr_job * ) ctx->pinned;
-    for( int i = 0; i < n; i++ )
-    {
-      const vtmhip_jccr_job &j = jobs[i];
-      const bool ts = j.typeHor == VTMHIP_TRSKIP;
-      VTMHIP_REQUIRE( ctx, j.cbfMask >= 1 && j.cbfMask <= 3, "cbfMask: 1 .. 3" );
-      VTMHIP_REQUIRE( ctx, ts || j.typeHor == VTMHIP_DCT2, "typeHor: VTMHIP_DCT2 or VTMHIP_TRSKIP" );
-      VTMHIP_REQUIRE( ctx, pow2( j.width ) && pow2( j.height ) && j.width >= 2 && j.height >= 2 && j.width <= maxWidth && j.height <= maxHeight,
-                      "width / height: powers of two, 2 .. maxWidth / maxHeight" );
-      VTMHIP_REQUIRE( ctx, !ts || ( j.width <= 32 && j.height <= 32 ), "transform skip: sides <= 32 (log2MaxTransformSkipBlockSize)" );
-      VTMHIP_REQUIRE( ctx, j.bitDepth >= 8 && j.bitDepth <= 12 && j.qpRem >= 0 && j.qpRem < 6 && j.qpPer >= 0, "bitDepth 8..12, qpRem 0..5, qpPer >= 0" );
-      VTMHIP_REQUIRE( ctx, !uniformSize || ( !ts && j.width == maxWidth && j.height == maxHeight ), "uniformSize: every job maxWidth x maxHeight with VTMHIP_DCT2" );
-    }
-  }
-  if( lanePath )
-  {
-    if( maxWidth == 4 && maxHeight == 4 ) return launch_lane<4, 4>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recCbBase, d_recCrBase, d_results );
-    if( maxWidth == 8 ) return launch_lane<8, 4>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recCbBase, d_recCrBase, d_results );
-    return launch_lane<4, 8>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recCbBase, d_recCrBase, d_results );
-  }
-  if( uniPath )
-  {
-    const int items = maxWidth * maxHeight / 16;   // one lane = 2 x 8 outputs of a transform pass
-#define VTMHIP_JCCR_UNI( LPT ) launch_uni<LPT>( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, d_levelsBase, d_recCbBase, d_recCrBase, d_results )
-    if( items <= 4 ) return VTMHIP_JCCR_UNI( 4 );
-    if( items <= 8 ) return VTMHIP_JCCR_UNI( 8 );
-    if( items <= 16 ) return VTMHIP_JCCR_UNI( 16 );
-    if( items <= 32 ) return VTMHIP_JCCR_UNI( 32 );
-    if( items <= 64 ) return VTMHIP_JCCR_UNI( 64 );
-    if( items <= 128 ) return VTMHIP_JCCR_UNI( 128 );
-    return VTMHIP_JCCR_UNI( 256 );
-#undef VTMHIP_JCCR_UNI
-  }
-  const int    mx    = maxWidth > maxHeight ? maxWidth : maxHeight;
-  const size_t perTu = ( size_t ) maxWidth * maxHeight + ( size_t ) maxWidth * ( maxHeight + 1 ) + ( ( mx * mx + 1 ) >> 1 );
-  VTMHIP_TIME_KERNEL( ctx, "jccr_chain_kernel" );
-  if( maxWidth * maxHeight <= 256 )
-    hipLaunchKernelGGL( jccr_chain_kernel<64>, dim3( ( n + 3 ) / 4 ), dim3( 256 ), 4 * perTu * sizeof( int ), ctx->stream, d_resiBase, d_jobs, n, tabs_of( ctx ), d_levelsBase,
-                        d_recCbBase, d_recCrBase, d_results, maxWidth, maxHeight );
-  else
-    hipLaunchKernelGGL( jccr_chain_kernel<256>, dim3( n ), dim3( 256 ), perTu * sizeof( int ), ctx->stream, d_resiBase, d_jobs, n, tabs_of( ctx ), d_levelsBase, d_recCbBase,
-                        d_recCrBase, d_results, maxWidth, maxHeight );
-  VTMHIP_LAUNCHED( ctx );
-  return VTMHIP_OK;
+  return jccr_chain_entry<false>( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, uniformSize, d_levelsBase, d_recCbBase, d_recCrBase, d_results );
+}
+
+int vtmhip_jccr_chain_crs_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
+                                     int32_t *d_levelsBase, int16_t *d_recCbBase, int16_t *d_recCrBase, vtmhip_jccr_result *d_results )
+{
+  return jccr_chain_entry<true>( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, uniformSize, d_levelsBase, d_recCbBase, d_recCrBase, d_results );
 }
 
 }   // extern "C"

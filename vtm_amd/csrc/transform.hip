@@ -13,6 +13,7 @@
 #include "ctx.hpp"
 #include "bucket.hpp"
 #include "tr_tables.hpp"
+#include "lmcs.hpp"
 
 #include <cmath>
 #include <vector>
@@ -347,6 +348,10 @@ __global__ __launch_bounds__( 256 ) void dequant_kernel( const int *__restrict__
 // = transformNxN + invTransformNxN + getDistPart( DF_SSE ) of xEstimateInterResidualQT (EncoderLib/InterSearch.cpp:6637-6733) without the
 // CABAC bit estimate in between (host).  Everything stays in LDS; TPT threads per TU (64: four independent TUs per workgroup, wave-level
 // synchronisation only; 256: one TU per workgroup).
+//
+// CRS (the three chain kernels): LMCS chroma residual scaling fused in (vtmhip_tu_chain_crs_batch_dev; reference InterSearch.cpp:6628-6632, 6728-6733) -- two
+// per-sample hooks with lmcs.hpp's rules: at the load the working block gets fwd( r ) while the SSE copy keeps r, and in the epilogue the reconstruction goes
+// through inv() before the rec store and the SSE.  The job's adj (vtmhip_tu_job.chromaAdj) is 0 for "leave this job alone".  CRS == false is the plain chain.
 template<int TPT>
 __device__ __forceinline__ void tu_sync()
 {
@@ -354,7 +359,7 @@ __device__ __forceinline__ void tu_sync()
   else __syncthreads();
 }
 
-template<int TPT>
+template<int TPT, bool CRS>
 __global__ __launch_bounds__( 256 ) void tu_chain_kernel( const int16_t *__restrict__ resiBase, const vtmhip_tu_job *__restrict__ jobs, int numJobs,
                                                          TrTables tabs, int *__restrict__ levelsBase, int16_t *__restrict__ recBase,
                                                          vtmhip_tu_result *__restrict__ results, int maxW, int maxH )
@@ -374,11 +379,13 @@ __global__ __launch_bounds__( 256 ) void tu_chain_kernel( const int16_t *__restr
   int16_t            *sM  = ( int16_t * ) ( tmp + maxW * ( maxH + 1 ) );
   int16_t            *sR  = sM + ( ( mx * mx + 1 ) & ~1 );   // residual copy for the SSE
   const int16_t      *resi = resiBase + j.resiOff;
+  const int           adj = CRS ? lmcs_job_adj( j.chromaAdj, w, h ) : 0, maxAbs = ( 1 << bd ) - 1;
+  const LmcsScale     sc  = lmcs_scale_of( CRS && adj ? adj : 1 );
   for( int i = t; i < w * h; i += TPT )
   {
     const int y = i / w, x = i - y * w;
     const int16_t v = resi[( long ) y * j.resiStride + x];
-    blk[i] = v;
+    blk[i] = CRS && adj ? lmcs_fwd( v, sc, maxAbs ) : v;
     sR[i]  = v;
   }
   const int lw = ilog2( w ), lh = ilog2( h );
@@ -412,8 +419,9 @@ __global__ __launch_bounds__( 256 ) void tu_chain_kernel( const int16_t *__restr
       if( rightShift > 0 ) v = ( int ) ( ( unsigned ) ( qq * iscale ) + ( 1u << ( rightShift - 1 ) ) ) >> rightShift;
       else v = ( int ) ( ( unsigned ) ( qq * iscale ) << ( -rightShift ) );
       v = ( int ) ( int16_t ) min( 32767, max( -32768, v ) );
+      if( CRS && adj ) v = lmcs_inv( v, adj, maxAbs );
       if( rec ) rec[i] = ( int16_t ) v;
-      const int d = c - v;
+      const int d = ( CRS ? ( int ) sR[i] : c ) - v;   // CRS: c is the scaled sample, the distortion is taken against the kept copy
       sse += ( long long ) ( unsigned long long ) ( ( unsigned ) d * ( unsigned ) d );
     }
   }
@@ -524,7 +532,8 @@ __global__ __launch_bounds__( 256 ) void tu_chain_kernel( const int16_t *__restr
         const int y = o / w, x = o - y * w;
         unsigned  sum = 0;
         for( int k = 0; k < cut; k++ ) sum += ( unsigned ) tmp[k * h + y] * ( unsigned ) ( int ) sM[k * w + x];
-        const int v = min( 32767, max( -32768, ( int ) ( sum + rnd ) >> s2 ) );
+        int       v = min( 32767, max( -32768, ( int ) ( sum + rnd ) >> s2 ) );
+        if( CRS && adj ) v = lmcs_inv( v, adj, maxAbs );
         if( rec ) rec[o] = ( int16_t ) v;
         const int d = ( int ) sR[o] - ( int ) ( int16_t ) v;
         sse += ( long long ) ( unsigned long long ) ( ( unsigned ) d * ( unsigned ) d );
@@ -560,7 +569,7 @@ __global__ __launch_bounds__( 256 ) void tu_chain_kernel( const int16_t *__restr
 // ---- the smallest TUs (4x4, 8x4, 4x8: the chroma TUs of 8x8 / 16x8 / 8x16 PUs; 4x4 luma) of a uniform batch: ONE LANE per TU ---------------------------
 // The whole block lives in registers (W * H <= 32 values), the 4- / 8-point core matrices of the three types sit in LDS (staged once per workgroup);
 // the generic kernel above spends 64 threads and a dozen LDS round trips on such a block.  Same arithmetic, same order of the integer operations.
-template<int W, int H>
+template<int W, int H, bool CRS>
 __global__ __launch_bounds__( 256 ) void tu_chain_lane_kernel( const int16_t *__restrict__ resiBase, const vtmhip_tu_job *__restrict__ jobs, int numJobs, TrTables tabs,
                                                               int *__restrict__ levelsBase, int16_t *__restrict__ recBase, vtmhip_tu_result *__restrict__ results )
 {
@@ -594,6 +603,14 @@ __global__ __launch_bounds__( 256 ) void tu_chain_lane_kernel( const int16_t *__
     for( int y = 0; y < H; y++ )
 #pragma unroll
       for( int x = 0; x < W; x++ ) r[y * W + x] = resi[( long ) y * j.resiStride + x];
+  }
+  // CRS: r becomes fwd( r ); the epilogue reads the unscaled residual again (L2) instead of holding a second block in registers
+  const int adj = CRS ? lmcs_job_adj( j.chromaAdj, W, H ) : 0, maxAbs = ( 1 << bd ) - 1;
+  if( CRS && adj )
+  {
+    const LmcsScale sc = lmcs_scale_of( adj );
+#pragma unroll
+    for( int i = 0; i < N; i++ ) r[i] = lmcs_fwd( r[i], sc, maxAbs );
   }
   long long sumAbs = 0, absSum = 0, sse = 0;
   // forward: rows with the horizontal matrix, then columns with the vertical one (TrQuant::xT; no zero-out at these sizes)
@@ -673,9 +690,10 @@ __global__ __launch_bounds__( 256 ) void tu_chain_lane_kernel( const int16_t *__
         unsigned sum = 0;
 #pragma unroll
         for( int k = 0; k < W; k++ ) sum += ( unsigned ) t[k * H + y] * ( unsigned ) ( int ) mh[k * W + x];
-        const int v = min( 32767, max( -32768, ( int ) ( sum + rnd2 ) >> s2 ) );
+        int       v = min( 32767, max( -32768, ( int ) ( sum + rnd2 ) >> s2 ) );
+        if( CRS && adj ) v = lmcs_inv( v, adj, maxAbs );
         if( rec ) rec[y * W + x] = ( int16_t ) v;
-        const int d = r[y * W + x] - v;
+        const int d = ( CRS ? ( int ) resi[( long ) y * j.resiStride + x] : r[y * W + x] ) - v;
         sse += ( long long ) ( unsigned long long ) ( ( unsigned ) d * ( unsigned ) d );
       }
   }
@@ -684,12 +702,12 @@ __global__ __launch_bounds__( 256 ) void tu_chain_lane_kernel( const int16_t *__
   results[jobIdx] = res;
 }
 
-template<int W, int H>
+template<int W, int H, bool CRS>
 int launch_tu_lane( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int32_t *d_levelsBase, int16_t *d_recBase, vtmhip_tu_result *d_results,
                     const TrTables &tb )
 {
   VTMHIP_TIME_KERNEL( ctx, "tu_chain_lane_kernel" );
-  hipLaunchKernelGGL( ( tu_chain_lane_kernel<W, H> ), dim3( ( n + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, d_resiBase, d_jobs, n, tb, d_levelsBase, d_recBase, d_results );
+  hipLaunchKernelGGL( ( tu_chain_lane_kernel<W, H, CRS> ), dim3( ( n + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, d_resiBase, d_jobs, n, tb, d_levelsBase, d_recBase, d_results );
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
 }
@@ -841,7 +859,7 @@ __device__ __forceinline__ void tuq_pass16( const int16_t *A, int aRowStride, co
   }
 }
 
-template<int LPT>
+template<int LPT, bool CRS>
 __global__ __launch_bounds__( 256 ) void tu_chain_uni_kernel( const int16_t *__restrict__ resiBase, const vtmhip_tu_job *__restrict__ jobs, int numJobs,
                                                              TrTables tabs, int *__restrict__ levelsBase, int16_t *__restrict__ recBase,
                                                              vtmhip_tu_result *__restrict__ results, int w, int h, int *__restrict__ fwdCoefBase )
@@ -889,10 +907,13 @@ __global__ __launch_bounds__( 256 ) void tu_chain_uni_kernel( const int16_t *__r
   const int16_t *mH0 = sq ? sMat + ( j.typeVer * 2 ) * w * w : sMat + hBase + ( j.typeVer * 2 ) * h * h;          // M_H, rows k, k+1 interleaved
   const int16_t *mH1 = sq ? sMat + ( j.typeVer * 2 + 1 ) * w * w : sMat + hBase + ( j.typeVer * 2 + 1 ) * h * h;   // M_H^T: pair-interleaved (square) / plain
   const int16_t *resi = resiBase + j.resiOff;
+  const int       adj = CRS ? lmcs_job_adj( j.chromaAdj, w, h ) : 0, maxAbs = ( 1 << bd ) - 1;
+  const LmcsScale sc  = lmcs_scale_of( CRS && adj ? adj : 1 );
   for( int i = t; i < w * h; i += LPT )
   {
     const int y = i >> lw, x = i & ( w - 1 );
-    sR[i] = resi[( long ) y * j.resiStride + x];
+    const int16_t v = resi[( long ) y * j.resiStride + x];
+    sR[i] = CRS && adj ? ( int16_t ) lmcs_fwd( v, sc, maxAbs ) : v;   // fwd() clips to +-(2^bitDepth - 1): the packed first pass keeps its headroom
   }
   int16_t *dq16 = reinterpret_cast<int16_t *>( tmp );   // dequantised coefficients [k][k2] (after the second forward pass has consumed tmp)
   int16_t *t16  = reinterpret_cast<int16_t *>( blk );   // first inverse pass output [y][i] (after quantisation has consumed blk)
@@ -949,7 +970,8 @@ __global__ __launch_bounds__( 256 ) void tu_chain_uni_kernel( const int16_t *__r
       int16_t *rec = ( recBase && live ) ? recBase + j.outOff : nullptr;
       for( int i = t; i < w * h; i += LPT )
       {
-        const int v = rec32[i];
+        int v = rec32[i];
+        if( CRS && adj ) v = lmcs_inv( v, adj, maxAbs );
         if( rec ) rec[i] = ( int16_t ) v;
         const int d = ( int ) resi[( long ) ( i >> lw ) * j.resiStride + ( i & ( w - 1 ) )] - v;   // the residual again, from L2: its LDS copy made room for a third workgroup per CU
         sse += ( long long ) ( unsigned long long ) ( ( unsigned ) d * ( unsigned ) d );
@@ -989,7 +1011,7 @@ __global__ __launch_bounds__( 256 ) void tu_chain_uni_kernel( const int16_t *__r
   }
 }
 
-template<int LPT>
+template<int LPT, bool CRS>
 int launch_tu_uni( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int w, int h, int32_t *d_levelsBase, int16_t *d_recBase,
                    vtmhip_tu_result *d_results, const TrTables &tabs, int32_t *d_fwdCoefBase = nullptr )
 {
@@ -997,26 +1019,27 @@ int launch_tu_uni( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_j
   const size_t  perTu = ( size_t ) w * h + ( size_t ) w * ( h + 1 );
   const size_t  lds   = TUS * perTu * sizeof( int ) + ( ( size_t ) ( w > 32 ? 2 : 6 ) * w * w + ( w == h ? 0 : ( size_t ) ( h > 32 ? 2 : 6 ) * h * h ) ) * sizeof( int16_t );
   if( lds > 64 * 1024 )
-    VTMHIP_HIP( ctx, hipFuncSetAttribute( reinterpret_cast<const void *>( tu_chain_uni_kernel<LPT> ), hipFuncAttributeMaxDynamicSharedMemorySize, ( int ) lds ) );
+    VTMHIP_HIP( ctx, hipFuncSetAttribute( reinterpret_cast<const void *>( tu_chain_uni_kernel<LPT, CRS> ), hipFuncAttributeMaxDynamicSharedMemorySize, ( int ) lds ) );
   VTMHIP_TIME_KERNEL( ctx, "tu_chain_uni_kernel" );
-  hipLaunchKernelGGL( tu_chain_uni_kernel<LPT>, dim3( ( n + TUS - 1 ) / TUS ), dim3( 256 ), lds, ctx->stream, d_resiBase, d_jobs, n, tabs, d_levelsBase, d_recBase,
+  hipLaunchKernelGGL( ( tu_chain_uni_kernel<LPT, CRS> ), dim3( ( n + TUS - 1 ) / TUS ), dim3( 256 ), lds, ctx->stream, d_resiBase, d_jobs, n, tabs, d_levelsBase, d_recBase,
                       d_results, w, h, d_fwdCoefBase );
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
 }
 
 // LPT by block size: one lane = 2 x 8 outputs of a transform pass
+template<bool CRS>
 int launch_tu_uni_sized( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int w, int h, int32_t *d_levelsBase, int16_t *d_recBase,
                          vtmhip_tu_result *d_results, const TrTables &tb, int32_t *d_fwdCoefBase )
 {
   const int items = w * h / 16;
-  if( items <= 4 ) return launch_tu_uni<4>( ctx, d_resiBase, d_jobs, n, w, h, d_levelsBase, d_recBase, d_results, tb, d_fwdCoefBase );
-  if( items <= 8 ) return launch_tu_uni<8>( ctx, d_resiBase, d_jobs, n, w, h, d_levelsBase, d_recBase, d_results, tb, d_fwdCoefBase );
-  if( items <= 16 ) return launch_tu_uni<16>( ctx, d_resiBase, d_jobs, n, w, h, d_levelsBase, d_recBase, d_results, tb, d_fwdCoefBase );
-  if( items <= 32 ) return launch_tu_uni<32>( ctx, d_resiBase, d_jobs, n, w, h, d_levelsBase, d_recBase, d_results, tb, d_fwdCoefBase );
-  if( items <= 64 ) return launch_tu_uni<64>( ctx, d_resiBase, d_jobs, n, w, h, d_levelsBase, d_recBase, d_results, tb, d_fwdCoefBase );
-  if( items <= 128 ) return launch_tu_uni<128>( ctx, d_resiBase, d_jobs, n, w, h, d_levelsBase, d_recBase, d_results, tb, d_fwdCoefBase );
-  return launch_tu_uni<256>( ctx, d_resiBase, d_jobs, n, w, h, d_levelsBase, d_recBase, d_results, tb, d_fwdCoefBase );
+  if( items <= 4 ) return launch_tu_uni<4, CRS>( ctx, d_resiBase, d_jobs, n, w, h, d_levelsBase, d_recBase, d_results, tb, d_fwdCoefBase );
+  if( items <= 8 ) return launch_tu_uni<8, CRS>( ctx, d_resiBase, d_jobs, n, w, h, d_levelsBase, d_recBase, d_results, tb, d_fwdCoefBase );
+  if( items <= 16 ) return launch_tu_uni<16, CRS>( ctx, d_resiBase, d_jobs, n, w, h, d_levelsBase, d_recBase, d_results, tb, d_fwdCoefBase );
+  if( items <= 32 ) return launch_tu_uni<32, CRS>( ctx, d_resiBase, d_jobs, n, w, h, d_levelsBase, d_recBase, d_results, tb, d_fwdCoefBase );
+  if( items <= 64 ) return launch_tu_uni<64, CRS>( ctx, d_resiBase, d_jobs, n, w, h, d_levelsBase, d_recBase, d_results, tb, d_fwdCoefBase );
+  if( items <= 128 ) return launch_tu_uni<128, CRS>( ctx, d_resiBase, d_jobs, n, w, h, d_levelsBase, d_recBase, d_results, tb, d_fwdCoefBase );
+  return launch_tu_uni<256, CRS>( ctx, d_resiBase, d_jobs, n, w, h, d_levelsBase, d_recBase, d_results, tb, d_fwdCoefBase );
 }
 
 // Transform-skip candidates of a uniform batch (every job typeHor == VTMHIP_TRSKIP): elementwise, LPT = 8 lanes per TU (8 TUs per wave)
@@ -1078,6 +1101,7 @@ struct TuClassOf   // {8, 16, 32, 64} x {8, 16, 32, 64} with a real transform: c
   }
 };
 
+template<bool CRS>
 int tu_chain_generic( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int maxWidth, int maxHeight, int32_t *d_levelsBase,
                       int16_t *d_recBase, vtmhip_tu_result *d_results )
 {
@@ -1085,16 +1109,63 @@ int tu_chain_generic( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_t
   const size_t perTu = ( size_t ) maxWidth * maxHeight + ( size_t ) maxWidth * ( maxHeight + 1 ) + ( ( mx * mx + 1 ) >> 1 ) + ( ( maxWidth * maxHeight + 1 ) >> 1 );
   if( maxWidth * maxHeight <= 256 )
   {
-    hipLaunchKernelGGL( tu_chain_kernel<64>, dim3( ( n + 3 ) / 4 ), dim3( 256 ), 4 * perTu * sizeof( int ), ctx->stream, d_resiBase, d_jobs, n,
+    hipLaunchKernelGGL( ( tu_chain_kernel<64, CRS> ), dim3( ( n + 3 ) / 4 ), dim3( 256 ), 4 * perTu * sizeof( int ), ctx->stream, d_resiBase, d_jobs, n,
                         tabs_of( ctx ), d_levelsBase, d_recBase, d_results, maxWidth, maxHeight );
   }
   else
   {
-    hipLaunchKernelGGL( tu_chain_kernel<256>, dim3( n ), dim3( 256 ), perTu * sizeof( int ), ctx->stream, d_resiBase, d_jobs, n,
+    hipLaunchKernelGGL( ( tu_chain_kernel<256, CRS> ), dim3( n ), dim3( 256 ), perTu * sizeof( int ), ctx->stream, d_resiBase, d_jobs, n,
                         tabs_of( ctx ), d_levelsBase, d_recBase, d_results, maxWidth, maxHeight );
   }
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
+}
+
+// vtmhip_tu_chain_batch_dev (CRS == false) and vtmhip_tu_chain_crs_batch_dev: one dispatch, the same launch paths
+template<bool CRS>
+int tu_chain_entry( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
+                    int32_t *d_levelsBase, int16_t *d_recBase, vtmhip_tu_result *d_results )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
+  if( n == 0 ) return VTMHIP_OK;
+  VTMHIP_REQUIRE( ctx, d_resiBase && d_jobs && d_results, "null pointer" );
+  VTMHIP_REQUIRE( ctx, maxWidth >= 2 && maxWidth <= TB && maxHeight >= 2 && maxHeight <= TB, "maxWidth / maxHeight: 2..64 (2-D transforms)" );
+  int st = ensure_tables( ctx );
+  if( st ) return st;
+  // a mixed batch with enough TUs: bucket by shape on the device (bucket.hpp), the register-blocked kernel per {8,16,32,64} x {8,16,32,64} class, the
+  // generic kernel for the rest (4-sample sides, transform skip).  VTMHIP_TU_BUCKET=0 keeps the generic kernel for the whole batch.
+  static const bool bucket = !( getenv( "VTMHIP_TU_BUCKET" ) && atoi( getenv( "VTMHIP_TU_BUCKET" ) ) == 0 );
+  if( bucket && !uniformSize && n >= 256 && maxWidth >= 8 && maxHeight >= 8 && bucket_allowed( ctx ) )
+  {
+    BucketPlan plan;
+    st = bucket_begin<vtmhip_tu_job, vtmhip_tu_result>( ctx, d_jobs, n, TuClassOf(), plan );
+    if( st ) return st;
+    for( int c = 0; c < BUCKET_CLASSES; c++ )
+    {
+      if( !plan.count[c] ) continue;
+      const vtmhip_tu_job *jobs = ( const vtmhip_tu_job * ) plan.d_jobs + plan.offset[c];
+      vtmhip_tu_result    *res  = ( vtmhip_tu_result * ) plan.d_results + plan.offset[c];
+      if( c < 16 ) st = launch_tu_uni_sized<CRS>( ctx, d_resiBase, jobs, plan.count[c], 8 << ( c >> 2 ), 8 << ( c & 3 ), d_levelsBase, d_recBase, res, tabs_of( ctx ), nullptr );
+      else         st = tu_chain_generic<CRS>( ctx, d_resiBase, jobs, plan.count[c], maxWidth, maxHeight, d_levelsBase, d_recBase, res );
+      if( st ) return st;
+    }
+    return bucket_finish<vtmhip_tu_result>( ctx, plan, n, d_results );
+  }
+  if( uniformSize && maxWidth * maxHeight <= 32 && maxWidth >= 4 && maxHeight >= 4 )
+  {
+    // caller's promise: every TU is exactly maxWidth x maxHeight (4x4, 8x4 or 4x8) with a real transform -> one lane per TU
+    if( maxWidth == 4 && maxHeight == 4 ) return launch_tu_lane<4, 4, CRS>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recBase, d_results, tabs_of( ctx ) );
+    if( maxWidth == 8 ) return launch_tu_lane<8, 4, CRS>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recBase, d_results, tabs_of( ctx ) );
+    return launch_tu_lane<4, 8, CRS>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recBase, d_results, tabs_of( ctx ) );
+  }
+  if( uniformSize && maxWidth >= 8 && maxHeight >= 8 )
+  {
+    VTMHIP_REQUIRE( ctx, ( maxWidth & ( maxWidth - 1 ) ) == 0 && ( maxHeight & ( maxHeight - 1 ) ) == 0, "uniformSize: width / height must be powers of two (TU sizes are)" );
+    // caller's promise: every TU is exactly maxWidth x maxHeight -> register-blocked kernel, LPT lanes per TU
+    return launch_tu_uni_sized<CRS>( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, d_levelsBase, d_recBase, d_results, tabs_of( ctx ), nullptr );
+  }
+  return tu_chain_generic<CRS>( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, d_levelsBase, d_recBase, d_results );
 }
 
 struct MtsSelectArgs { double scaleSAD, fac; int numTU, numCand, maxCand; bool skip[8]; };
@@ -1235,46 +1306,13 @@ int vtmhip_dequant_batch_dev( vtmhip_ctx *ctx, const int32_t *d_qBase, int32_t *
 int vtmhip_tu_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int maxWidth, int maxHeight,
                                int uniformSize, int32_t *d_levelsBase, int16_t *d_recBase, vtmhip_tu_result *d_results )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_resiBase && d_jobs && d_results, "null pointer" );
-  VTMHIP_REQUIRE( ctx, maxWidth >= 2 && maxWidth <= TB && maxHeight >= 2 && maxHeight <= TB, "maxWidth / maxHeight: 2..64 (2-D transforms)" );
-  int st = ensure_tables( ctx );
-  if( st ) return st;
-  // a mixed batch with enough TUs: bucket by shape on the device (bucket.hpp), the register-blocked kernel per {8,16,32,64} x {8,16,32,64} class, the
-  // generic kernel for the rest (4-sample sides, transform skip).  VTMHIP_TU_BUCKET=0 keeps the generic kernel for the whole batch.
-  static const bool bucket = !( getenv( "VTMHIP_TU_BUCKET" ) && atoi( getenv( "VTMHIP_TU_BUCKET" ) ) == 0 );
-  if( bucket && !uniformSize && n >= 256 && maxWidth >= 8 && maxHeight >= 8 && bucket_allowed( ctx ) )
-  {
-    BucketPlan plan;
-    st = bucket_begin<vtmhip_tu_job, vtmhip_tu_result>( ctx, d_jobs, n, TuClassOf(), plan );
-    if( st ) return st;
-    for( int c = 0; c < BUCKET_CLASSES; c++ )
-    {
-      if( !plan.count[c] ) continue;
-      const vtmhip_tu_job *jobs = ( const vtmhip_tu_job * ) plan.d_jobs + plan.offset[c];
-      vtmhip_tu_result    *res  = ( vtmhip_tu_result * ) plan.d_results + plan.offset[c];
-      if( c < 16 ) st = launch_tu_uni_sized( ctx, d_resiBase, jobs, plan.count[c], 8 << ( c >> 2 ), 8 << ( c & 3 ), d_levelsBase, d_recBase, res, tabs_of( ctx ), nullptr );
-      else         st = tu_chain_generic( ctx, d_resiBase, jobs, plan.count[c], maxWidth, maxHeight, d_levelsBase, d_recBase, res );
-      if( st ) return st;
-    }
-    return bucket_finish<vtmhip_tu_result>( ctx, plan, n, d_results );
-  }
-  if( uniformSize && maxWidth * maxHeight <= 32 && maxWidth >= 4 && maxHeight >= 4 )
-  {
-    // caller's promise: every TU is exactly maxWidth x maxHeight (4x4, 8x4 or 4x8) with a real transform -> one lane per TU
-    if( maxWidth == 4 && maxHeight == 4 ) return launch_tu_lane<4, 4>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recBase, d_results, tabs_of( ctx ) );
-    if( maxWidth == 8 ) return launch_tu_lane<8, 4>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recBase, d_results, tabs_of( ctx ) );
-    return launch_tu_lane<4, 8>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recBase, d_results, tabs_of( ctx ) );
-  }
-  if( uniformSize && maxWidth >= 8 && maxHeight >= 8 )
-  {
-    VTMHIP_REQUIRE( ctx, ( maxWidth & ( maxWidth - 1 ) ) == 0 && ( maxHeight & ( maxHeight - 1 ) ) == 0, "uniformSize: width / height must be powers of two (TU sizes are)" );
-    // caller's promise: every TU is exactly maxWidth x maxHeight -> register-blocked kernel, LPT lanes per TU
-    return launch_tu_uni_sized( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, d_levelsBase, d_recBase, d_results, tabs_of( ctx ), nullptr );
-  }
-  return tu_chain_generic( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, d_levelsBase, d_recBase, d_results );
+  return tu_chain_entry<false>( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, uniformSize, d_levelsBase, d_recBase, d_results );
+}
+
+int vtmhip_tu_chain_crs_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int maxWidth, int maxHeight,
+                                   int uniformSize, int32_t *d_levelsBase, int16_t *d_recBase, vtmhip_tu_result *d_results )
+{
+  return tu_chain_entry<true>( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, uniformSize, d_levelsBase, d_recBase, d_results );
 }
 
 int vtmhip_tu_ts_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int width, int height,
@@ -1377,7 +1415,7 @@ extern "C" int vtmhip_xT_uniform_batch_dev( vtmhip_ctx *ctx, const int16_t *d_re
   VTMHIP_REQUIRE( ctx, width >= 8 && width <= TB && height >= 8 && height <= TB && pow2( width ) && pow2( height ), "width / height: powers of two 8..64" );
   int st = ensure_tables( ctx );
   if( st ) return st;
-  return launch_tu_uni_sized( ctx, d_resiBase, d_jobs, n, width, height, nullptr, nullptr, d_results, tabs_of( ctx ), d_coefBase );
+  return launch_tu_uni_sized<false>( ctx, d_resiBase, d_jobs, n, width, height, nullptr, nullptr, d_results, tabs_of( ctx ), d_coefBase );
 }
 
 

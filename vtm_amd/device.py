@@ -8,8 +8,8 @@ import ctypes as C
 import numpy as np
 
 from . import lib as _lib
-from .lib import (AffineJob, DistJob, FracJob, FracResult, FullJob, IctJob, IfJob, JccrJob, JccrResult, McJob, MeResult, PelOpJob, PicParams, QuantJob,   # noqa: F401
-                  TrJob, TuJob, TuResult, TzJob, VtmHipError, WpDistJob, WpParam, WpPredJob, WtdJob)
+from .lib import (AffineJob, DistJob, FracJob, FracResult, FullJob, IctJob, IfJob, JccrJob, JccrResult, LmcsJob, McJob, MeResult, PelOpJob, PicParams, QuantJob,   # noqa: F401
+                  ScaleJob, TrJob, TuJob, TuResult, TzJob, VtmHipError, WpDistJob, WpParam, WpPredJob, WtdJob)
 
 
 class DevBuf:
@@ -234,6 +234,25 @@ class Context:
         assert cr.shape == cb.shape and cb.strides[1] == 2 and cr.strides[1] == 2
         self._check(self.L.vtmhip_invTransformCbCr(self.h, mode, cb.ctypes.data, cb.strides[0] // 2, cr.ctypes.data, cr.strides[0] // 2, w, h))
 
+    def set_lmcs_fwd_lut(self, fwd_lut, luma_bd):
+        """The reshaper's forward LUT (int16, 1 << luma_bd entries) for lmcs_resi_batch / lmcs_reco_batch."""
+        lut = np.ascontiguousarray(fwd_lut, np.int16)
+        assert lut.size >= 1 << luma_bd
+        self._check(self.L.vtmhip_set_lmcs_fwd_lut(self.h, lut.ctypes.data, luma_bd))
+
+    def rspSignal(self, buf, lut):
+        """AreaBuf<Pel>::rspSignal( lut ), in place on a 2-D int16 host array (any row stride)."""
+        h, w = buf.shape
+        lut = np.ascontiguousarray(lut, np.int16)
+        assert buf.strides[1] == 2
+        self._check(self.L.vtmhip_rspSignal(self.h, buf.ctypes.data, buf.strides[0] // 2, w, h, lut.ctypes.data, lut.size))
+
+    def scaleSignal(self, buf, scale, fwd, bit_depth):
+        """AreaBuf<Pel>::scaleSignal( scale, dir, clpRng ), in place on a 2-D int16 host array (any row stride)."""
+        h, w = buf.shape
+        assert buf.strides[1] == 2
+        self._check(self.L.vtmhip_scaleSignal(self.h, buf.ctypes.data, buf.strides[0] // 2, w, h, scale, int(fwd), bit_depth))
+
     # ---- batched device calls (device pointers: DevBuf.ptr or tensor.data_ptr()) ---------------------------------
     def dist_batch(self, d_org, d_cur, d_jobs, n, d_out):
         self._check(self.L.vtmhip_dist_batch_dev(self.h, d_org, d_cur, d_jobs, n, d_out))
@@ -416,6 +435,26 @@ class Context:
     def jccr_chain_batch(self, d_resi, d_jobs, n, max_w, max_h, d_results, d_levels=None, d_rec_cb=None, d_rec_cr=None, uniform=False):
         """the joint Cb-Cr candidate of n JccrJob pairs: forward ICT -> xT -> quant -> dequant -> xIT -> inverse ICT -> SSE of Cb and of Cr (JccrResult)"""
         self._check(self.L.vtmhip_jccr_chain_batch_dev(self.h, d_resi, d_jobs, n, max_w, max_h, int(uniform), d_levels, d_rec_cb, d_rec_cr, d_results))
+
+    def tu_chain_crs_batch(self, d_resi, d_jobs, n, max_w, max_h, d_results, d_levels=None, d_rec=None, uniform=False):
+        """tu_chain_batch with LMCS chroma residual scaling fused in: TuJob.chromaAdj = tu.getChromaAdj() or 0; sse against the unscaled residual"""
+        self._check(self.L.vtmhip_tu_chain_crs_batch_dev(self.h, d_resi, d_jobs, n, max_w, max_h, int(uniform), d_levels, d_rec, d_results))
+
+    def jccr_chain_crs_batch(self, d_resi, d_jobs, n, max_w, max_h, d_results, d_levels=None, d_rec_cb=None, d_rec_cr=None, uniform=False):
+        """jccr_chain_batch with LMCS chroma residual scaling around the joint candidate: JccrJob.chromaAdj = tu.getChromaAdj() or 0"""
+        self._check(self.L.vtmhip_jccr_chain_crs_batch_dev(self.h, d_resi, d_jobs, n, max_w, max_h, int(uniform), d_levels, d_rec_cb, d_rec_cr, d_results))
+
+    def scale_signal_batch(self, d_src, d_dst, d_jobs, n):
+        """scaleSignal of n ScaleJob blocks, each with its own scale and direction (d_dst may be d_src: in place)"""
+        self._check(self.L.vtmhip_scale_signal_batch_dev(self.h, d_src, d_dst, d_jobs, n))
+
+    def lmcs_resi_batch(self, d_org, d_pred, d_resi, d_jobs, n, d_dst=None):
+        """resi = fwdLUT[org] - (MAP_PRED ? fwdLUT[pred] : pred) for n LmcsJob blocks; WRITE_MAPPED jobs also write that prediction to d_dst"""
+        self._check(self.L.vtmhip_lmcs_resi_batch_dev(self.h, d_org, d_pred, d_resi, d_dst, d_jobs, n))
+
+    def lmcs_reco_batch(self, d_pred, d_resi, d_dst, d_jobs, n):
+        """reco = clip((MAP_PRED ? fwdLUT[pred] : pred) + resi) for n LmcsJob blocks"""
+        self._check(self.L.vtmhip_lmcs_reco_batch_dev(self.h, d_pred, d_resi, d_dst, d_jobs, n))
 
     def affine_sobel_batch(self, d_pred, d_deriv, d_jobs, n):
         self._check(self.L.vtmhip_affine_sobel_batch_dev(self.h, d_pred, d_deriv, d_jobs, n))

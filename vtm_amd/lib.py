@@ -15,6 +15,7 @@ WP_INVALID_DIST = (1 << 64) - 1   # d_dist of a rejected vtmhip_wp_dist_job
 WP_UNI, WP_BI = 0, 1              # vtmhip_wp_pred_job.mode
 DCT2, DCT8, DST7, TRSKIP = 0, 1, 2, 3
 ICT_MODES = ((0, 3, 1, 2), (0, -3, -1, -2))   # g_ictModes[signFlag][cbfMask]
+LMCS_MAP_PRED, LMCS_WRITE_MAPPED = 1, 2       # vtmhip_lmcs_job.flags
 
 
 class DistJob(C.Structure):
@@ -97,7 +98,8 @@ class PelOpJob(C.Structure):
 class TuJob(C.Structure):
     _fields_ = [("resiOff", C.c_int64), ("outOff", C.c_int64), ("resiStride", C.c_int32), ("width", C.c_int16),
                 ("height", C.c_int16), ("qpPer", C.c_int16), ("qpRem", C.c_int16), ("typeHor", C.c_uint8),
-                ("typeVer", C.c_uint8), ("bitDepth", C.c_uint8), ("isIRAP", C.c_uint8), ("pad", C.c_int32)]
+                ("typeVer", C.c_uint8), ("bitDepth", C.c_uint8), ("isIRAP", C.c_uint8), ("pad", C.c_int32),
+                ("chromaAdj", C.c_int32)]   # bytes 36 .. 39: read by vtmhip_tu_chain_crs_batch_dev only
 
 
 class TuResult(C.Structure):
@@ -268,14 +270,37 @@ class IctJob(C.Structure):
                 ("height", C.c_int16), ("signFlag", C.c_uint8), ("maskBits", C.c_uint8), ("pad0", C.c_uint8), ("pad1", C.c_uint8)]
 
 
+class _JccrAdj(C.Structure):   # overlays JccrJob.pad (byte 41 on): chromaAdj at byte 42, read by vtmhip_jccr_chain_crs_batch_dev only
+    _pack_ = 1
+    _fields_ = [("reserved0", C.c_uint8), ("chromaAdj", C.c_uint16), ("reserved1", C.c_uint8 * 4)]
+
+
+class _JccrTail(C.Union):
+    _pack_ = 1
+    _anonymous_ = ("crs",)
+    _fields_ = [("pad", C.c_uint8 * 7), ("crs", _JccrAdj)]
+
+
 class JccrJob(C.Structure):
+    _anonymous_ = ("tail",)
     _fields_ = [("cbOff", C.c_int64), ("crOff", C.c_int64), ("outOff", C.c_int64), ("resiStride", C.c_int32), ("width", C.c_int16), ("height", C.c_int16),
                 ("qpPer", C.c_int16), ("qpRem", C.c_int16), ("typeHor", C.c_uint8), ("bitDepth", C.c_uint8), ("isIRAP", C.c_uint8), ("cbfMask", C.c_uint8),
-                ("signFlag", C.c_uint8), ("pad", C.c_uint8 * 7)]
+                ("signFlag", C.c_uint8), ("tail", _JccrTail)]
 
 
 class JccrResult(C.Structure):
     _fields_ = [("sseCb", C.c_uint64), ("sseCr", C.c_uint64), ("fwdDist", C.c_int64), ("sumAbs", C.c_int32), ("absSum", C.c_int32)]
+
+
+class LmcsJob(C.Structure):
+    _fields_ = [("orgOff", C.c_int64), ("predOff", C.c_int64), ("resiOff", C.c_int64), ("dstOff", C.c_int64), ("orgStride", C.c_int32), ("predStride", C.c_int32),
+                ("resiStride", C.c_int32), ("dstStride", C.c_int32), ("width", C.c_int16), ("height", C.c_int16), ("bitDepth", C.c_uint8), ("flags", C.c_uint8),
+                ("pad0", C.c_uint8), ("pad1", C.c_uint8)]
+
+
+class ScaleJob(C.Structure):
+    _fields_ = [("srcOff", C.c_int64), ("dstOff", C.c_int64), ("srcStride", C.c_int32), ("dstStride", C.c_int32), ("width", C.c_int16), ("height", C.c_int16),
+                ("scale", C.c_uint16), ("dir", C.c_uint8), ("bitDepth", C.c_uint8)]
 
 
 _STRUCTS = [DistJob, TzJob, MeResult, PicParams, IfJob, FracJob, FracResult, TrJob, QuantJob, FullJob, McJob, PelOpJob,
@@ -283,6 +308,7 @@ _STRUCTS = [DistJob, TzJob, MeResult, PicParams, IfJob, FracJob, FracResult, TrJ
             PisRow, PisPu, PisLevel, AffineMeJob, AffineMeOut, LfnstTuJob, PisLevelRun, PisBuffers, SmvdJob, PisPuIn, WtdJob,
             WpDistJob, WpPredJob]   # order of vtmhip_struct_size(which)
 _JCCR_STRUCTS = [IctJob, JccrJob, JccrResult]   # order of vtmhip_jccr_struct_size(which)
+_LMCS_STRUCTS = [LmcsJob, ScaleJob]             # order of vtmhip_lmcs_struct_size(which)
 
 # every symbol include/vtmhip.h declares (tests/test_abi.py checks the exports against the header text)
 _PROTOS = {
@@ -346,6 +372,15 @@ _PROTOS = {
     "vtmhip_ict_fwd_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vtmhip_ict_select": (C.c_int, [C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vtmhip_jccr_chain_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtmhip_tu_chain_crs_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtmhip_jccr_chain_crs_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtmhip_lmcs_struct_size": (C.c_int, [C.c_int]),
+    "vtmhip_set_lmcs_fwd_lut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "vtmhip_rspSignal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "vtmhip_scaleSignal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vtmhip_scale_signal_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "vtmhip_lmcs_resi_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "vtmhip_lmcs_reco_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "vtmhip_filterHor": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                    C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vtmhip_filterVer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
@@ -466,6 +501,10 @@ def load():
         if lib.vtmhip_jccr_struct_size(i) != C.sizeof(s):
             raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
                               % (s.__name__, C.sizeof(s), lib.vtmhip_jccr_struct_size(i)))
+    for i, s in enumerate(_LMCS_STRUCTS):
+        if lib.vtmhip_lmcs_struct_size(i) != C.sizeof(s):
+            raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
+                              % (s.__name__, C.sizeof(s), lib.vtmhip_lmcs_struct_size(i)))
     _lib = lib
     return lib
 
