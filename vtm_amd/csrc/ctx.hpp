@@ -104,6 +104,7 @@ struct vtmhip_launch_timer
 #define VTMHIP_LAUNCHED( ctx ) VTMHIP_HIP( ctx, hipGetLastError() )
 
 int vtmhip_internal_scratch( vtmhip_ctx *ctx, size_t bytes );   // grows ctx->scratch / ctx->pinned
+int vtmhip_internal_tr_tables( vtmhip_ctx *ctx );               // transform.hip: fills ctx->trTab / trTabBuf on first use (under initMutex)
 int vtmhip_internal_mc_launch( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_refBase, int16_t *d_predBase, int16_t *d_outBase, const vtmhip_pred_job *d_jobs,
                                int n, int maxWidth, int maxHeight, unsigned long long *d_sadOut );   // mc.hip: motionCompensation, optionally reduced to the SAD against the original
 int vtmhip_internal_mc_amvp_launch( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, const vtmhip_me_job *d_rows, int n,

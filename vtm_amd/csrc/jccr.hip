@@ -5,14 +5,13 @@
 // xEstimateInterResidualQT, EncoderLib/InterSearch.cpp:6813-7032 (forward ICT :6851, transformNxN on the coded component :6884-6890, invTransformNxN +
 // invTransformICT :6964-6975, DF_SSE of Cb and Cr against the original residuals :6984-6998).
 //
-// The chain kernels repeat the arithmetic of the single-component chain (transform.hip tu_chain_kernel / tu_chain_lane_kernel / tu_chain_uni_kernel, same
-// order of the integer operations) between a forward ICT at the load and an inverse ICT + two SSEs at the end; chroma joint candidates are DCT2 / DCT2 or
-// transform skip, so only the DCT-2 matrices are staged.  transform.hip itself is untouched.
+// The chain kernels run the stages of the single-component chain (tu_stages.hpp: the same definitions transform.hip's tu_chain_kernel / tu_chain_lane_kernel /
+// tu_chain_uni_kernel call) between a forward ICT at the load and an inverse ICT + two SSEs at the end; chroma joint candidates are DCT2 / DCT2 or transform
+// skip, so only the DCT-2 matrices are staged.
 //
 // Headroom: a joint residual is a Pel, so every path takes the whole int16 range.  The generic and the lane kernel multiply and accumulate in 32 bits like the
-// reference.  The register-blocked kernel keeps the int16-packed first pass: v_dot2 of int16 pairs into a 32-bit accumulator is exact for |sum| <= N * 32768 *
-// 90 < 2^31 (N <= 64), and the pass's output is bounded by sum|m| * 32768 >> (log2 N + bitDepth - 9) <= 64 N * 2^15 >> (log2 N + bitDepth - 9) = 2^(30 - bitDepth)
-// <= 2^22 for bitDepth >= 8, inside the signed 24-bit operands of the second pass.  The residuals an encoder produces stay far below: 6 (2^bitDepth - 1) / 5.
+// reference; the register-blocked kernel's packed passes are exact for it too (tu_stages.hpp states the bound).  The residuals an encoder produces stay far
+// below: 6 (2^bitDepth - 1) / 5.
 //
 // CRS (template flag of the three chain kernels, vtmhip_jccr_chain_crs_batch_dev): LMCS chroma residual scaling around the joint candidate (InterSearch.cpp:6822-6823,
 // 6838-6842, 6977-6998) with lmcs.hpp's rules -- Cb and Cr go through fwd() before the forward ICT (fwdDist is the distance on the scaled pair), both rebuilt blocks
@@ -21,17 +20,12 @@
 // Out of scope: ACT, the picture-level sign decision (the caller passes signFlag), the CABAC estimate.
 #include "ctx.hpp"
 #include "lmcs.hpp"
+#include "tu_stages.hpp"
 
 namespace
 {
 
 struct DctTabs { const int16_t *m[7]; };   // [log2 N] -> device pointer to the N x N forward DCT-2 matrix (row-major)
-
-__constant__ int c_jqScales[2][6]    = { { 26214, 23302, 20560, 18396, 16384, 14564 }, { 18396, 16384, 14564, 13107, 11651, 10280 } };   // g_quantScales, Rom.cpp:463-473
-__constant__ int c_jqInvScales[2][6] = { { 40, 45, 51, 57, 64, 72 }, { 57, 64, 72, 80, 90, 102 } };
-
-__device__ __forceinline__ int ilog2( int v ) { return 31 - __clz( v ); }
-__device__ __forceinline__ int zero_out( int n ) { return n > 32 ? n - 32 : 0; }   // DCT-2: the columns / rows past 32 (TrQuant.cpp:792-796)
 
 // ---- the ICT rules ---------------------------------------------------------------------------------------------------------------------------------
 __host__ __device__ __forceinline__ int ict_abs_mode( int cbfMask ) { return cbfMask == 1 ? 3 : cbfMask - 1; }   // |g_ictModes[.][cbfMask]|, cbfMask 1 .. 3
@@ -93,41 +87,7 @@ __device__ __forceinline__ void crs_fwd_pair( const CrsParams &p, int &cb, int &
   if( CRS && p.adj ) { cb = lmcs_fwd( cb, p.sc, p.maxAbs ); cr = lmcs_fwd( cr, p.sc, p.maxAbs ); }
 }
 
-// ---- Quant::quant + Quant::dequant of one coefficient, flat scaling list (Quant.cpp:955-1038, 357-482), as tu_chain_kernel has them ---------------------
-struct QParams { long long add; int qBits, scale, iscale, rightShift, inMin, inMax; };
-
-__device__ __forceinline__ QParams q_params( const vtmhip_jccr_job &j, int lw, int lh, bool ts )
-{
-  const int needSqrt = ts ? 0 : ( lw + lh ) & 1;
-  const int trShift  = ts ? 0 : 15 - j.bitDepth - ( ( lw + lh ) >> 1 ) + ( needSqrt ? -1 : 0 );
-  QParams   p;
-  p.qBits      = 14 + j.qpPer + trShift;
-  p.add        = ( long long ) ( j.isIRAP ? 171 : 85 ) << ( p.qBits - 9 );
-  p.scale      = c_jqScales[needSqrt][j.qpRem];
-  p.iscale     = c_jqInvScales[needSqrt][j.qpRem];
-  p.rightShift = 6 - ( trShift + j.qpPer );
-  const int inBits = min( 16, 32 + p.rightShift - 7 );
-  p.inMin = -( 1 << ( inBits - 1 ) );
-  p.inMax = ( 1 << ( inBits - 1 ) ) - 1;
-  return p;
-}
-
-__device__ __forceinline__ int q_level( const QParams &p, int c, long long &absSum )
-{
-  const long long tt  = ( long long ) abs( c ) * p.scale;
-  const int       mag = ( int ) ( ( tt + p.add ) >> p.qBits );
-  absSum += mag;
-  return min( 32767, max( -32768, c < 0 ? -mag : mag ) );
-}
-
-__device__ __forceinline__ int q_dequant( const QParams &p, int q )
-{
-  const int qq = min( p.inMax, max( p.inMin, q ) );
-  int       v;
-  if( p.rightShift > 0 ) v = ( int ) ( ( unsigned ) ( qq * p.iscale ) + ( 1u << ( p.rightShift - 1 ) ) ) >> p.rightShift;
-  else v = ( int ) ( ( unsigned ) ( qq * p.iscale ) << ( -p.rightShift ) );
-  return min( 32767, max( -32768, v ) );
-}
+__device__ __forceinline__ QuantRule quant_rule_of( const vtmhip_jccr_job &j, int lw, int lh, bool ts ) { return quant_rule( j.bitDepth, j.qpPer, j.qpRem, j.isIRAP, lw, lh, ts ); }
 
 // ---- forward ICT of all four cbfMasks: one wave per (Cb, Cr) pair --------------------------------------------------------------------------------------
 __global__ __launch_bounds__( 256 ) void ict_fwd_kernel( const int16_t *__restrict__ resiBase, const vtmhip_ict_job *__restrict__ jobs, int n,
@@ -177,13 +137,6 @@ __global__ __launch_bounds__( 256 ) void ict_inv_kernel( int16_t *__restrict__ c
 
 // ---- the joint chain, generic path: everything in LDS, TPT threads per pair (64: four independent pairs per workgroup, wave-level synchronisation only;
 // 256: one pair per workgroup) -- tu_chain_kernel between the two ICTs ---------------------------------------------------------------------------------
-template<int TPT>
-__device__ __forceinline__ void jc_sync()
-{
-  if( TPT <= 64 ) { __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" ); __builtin_amdgcn_wave_barrier(); }
-  else __syncthreads();
-}
-
 struct JccrSums { long long sumAbs, absSum, sseCb, sseCr, fwdDist; };
 
 __device__ __forceinline__ vtmhip_jccr_result jccr_result_of( const JccrSums &a )
@@ -193,42 +146,12 @@ __device__ __forceinline__ vtmhip_jccr_result jccr_result_of( const JccrSums &a 
   return r;
 }
 
-// the five sums over the TPT threads of a pair (TPT > 64: across its waves through sRed)
+// the five sums over the TPT threads of a pair
 template<int TPT>
-__device__ __forceinline__ void jccr_reduce_store( JccrSums a, long long ( *sRed )[5], int sub, int t, bool live, vtmhip_jccr_result *out )
+__device__ __forceinline__ void jccr_reduce_store( const JccrSums &a, long long ( *sRed )[5], int sub, int t, bool live, vtmhip_jccr_result *out )
 {
   long long v[5] = { a.sumAbs, a.absSum, a.sseCb, a.sseCr, a.fwdDist };
-  if( TPT <= 64 )
-  {
-#pragma unroll
-    for( int o = 32; o > 0; o >>= 1 )
-      if( o < TPT )
-      {
-#pragma unroll
-        for( int k = 0; k < 5; k++ ) v[k] += __shfl_xor( v[k], o, 64 );
-      }
-    if( t == 0 && live ) { const JccrSums r = { v[0], v[1], v[2], v[3], v[4] }; *out = jccr_result_of( r ); }
-    return;
-  }
-#pragma unroll
-  for( int k = 0; k < 5; k++ ) v[k] = ( long long ) wave_reduce_add_u64( ( unsigned long long ) v[k] );
-  __syncthreads();
-  if( ( threadIdx.x & 63 ) == 0 )
-  {
-#pragma unroll
-    for( int k = 0; k < 5; k++ ) sRed[threadIdx.x >> 6][k] = v[k];
-  }
-  __syncthreads();
-  constexpr int WPT = TPT > 64 ? TPT / 64 : 1;   // waves per pair
-  if( t == 0 && live )
-  {
-    long long r[5] = { 0, 0, 0, 0, 0 };
-    for( int q = 0; q < WPT; q++ )
-#pragma unroll
-      for( int k = 0; k < 5; k++ ) r[k] += sRed[sub * WPT + q][k];
-    const JccrSums rs = { r[0], r[1], r[2], r[3], r[4] };
-    *out = jccr_result_of( rs );
-  }
+  chain_reduce_store<TPT, 5>( v, sRed, sub, t, live, [out]( const long long ( &r )[5] ) { const JccrSums rs = { r[0], r[1], r[2], r[3], r[4] }; *out = jccr_result_of( rs ); } );
 }
 
 template<int TPT, bool CRS>
@@ -251,8 +174,6 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_kernel( const int16_t *__res
   int16_t       *sM  = ( int16_t * ) ( tmp + maxW * ( maxH + 1 ) );
   const int16_t *cbp = resiBase + j.cbOff, *crp = resiBase + j.crOff;
   const int      am = ict_abs_mode( j.cbfMask ), s = j.signFlag ? -1 : 1;
-  int           *levels = levelsBase ? levelsBase + j.outOff : nullptr;
-  int16_t       *recCb = recCbBase ? recCbBase + j.outOff : nullptr, *recCr = recCrBase ? recCrBase + j.outOff : nullptr;
   JccrSums       a = { 0, 0, 0, 0, 0 };
   const CrsParams crs = crs_params<CRS>( j, w, h );
   // load Cb and Cr once: the joint residual of the job's mode and its own distance
@@ -268,119 +189,60 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_kernel( const int16_t *__res
   }
   const int  lw = ilog2( w ), lh = ilog2( h );
   const bool ts = j.typeHor == VTMHIP_TRSKIP;
-  const int  skipW = ts ? 0 : zero_out( w ), skipH = ts ? 0 : zero_out( h );
-  jc_sync<TPT>();
+  const int  skipW = ts ? 0 : tr_skip( VTMHIP_DCT2, w ), skipH = ts ? 0 : tr_skip( VTMHIP_DCT2, h );
+  chain_sync<TPT>();
   if( ts )
   {
     // xTransformSkip / xITransformSkip are plain copies: quantise the joint residual itself, without transform shift or sqrt(2) compensation
-    const QParams qp = q_params( j, lw, lh, true );
+    const QuantRule qr = quant_rule_of( j, lw, lh, true );
+    int            *levels = levelsBase ? levelsBase + j.outOff : nullptr;
+    int16_t        *recCb = recCbBase ? recCbBase + j.outOff : nullptr, *recCr = recCrBase ? recCrBase + j.outOff : nullptr;
     for( int i = t; i < w * h; i += TPT )
     {
       const int c = blk[i];
       a.sumAbs += abs( c );
-      const int q = q_level( qp, c, a.absSum );
+      const int q = qr.level( c, a.absSum );
       if( levels ) levels[i] = q;
       const int  y = i / w, x = i - y * w;
       const long o = ( long ) y * j.resiStride + x;
-      jccr_finish<CRS>( am, s, ( int ) ( int16_t ) q_dequant( qp, q ), cbp[o], crp[o], recCb, recCr, i, a.sseCb, a.sseCr, crs.adj, crs.maxAbs );
+      jccr_finish<CRS>( am, s, ( int ) ( int16_t ) qr.dequant( q ), cbp[o], crp[o], recCb, recCr, i, a.sseCb, a.sseCr, crs.adj, crs.maxAbs );
     }
   }
   else
   {
-    // ---- forward: TrQuant::xT --------------------------------------------------------------------------------------------------------
+    // forward: TrQuant::xT
+    lds_load_matrix_T( tabs.m[lw], w, sM, t, TPT );
+    chain_sync<TPT>();
+    lds_fwd_pass( blk, w, tmp, h + 1, sM, w, h, ALL_LINES, w - skipW, lw + bd + 6 - 15, t, TPT, ( long long * ) nullptr );
+    chain_sync<TPT>();
+    lds_load_matrix_T( tabs.m[lh], h, sM, t, TPT );
+    chain_sync<TPT>();
+    lds_fwd_pass( tmp, h + 1, blk, w, sM, h, w, w - skipW, h - skipH, lh + 6, t, TPT, &a.sumAbs );
+    chain_sync<TPT>();
+    // Quant::quant + Quant::dequant, in place
     {
-      const int s1 = lw + bd + 6 - 15, s2 = lh + 6;
-      const int16_t *m = tabs.m[lw];
-      for( int i = t; i < w * w; i += TPT ) { const int k = i / w, n = i - k * w; sM[n * w + k] = m[i]; }
-      jc_sync<TPT>();
-      {
-        const int rnd = s1 > 0 ? 1 << ( s1 - 1 ) : 0, kEff = w - skipW;
-        for( int o = t; o < h * w; o += TPT )
-        {
-          const int jj = o / w, k = o - jj * w;
-          int       v  = 0;
-          if( k < kEff )
-          {
-            unsigned sum = 0;
-            for( int n = 0; n < w; n++ ) sum += ( unsigned ) blk[jj * w + n] * ( unsigned ) ( int ) sM[n * w + k];
-            v = ( int ) ( sum + ( unsigned ) rnd ) >> s1;
-          }
-          tmp[k * ( h + 1 ) + jj] = v;
-        }
-      }
-      jc_sync<TPT>();
-      m = tabs.m[lh];
-      for( int i = t; i < h * h; i += TPT ) { const int k = i / h, n = i - k * h; sM[n * h + k] = m[i]; }
-      jc_sync<TPT>();
-      {
-        const int rnd = 1 << ( s2 - 1 ), kEff = h - skipH, jEff = w - skipW;
-        for( int o = t; o < w * h; o += TPT )
-        {
-          const int j2 = o / h, k2 = o - j2 * h;
-          int       v  = 0;
-          if( j2 < jEff && k2 < kEff )
-          {
-            unsigned sum = 0;
-            for( int n = 0; n < h; n++ ) sum += ( unsigned ) tmp[j2 * ( h + 1 ) + n] * ( unsigned ) ( int ) sM[n * h + k2];
-            v = ( int ) ( sum + ( unsigned ) rnd ) >> s2;
-          }
-          blk[k2 * w + j2] = v;
-          a.sumAbs += abs( v );
-        }
-      }
-      jc_sync<TPT>();
-    }
-    // ---- Quant::quant + Quant::dequant, in place ---------------------------------------------------------------------------------------
-    {
-      const QParams qp = q_params( j, lw, lh, false );
+      const QuantRule qr = quant_rule_of( j, lw, lh, false );
+      int            *levels = levelsBase ? levelsBase + j.outOff : nullptr;
       for( int i = t; i < w * h; i += TPT )
       {
-        const int q = q_level( qp, blk[i], a.absSum );
+        const int q = qr.level( blk[i], a.absSum );
         if( levels ) levels[i] = q;
-        blk[i] = q_dequant( qp, q );
-      }
-      jc_sync<TPT>();
-    }
-    // ---- inverse: TrQuant::xIT, then the inverse ICT and the two SSEs ---------------------------------------------------------------------
-    {
-      const int s1 = 7, s2 = 20 - bd;
-      const int16_t *m = tabs.m[lh];
-      for( int i = t; i < h * h; i += TPT ) sM[i] = m[i];
-      jc_sync<TPT>();
-      {
-        const unsigned rnd = 1u << ( s1 - 1 );
-        const int      linesEff = w - skipW, cut = h - skipH;
-        for( int o = t; o < w * h; o += TPT )
-        {
-          const int i = o / h, jj = o - i * h;
-          int       v = 0;
-          if( i < linesEff )
-          {
-            unsigned sum = 0;
-            for( int k = 0; k < cut; k++ ) sum += ( unsigned ) blk[k * w + i] * ( unsigned ) ( int ) sM[k * h + jj];
-            v = min( 32767, max( -32768, ( int ) ( sum + rnd ) >> s1 ) );
-          }
-          tmp[i * h + jj] = v;
-        }
-      }
-      jc_sync<TPT>();
-      m = tabs.m[lw];
-      for( int i = t; i < w * w; i += TPT ) sM[i] = m[i];
-      jc_sync<TPT>();
-      {
-        const unsigned rnd = 1u << ( s2 - 1 );
-        const int      cut = w - skipW;
-        for( int o = t; o < w * h; o += TPT )
-        {
-          const int y = o / w, x = o - y * w;
-          unsigned  sum = 0;
-          for( int k = 0; k < cut; k++ ) sum += ( unsigned ) tmp[k * h + y] * ( unsigned ) ( int ) sM[k * w + x];
-          const int  v  = min( 32767, max( -32768, ( int ) ( sum + rnd ) >> s2 ) );
-          const long ro = ( long ) y * j.resiStride + x;   // the two original residuals again, from L2
-          jccr_finish<CRS>( am, s, v, cbp[ro], crp[ro], recCb, recCr, o, a.sseCb, a.sseCr, crs.adj, crs.maxAbs );
-        }
+        blk[i] = qr.dequant( q );
       }
     }
+    chain_sync<TPT>();
+    // inverse: TrQuant::xIT, then the inverse ICT and the two SSEs
+    lds_load_matrix( tabs.m[lh], h, sM, t, TPT );
+    chain_sync<TPT>();
+    lds_inv_pass( blk, w, sM, h, w, w - skipW, h - skipH, 7, t, TPT, [&]( int, int i, int y, int v ) { tmp[i * h + y] = v; } );
+    chain_sync<TPT>();
+    lds_load_matrix( tabs.m[lw], w, sM, t, TPT );
+    chain_sync<TPT>();
+    int16_t *recCb = recCbBase ? recCbBase + j.outOff : nullptr, *recCr = recCrBase ? recCrBase + j.outOff : nullptr;
+    lds_inv_pass( tmp, h, sM, w, h, ALL_LINES, w - skipW, 20 - bd, t, TPT, [&]( int o, int y, int x, int v ) {
+      const long ro = ( long ) y * j.resiStride + x;   // the two original residuals again, from L2
+      jccr_finish<CRS>( am, s, v, cbp[ro], crp[ro], recCb, recCr, o, a.sseCb, a.sseCr, crs.adj, crs.maxAbs );
+    } );
   }
   jccr_reduce_store<TPT>( a, sRed, sub, t, true, results + jobIdx );
 }
@@ -401,7 +263,7 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_lane_kernel( const int16_t *
   const vtmhip_jccr_job j = jobs[jobIdx];
   const int      bd = j.bitDepth, am = ict_abs_mode( j.cbfMask ), s = j.signFlag ? -1 : 1;
   const int16_t *cbp = resiBase + j.cbOff, *crp = resiBase + j.crOff;
-  int            r[N], b[N], t[N];
+  int            r[N], b[N];
   JccrSums       a = { 0, 0, 0, 0, 0 };
   const CrsParams crs = crs_params<CRS>( j, W, H );
   const bool     aligned = ( ( j.cbOff | j.crOff | j.resiStride ) & 3 ) == 0;   // 8-byte aligned rows: 4 samples per load
@@ -438,70 +300,23 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_lane_kernel( const int16_t *
         r[y * W + x] = c;
       }
   }
-  // forward: rows, then columns (TrQuant::xT; no zero-out at these sizes)
-  {
-    const int s1 = LW + bd + 6 - 15, s2 = LH + 6;
-    const int rnd1 = s1 > 0 ? 1 << ( s1 - 1 ) : 0, rnd2 = 1 << ( s2 - 1 );
-#pragma unroll
-    for( int y = 0; y < H; y++ )
-#pragma unroll
-      for( int k = 0; k < W; k++ )
-      {
-        unsigned sum = 0;
-#pragma unroll
-        for( int n = 0; n < W; n++ ) sum += ( unsigned ) r[y * W + n] * ( unsigned ) ( int ) sMH[k * W + n];
-        t[k * H + y] = ( int ) ( sum + ( unsigned ) rnd1 ) >> s1;
-      }
-#pragma unroll
-    for( int x = 0; x < W; x++ )
-#pragma unroll
-      for( int k = 0; k < H; k++ )
-      {
-        unsigned sum = 0;
-#pragma unroll
-        for( int n = 0; n < H; n++ ) sum += ( unsigned ) t[x * H + n] * ( unsigned ) ( int ) sMV[k * H + n];
-        const int v = ( int ) ( sum + ( unsigned ) rnd2 ) >> s2;
-        b[k * W + x] = v;
-        a.sumAbs += abs( v );
-      }
-  }
+  lane_fwd_2d<W, H>( r, b, sMH, sMV, bd, a.sumAbs );
   // Quant::quant + Quant::dequant
   {
-    const QParams qp = q_params( j, LW, LH, false );
-    int          *levels = levelsBase ? levelsBase + j.outOff : nullptr;
+    const QuantRule qr = quant_rule_of( j, LW, LH, false );
+    int            *levels = levelsBase ? levelsBase + j.outOff : nullptr;
 #pragma unroll
     for( int i = 0; i < N; i++ )
     {
-      const int q = q_level( qp, b[i], a.absSum );
+      const int q = qr.level( b[i], a.absSum );
       if( levels ) levels[i] = q;
-      b[i] = q_dequant( qp, q );
+      b[i] = qr.dequant( q );
     }
   }
-  // inverse: columns, then rows (TrQuant::xIT); the inverse ICT and both SSEs per sample, the original residuals read again (L2) instead of held in registers
+  // inverse; then the inverse ICT and both SSEs per sample, the original residuals read again (L2) instead of held in registers
   {
-    const int      s2 = 20 - bd;
-    const unsigned rnd1 = 1u << 6, rnd2 = 1u << ( s2 - 1 );
-    int16_t       *recCb = recCbBase ? recCbBase + j.outOff : nullptr, *recCr = recCrBase ? recCrBase + j.outOff : nullptr;
-#pragma unroll
-    for( int x = 0; x < W; x++ )
-#pragma unroll
-      for( int y = 0; y < H; y++ )
-      {
-        unsigned sum = 0;
-#pragma unroll
-        for( int k = 0; k < H; k++ ) sum += ( unsigned ) b[k * W + x] * ( unsigned ) ( int ) sMV[k * H + y];
-        t[x * H + y] = min( 32767, max( -32768, ( int ) ( sum + rnd1 ) >> 7 ) );
-      }
-#pragma unroll
-    for( int y = 0; y < H; y++ )
-#pragma unroll
-      for( int x = 0; x < W; x++ )
-      {
-        unsigned sum = 0;
-#pragma unroll
-        for( int k = 0; k < W; k++ ) sum += ( unsigned ) t[k * H + y] * ( unsigned ) ( int ) sMH[k * W + x];
-        r[y * W + x] = min( 32767, max( -32768, ( int ) ( sum + rnd2 ) >> s2 ) );
-      }
+    int16_t *recCb = recCbBase ? recCbBase + j.outOff : nullptr, *recCr = recCrBase ? recCrBase + j.outOff : nullptr;
+    lane_inv_2d<W, H>( b, sMH, sMV, bd, [&]( int y, int x, int v ) { r[y * W + x] = v; } );
     if( aligned )
     {
 #pragma unroll
@@ -528,92 +343,7 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_lane_kernel( const int16_t *
   results[jobIdx] = jccr_result_of( a );
 }
 
-// ---- uniform batches with power-of-two sides >= 8: the register-blocked passes of tu_chain_uni_kernel (a lane owns a 2 x 8 block of outputs) ------------
-// rows x cols outputs (cols multiple of 8); rEff / cEff: outputs beyond them are zero (zero-out); inner: summation length.  32-bit A values below 2^23 in
-// magnitude (the header comment has the bound), matrix entries |m| <= 90: the 24-bit multiply is exact.
-template<int LPT, bool CLIP>
-__device__ __forceinline__ void jq_pass( const int *A, int aRowStride, int aColStride, const int16_t *B, int ldb, int inner, int rows, int cols, int rEff, int cEff,
-                                         int *out, int oRowStride, int oColStride, int shift, int t, long long *sumAbs )
-{
-  const int cb = cols >> 3, lcb = 31 - __clz( cb ), rnd = shift > 0 ? 1 << ( shift - 1 ) : 0;
-  for( int it = t; it < ( rows >> 1 ) * cb; it += LPT )
-  {
-    const int r = ( it >> lcb ) << 1, c0 = ( it & ( cb - 1 ) ) << 3;   // cb is a power of two
-    int       acc[2][8];
-#pragma unroll
-    for( int i = 0; i < 8; i++ ) acc[0][i] = acc[1][i] = rnd;
-    if( r < rEff && c0 < cEff )
-    {
-      const int *a0 = A + r * aRowStride, *a1 = a0 + aRowStride;
-      for( int n = 0; n < inner; n++ )
-      {
-        const int  av0 = a0[n * aColStride], av1 = a1[n * aColStride];
-        const int4 bv = *reinterpret_cast<const int4 *>( B + n * ldb + c0 );
-        const int  b[8] = { ( int ) ( short ) bv.x, bv.x >> 16, ( int ) ( short ) bv.y, bv.y >> 16, ( int ) ( short ) bv.z, bv.z >> 16, ( int ) ( short ) bv.w, bv.w >> 16 };
-#pragma unroll
-        for( int i = 0; i < 8; i++ ) { acc[0][i] += __mul24( av0, b[i] ); acc[1][i] += __mul24( av1, b[i] ); }
-      }
-    }
-#pragma unroll
-    for( int q = 0; q < 2; q++ )
-#pragma unroll
-      for( int i = 0; i < 8; i++ )
-      {
-        int v = ( r + q < rEff && c0 + i < cEff ) ? acc[q][i] >> shift : 0;
-        if( CLIP ) v = min( 32767, max( -32768, v ) );
-        out[( r + q ) * oRowStride + ( c0 + i ) * oColStride] = v;
-        if( sumAbs ) *sumAbs += abs( v );
-      }
-  }
-}
-
-// The same product for int16 A values with the summation index contiguous: v_dot2_i32_i16 takes two summation steps per instruction into a 32-bit
-// accumulator.  Bp: the matrix with rows n, n + 1 interleaved per column -- Bp[(n >> 1) * cols + c] = (B[n][c], B[n+1][c]).
-template<int LPT, bool CLIP, class OutT>
-__device__ __forceinline__ void jq_pass16( const int16_t *A, int aRowStride, const unsigned *Bp, int inner, int rows, int cols, int rEff, int cEff, OutT *out,
-                                           int oRowStride, int oColStride, int shift, int t )
-{
-  typedef short v2s __attribute__( ( ext_vector_type( 2 ) ) );
-  const int cb = cols >> 3, lcb = 31 - __clz( cb ), rnd = shift > 0 ? 1 << ( shift - 1 ) : 0;
-  for( int it = t; it < ( rows >> 1 ) * cb; it += LPT )
-  {
-    const int r = ( it >> lcb ) << 1, c0 = ( it & ( cb - 1 ) ) << 3;
-    int       acc[2][8];
-#pragma unroll
-    for( int i = 0; i < 8; i++ ) acc[0][i] = acc[1][i] = rnd;
-    if( r < rEff && c0 < cEff )
-    {
-      const unsigned *a0 = reinterpret_cast<const unsigned *>( A + r * aRowStride ), *a1 = reinterpret_cast<const unsigned *>( A + ( r + 1 ) * aRowStride );
-      for( int n2 = 0; n2 < ( inner >> 1 ); n2++ )
-      {
-        const unsigned av0 = a0[n2], av1 = a1[n2];
-        const uint4    b0 = *reinterpret_cast<const uint4 *>( Bp + n2 * cols + c0 ), b1 = *reinterpret_cast<const uint4 *>( Bp + n2 * cols + c0 + 4 );
-        const unsigned bw[8] = { b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w };
-        v2s va0, va1;
-        __builtin_memcpy( &va0, &av0, 4 );
-        __builtin_memcpy( &va1, &av1, 4 );
-#pragma unroll
-        for( int i = 0; i < 8; i++ )
-        {
-          v2s vb;
-          __builtin_memcpy( &vb, &bw[i], 4 );
-          acc[0][i] = __builtin_amdgcn_sdot2( va0, vb, acc[0][i], false );
-          acc[1][i] = __builtin_amdgcn_sdot2( va1, vb, acc[1][i], false );
-        }
-      }
-    }
-#pragma unroll
-    for( int q = 0; q < 2; q++ )
-#pragma unroll
-      for( int i = 0; i < 8; i++ )
-      {
-        int v = ( r + q < rEff && c0 + i < cEff ) ? acc[q][i] >> shift : 0;
-        if( CLIP ) v = min( 32767, max( -32768, v ) );
-        out[( r + q ) * oRowStride + ( c0 + i ) * oColStride] = ( OutT ) v;
-      }
-  }
-}
-
+// ---- uniform batches with power-of-two sides >= 8: tu_stages.hpp's register-blocked passes (a lane owns a 2 x 8 block of outputs), as tu_chain_uni_kernel ----
 template<int LPT, bool CRS>
 __global__ __launch_bounds__( 256 ) void jccr_chain_uni_kernel( const int16_t *__restrict__ resiBase, const vtmhip_jccr_job *__restrict__ jobs, int numJobs, DctTabs tabs,
                                                                int *__restrict__ levelsBase, int16_t *__restrict__ recCbBase, int16_t *__restrict__ recCrBase,
@@ -629,21 +359,8 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_uni_kernel( const int16_t *_
   // width:  mW0 = M_W with rows k, k+1 interleaved (second inverse pass), mW1 = M_W^T with rows n, n+1 interleaved (first forward pass)
   // height: mH0 = M_H with rows k, k+1 interleaved (first inverse pass),   mH1 = M_H^T plain (second forward pass: 32-bit input)
   int16_t *mW0 = sMat, *mW1 = mW0 + w * w, *mH0 = mW1 + w * w, *mH1 = mH0 + h * h;
-  {
-    const int16_t *mw = tabs.m[lw], *mh = tabs.m[lh];
-    for( int i = threadIdx.x; i < w * w; i += 256 )
-    {
-      const int k = i >> lw, n = i & ( w - 1 );
-      mW0[( ( k >> 1 ) * w + n ) * 2 + ( k & 1 )] = mw[i];
-      mW1[( ( n >> 1 ) * w + k ) * 2 + ( n & 1 )] = mw[i];
-    }
-    for( int i = threadIdx.x; i < h * h; i += 256 )
-    {
-      const int k = i >> lh, n = i & ( h - 1 );
-      mH0[( ( k >> 1 ) * h + n ) * 2 + ( k & 1 )] = mh[i];
-      mH1[n * h + k]                              = mh[i];
-    }
-  }
+  tuq_stage_matrix<false>( tabs.m[lw], w, lw, mW0, mW1 );
+  tuq_stage_matrix<true>( tabs.m[lh], h, lh, mH0, mH1 );
   __syncthreads();
   const int  jobIdx = blockIdx.x * TUS + sub;
   const bool live   = jobIdx < numJobs;   // dead groups (whole waves or idle lane groups) compute the last job again and write nothing: they only meet the barriers
@@ -666,29 +383,29 @@ __global__ __launch_bounds__( 256 ) void jccr_chain_uni_kernel( const int16_t *_
   int16_t *dq16 = reinterpret_cast<int16_t *>( tmp );   // dequantised coefficients [k][k2] (after the second forward pass has consumed tmp)
   int16_t *t16  = reinterpret_cast<int16_t *>( blk );   // first inverse pass output [y][i] (after quantisation has consumed blk)
   int     *rec32 = tmp;                                  // reconstructed joint residual [y][x]
-  const int skipW = zero_out( w ), skipH = zero_out( h );
-  jc_sync<LPT>();
+  const int skipW = tr_skip( VTMHIP_DCT2, w ), skipH = tr_skip( VTMHIP_DCT2, h );
+  chain_sync<LPT>();
   // forward (TrQuant::xT): tmp[k][y] = sum_n sR[y][n] * MT_hor[n][k];  blk[k2][j2] = sum_n tmp[j2][n] * MT_ver[n][k2]
-  jq_pass16<LPT, false>( sR, w, reinterpret_cast<const unsigned *>( mW1 ), w, h, w, h, w - skipW, tmp, 1, h + 1, lw + bd + 6 - 15, t );
-  jc_sync<LPT>();
-  jq_pass<LPT, false>( tmp, h + 1, 1, mH1, h, h, w, h, w - skipW, h - skipH, blk, 1, w, lh + 6, t, &a.sumAbs );
-  jc_sync<LPT>();
+  tuq_pass16<LPT, false>( sR, w, reinterpret_cast<const unsigned *>( mW1 ), w, h, w, h, w - skipW, tmp, 1, h + 1, lw + bd + 6 - 15, t );
+  chain_sync<LPT>();
+  tuq_pass<LPT, false>( tmp, h + 1, 1, mH1, h, h, w, h, w - skipW, h - skipH, blk, 1, w, lh + 6, t, &a.sumAbs );
+  chain_sync<LPT>();
   {
-    const QParams qp = q_params( j, lw, lh, false );
-    int          *levels = ( levelsBase && live ) ? levelsBase + j.outOff : nullptr;
+    const QuantRule qr = quant_rule_of( j, lw, lh, false );
+    int            *levels = ( levelsBase && live ) ? levelsBase + j.outOff : nullptr;
     for( int i = t; i < w * h; i += LPT )
     {
-      const int q = q_level( qp, blk[i], a.absSum );
+      const int q = qr.level( blk[i], a.absSum );
       if( levels ) levels[i] = q;
-      dq16[( ( i & ( w - 1 ) ) << lh ) + ( i >> lw )] = ( int16_t ) q_dequant( qp, q );   // transposed: the vertical index contiguous
+      dq16[( ( i & ( w - 1 ) ) << lh ) + ( i >> lw )] = ( int16_t ) qr.dequant( q );   // transposed: the vertical index contiguous
     }
   }
-  jc_sync<LPT>();
+  chain_sync<LPT>();
   // inverse (TrQuant::xIT): t16[y][i] = clip( sum_k dq[k][i] * M_ver[k][y] );  rec[y][x] = clip( sum_k t16[y][k] * M_hor[k][x] )
-  jq_pass16<LPT, true>( dq16, h, reinterpret_cast<const unsigned *>( mH0 ), h - skipH, w, h, w - skipW, h, t16, 1, w, 7, t );
-  jc_sync<LPT>();
-  jq_pass16<LPT, true>( t16, w, reinterpret_cast<const unsigned *>( mW0 ), w - skipW, h, w, h, w, rec32, w, 1, 20 - bd, t );
-  jc_sync<LPT>();
+  tuq_pass16<LPT, true>( dq16, h, reinterpret_cast<const unsigned *>( mH0 ), h - skipH, w, h, w - skipW, h, t16, 1, w, 7, t );
+  chain_sync<LPT>();
+  tuq_pass16<LPT, true>( t16, w, reinterpret_cast<const unsigned *>( mW0 ), w - skipW, h, w, h, w, rec32, w, 1, 20 - bd, t );
+  chain_sync<LPT>();
   {
     int16_t *recCb = ( recCbBase && live ) ? recCbBase + j.outOff : nullptr, *recCr = ( recCrBase && live ) ? recCrBase + j.outOff : nullptr;
     for( int i = t; i < w * h; i += LPT )
@@ -705,15 +422,6 @@ DctTabs tabs_of( const vtmhip_ctx *ctx )
   DctTabs t;
   for( int l = 0; l < 7; l++ ) t.m[l] = ctx->trTab[VTMHIP_DCT2][l];
   return t;
-}
-
-// The core matrices belong to the context and are filled by transform.hip's entries on their first use: run its smallest one once.
-int ensure_tables( vtmhip_ctx *ctx )
-{
-  if( ctx->trTabBuf ) return VTMHIP_OK;
-  const int32_t src[2] = { 0, 0 };
-  int32_t       dst[2];
-  return vtmhip_fastFwdTrans( ctx, VTMHIP_DCT2, 2, src, dst, 0, 1, 0, 0 );
 }
 
 bool pow2( int v ) { return v > 0 && ( v & ( v - 1 ) ) == 0; }
@@ -773,7 +481,7 @@ int jccr_chain_entry( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_j
   const bool lanePath = uniformSize && maxWidth * maxHeight <= 32 && maxWidth >= 4 && maxHeight >= 4;
   const bool uniPath  = uniformSize && maxWidth >= 8 && maxHeight >= 8;
   if( uniPath ) VTMHIP_REQUIRE( ctx, pow2( maxWidth ) && pow2( maxHeight ), "uniformSize: width / height must be powers of two (TU sizes are)" );
-  int st = ensure_tables( ctx );
+  int st = vtmhip_internal_tr_tables( ctx );
   if( st ) return st;
   // the job table, checked on the host before anything is launched (the kernels index LDS and the core matrices by these fields)
   {

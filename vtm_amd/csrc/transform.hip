@@ -14,18 +14,14 @@
 #include "bucket.hpp"
 #include "tr_tables.hpp"
 #include "lmcs.hpp"
+#include "tu_stages.hpp"
 
 #include <cmath>
 #include <vector>
 
-namespace
-{
-
-struct TrTables { const int16_t *m[3][7]; };   // [type][log2 N] -> device pointer to the N x N forward matrix (row-major)
-
 // The core matrices live in the CONTEXT (one copy per context, on the context's device, freed by vtmhip_destroy): no process-global
 // state, so two contexts on two GPUs -- or two encoder threads with a context each -- cannot race or see the other device's pointers.
-int ensure_tables( vtmhip_ctx *ctx )
+int vtmhip_internal_tr_tables( vtmhip_ctx *ctx )
 {
   std::lock_guard<std::mutex> lock( ctx->initMutex );
   if( ctx->trTabBuf ) return VTMHIP_OK;
@@ -58,63 +54,17 @@ int ensure_tables( vtmhip_ctx *ctx )
   return VTMHIP_OK;
 }
 
+namespace
+{
+
+struct TrTables { const int16_t *m[3][7]; };   // [type][log2 N] -> device pointer to the N x N forward matrix (row-major)
+
 TrTables tabs_of( const vtmhip_ctx *ctx )
 {
   TrTables t;
   for( int a = 0; a < 3; a++ )
     for( int l = 0; l < 7; l++ ) t.m[a][l] = ctx->trTab[a][l];
   return t;
-}
-
-__device__ __forceinline__ int ilog2( int v ) { return 31 - __clz( v ); }
-__device__ __forceinline__ int tr_skip( int type, int n ) { return ( type != VTMHIP_DCT2 && n == 32 ) ? 16 : ( n > 32 ? n - 32 : 0 ); }
-
-// sMT[n * N + k] = M[k][n]
-__device__ __forceinline__ void load_matrix_T( const int16_t *__restrict__ m, int N, int16_t *sMT )
-{
-  for( int i = threadIdx.x; i < N * N; i += blockDim.x )
-  {
-    const int k = i / N, n = i - k * N;
-    sMT[n * N + k] = m[i];
-  }
-}
-
-// dst[k * dstLd + j] = (sum_n M[k][n] * src[j * srcLd + n] + rnd) >> shift   for j < lines, k < kEff; zero for kEff <= k < N
-__device__ __forceinline__ void fwd_pass( const int *src, int srcLd, int *dst, int dstLd, const int16_t *sMT, int N, int lines, int kEff, int shift )
-{
-  const int rnd = shift > 0 ? 1 << ( shift - 1 ) : 0;
-  for( int o = threadIdx.x; o < lines * N; o += blockDim.x )
-  {
-    const int j = o / N, k = o - j * N;
-    int       v = 0;
-    if( k < kEff )
-    {
-      unsigned sum = 0;
-      for( int n = 0; n < N; n++ ) sum += ( unsigned ) src[j * srcLd + n] * ( unsigned ) ( int ) sMT[n * N + k];
-      v = ( int ) ( sum + ( unsigned ) rnd ) >> shift;
-    }
-    dst[k * dstLd + j] = v;
-  }
-}
-
-// dst[i * dstLd + j] = clip((sum_{k<cut} src[k * srcLd + i] * M[k][j] + rnd) >> shift)   for i < lines; M[k][j] = sMT[j * N + k]... we need
-// M row-major here: sM[k * N + j]
-__device__ __forceinline__ void inv_pass( const int *src, int srcLd, int *dst, int dstLd, const int16_t *sM, int N, int lines, int linesEff, int cut,
-                                          int shift, int cmin, int cmax )
-{
-  const unsigned rnd = 1u << ( shift - 1 );
-  for( int o = threadIdx.x; o < lines * N; o += blockDim.x )
-  {
-    const int i = o / N, j = o - i * N;
-    int       v = 0;
-    if( i < linesEff )
-    {
-      unsigned sum = 0;
-      for( int k = 0; k < cut; k++ ) sum += ( unsigned ) src[k * srcLd + i] * ( unsigned ) ( int ) sM[k * N + j];
-      v = min( cmax, max( cmin, ( int ) ( sum + rnd ) >> shift ) );
-    }
-    dst[i * dstLd + j] = v;
-  }
 }
 
 constexpr int TB = 64;   // MAX_TB_SIZEY
@@ -130,7 +80,8 @@ __global__ __launch_bounds__( 256 ) void xT_kernel( const int16_t *__restrict__ 
   int16_t            *sMT = ( int16_t * ) ( tmp + w * ( h + 1 ) );
   const int16_t      *resi = resiBase + j.srcOff;
   int                *coef = coefBase + j.dstOff;
-  for( int i = threadIdx.x; i < w * h; i += blockDim.x )
+  const int           t = threadIdx.x, step = blockDim.x;
+  for( int i = t; i < w * h; i += step )
   {
     const int y = i / w, x = i - y * w;
     blk[i]      = resi[( long ) y * j.srcStride + x];
@@ -139,39 +90,22 @@ __global__ __launch_bounds__( 256 ) void xT_kernel( const int16_t *__restrict__ 
   int       sumAbs = 0;
   if( w > 1 && h > 1 )
   {
-    const int s1 = ilog2( w ) + bd + 6 - 15, s2 = ilog2( h ) + 6;
-    load_matrix_T( tabs.m[j.typeHor][ilog2( w )], w, sMT );
+    lds_load_matrix_T( tabs.m[j.typeHor][ilog2( w )], w, sMT, t, step );
     __syncthreads();
-    fwd_pass( blk, w, tmp, h + 1, sMT, w, h, w - skipW, s1 );   // tmp[k][y]
+    lds_fwd_pass( blk, w, tmp, h + 1, sMT, w, h, ALL_LINES, w - skipW, ilog2( w ) + bd + 6 - 15, t, step, ( int * ) nullptr );   // tmp[k][y]
     __syncthreads();
-    load_matrix_T( tabs.m[j.typeVer][ilog2( h )], h, sMT );
+    lds_load_matrix_T( tabs.m[j.typeVer][ilog2( h )], h, sMT, t, step );
     __syncthreads();
     // second pass straight to global: coef[k2 * w + j2], zero where j2 >= w - skipW or k2 >= h - skipH
-    const int rnd = 1 << ( s2 - 1 ), kEff = h - skipH, jEff = w - skipW;
-    for( int o = threadIdx.x; o < w * h; o += blockDim.x )
-    {
-      const int j2 = o / h, k2 = o - j2 * h;
-      int       v  = 0;
-      if( j2 < jEff && k2 < kEff )
-      {
-        unsigned sum = 0;
-        for( int n = 0; n < h; n++ ) sum += ( unsigned ) tmp[j2 * ( h + 1 ) + n] * ( unsigned ) ( int ) sMT[n * h + k2];
-        v = ( int ) ( sum + ( unsigned ) rnd ) >> s2;
-      }
-      coef[k2 * w + j2] = v;
-      sumAbs += abs( v );
-    }
+    lds_fwd_pass( tmp, h + 1, coef, w, sMT, h, w, w - skipW, h - skipH, ilog2( h ) + 6, t, step, &sumAbs );
   }
   else
   {
     // 1-D cases (W == 1 or H == 1, TrQuant.cpp:836-850)
     const int n = h == 1 ? w : h, type = h == 1 ? j.typeHor : j.typeVer, skip = h == 1 ? skipW : skipH;
-    const int s = ilog2( n ) + bd + 6 - 15;
-    load_matrix_T( tabs.m[type][ilog2( n )], n, sMT );
+    lds_load_matrix_T( tabs.m[type][ilog2( n )], n, sMT, t, step );
     __syncthreads();
-    fwd_pass( blk, n, tmp, 1, sMT, n, 1, n - skip, s );
-    __syncthreads();
-    for( int i = threadIdx.x; i < n; i += blockDim.x ) { coef[i] = tmp[i]; sumAbs += abs( tmp[i] ); }
+    lds_fwd_pass( blk, n, coef, 1, sMT, n, 1, ALL_LINES, n - skip, ilog2( n ) + bd + 6 - 15, t, step, &sumAbs );
   }
   if( sumAbsOut )
   {
@@ -182,9 +116,9 @@ __global__ __launch_bounds__( 256 ) void xT_kernel( const int16_t *__restrict__ 
     __syncthreads();
     if( threadIdx.x == 0 )
     {
-      int t = 0;
-      for( int k = 0; k < ( int ) ( blockDim.x >> 6 ); k++ ) t += blk[k];
-      sumAbsOut[blockIdx.x] = t;
+      int s = 0;
+      for( int k = 0; k < ( int ) ( blockDim.x >> 6 ); k++ ) s += blk[k];
+      sumAbsOut[blockIdx.x] = s;
     }
   }
 }
@@ -200,49 +134,25 @@ __global__ __launch_bounds__( 256 ) void xIT_kernel( const int *__restrict__ coe
   int16_t            *sM  = ( int16_t * ) ( tmp + w * h );
   const int          *coef = coefBase + j.srcOff;
   int16_t            *resi = resiBase + j.dstOff;
-  const int           cmin = -32768, cmax = 32767;
-  for( int i = threadIdx.x; i < w * h; i += blockDim.x ) blk[i] = coef[i];
+  const int           t = threadIdx.x, step = blockDim.x;
+  for( int i = t; i < w * h; i += step ) blk[i] = coef[i];
   const int skipW = tr_skip( j.typeHor, w ), skipH = tr_skip( j.typeVer, h );
   if( w > 1 && h > 1 )
   {
-    const int s1 = 7, s2 = 20 - bd;
-    {
-      const int16_t *m = tabs.m[j.typeVer][ilog2( h )];
-      for( int i = threadIdx.x; i < h * h; i += blockDim.x ) sM[i] = m[i];
-    }
+    lds_load_matrix( tabs.m[j.typeVer][ilog2( h )], h, sM, t, step );
     __syncthreads();
-    inv_pass( blk, w, tmp, h, sM, h, w, w - skipW, h - skipH, s1, cmin, cmax );   // tmp[i (x-frequency)][y]
+    lds_inv_pass( blk, w, sM, h, w, w - skipW, h - skipH, 7, t, step, [&]( int, int i, int y, int v ) { tmp[i * h + y] = v; } );   // tmp[i (x-frequency)][y]
     __syncthreads();
-    {
-      const int16_t *m = tabs.m[j.typeHor][ilog2( w )];
-      for( int i = threadIdx.x; i < w * w; i += blockDim.x ) sM[i] = m[i];
-    }
+    lds_load_matrix( tabs.m[j.typeHor][ilog2( w )], w, sM, t, step );
     __syncthreads();
-    const unsigned rnd = 1u << ( s2 - 1 );
-    const int      cut = w - skipW;
-    for( int o = threadIdx.x; o < w * h; o += blockDim.x )
-    {
-      const int y = o / w, x = o - y * w;
-      unsigned  sum = 0;
-      for( int k = 0; k < cut; k++ ) sum += ( unsigned ) tmp[k * h + y] * ( unsigned ) ( int ) sM[k * w + x];
-      const int v = min( cmax, max( cmin, ( int ) ( sum + rnd ) >> s2 ) );
-      resi[( long ) y * j.dstStride + x] = ( int16_t ) v;
-    }
+    lds_inv_pass( tmp, h, sM, w, h, ALL_LINES, w - skipW, 20 - bd, t, step, [&]( int, int y, int x, int v ) { resi[( long ) y * j.dstStride + x] = ( int16_t ) v; } );
   }
   else
   {
     const int n = w == 1 ? h : w, type = w == 1 ? j.typeVer : j.typeHor, skip = w == 1 ? skipH : skipW;
-    const int s = 20 - bd + 1;
-    const int16_t *m = tabs.m[type][ilog2( n )];
-    for( int i = threadIdx.x; i < n * n; i += blockDim.x ) sM[i] = m[i];
+    lds_load_matrix( tabs.m[type][ilog2( n )], n, sM, t, step );
     __syncthreads();
-    inv_pass( blk, 1, tmp, n, sM, n, 1, 1, n - skip, s, cmin, cmax );
-    __syncthreads();
-    for( int i = threadIdx.x; i < n; i += blockDim.x )
-    {
-      if( w == 1 ) resi[( long ) i * j.dstStride] = ( int16_t ) tmp[i];
-      else resi[i] = ( int16_t ) tmp[i];
-    }
+    lds_inv_pass( blk, 1, sM, n, 1, ALL_LINES, n - skip, 20 - bd + 1, t, step, [&]( int, int, int i, int v ) { resi[w == 1 ? ( long ) i * j.dstStride : i] = ( int16_t ) v; } );
   }
 }
 
@@ -285,34 +195,32 @@ __global__ __launch_bounds__( 256 ) void inv1d_kernel( const int *__restrict__ s
   }
 }
 
-// ---- scalar quantisation (flat scaling list) -----------------------------------------------------------------------------
-__constant__ int c_quantScales[2][6]    = { { 26214, 23302, 20560, 18396, 16384, 14564 }, { 18396, 16384, 14564, 13107, 11651, 10280 } };
-__constant__ int c_invQuantScales[2][6] = { { 40, 45, 51, 57, 64, 72 }, { 57, 64, 72, 80, 90, 102 } };
+// ---- scalar quantisation (flat scaling list): tu_stages.hpp's QuantRule per job -------------------------------------------
+__device__ __forceinline__ QuantRule quant_rule_of( const vtmhip_quant_job &j )
+{
+  return quant_rule( j.bitDepth, j.qpPer, j.qpRem, j.isIRAP, ilog2( j.width ), ilog2( j.height ), j.isTransformSkip );
+}
 
 __global__ __launch_bounds__( 256 ) void quant_kernel( const int *__restrict__ coefBase, int *__restrict__ qBase, int *__restrict__ deltaUBase,
                                                       const vtmhip_quant_job *__restrict__ jobs, int *__restrict__ absSumOut )
 {
   __shared__ int            sRed[4];
   const vtmhip_quant_job j  = jobs[blockIdx.x];
-  const int              w = j.width, h = j.height, lw = ilog2( w ), lh = ilog2( h );
-  const int              needSqrt = ( ( lw + lh ) & 1 ) && !j.isTransformSkip;
-  const int              scale    = c_quantScales[needSqrt][j.qpRem];
-  const int              trShift  = 15 - j.bitDepth - ( ( lw + lh ) >> 1 ) + ( needSqrt ? -1 : 0 );
-  const int              qBits    = 14 + j.qpPer + ( j.isTransformSkip ? 0 : trShift );
-  const long long        add      = ( long long ) ( j.isIRAP ? 171 : 85 ) << ( qBits - 9 );
-  const int             *coef     = coefBase + j.srcOff;
-  int                   *q        = qBase + j.dstOff;
-  int                    sum      = 0;
+  const int              w = j.width, h = j.height;
+  const QuantRule        qr = quant_rule_of( j );
+  const int             *coef = coefBase + j.srcOff;
+  int                   *q    = qBase + j.dstOff;
+  int                    sum  = 0;
   for( int i = threadIdx.x; i < w * h; i += blockDim.x )
   {
     // the reference's scan covers only the 32x32 zero-out region of larger blocks: positions outside keep level 0 (Quant.cpp:1004-1008)
     if( ( i % w ) >= 32 || ( i / w ) >= 32 ) { q[i] = 0; if( deltaUBase ) deltaUBase[j.dstOff + i] = 0; continue; }
-    const int       c   = coef[i];
-    const long long t   = ( long long ) abs( c ) * scale;
-    const int       mag = ( int ) ( ( t + add ) >> qBits );
-    if( deltaUBase ) deltaUBase[j.dstOff + i] = ( int ) ( ( t - ( ( long long ) mag << qBits ) ) >> ( qBits - 8 ) );
+    const int c = coef[i];
+    long long t;
+    const int mag = qr.mag( c, t );
+    if( deltaUBase ) deltaUBase[j.dstOff + i] = ( int ) ( ( t - ( ( long long ) mag << qr.qBits ) ) >> ( qr.qBits - 8 ) );
     sum += mag;
-    q[i] = min( 32767, max( -32768, c < 0 ? -mag : mag ) );
+    q[i] = qr.signed_level( c, mag );
   }
   sum = wave_reduce_add( sum );
   if( ( threadIdx.x & 63 ) == 0 ) sRed[threadIdx.x >> 6] = sum;
@@ -324,40 +232,36 @@ __global__ __launch_bounds__( 256 ) void dequant_kernel( const int *__restrict__
                                                         const vtmhip_quant_job *__restrict__ jobs )
 {
   const vtmhip_quant_job j = jobs[blockIdx.x];
-  const int              w = j.width, h = j.height, lw = ilog2( w ), lh = ilog2( h );
-  const int              needSqrt   = ( ( lw + lh ) & 1 ) && !j.isTransformSkip;
-  const int              trShift    = 15 - j.bitDepth - ( ( lw + lh ) >> 1 ) + ( needSqrt ? -1 : 0 );
-  const int              rightShift = 6 - ( ( j.isTransformSkip ? 0 : trShift ) + j.qpPer );
-  const int              scale      = c_invQuantScales[needSqrt][j.qpRem];
-  const int              inBits     = min( 16, 32 + rightShift - 7 );
-  const int              inMin = -( 1 << ( inBits - 1 ) ), inMax = ( 1 << ( inBits - 1 ) ) - 1;
+  const QuantRule        qr = quant_rule_of( j );   // the dequant half
   const int             *q    = qBase + j.srcOff;
   int                   *coef = coefBase + j.dstOff;
-  for( int i = threadIdx.x; i < w * h; i += blockDim.x )
-  {
-    const int qq = min( inMax, max( inMin, q[i] ) );
-    int       v;
-    if( rightShift > 0 ) v = ( int ) ( ( unsigned ) ( qq * scale ) + ( 1u << ( rightShift - 1 ) ) ) >> rightShift;
-    else v = ( int ) ( ( unsigned ) ( qq * scale ) << ( -rightShift ) );
-    coef[i] = min( 32767, max( -32768, v ) );
-  }
+  for( int i = threadIdx.x; i < j.width * j.height; i += blockDim.x ) coef[i] = qr.dequant( q[i] );
 }
 
 
 // ---- fused residual-coding chain of one TU: xT -> Quant::quant -> Quant::dequant -> xIT -> SSE(residual, reconstructed residual) ----
 // = transformNxN + invTransformNxN + getDistPart( DF_SSE ) of xEstimateInterResidualQT (EncoderLib/InterSearch.cpp:6637-6733) without the
-// CABAC bit estimate in between (host).  Everything stays in LDS; TPT threads per TU (64: four independent TUs per workgroup, wave-level
-// synchronisation only; 256: one TU per workgroup).
+// CABAC bit estimate in between (host).  The stages are tu_stages.hpp's.  Everything stays in LDS; TPT threads per TU (64: four independent TUs
+// per workgroup, wave-level synchronisation only; 256: one TU per workgroup).
 //
 // CRS (the three chain kernels): LMCS chroma residual scaling fused in (vtmhip_tu_chain_crs_batch_dev; reference InterSearch.cpp:6628-6632, 6728-6733) -- two
 // per-sample hooks with lmcs.hpp's rules: at the load the working block gets fwd( r ) while the SSE copy keeps r, and in the epilogue the reconstruction goes
 // through inv() before the rec store and the SSE.  The job's adj (vtmhip_tu_job.chromaAdj) is 0 for "leave this job alone".  CRS == false is the plain chain.
-template<int TPT>
-__device__ __forceinline__ void tu_sync()
+__device__ __forceinline__ QuantRule quant_rule_of( const vtmhip_tu_job &j, int lw, int lh, bool ts ) { return quant_rule( j.bitDepth, j.qpPer, j.qpRem, j.isIRAP, lw, lh, ts ); }
+
+__device__ __forceinline__ void sse_add( long long &sse, int d ) { sse += ( long long ) ( unsigned long long ) ( ( unsigned ) d * ( unsigned ) d ); }
+
+// the packing of the three reduced sums { sumAbs, absSum, sse }
+struct TuResultStore
 {
-  if( TPT == 64 ) { __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" ); __builtin_amdgcn_wave_barrier(); }
-  else __syncthreads();
-}
+  vtmhip_tu_result *out;
+  __device__ __forceinline__ void operator()( const long long ( &v )[3] ) const
+  {
+    vtmhip_tu_result r;
+    r.sse = ( uint64_t ) v[2]; r.sumAbs = ( int32_t ) v[0]; r.absSum = ( int32_t ) v[1];
+    *out = r;
+  }
+};
 
 template<int TPT, bool CRS>
 __global__ __launch_bounds__( 256 ) void tu_chain_kernel( const int16_t *__restrict__ resiBase, const vtmhip_tu_job *__restrict__ jobs, int numJobs,
@@ -390,179 +294,65 @@ __global__ __launch_bounds__( 256 ) void tu_chain_kernel( const int16_t *__restr
   }
   const int lw = ilog2( w ), lh = ilog2( h );
   long long sumAbs = 0, absSum = 0, sse = 0;
-  const bool ts = j.typeHor == VTMHIP_TRSKIP;   // MTS_SKIP candidate: xTransformSkip / xITransformSkip are plain copies (TrQuant.cpp:1200-1213, 925-941)
-  const int skipW = ts ? 0 : tr_skip( j.typeHor, w ), skipH = ts ? 0 : tr_skip( j.typeVer, h );
-  tu_sync<TPT>();
+  const bool ts = j.typeHor == VTMHIP_TRSKIP;   // MTS_SKIP candidate: the coefficients are the residual samples
+  const int  skipW = ts ? 0 : tr_skip( j.typeHor, w ), skipH = ts ? 0 : tr_skip( j.typeVer, h );
+  chain_sync<TPT>();
   if( ts )
   {
-    // coefficients = residual samples; Quant::quant / dequant with useTransformSkip: no transform shift, no sqrt(2) compensation
-    // (Quant.cpp:966-997, 357-482); the caller puts QpParam::per( true ) / rem( true ) into the job
-    const int       qBits = 14 + j.qpPer;
-    const long long add   = ( long long ) ( j.isIRAP ? 171 : 85 ) << ( qBits - 9 );
-    const int       scale = c_quantScales[0][j.qpRem], iscale = c_invQuantScales[0][j.qpRem];
-    const int       rightShift = 6 - j.qpPer;
-    const int       inBits = min( 16, 32 + rightShift - 7 );
-    const int       inMin = -( 1 << ( inBits - 1 ) ), inMax = ( 1 << ( inBits - 1 ) ) - 1;
+    const QuantRule qr = quant_rule_of( j, lw, lh, true );
     int            *levels = levelsBase ? levelsBase + j.outOff : nullptr;
     int16_t        *rec    = recBase ? recBase + j.outOff : nullptr;
     for( int i = t; i < w * h; i += TPT )
     {
       const int c = blk[i];
       sumAbs += abs( c );
-      const long long tt  = ( long long ) abs( c ) * scale;
-      const int       mag = ( int ) ( ( tt + add ) >> qBits );
-      absSum += mag;
-      const int q = min( 32767, max( -32768, c < 0 ? -mag : mag ) );
+      const int q = qr.level( c, absSum );
       if( levels ) levels[i] = q;
-      const int qq = min( inMax, max( inMin, q ) );
-      int       v;
-      if( rightShift > 0 ) v = ( int ) ( ( unsigned ) ( qq * iscale ) + ( 1u << ( rightShift - 1 ) ) ) >> rightShift;
-      else v = ( int ) ( ( unsigned ) ( qq * iscale ) << ( -rightShift ) );
-      v = ( int ) ( int16_t ) min( 32767, max( -32768, v ) );
+      int v = ( int ) ( int16_t ) qr.dequant( q );
       if( CRS && adj ) v = lmcs_inv( v, adj, maxAbs );
       if( rec ) rec[i] = ( int16_t ) v;
-      const int d = ( CRS ? ( int ) sR[i] : c ) - v;   // CRS: c is the scaled sample, the distortion is taken against the kept copy
-      sse += ( long long ) ( unsigned long long ) ( ( unsigned ) d * ( unsigned ) d );
+      sse_add( sse, ( CRS ? ( int ) sR[i] : c ) - v );   // CRS: c is the scaled sample, the distortion is taken against the kept copy
     }
   }
   else
   {
-  // ---- forward: TrQuant::xT ----------------------------------------------------------------------------------------------------
-  {
-    const int s1 = lw + bd + 6 - 15, s2 = lh + 6;
-    const int16_t *m = tabs.m[j.typeHor][lw];
-    for( int i = t; i < w * w; i += TPT ) { const int k = i / w, n = i - k * w; sM[n * w + k] = m[i]; }
-    tu_sync<TPT>();
+    // forward: TrQuant::xT
+    lds_load_matrix_T( tabs.m[j.typeHor][lw], w, sM, t, TPT );
+    chain_sync<TPT>();
+    lds_fwd_pass( blk, w, tmp, h + 1, sM, w, h, ALL_LINES, w - skipW, lw + bd + 6 - 15, t, TPT, ( long long * ) nullptr );
+    chain_sync<TPT>();
+    lds_load_matrix_T( tabs.m[j.typeVer][lh], h, sM, t, TPT );
+    chain_sync<TPT>();
+    lds_fwd_pass( tmp, h + 1, blk, w, sM, h, w, w - skipW, h - skipH, lh + 6, t, TPT, &sumAbs );
+    chain_sync<TPT>();
+    // Quant::quant + Quant::dequant, in place
     {
-      const int rnd = s1 > 0 ? 1 << ( s1 - 1 ) : 0, kEff = w - skipW;
-      for( int o = t; o < h * w; o += TPT )
+      const QuantRule qr = quant_rule_of( j, lw, lh, false );
+      int            *levels = levelsBase ? levelsBase + j.outOff : nullptr;
+      for( int i = t; i < w * h; i += TPT )
       {
-        const int jj = o / w, k = o - jj * w;
-        int       v  = 0;
-        if( k < kEff )
-        {
-          unsigned sum = 0;
-          for( int n = 0; n < w; n++ ) sum += ( unsigned ) blk[jj * w + n] * ( unsigned ) ( int ) sM[n * w + k];
-          v = ( int ) ( sum + ( unsigned ) rnd ) >> s1;
-        }
-        tmp[k * ( h + 1 ) + jj] = v;
+        const int q = qr.level( blk[i], absSum );
+        if( levels ) levels[i] = q;
+        blk[i] = qr.dequant( q );
       }
     }
-    tu_sync<TPT>();
-    m = tabs.m[j.typeVer][lh];
-    for( int i = t; i < h * h; i += TPT ) { const int k = i / h, n = i - k * h; sM[n * h + k] = m[i]; }
-    tu_sync<TPT>();
-    {
-      const int rnd = 1 << ( s2 - 1 ), kEff = h - skipH, jEff = w - skipW;
-      for( int o = t; o < w * h; o += TPT )
-      {
-        const int j2 = o / h, k2 = o - j2 * h;
-        int       v  = 0;
-        if( j2 < jEff && k2 < kEff )
-        {
-          unsigned sum = 0;
-          for( int n = 0; n < h; n++ ) sum += ( unsigned ) tmp[j2 * ( h + 1 ) + n] * ( unsigned ) ( int ) sM[n * h + k2];
-          v = ( int ) ( sum + ( unsigned ) rnd ) >> s2;
-        }
-        blk[k2 * w + j2] = v;
-        sumAbs += abs( v );
-      }
-    }
-    tu_sync<TPT>();
+    chain_sync<TPT>();
+    // inverse: TrQuant::xIT, then SSE against the residual
+    lds_load_matrix( tabs.m[j.typeVer][lh], h, sM, t, TPT );
+    chain_sync<TPT>();
+    lds_inv_pass( blk, w, sM, h, w, w - skipW, h - skipH, 7, t, TPT, [&]( int, int i, int y, int v ) { tmp[i * h + y] = v; } );
+    chain_sync<TPT>();
+    lds_load_matrix( tabs.m[j.typeHor][lw], w, sM, t, TPT );
+    chain_sync<TPT>();
+    int16_t *rec = recBase ? recBase + j.outOff : nullptr;
+    lds_inv_pass( tmp, h, sM, w, h, ALL_LINES, w - skipW, 20 - bd, t, TPT, [&]( int o, int, int, int v ) {
+      if( CRS && adj ) v = lmcs_inv( v, adj, maxAbs );
+      if( rec ) rec[o] = ( int16_t ) v;
+      sse_add( sse, ( int ) sR[o] - ( int ) ( int16_t ) v );
+    } );
   }
-  // ---- Quant::quant + Quant::dequant (flat scaling list), in place ------------------------------------------------------------
-  {
-    const int       needSqrt = ( lw + lh ) & 1;
-    const int       trShift  = 15 - bd - ( ( lw + lh ) >> 1 ) + ( needSqrt ? -1 : 0 );
-    const int       qBits    = 14 + j.qpPer + trShift;
-    const long long add      = ( long long ) ( j.isIRAP ? 171 : 85 ) << ( qBits - 9 );
-    const int       scale    = c_quantScales[needSqrt][j.qpRem], iscale = c_invQuantScales[needSqrt][j.qpRem];
-    const int       rightShift = 6 - ( trShift + j.qpPer );
-    const int       inBits   = min( 16, 32 + rightShift - 7 );
-    const int       inMin = -( 1 << ( inBits - 1 ) ), inMax = ( 1 << ( inBits - 1 ) ) - 1;
-    int            *levels   = levelsBase ? levelsBase + j.outOff : nullptr;
-    for( int i = t; i < w * h; i += TPT )
-    {
-      const int       c   = blk[i];
-      const long long tt  = ( long long ) abs( c ) * scale;
-      const int       mag = ( int ) ( ( tt + add ) >> qBits );
-      absSum += mag;
-      const int q = min( 32767, max( -32768, c < 0 ? -mag : mag ) );
-      if( levels ) levels[i] = q;
-      const int qq = min( inMax, max( inMin, q ) );
-      int       v;
-      if( rightShift > 0 ) v = ( int ) ( ( unsigned ) ( qq * iscale ) + ( 1u << ( rightShift - 1 ) ) ) >> rightShift;
-      else v = ( int ) ( ( unsigned ) ( qq * iscale ) << ( -rightShift ) );
-      blk[i] = min( 32767, max( -32768, v ) );
-    }
-    tu_sync<TPT>();
-  }
-  // ---- inverse: TrQuant::xIT, then SSE against the residual ------------------------------------------------------------------
-  {
-    const int s1 = 7, s2 = 20 - bd;
-    const int16_t *m = tabs.m[j.typeVer][lh];
-    for( int i = t; i < h * h; i += TPT ) sM[i] = m[i];
-    tu_sync<TPT>();
-    {
-      const unsigned rnd = 1u << ( s1 - 1 );
-      const int      linesEff = w - skipW, cut = h - skipH;
-      for( int o = t; o < w * h; o += TPT )
-      {
-        const int i = o / h, jj = o - i * h;
-        int       v = 0;
-        if( i < linesEff )
-        {
-          unsigned sum = 0;
-          for( int k = 0; k < cut; k++ ) sum += ( unsigned ) blk[k * w + i] * ( unsigned ) ( int ) sM[k * h + jj];
-          v = min( 32767, max( -32768, ( int ) ( sum + rnd ) >> s1 ) );
-        }
-        tmp[i * h + jj] = v;
-      }
-    }
-    tu_sync<TPT>();
-    m = tabs.m[j.typeHor][lw];
-    for( int i = t; i < w * w; i += TPT ) sM[i] = m[i];
-    tu_sync<TPT>();
-    {
-      const unsigned rnd = 1u << ( s2 - 1 );
-      const int      cut = w - skipW;
-      int16_t       *rec = recBase ? recBase + j.outOff : nullptr;
-      for( int o = t; o < w * h; o += TPT )
-      {
-        const int y = o / w, x = o - y * w;
-        unsigned  sum = 0;
-        for( int k = 0; k < cut; k++ ) sum += ( unsigned ) tmp[k * h + y] * ( unsigned ) ( int ) sM[k * w + x];
-        int       v = min( 32767, max( -32768, ( int ) ( sum + rnd ) >> s2 ) );
-        if( CRS && adj ) v = lmcs_inv( v, adj, maxAbs );
-        if( rec ) rec[o] = ( int16_t ) v;
-        const int d = ( int ) sR[o] - ( int ) ( int16_t ) v;
-        sse += ( long long ) ( unsigned long long ) ( ( unsigned ) d * ( unsigned ) d );
-      }
-    }
-  }
-  }   // !ts
-  // ---- reduce the three sums over the TU's threads ------------------------------------------------------------------------------
-  sumAbs = ( long long ) wave_reduce_add_u64( ( unsigned long long ) sumAbs );
-  absSum = ( long long ) wave_reduce_add_u64( ( unsigned long long ) absSum );
-  sse    = ( long long ) wave_reduce_add_u64( ( unsigned long long ) sse );
-  if( TPT == 64 )
-  {
-    if( t == 0 ) { vtmhip_tu_result r; r.sse = ( uint64_t ) sse; r.sumAbs = ( int32_t ) sumAbs; r.absSum = ( int32_t ) absSum; results[jobIdx] = r; }
-  }
-  else
-  {
-    __syncthreads();
-    if( ( threadIdx.x & 63 ) == 0 ) { sRed[threadIdx.x >> 6][0] = sumAbs; sRed[threadIdx.x >> 6][1] = absSum; sRed[threadIdx.x >> 6][2] = sse; }
-    __syncthreads();
-    if( threadIdx.x == 0 )
-    {
-      vtmhip_tu_result r;
-      r.sumAbs = ( int32_t ) ( sRed[0][0] + sRed[1][0] + sRed[2][0] + sRed[3][0] );
-      r.absSum = ( int32_t ) ( sRed[0][1] + sRed[1][1] + sRed[2][1] + sRed[3][1] );
-      r.sse    = ( uint64_t ) ( sRed[0][2] + sRed[1][2] + sRed[2][2] + sRed[3][2] );
-      results[jobIdx] = r;
-    }
-  }
+  long long sums[3] = { sumAbs, absSum, sse };
+  chain_reduce_store<TPT, 3>( sums, sRed, sub, t, true, TuResultStore{ results + jobIdx } );
 }
 
 
@@ -584,7 +374,7 @@ __global__ __launch_bounds__( 256 ) void tu_chain_lane_kernel( const int16_t *__
   if( j.width != W || j.height != H || j.typeHor > 2 || j.typeVer > 2 ) return;   // the caller's promise is broken: leave the result untouched
   const int      bd = j.bitDepth;
   const int16_t *mh = sMH[j.typeHor], *mv = sMV[j.typeVer];
-  int            r[N], b[N], t[N];
+  int            r[N], b[N];
   const int16_t *resi = resiBase + j.resiOff;
   if( ( ( j.resiOff | j.resiStride ) & 3 ) == 0 )   // 8-byte aligned rows (offsets and strides of 4-sample blocks normally are): 4 samples per load
   {
@@ -613,90 +403,26 @@ __global__ __launch_bounds__( 256 ) void tu_chain_lane_kernel( const int16_t *__
     for( int i = 0; i < N; i++ ) r[i] = lmcs_fwd( r[i], sc, maxAbs );
   }
   long long sumAbs = 0, absSum = 0, sse = 0;
-  // forward: rows with the horizontal matrix, then columns with the vertical one (TrQuant::xT; no zero-out at these sizes)
-  {
-    const int s1 = LW + bd + 6 - 15, s2 = LH + 6;
-    const int rnd1 = s1 > 0 ? 1 << ( s1 - 1 ) : 0, rnd2 = 1 << ( s2 - 1 );
-#pragma unroll
-    for( int y = 0; y < H; y++ )
-#pragma unroll
-      for( int k = 0; k < W; k++ )
-      {
-        unsigned sum = 0;
-#pragma unroll
-        for( int n = 0; n < W; n++ ) sum += ( unsigned ) r[y * W + n] * ( unsigned ) ( int ) mh[k * W + n];
-        t[k * H + y] = ( int ) ( sum + ( unsigned ) rnd1 ) >> s1;
-      }
-#pragma unroll
-    for( int x = 0; x < W; x++ )
-#pragma unroll
-      for( int k = 0; k < H; k++ )
-      {
-        unsigned sum = 0;
-#pragma unroll
-        for( int n = 0; n < H; n++ ) sum += ( unsigned ) t[x * H + n] * ( unsigned ) ( int ) mv[k * H + n];
-        const int v = ( int ) ( sum + ( unsigned ) rnd2 ) >> s2;
-        b[k * W + x] = v;
-        sumAbs += abs( v );
-      }
-  }
+  lane_fwd_2d<W, H>( r, b, mh, mv, bd, sumAbs );
   // Quant::quant + Quant::dequant, flat scaling list
   {
-    constexpr int   needSqrt = ( LW + LH ) & 1;
-    const int       trShift  = 15 - bd - ( ( LW + LH ) >> 1 ) + ( needSqrt ? -1 : 0 );
-    const int       qBits    = 14 + j.qpPer + trShift;
-    const long long add      = ( long long ) ( j.isIRAP ? 171 : 85 ) << ( qBits - 9 );
-    const int       scale    = c_quantScales[needSqrt][j.qpRem], iscale = c_invQuantScales[needSqrt][j.qpRem];
-    const int       rightShift = 6 - ( trShift + j.qpPer );
-    const int       inBits   = min( 16, 32 + rightShift - 7 );
-    const int       inMin = -( 1 << ( inBits - 1 ) ), inMax = ( 1 << ( inBits - 1 ) ) - 1;
-    int            *levels   = levelsBase ? levelsBase + j.outOff : nullptr;
+    const QuantRule qr = quant_rule_of( j, LW, LH, false );
+    int            *levels = levelsBase ? levelsBase + j.outOff : nullptr;
 #pragma unroll
     for( int i = 0; i < N; i++ )
     {
-      const int       c   = b[i];
-      const long long tt  = ( long long ) abs( c ) * scale;
-      const int       mag = ( int ) ( ( tt + add ) >> qBits );
-      absSum += mag;
-      const int q = min( 32767, max( -32768, c < 0 ? -mag : mag ) );
+      const int q = qr.level( b[i], absSum );
       if( levels ) levels[i] = q;
-      const int qq = min( inMax, max( inMin, q ) );
-      int       v;
-      if( rightShift > 0 ) v = ( int ) ( ( unsigned ) ( qq * iscale ) + ( 1u << ( rightShift - 1 ) ) ) >> rightShift;
-      else v = ( int ) ( ( unsigned ) ( qq * iscale ) << ( -rightShift ) );
-      b[i] = min( 32767, max( -32768, v ) );
+      b[i] = qr.dequant( q );
     }
   }
-  // inverse: columns, then rows (TrQuant::xIT), SSE against the residual
-  {
-    const int      s2 = 20 - bd;
-    const unsigned rnd1 = 1u << 6, rnd2 = 1u << ( s2 - 1 );
-    int16_t       *rec = recBase ? recBase + j.outOff : nullptr;
-#pragma unroll
-    for( int x = 0; x < W; x++ )
-#pragma unroll
-      for( int y = 0; y < H; y++ )
-      {
-        unsigned sum = 0;
-#pragma unroll
-        for( int k = 0; k < H; k++ ) sum += ( unsigned ) b[k * W + x] * ( unsigned ) ( int ) mv[k * H + y];
-        t[x * H + y] = min( 32767, max( -32768, ( int ) ( sum + rnd1 ) >> 7 ) );
-      }
-#pragma unroll
-    for( int y = 0; y < H; y++ )
-#pragma unroll
-      for( int x = 0; x < W; x++ )
-      {
-        unsigned sum = 0;
-#pragma unroll
-        for( int k = 0; k < W; k++ ) sum += ( unsigned ) t[k * H + y] * ( unsigned ) ( int ) mh[k * W + x];
-        int       v = min( 32767, max( -32768, ( int ) ( sum + rnd2 ) >> s2 ) );
-        if( CRS && adj ) v = lmcs_inv( v, adj, maxAbs );
-        if( rec ) rec[y * W + x] = ( int16_t ) v;
-        const int d = ( CRS ? ( int ) resi[( long ) y * j.resiStride + x] : r[y * W + x] ) - v;
-        sse += ( long long ) ( unsigned long long ) ( ( unsigned ) d * ( unsigned ) d );
-      }
-  }
+  // inverse, SSE against the residual
+  int16_t *rec = recBase ? recBase + j.outOff : nullptr;
+  lane_inv_2d<W, H>( b, mh, mv, bd, [&]( int y, int x, int v ) {
+    if( CRS && adj ) v = lmcs_inv( v, adj, maxAbs );
+    if( rec ) rec[y * W + x] = ( int16_t ) v;
+    sse_add( sse, ( CRS ? ( int ) resi[( long ) y * j.resiStride + x] : r[y * W + x] ) - v );
+  } );
   vtmhip_tu_result res;
   res.sse = ( uint64_t ) sse; res.sumAbs = ( int32_t ) sumAbs; res.absSum = ( int32_t ) absSum;
   results[jobIdx] = res;
@@ -714,151 +440,8 @@ int launch_tu_lane( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_
 
 
 // ---- register-blocked fast path of the fused chain for batches of ONE TU size (W, H >= 8) --------------------------------------
-// Every pass is out[r][c] = sum_n A(r, n) * B[n][c] with B = the core matrix in the orientation that makes B[n][c .. c+7]
-// contiguous (forward: transposed, inverse: plain).  A lane owns 8 consecutive outputs of one row: per inner step it needs ONE
-// 32-bit LDS read of A and ONE 128-bit LDS read of B for 8 multiply-adds (the simple kernel above needs two LDS reads per
-// multiply-add and is LDS-issue bound).  LPT lanes share one TU; 256 / LPT TUs per workgroup; matrices staged once per workgroup.
-//
-// 24-bit multiplies are exact here: every B entry is a matrix coefficient (|m| <= 91) and every A value is bounded by 2^23 --
-// residuals / clipped coefficients are 16-bit and the first forward pass of 16-bit input stays below (sum|m| * 32768) >> shift1
-// < 2^23 for every size and bit depth >= 8.  v_mad_i32_i24 issues at full rate, v_mul_lo_u32 at a quarter of it.
-template<int LPT>
-__device__ __forceinline__ void tuq_sync()
-{
-  if( LPT <= 64 ) { __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" ); __builtin_amdgcn_wave_barrier(); }
-  else __syncthreads();
-}
-
-// rows x cols outputs (cols multiple of 8); rEff / cEff: outputs beyond them are zero (zero-out); inner: summation length
-template<int LPT, bool CLIP>
-__device__ __forceinline__ void tuq_pass( const int *A, int aRowStride, int aColStride, const int16_t *B, int ldb, int inner, int rows, int cols,
-                                          int rEff, int cEff, int *out, int oRowStride, int oColStride, int shift, int t, long long *sumAbs )
-{
-  // one lane: a 2 x 8 block of outputs (rows r, r + 1): the 16-byte matrix read of a summation step feeds 16 multiply-adds
-  const int cb = cols >> 3, lcb = 31 - __clz( cb ), rnd = shift > 0 ? 1 << ( shift - 1 ) : 0;
-  for( int it = t; it < ( rows >> 1 ) * cb; it += LPT )
-  {
-    const int r = ( it >> lcb ) << 1, c0 = ( it & ( cb - 1 ) ) << 3;   // cb is a power of two (TU sizes are)
-    int       acc[2][8];
-#pragma unroll
-    for( int i = 0; i < 8; i++ ) acc[0][i] = acc[1][i] = rnd;
-    if( r < rEff && c0 < cEff )
-    {
-      const int *a0 = A + r * aRowStride, *a1 = a0 + aRowStride;
-      for( int n = 0; n < inner; n++ )
-      {
-        const int  av0 = a0[n * aColStride], av1 = a1[n * aColStride];
-        const int4 bv = *reinterpret_cast<const int4 *>( B + n * ldb + c0 );
-        const int  b[8] = { ( int ) ( short ) bv.x, bv.x >> 16, ( int ) ( short ) bv.y, bv.y >> 16, ( int ) ( short ) bv.z, bv.z >> 16, ( int ) ( short ) bv.w, bv.w >> 16 };
-#pragma unroll
-        for( int i = 0; i < 8; i++ ) { acc[0][i] += __mul24( av0, b[i] ); acc[1][i] += __mul24( av1, b[i] ); }
-      }
-    }
-#pragma unroll
-    for( int q = 0; q < 2; q++ )
-#pragma unroll
-      for( int i = 0; i < 8; i++ )
-      {
-        int v = ( r + q < rEff && c0 + i < cEff ) ? acc[q][i] >> shift : 0;
-        if( CLIP ) v = min( 32767, max( -32768, v ) );
-        out[( r + q ) * oRowStride + ( c0 + i ) * oColStride] = v;
-        if( sumAbs ) *sumAbs += abs( v );
-      }
-  }
-}
-
-// tuq_pass with the matrix in the pair-interleaved layout of tuq_pass16 (Bp[(n >> 1) * cols + c] = (B[n][c], B[n+1][c])): square TUs take the second
-// forward pass's M^T from the slot the first one uses, so no plain copy is staged.  Two summation steps per trip; same loads per step as tuq_pass.
-template<int LPT, bool CLIP>
-__device__ __forceinline__ void tuq_pass_il( const int *A, int aRowStride, int aColStride, const unsigned *Bp, int inner, int rows, int cols, int rEff, int cEff,
-                                             int *out, int oRowStride, int oColStride, int shift, int t, long long *sumAbs )
-{
-  const int cb = cols >> 3, lcb = 31 - __clz( cb ), rnd = shift > 0 ? 1 << ( shift - 1 ) : 0;
-  for( int it = t; it < ( rows >> 1 ) * cb; it += LPT )
-  {
-    const int r = ( it >> lcb ) << 1, c0 = ( it & ( cb - 1 ) ) << 3;
-    int       acc[2][8];
-#pragma unroll
-    for( int i = 0; i < 8; i++ ) acc[0][i] = acc[1][i] = rnd;
-    if( r < rEff && c0 < cEff )
-    {
-      const int *a0 = A + r * aRowStride, *a1 = a0 + aRowStride;
-      for( int n2 = 0; n2 < ( inner >> 1 ); n2++ )
-      {
-        const int   n = n2 << 1;
-        const int   e0 = a0[n * aColStride], o0 = a0[( n + 1 ) * aColStride], e1 = a1[n * aColStride], o1 = a1[( n + 1 ) * aColStride];
-        const uint4 b0 = *reinterpret_cast<const uint4 *>( Bp + n2 * cols + c0 ), b1 = *reinterpret_cast<const uint4 *>( Bp + n2 * cols + c0 + 4 );
-        const unsigned bw[8] = { b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w };
-#pragma unroll
-        for( int i = 0; i < 8; i++ )
-        {
-          const int be = ( int ) ( short ) bw[i], bo = ( int ) bw[i] >> 16;
-          acc[0][i] += __mul24( e0, be ) + __mul24( o0, bo );
-          acc[1][i] += __mul24( e1, be ) + __mul24( o1, bo );
-        }
-      }
-    }
-#pragma unroll
-    for( int q = 0; q < 2; q++ )
-#pragma unroll
-      for( int i = 0; i < 8; i++ )
-      {
-        int v = ( r + q < rEff && c0 + i < cEff ) ? acc[q][i] >> shift : 0;
-        if( CLIP ) v = min( 32767, max( -32768, v ) );
-        out[( r + q ) * oRowStride + ( c0 + i ) * oColStride] = v;
-        if( sumAbs ) *sumAbs += abs( v );
-      }
-  }
-}
-
-// The same product when every A value fits 16 bits (residuals; dequantised coefficients and the first inverse pass are clipped to
-// 16 bits): v_dot2c_i32_i16 takes two summation steps per instruction.  A: int16, the summation index contiguous (rows of
-// aRowStride samples, even); Bp: the matrix with rows n, n + 1 interleaved per column -- Bp[(n >> 1) * cols + c] = (B[n][c], B[n+1][c]).
-template<int LPT, bool CLIP, class OutT>
-__device__ __forceinline__ void tuq_pass16( const int16_t *A, int aRowStride, const unsigned *Bp, int inner, int rows, int cols, int rEff, int cEff, OutT *out,
-                                            int oRowStride, int oColStride, int shift, int t )
-{
-  typedef short v2s __attribute__( ( ext_vector_type( 2 ) ) );
-  const int cb = cols >> 3, lcb = 31 - __clz( cb ), rnd = shift > 0 ? 1 << ( shift - 1 ) : 0;
-  for( int it = t; it < ( rows >> 1 ) * cb; it += LPT )   // a 2 x 8 block of outputs per lane
-  {
-    const int r = ( it >> lcb ) << 1, c0 = ( it & ( cb - 1 ) ) << 3;   // cb is a power of two (TU sizes are)
-    int       acc[2][8];
-#pragma unroll
-    for( int i = 0; i < 8; i++ ) acc[0][i] = acc[1][i] = rnd;
-    if( r < rEff && c0 < cEff )
-    {
-      const unsigned *a0 = reinterpret_cast<const unsigned *>( A + r * aRowStride ), *a1 = reinterpret_cast<const unsigned *>( A + ( r + 1 ) * aRowStride );
-      for( int n2 = 0; n2 < ( inner >> 1 ); n2++ )
-      {
-        const unsigned av0 = a0[n2], av1 = a1[n2];
-        const uint4    b0 = *reinterpret_cast<const uint4 *>( Bp + n2 * cols + c0 ), b1 = *reinterpret_cast<const uint4 *>( Bp + n2 * cols + c0 + 4 );
-        const unsigned bw[8] = { b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w };
-        v2s va0, va1;
-        __builtin_memcpy( &va0, &av0, 4 );
-        __builtin_memcpy( &va1, &av1, 4 );
-#pragma unroll
-        for( int i = 0; i < 8; i++ )
-        {
-          v2s vb;
-          __builtin_memcpy( &vb, &bw[i], 4 );
-          acc[0][i] = __builtin_amdgcn_sdot2( va0, vb, acc[0][i], false );
-          acc[1][i] = __builtin_amdgcn_sdot2( va1, vb, acc[1][i], false );
-        }
-      }
-    }
-#pragma unroll
-    for( int q = 0; q < 2; q++ )
-#pragma unroll
-      for( int i = 0; i < 8; i++ )
-      {
-        int v = ( r + q < rEff && c0 + i < cEff ) ? acc[q][i] >> shift : 0;
-        if( CLIP ) v = min( 32767, max( -32768, v ) );
-        out[( r + q ) * oRowStride + ( c0 + i ) * oColStride] = ( OutT ) v;
-      }
-  }
-}
-
+// tu_stages.hpp's blocked passes: a lane owns 2 x 8 outputs of a pass.  LPT lanes share one TU; 256 / LPT TUs per workgroup; the matrices
+// of the three transform types are staged once per workgroup.
 template<int LPT, bool CRS>
 __global__ __launch_bounds__( 256 ) void tu_chain_uni_kernel( const int16_t *__restrict__ resiBase, const vtmhip_tu_job *__restrict__ jobs, int numJobs,
                                                              TrTables tabs, int *__restrict__ levelsBase, int16_t *__restrict__ recBase,
@@ -876,23 +459,10 @@ __global__ __launch_bounds__( 256 ) void tu_chain_uni_kernel( const int16_t *__r
   const bool    sq    = w == h;                       // square TUs: both height matrices ARE the width's slots (tuq_pass_il reads the interleaved transpose)
   for( int ty = 0; ty < 3; ty++ )
   {
+    // [type][slot]: slot 0 = M (the inverse passes), slot 1 = M^T (the forward passes; the height's is plain: 32-bit input)
     const int16_t *mw = ( ty == 0 || w <= 32 ) ? tabs.m[ty][lw] : nullptr, *mh = ( ty == 0 || h <= 32 ) ? tabs.m[ty][lh] : nullptr;   // DST-7 / DCT-8 exist up to 32
-    // width:  slot 0 = M_W with rows k, k+1 interleaved (second inverse pass), slot 1 = M_W^T with rows n, n+1 interleaved (first forward pass)
-    // height: slot 0 = M_H with rows k, k+1 interleaved (first inverse pass),   slot 1 = M_H^T plain (second forward pass: 32-bit input)
-    if( mw )
-      for( int i = threadIdx.x; i < w * w; i += 256 )
-      {
-        const int k = i >> lw, n = i & ( w - 1 );   // w, h: powers of two
-        sMat[( ty * 2 + 0 ) * w * w + ( ( k >> 1 ) * w + n ) * 2 + ( k & 1 )] = mw[i];   // (M[k][n], M[k+1][n]) at pair-row k >> 1, column n
-        sMat[( ty * 2 + 1 ) * w * w + ( ( n >> 1 ) * w + k ) * 2 + ( n & 1 )] = mw[i];   // (M[k][n], M[k][n+1]) at pair-row n >> 1, column k
-      }
-    if( mh && !sq )
-      for( int i = threadIdx.x; i < h * h; i += 256 )
-      {
-        const int k = i >> lh, n = i & ( h - 1 );
-        sMat[hBase + ( ty * 2 + 0 ) * h * h + ( ( k >> 1 ) * h + n ) * 2 + ( k & 1 )] = mh[i];
-        sMat[hBase + ( ty * 2 + 1 ) * h * h + n * h + k]                              = mh[i];
-      }
+    if( mw ) tuq_stage_matrix<false>( mw, w, lw, sMat + ( ty * 2 ) * w * w, sMat + ( ty * 2 + 1 ) * w * w );
+    if( mh && !sq ) tuq_stage_matrix<true>( mh, h, lh, sMat + hBase + ( ty * 2 ) * h * h, sMat + hBase + ( ty * 2 + 1 ) * h * h );
   }
   __syncthreads();
   const int  jobIdx = blockIdx.x * TUS + sub;
@@ -920,13 +490,13 @@ __global__ __launch_bounds__( 256 ) void tu_chain_uni_kernel( const int16_t *__r
   int     *rec32 = tmp;                                  // reconstructed residual [y][x]
   const int skipW = tr_skip( j.typeHor, w ), skipH = tr_skip( j.typeVer, h );
   long long sumAbs = 0, absSum = 0, sse = 0;
-  tuq_sync<LPT>();
+  chain_sync<LPT>();
   // forward (TrQuant::xT): tmp[k][y] = sum_n blk[y][n] * MT_hor[n][k];  blk[k2][j2] = sum_n tmp[j2][n] * MT_ver[n][k2]
   tuq_pass16<LPT, false>( sR, w, reinterpret_cast<const unsigned *>( mW + w * w ), w, h, w, h, w - skipW, tmp, 1, h + 1, lw + bd + 6 - 15, t );
-  tuq_sync<LPT>();
+  chain_sync<LPT>();
   if( sq ) tuq_pass_il<LPT, false>( tmp, h + 1, 1, reinterpret_cast<const unsigned *>( mH1 ), h, w, h, w - skipW, h - skipH, blk, 1, w, lh + 6, t, &sumAbs );
   else tuq_pass<LPT, false>( tmp, h + 1, 1, mH1, h, h, w, h, w - skipW, h - skipH, blk, 1, w, lh + 6, t, &sumAbs );
-  tuq_sync<LPT>();
+  chain_sync<LPT>();
   if( fwdCoefBase )
   {
     if( live )
@@ -934,38 +504,23 @@ __global__ __launch_bounds__( 256 ) void tu_chain_uni_kernel( const int16_t *__r
   }
   else
   {
-    // Quant::quant + Quant::dequant (flat scaling list), in place
+    // Quant::quant + Quant::dequant (flat scaling list)
     {
-      const int       needSqrt = ( lw + lh ) & 1;
-      const int       trShift  = 15 - bd - ( ( lw + lh ) >> 1 ) + ( needSqrt ? -1 : 0 );
-      const int       qBits    = 14 + j.qpPer + trShift;
-      const long long add      = ( long long ) ( j.isIRAP ? 171 : 85 ) << ( qBits - 9 );
-      const int       scale    = c_quantScales[needSqrt][j.qpRem], iscale = c_invQuantScales[needSqrt][j.qpRem];
-      const int       rightShift = 6 - ( trShift + j.qpPer );
-      const int       inBits   = min( 16, 32 + rightShift - 7 );
-      const int       inMin = -( 1 << ( inBits - 1 ) ), inMax = ( 1 << ( inBits - 1 ) ) - 1;
-      int            *levels   = ( levelsBase && live ) ? levelsBase + j.outOff : nullptr;
+      const QuantRule qr = quant_rule_of( j, lw, lh, false );
+      int            *levels = ( levelsBase && live ) ? levelsBase + j.outOff : nullptr;
       for( int i = t; i < w * h; i += LPT )
       {
-        const int       c   = blk[i];
-        const long long tt  = ( long long ) abs( c ) * scale;
-        const int       mag = ( int ) ( ( tt + add ) >> qBits );
-        absSum += mag;
-        const int q = min( 32767, max( -32768, c < 0 ? -mag : mag ) );
+        const int q = qr.level( blk[i], absSum );
         if( levels ) levels[i] = q;
-        const int qq = min( inMax, max( inMin, q ) );
-        int       v;
-        if( rightShift > 0 ) v = ( int ) ( ( unsigned ) ( qq * iscale ) + ( 1u << ( rightShift - 1 ) ) ) >> rightShift;
-        else v = ( int ) ( ( unsigned ) ( qq * iscale ) << ( -rightShift ) );
-        dq16[( ( i & ( w - 1 ) ) << lh ) + ( i >> lw )] = ( int16_t ) min( 32767, max( -32768, v ) );   // transposed: the vertical index contiguous
+        dq16[( ( i & ( w - 1 ) ) << lh ) + ( i >> lw )] = ( int16_t ) qr.dequant( q );   // transposed: the vertical index contiguous
       }
     }
-    tuq_sync<LPT>();
+    chain_sync<LPT>();
     // inverse (TrQuant::xIT): tmp[i][y] = clip( sum_k blk[k][i] * M_ver[k][y] );  rec[y][x] = clip( sum_k tmp[k][y] * M_hor[k][x] )
     tuq_pass16<LPT, true>( dq16, h, reinterpret_cast<const unsigned *>( mH0 ), h - skipH, w, h, w - skipW, h, t16, 1, w, 7, t );
-    tuq_sync<LPT>();
+    chain_sync<LPT>();
     tuq_pass16<LPT, true>( t16, w, reinterpret_cast<const unsigned *>( mW ), w - skipW, h, w, h, w, rec32, w, 1, 20 - bd, t );
-    tuq_sync<LPT>();
+    chain_sync<LPT>();
     {
       int16_t *rec = ( recBase && live ) ? recBase + j.outOff : nullptr;
       for( int i = t; i < w * h; i += LPT )
@@ -973,42 +528,12 @@ __global__ __launch_bounds__( 256 ) void tu_chain_uni_kernel( const int16_t *__r
         int v = rec32[i];
         if( CRS && adj ) v = lmcs_inv( v, adj, maxAbs );
         if( rec ) rec[i] = ( int16_t ) v;
-        const int d = ( int ) resi[( long ) ( i >> lw ) * j.resiStride + ( i & ( w - 1 ) )] - v;   // the residual again, from L2: its LDS copy made room for a third workgroup per CU
-        sse += ( long long ) ( unsigned long long ) ( ( unsigned ) d * ( unsigned ) d );
+        sse_add( sse, ( int ) resi[( long ) ( i >> lw ) * j.resiStride + ( i & ( w - 1 ) )] - v );   // the residual again, from L2: its LDS copy made room for a third workgroup per CU
       }
     }
   }
-  // reduce the three sums over the LPT lanes of the TU
-  if( LPT <= 64 )
-  {
-#pragma unroll
-    for( int o = 32; o > 0; o >>= 1 )
-      if( o < LPT )
-      {
-        sumAbs += __shfl_xor( sumAbs, o, 64 );
-        absSum += __shfl_xor( absSum, o, 64 );
-        sse += __shfl_xor( sse, o, 64 );
-      }
-    if( t == 0 && live ) { vtmhip_tu_result r; r.sse = ( uint64_t ) sse; r.sumAbs = ( int32_t ) sumAbs; r.absSum = ( int32_t ) absSum; results[jobIdx] = r; }
-  }
-  else
-  {
-    sumAbs = ( long long ) wave_reduce_add_u64( ( unsigned long long ) sumAbs );
-    absSum = ( long long ) wave_reduce_add_u64( ( unsigned long long ) absSum );
-    sse    = ( long long ) wave_reduce_add_u64( ( unsigned long long ) sse );
-    __syncthreads();
-    if( ( threadIdx.x & 63 ) == 0 ) { sRed[threadIdx.x >> 6][0] = sumAbs; sRed[threadIdx.x >> 6][1] = absSum; sRed[threadIdx.x >> 6][2] = sse; }
-    __syncthreads();
-    constexpr int WPT = LPT / 64;   // waves per TU
-    if( t == 0 && live )
-    {
-      vtmhip_tu_result r;
-      long long a0 = 0, a1 = 0, a2 = 0;
-      for( int k = 0; k < WPT; k++ ) { a0 += sRed[sub * WPT + k][0]; a1 += sRed[sub * WPT + k][1]; a2 += sRed[sub * WPT + k][2]; }
-      r.sumAbs = ( int32_t ) a0; r.absSum = ( int32_t ) a1; r.sse = ( uint64_t ) a2;
-      results[jobIdx] = r;
-    }
-  }
+  long long sums[3] = { sumAbs, absSum, sse };
+  chain_reduce_store<LPT, 3>( sums, sRed, sub, t, live, TuResultStore{ results + ( live ? jobIdx : 0 ) } );
 }
 
 template<int LPT, bool CRS>
@@ -1050,12 +575,7 @@ __global__ __launch_bounds__( 256 ) void tu_ts_kernel( const int16_t *__restrict
   const bool live  = jobIdx < numJobs;
   const vtmhip_tu_job j = jobs[live ? jobIdx : numJobs - 1];
   const int       lw = ilog2( w );
-  const int       qBits = 14 + j.qpPer;
-  const long long add   = ( long long ) ( j.isIRAP ? 171 : 85 ) << ( qBits - 9 );
-  const int       scale = c_quantScales[0][j.qpRem], iscale = c_invQuantScales[0][j.qpRem];
-  const int       rightShift = 6 - j.qpPer;
-  const int       inBits = min( 16, 32 + rightShift - 7 );
-  const int       inMin = -( 1 << ( inBits - 1 ) ), inMax = ( 1 << ( inBits - 1 ) ) - 1;
+  const QuantRule qr = quant_rule_of( j, lw, ilog2( h ), true );
   int            *levels = ( levelsBase && live ) ? levelsBase + j.outOff : nullptr;
   int16_t        *rec    = ( recBase && live ) ? recBase + j.outOff : nullptr;
   const int16_t  *resi   = resiBase + j.resiOff;
@@ -1064,28 +584,14 @@ __global__ __launch_bounds__( 256 ) void tu_ts_kernel( const int16_t *__restrict
   {
     const int c = resi[( long ) ( i >> lw ) * j.resiStride + ( i & ( w - 1 ) )];
     sumAbs += abs( c );
-    const long long tt  = ( long long ) abs( c ) * scale;
-    const int       mag = ( int ) ( ( tt + add ) >> qBits );
-    absSum += mag;
-    const int q = min( 32767, max( -32768, c < 0 ? -mag : mag ) );
+    const int q = qr.level( c, absSum );
     if( levels ) levels[i] = q;
-    const int qq = min( inMax, max( inMin, q ) );
-    int       v;
-    if( rightShift > 0 ) v = ( int ) ( ( unsigned ) ( qq * iscale ) + ( 1u << ( rightShift - 1 ) ) ) >> rightShift;
-    else v = ( int ) ( ( unsigned ) ( qq * iscale ) << ( -rightShift ) );
-    v = ( int ) ( int16_t ) min( 32767, max( -32768, v ) );
+    const int v = ( int ) ( int16_t ) qr.dequant( q );
     if( rec ) rec[i] = ( int16_t ) v;
-    const int d = c - v;
-    sse += ( long long ) ( unsigned long long ) ( ( unsigned ) d * ( unsigned ) d );
+    sse_add( sse, c - v );
   }
-#pragma unroll
-  for( int o = 4; o > 0; o >>= 1 )
-  {
-    sumAbs += __shfl_xor( sumAbs, o, 64 );
-    absSum += __shfl_xor( absSum, o, 64 );
-    sse += __shfl_xor( sse, o, 64 );
-  }
-  if( t == 0 && live ) { vtmhip_tu_result r; r.sse = ( uint64_t ) sse; r.sumAbs = ( int32_t ) sumAbs; r.absSum = ( int32_t ) absSum; results[jobIdx] = r; }
+  long long sums[3] = { sumAbs, absSum, sse };
+  chain_reduce_store<8, 3>( sums, nullptr, 0, t, live, TuResultStore{ results + ( live ? jobIdx : 0 ) } );
 }
 
 bool pow2( int v ) { return v > 0 && ( v & ( v - 1 ) ) == 0; }
@@ -1131,7 +637,7 @@ int tu_chain_entry( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_
   if( n == 0 ) return VTMHIP_OK;
   VTMHIP_REQUIRE( ctx, d_resiBase && d_jobs && d_results, "null pointer" );
   VTMHIP_REQUIRE( ctx, maxWidth >= 2 && maxWidth <= TB && maxHeight >= 2 && maxHeight <= TB, "maxWidth / maxHeight: 2..64 (2-D transforms)" );
-  int st = ensure_tables( ctx );
+  int st = vtmhip_internal_tr_tables( ctx );
   if( st ) return st;
   // a mixed batch with enough TUs: bucket by shape on the device (bucket.hpp), the register-blocked kernel per {8,16,32,64} x {8,16,32,64} class, the
   // generic kernel for the rest (4-sample sides, transform skip).  VTMHIP_TU_BUCKET=0 keeps the generic kernel for the whole batch.
@@ -1202,7 +708,7 @@ int vtmhip_fastFwdTrans( vtmhip_ctx *ctx, int type, int n, const int32_t *src, i
   VTMHIP_REQUIRE( ctx, type >= 0 && type < 3 && pow2( n ) && n >= 2 && n <= 64 && ( type == VTMHIP_DCT2 || ( n >= 4 && n <= 32 ) ),
                   "no such transform (fastFwdTrans slot is nullptr)" );
   VTMHIP_REQUIRE( ctx, line >= 1 && line <= 64 && shift >= 0 && shift < 32 && skipLine >= 0 && skipLine <= line && skipLine2 >= 0 && skipLine2 <= n, "shape" );
-  int st = ensure_tables( ctx );
+  int st = vtmhip_internal_tr_tables( ctx );
   if( st ) return st;
   const size_t bytes = ( size_t ) n * line * 4;
   st = vtmhip_internal_scratch( ctx, 2 * bytes + 128 );
@@ -1228,7 +734,7 @@ int vtmhip_fastInvTrans( vtmhip_ctx *ctx, int type, int n, const int32_t *src, i
   VTMHIP_REQUIRE( ctx, type >= 0 && type < 3 && pow2( n ) && n >= 2 && n <= 64 && ( type == VTMHIP_DCT2 || ( n >= 4 && n <= 32 ) ),
                   "no such transform (fastInvTrans slot is nullptr)" );
   VTMHIP_REQUIRE( ctx, line >= 1 && line <= 64 && shift >= 1 && shift < 32 && skipLine >= 0 && skipLine <= line && skipLine2 >= 0 && skipLine2 <= n, "shape" );
-  int st = ensure_tables( ctx );
+  int st = vtmhip_internal_tr_tables( ctx );
   if( st ) return st;
   const size_t bytes = ( size_t ) n * line * 4;
   st = vtmhip_internal_scratch( ctx, 2 * bytes + 128 );
@@ -1254,7 +760,7 @@ int vtmhip_xT_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, int32_t *d_
   if( n == 0 ) return VTMHIP_OK;
   VTMHIP_REQUIRE( ctx, d_resiBase && d_coefBase && d_jobs, "null pointer" );
   VTMHIP_REQUIRE( ctx, maxWidth >= 1 && maxWidth <= TB && maxHeight >= 1 && maxHeight <= TB, "maxWidth / maxHeight (max transform size 64)" );
-  int st = ensure_tables( ctx );
+  int st = vtmhip_internal_tr_tables( ctx );
   if( st ) return st;
   const int    mx  = maxWidth > maxHeight ? maxWidth : maxHeight;
   const size_t lds = ( size_t ) ( maxWidth * maxHeight + maxWidth * ( maxHeight + 1 ) ) * 4 + ( size_t ) mx * mx * 2 + 16;
@@ -1271,7 +777,7 @@ int vtmhip_xIT_batch_dev( vtmhip_ctx *ctx, const int32_t *d_coefBase, int16_t *d
   if( n == 0 ) return VTMHIP_OK;
   VTMHIP_REQUIRE( ctx, d_resiBase && d_coefBase && d_jobs, "null pointer" );
   VTMHIP_REQUIRE( ctx, maxWidth >= 1 && maxWidth <= TB && maxHeight >= 1 && maxHeight <= TB, "maxWidth / maxHeight (max transform size 64)" );
-  int st = ensure_tables( ctx );
+  int st = vtmhip_internal_tr_tables( ctx );
   if( st ) return st;
   const int    mx  = maxWidth > maxHeight ? maxWidth : maxHeight;
   const size_t lds = ( size_t ) ( 2 * maxWidth * maxHeight ) * 4 + ( size_t ) mx * mx * 2 + 16;
@@ -1413,7 +919,7 @@ extern "C" int vtmhip_xT_uniform_batch_dev( vtmhip_ctx *ctx, const int16_t *d_re
   if( n == 0 ) return VTMHIP_OK;
   VTMHIP_REQUIRE( ctx, d_resiBase && d_jobs && d_coefBase && d_results, "null pointer" );
   VTMHIP_REQUIRE( ctx, width >= 8 && width <= TB && height >= 8 && height <= TB && pow2( width ) && pow2( height ), "width / height: powers of two 8..64" );
-  int st = ensure_tables( ctx );
+  int st = vtmhip_internal_tr_tables( ctx );
   if( st ) return st;
   return launch_tu_uni_sized<false>( ctx, d_resiBase, d_jobs, n, width, height, nullptr, nullptr, d_results, tabs_of( ctx ), d_coefBase );
 }
