@@ -4,6 +4,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <utility>
@@ -103,6 +104,31 @@ struct vtmhip_launch_timer
 // launch-error check after a kernel launch (asynchronous errors surface at the next sync)
 #define VTMHIP_LAUNCHED( ctx ) VTMHIP_HIP( ctx, hipGetLastError() )
 
+// a call that returns a status: a failure is the caller's result
+#define VTMHIP_TRY( call )                                 \
+  do {                                                     \
+    const int st_ = ( call );                              \
+    if( st_ ) return st_;                                  \
+  } while( 0 )
+
+// how a _batch_dev entry starts: the context, n >= 0, nothing to do for n == 0, then the pointers the entry needs (`ptrs`: their conjunction).  An entry
+// that checks something between the context and n (lmcs_resi: its LUT) writes VTMHIP_CHECK_CTX, that check, then VTMHIP_BATCH_ARGS.
+#define VTMHIP_BATCH_ARGS( ctx, n, ptrs )                  \
+  do {                                                     \
+    VTMHIP_REQUIRE( ctx, ( n ) >= 0, "n" );                \
+    if( ( n ) == 0 ) return VTMHIP_OK;                     \
+    VTMHIP_REQUIRE( ctx, ptrs, "null pointer" );           \
+  } while( 0 )
+#define VTMHIP_BATCH_ENTRY( ctx, n, ptrs )                 \
+  do {                                                     \
+    VTMHIP_CHECK_CTX( ctx );                               \
+    VTMHIP_BATCH_ARGS( ctx, n, ptrs );                     \
+  } while( 0 )
+
+// tuning switches of the environment; a call site keeps the value in a function-local static, so each is read once per process
+inline int  env_int( const char *name, int dflt ) { const char *v = getenv( name ); return v ? atoi( v ) : dflt; }
+inline bool env_switch( const char *name, bool dflt ) { return env_int( name, dflt ) != 0; }
+
 int vtmhip_internal_scratch( vtmhip_ctx *ctx, size_t bytes );   // grows ctx->scratch / ctx->pinned
 int vtmhip_internal_tr_tables( vtmhip_ctx *ctx );               // transform.hip: fills ctx->trTab / trTabBuf on first use (under initMutex)
 int vtmhip_internal_mc_launch( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_refBase, int16_t *d_predBase, int16_t *d_outBase, const vtmhip_pred_job *d_jobs,
@@ -127,6 +153,14 @@ int vtmhip_internal_mest_with_amvp( vtmhip_ctx *ctx, const vtmhip_pic_params *pi
                                     unsigned long long *d_distBiP, int addIdxBits );   // mest.hip
 int vtmhip_internal_mest_fusable( const vtmhip_me_cfg *cfg );
 int vtmhip_internal_workspace( vtmhip_ctx *ctx, size_t bytes, void **out, int slot = 0 ); // the arena (slot) of ctx->stream, grown to `bytes` (device only)
+
+// the uniform PU shapes that have tiled search kernels of their own, listed once: X( W, H ) for a shape both the exhaustive search (full_search_sq_kernel, me.hip) and
+// the fractional search (frac_search_sq_kernel, interp.hip) are instantiated for, X_FRAC( W, H ) for the one only the fractional search has.  vtmhip_is_uniform_shape
+// (driver.hip) answers for all of them.
+#define VTMHIP_UNIFORM_SHAPES( X, X_FRAC )                                                      \
+  X( 8, 8 ) X( 16, 16 ) X( 32, 32 ) X( 64, 64 ) X_FRAC( 128, 128 )                              \
+  X( 16, 8 ) X( 8, 16 ) X( 32, 8 ) X( 8, 32 ) X( 32, 16 ) X( 16, 32 ) X( 64, 16 ) X( 16, 64 ) X( 64, 32 ) X( 32, 64 )
+#define VTMHIP_SHAPE_NONE( W, H )
 
 // ---- device helpers -------------------------------------------------------------------------------------------
 __device__ __forceinline__ int wave_reduce_add( int v )

@@ -12,6 +12,7 @@
 //                       (HBM traffic ~ one read of each picture; the kernel is integer-VALU bound).
 #include <cstdlib>
 #include "ctx.hpp"
+#include "stage.hpp"
 #include "had.hpp"
 #include "dist_block.hpp"
 
@@ -248,29 +249,23 @@ int dist_single( vtmhip_ctx *ctx, int kind, const int16_t *org, int orgStride, c
 {
   VTMHIP_CHECK_CTX( ctx );
   VTMHIP_REQUIRE( ctx, org && cur && dist, "null pointer" );
-  int st = check_dist_args( ctx, w, h, subShift, kind );
-  if( st ) return st;
+  VTMHIP_TRY( check_dist_args( ctx, w, h, subShift, kind ) );
+  HostStage    s( ctx );
   const size_t blk = ( size_t ) w * h * sizeof( int16_t );
-  const size_t jobOff = ( 2 * blk + 63 ) & ~( size_t ) 63, outOff = jobOff + 64;
-  st = vtmhip_internal_scratch( ctx, outOff + 64 );
-  if( st ) return st;
-  char *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
-  for( int y = 0; y < h; y++ )
-  {
-    memcpy( hp + ( size_t ) y * w * 2, org + ( ptrdiff_t ) y * orgStride, ( size_t ) w * 2 );
-    memcpy( hp + blk + ( size_t ) y * w * 2, cur + ( ptrdiff_t ) y * curStride, ( size_t ) w * 2 );
-  }
+  const size_t orgOff = s.region( blk ), curOff = s.region( blk ), jobOff = s.region( sizeof( vtmhip_dist_job ) ), outOff = s.region( 8 );
+  VTMHIP_TRY( s.reserve() );
+  s.pack( orgOff, org, orgStride, w, h );
+  s.pack( curOff, cur, curStride, w, h );
   vtmhip_dist_job j;
-  j.orgOff = 0; j.curOff = ( int64_t ) w * h; j.orgStride = w; j.curStride = w;
+  j.orgOff = ( int64_t ) ( orgOff / 2 ); j.curOff = ( int64_t ) ( curOff / 2 ); j.orgStride = w; j.curStride = w;
   j.width = ( int16_t ) w; j.height = ( int16_t ) h; j.subShift = ( int16_t ) subShift; j.kind = ( int16_t ) kind;
-  memcpy( hp + jobOff, &j, sizeof( j ) );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, outOff, hipMemcpyHostToDevice, ctx->stream ) );
-  hipLaunchKernelGGL( dist_batch_kernel, dim3( 1 ), dim3( 256 ), 0, ctx->stream, ( const int16_t * ) dp, ( const int16_t * ) dp,
-                      ( const vtmhip_dist_job * ) ( dp + jobOff ), 1, ( unsigned long long * ) ( dp + outOff ) );
+  s.put( jobOff, j );
+  VTMHIP_TRY( s.upload( 0, outOff ) );
+  hipLaunchKernelGGL( dist_batch_kernel, dim3( 1 ), dim3( 256 ), 0, ctx->stream, s.dev<const int16_t>( 0 ), s.dev<const int16_t>( 0 ),
+                      s.dev<const vtmhip_dist_job>( jobOff ), 1, s.dev<unsigned long long>( outOff ) );
   VTMHIP_LAUNCHED( ctx );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( hp + outOff, dp + outOff, 8, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
-  memcpy( dist, hp + outOff, 8 );
+  VTMHIP_TRY( s.fetch( outOff, 8 ) );
+  memcpy( dist, s.hp + outOff, 8 );
   return VTMHIP_OK;
 }
 
@@ -298,10 +293,7 @@ int vtmhip_xGetSSE( vtmhip_ctx *ctx, const int16_t *org, int orgStride, const in
 int vtmhip_dist_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_curBase, const vtmhip_dist_job *d_jobs, int n,
                            uint64_t *d_dist )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_orgBase && d_curBase && d_jobs && d_dist, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_orgBase && d_curBase && d_jobs && d_dist );
   const int wavesPerBlock = 4;
   hipLaunchKernelGGL( dist_batch_kernel, dim3( ( n + wavesPerBlock - 1 ) / wavesPerBlock ), dim3( 64 * wavesPerBlock ), 0, ctx->stream,
                       d_orgBase, d_curBase, d_jobs, n, ( unsigned long long * ) d_dist );
@@ -353,7 +345,7 @@ int vtmhip_satd8_grid_dev( vtmhip_ctx *ctx, const int16_t *d_org, int orgStride,
   VTMHIP_REQUIRE( ctx, ( orgStride & 7 ) == 0 && ( ( ( uintptr_t ) d_org ) & 15 ) == 0, "org plane must be 16-byte aligned with a stride multiple of 8" );
   const int bw = width / 8, bh = height / 8;
   // workgroup shape: 8 x TBY blocks, THREADS lanes over the TBY * 8 * (2r+1)^2 pairs.  Tuned on 3840x2160, r = 4 (VTMHIP_SATD_VARIANT overrides it)
-  static const int variant = getenv( "VTMHIP_SATD_VARIANT" ) ? atoi( getenv( "VTMHIP_SATD_VARIANT" ) ) : 0;
+  static const int variant = env_int( "VTMHIP_SATD_VARIANT", 0 );
   auto launch = [&]( auto kern, int threads, int tby ) {
     const int    refW = GRID_TBX * 8 + 2 * r, refH = tby * 8 + 2 * r, refLd = ( refW + 7 ) & ~7;
     const size_t lds = ( size_t ) ( tby * 8 * GRID_TBX * 8 + refH * refLd ) * sizeof( int16_t ) + 16;   // + one spare vector: the packed path reads a fifth dword per row
@@ -382,10 +374,7 @@ int vtmhip_satd8_grid_dev( vtmhip_ctx *ctx, const int16_t *d_org, int orgStride,
 extern "C" int vtmhip_masked_sad_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_curBase, const int16_t *d_maskBase,
                                             const vtmhip_masked_sad_job *d_jobs, int n, uint64_t *d_dist )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_orgBase && d_curBase && d_maskBase && d_jobs && d_dist, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_orgBase && d_curBase && d_maskBase && d_jobs && d_dist );
   hipLaunchKernelGGL( sad_mask_kernel, dim3( ( n + 3 ) / 4 ), dim3( 256 ), 0, ctx->stream, d_orgBase, d_curBase, d_maskBase, d_jobs, n, ( unsigned long long * ) d_dist );
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
@@ -399,38 +388,29 @@ extern "C" int vtmhip_xGetSADwMask( vtmhip_ctx *ctx, const int16_t *org, int org
   VTMHIP_REQUIRE( ctx, width >= 1 && height >= 1 && width <= 128 && height <= 128, "block size must be 1..128" );
   VTMHIP_REQUIRE( ctx, subShift >= 0 && subShift <= 4 && ( height & ( ( 1 << subShift ) - 1 ) ) == 0, "subShift" );
   VTMHIP_REQUIRE( ctx, stepX == 1 || stepX == -1, "stepX must be +1 or -1" );
-  // span of the mask the walk touches: offsets i * rowStep + x * stepX over the corners
-  const int  rows = height >> subShift;
-  const long rowStep = ( long ) width * stepX + ( long ) maskStride * ( 1 << subShift ) + maskStride2;
-  long lo = 0, hi = 0;
-  const long corners[4] = { 0, ( long ) ( width - 1 ) * stepX, ( long ) ( rows - 1 ) * rowStep, ( long ) ( rows - 1 ) * rowStep + ( long ) ( width - 1 ) * stepX };
-  for( long c : corners ) { lo = c < lo ? c : lo; hi = c > hi ? c : hi; }
-  const size_t maskN = ( size_t ) ( hi - lo + 1 );
-  VTMHIP_REQUIRE( ctx, maskN <= ( size_t ) 1 << 22, "mask walk spans more than 4 M samples" );
+  // the part of the mask the walk touches (sad_mask_kernel: offsets r * rowStep + x * stepX)
+  const StageSpan span = stage_walk_span( width, height >> subShift, stepX, ( long ) width * stepX + ( long ) maskStride * ( 1 << subShift ) + maskStride2 );
+  VTMHIP_REQUIRE( ctx, span.count() <= ( size_t ) 1 << 22, "mask walk spans more than 4 M samples" );
+  HostStage    s( ctx );
   const size_t blk = ( size_t ) width * height * sizeof( int16_t );
-  const size_t maskOff = ( 2 * blk + 63 ) & ~( size_t ) 63, jobOff = ( maskOff + maskN * 2 + 63 ) & ~( size_t ) 63, outOff = jobOff + 64;
-  int st = vtmhip_internal_scratch( ctx, outOff + 64 );
-  if( st ) return st;
-  char *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
-  for( int y = 0; y < height; y++ )
-  {
-    memcpy( hp + ( size_t ) y * width * 2, org + ( ptrdiff_t ) y * orgStride, ( size_t ) width * 2 );
-    memcpy( hp + blk + ( size_t ) y * width * 2, cur + ( ptrdiff_t ) y * curStride, ( size_t ) width * 2 );
-  }
-  memcpy( hp + maskOff, mask + lo, maskN * 2 );
+  const size_t orgOff = s.region( blk ), curOff = s.region( blk ), maskOff = s.region( span.count() * 2 );
+  const size_t jobOff = s.region( sizeof( vtmhip_masked_sad_job ) ), outOff = s.region( 8 );
+  VTMHIP_TRY( s.reserve() );
+  s.pack( orgOff, org, orgStride, width, height );
+  s.pack( curOff, cur, curStride, width, height );
+  memcpy( s.hp + maskOff, mask + span.lo, span.count() * 2 );
   vtmhip_masked_sad_job j;
   memset( &j, 0, sizeof( j ) );
-  j.orgOff = 0; j.curOff = ( int64_t ) width * height; j.maskOff = ( int64_t ) ( maskOff / 2 ) - lo;
+  j.orgOff = ( int64_t ) ( orgOff / 2 ); j.curOff = ( int64_t ) ( curOff / 2 ); j.maskOff = ( int64_t ) ( maskOff / 2 ) - span.lo;
   j.orgStride = width; j.curStride = width; j.maskStride = maskStride; j.maskStride2 = maskStride2;
   j.width = ( int16_t ) width; j.height = ( int16_t ) height; j.subShift = ( int16_t ) subShift; j.stepX = ( int16_t ) stepX;
-  memcpy( hp + jobOff, &j, sizeof( j ) );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, outOff, hipMemcpyHostToDevice, ctx->stream ) );
-  hipLaunchKernelGGL( sad_mask_kernel, dim3( 1 ), dim3( 256 ), 0, ctx->stream, ( const int16_t * ) dp, ( const int16_t * ) dp, ( const int16_t * ) dp,
-                      ( const vtmhip_masked_sad_job * ) ( dp + jobOff ), 1, ( unsigned long long * ) ( dp + outOff ) );
+  s.put( jobOff, j );
+  VTMHIP_TRY( s.upload( 0, outOff ) );
+  hipLaunchKernelGGL( sad_mask_kernel, dim3( 1 ), dim3( 256 ), 0, ctx->stream, s.dev<const int16_t>( 0 ), s.dev<const int16_t>( 0 ), s.dev<const int16_t>( 0 ),
+                      s.dev<const vtmhip_masked_sad_job>( jobOff ), 1, s.dev<unsigned long long>( outOff ) );
   VTMHIP_LAUNCHED( ctx );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( hp + outOff, dp + outOff, 8, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
-  memcpy( dist, hp + outOff, 8 );
+  VTMHIP_TRY( s.fetch( outOff, 8 ) );
+  memcpy( dist, s.hp + outOff, 8 );
   return VTMHIP_OK;
 }
 
@@ -438,10 +418,7 @@ extern "C" int vtmhip_xGetSADwMask( vtmhip_ctx *ctx, const int16_t *org, int org
 extern "C" int vtmhip_dist_uniform_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_curBase, const vtmhip_dist_job *d_jobs, int n,
                                               int kind, int width, int height, int subShift, uint64_t *d_dist )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_orgBase && d_curBase && d_jobs && d_dist, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_orgBase && d_curBase && d_jobs && d_dist );
   int st = check_dist_args( ctx, width, height, subShift, kind );
   if( st ) return st;
   if( kind != VTMHIP_DIST_SATD && ( width & 7 ) != 0 )   // narrow / odd widths: the wave-per-job kernel (reads width / height / kind from the jobs)

@@ -10,6 +10,7 @@
 //   - a lane accumulates in 64 bits while its segments belong to one job and adds the partial into the job's LDS slot when it moves on (integer sum:
 //     order-free); the 64-bit weighted square is one 32 x 32 -> 64 multiply (fixed < 2^31, d * d < 2^24), never a generic 64 x 64 one.
 #include "ctx.hpp"
+#include "stage.hpp"
 
 namespace
 {
@@ -223,9 +224,7 @@ int vtmhip_sse_wtd_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const i
 {
   VTMHIP_CHECK_CTX( ctx );
   VTMHIP_REQUIRE( ctx, ctx->wtdLumaBD != 0, "vtmhip_set_luma_level_weights has not been called" );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_orgBase && d_curBase && d_orgLumaBase && d_jobs && d_dist, "null pointer" );
+  VTMHIP_BATCH_ARGS( ctx, n, d_orgBase && d_curBase && d_orgLumaBase && d_jobs && d_dist );
   return wtd_launch( ctx, d_orgBase, d_curBase, d_orgLumaBase, d_jobs, n, wtd_jobs_per_wave( ctx, n ), ( unsigned long long * ) d_dist );
 }
 
@@ -242,33 +241,26 @@ int vtmhip_xGetSSE_WTD( vtmhip_ctx *ctx, const int16_t *org, int orgStride, cons
   VTMHIP_REQUIRE( ctx, compID == 0 || orgLuma, "a chroma block needs orgLuma" );
   // stage org, cur and (chroma) the luma samples the block reads compactly: stride = width, luma rows of lw = ((width - 1) << cShiftX) + 1 samples
   const int    lw  = compID != 0 ? ( ( width - 1 ) << cShiftX ) + 1 : 1;
+  HostStage    s( ctx );
   const size_t blk = ( size_t ) width * height * sizeof( int16_t ), lblk = ( size_t ) lw * height * sizeof( int16_t );
-  const size_t lumaOff = ( 2 * blk + 63 ) & ~( size_t ) 63, jobOff = ( lumaOff + lblk + 63 ) & ~( size_t ) 63, outOff = jobOff + 64;
-  int st = vtmhip_internal_scratch( ctx, outOff + 64 );
-  if( st ) return st;
-  char *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
-  for( int y = 0; y < height; y++ )
-  {
-    const int16_t *o = org + ( ptrdiff_t ) y * orgStride;
-    for( int x = 0; x < width; x++ ) VTMHIP_REQUIRE( ctx, o[x] >= 0, "negative org sample (RdCost.cpp:3060: CHECK( org < 0 ))" );
-    memcpy( hp + ( size_t ) y * width * 2, o, ( size_t ) width * 2 );
-    memcpy( hp + blk + ( size_t ) y * width * 2, cur + ( ptrdiff_t ) y * curStride, ( size_t ) width * 2 );
-    if( lumaW ) memcpy( hp + lumaOff + ( size_t ) y * lw * 2, orgLuma + ( ptrdiff_t ) ( y << cShiftY ) * orgLumaStride, ( size_t ) lw * 2 );
-  }
+  const size_t orgOff = s.region( blk ), curOff = s.region( blk ), lumaOff = s.region( lblk ), jobOff = s.region( sizeof( vtmhip_wtd_job ) ), outOff = s.region( 8 );
+  VTMHIP_TRY( s.reserve() );
+  s.pack( orgOff, org, orgStride, width, height );
+  for( int i = 0; i < width * height; i++ ) VTMHIP_REQUIRE( ctx, s.host<int16_t>( orgOff )[i] >= 0, "negative org sample (RdCost.cpp:3060: CHECK( org < 0 ))" );
+  s.pack( curOff, cur, curStride, width, height );
+  if( lumaW ) s.pack( lumaOff, orgLuma, ( ptrdiff_t ) orgLumaStride * ( 1 << cShiftY ), lw, height );
   vtmhip_wtd_job j;
   memset( &j, 0, sizeof( j ) );
-  j.orgOff = 0; j.curOff = ( int64_t ) width * height; j.orgLumaOff = ( int64_t ) ( lumaOff / 2 );
+  j.orgOff = ( int64_t ) ( orgOff / 2 ); j.curOff = ( int64_t ) ( curOff / 2 ); j.orgLumaOff = ( int64_t ) ( lumaOff / 2 );
   j.orgStride = width; j.curStride = width; j.orgLumaStride = lw;
   j.width = ( int16_t ) width; j.height = ( int16_t ) height; j.compID = ( uint8_t ) compID;
   j.cShiftX = ( uint8_t ) cShiftX; j.cShiftY = 0;   // the staged luma rows are already the (y << cShiftY) ones
-  memcpy( hp + jobOff, &j, sizeof( j ) );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, outOff, hipMemcpyHostToDevice, ctx->stream ) );
-  st = wtd_launch( ctx, ( const int16_t * ) dp, ( const int16_t * ) dp, ( const int16_t * ) dp, ( const vtmhip_wtd_job * ) ( dp + jobOff ), 1, 1,
-                   ( unsigned long long * ) ( dp + outOff ) );
-  if( st ) return st;
-  VTMHIP_HIP( ctx, hipMemcpyAsync( hp + outOff, dp + outOff, 8, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
-  memcpy( dist, hp + outOff, 8 );
+  s.put( jobOff, j );
+  VTMHIP_TRY( s.upload( 0, outOff ) );
+  VTMHIP_TRY( wtd_launch( ctx, s.dev<const int16_t>( 0 ), s.dev<const int16_t>( 0 ), s.dev<const int16_t>( 0 ), s.dev<const vtmhip_wtd_job>( jobOff ), 1, 1,
+                          s.dev<unsigned long long>( outOff ) ) );
+  VTMHIP_TRY( s.fetch( outOff, 8 ) );
+  memcpy( dist, s.hp + outOff, 8 );
   return VTMHIP_OK;
 }
 

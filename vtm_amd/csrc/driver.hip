@@ -143,9 +143,9 @@ int run_rest( vtmhip_ctx *ctx, const vtmhip_pis_level_run &L, const vtmhip_pis_b
 
 extern "C" int vtmhip_is_uniform_shape( int w, int h )
 {
-  if( w == h ) return w == 8 || w == 16 || w == 32 || w == 64 || w == 128;
-  const int a = w > h ? w : h, b = w > h ? h : w;
-  return ( a == 16 && b == 8 ) || ( a == 32 && ( b == 8 || b == 16 ) ) || ( a == 64 && ( b == 16 || b == 32 ) );
+#define VTMHIP_IS_SHAPE( W, H ) || ( w == W && h == H )
+  return 0 VTMHIP_UNIFORM_SHAPES( VTMHIP_IS_SHAPE, VTMHIP_IS_SHAPE );
+#undef VTMHIP_IS_SHAPE
 }
 
 extern "C" int vtmhip_predInterSearch_batch_dev( vtmhip_ctx *ctx, const vtmhip_pis_level_run *L, const vtmhip_pis_buffers *buf )

@@ -14,6 +14,7 @@
 // through the same FIR with taps {0,0,0,64,0,0,0,0}, which is arithmetically identical to filterCopy.
 // One wave per PU: window -> LDS once, 3 H passes per round (one per horizontal phase), 9 V passes + SATDs.
 #include "ctx.hpp"
+#include "stage.hpp"
 #include "mest_glue.hpp"
 #include "mv_rules.hpp"
 #include "had.hpp"
@@ -782,29 +783,25 @@ int if_single( vtmhip_ctx *ctx, int vertical, int taps, int isFirst, int isLast,
   // stage the source region the filter touches: (taps/2 - 1) samples before, taps/2 after, along the filter direction
   const int before = taps ? taps / 2 - 1 : 0, after = taps ? taps / 2 : 0;
   const int sw = w + ( vertical ? 0 : before + after ), sh = h + ( vertical ? before + after : 0 );
+  HostStage    s( ctx );
   const size_t srcBytes = ( size_t ) sw * sh * 2, dstBytes = ( size_t ) w * h * 2;
-  const size_t dstOffB = ( srcBytes + 63 ) & ~( size_t ) 63, jobOffB = ( dstOffB + dstBytes + 63 ) & ~( size_t ) 63;
-  int st = vtmhip_internal_scratch( ctx, jobOffB + sizeof( vtmhip_if_job ) );
-  if( st ) return st;
-  char          *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
-  const int16_t *s0 = src - ( vertical ? ( ptrdiff_t ) before * srcStride : before );
-  for( int y = 0; y < sh; y++ ) memcpy( hp + ( size_t ) y * sw * 2, s0 + ( ptrdiff_t ) y * srcStride, ( size_t ) sw * 2 );
+  const size_t srcOffB = s.region( srcBytes ), dstOffB = s.region( dstBytes ), jobOffB = s.region( sizeof( vtmhip_if_job ) );
+  VTMHIP_TRY( s.reserve() );
+  s.pack( srcOffB, src - ( vertical ? ( ptrdiff_t ) before * srcStride : before ), srcStride, sw, sh );
   vtmhip_if_job j;
   memset( &j, 0, sizeof( j ) );
-  j.srcOff = vertical ? ( int64_t ) before * sw : before;
+  j.srcOff = ( int64_t ) ( srcOffB / 2 ) + ( vertical ? ( int64_t ) before * sw : before );
   j.dstOff = 0; j.srcStride = sw; j.dstStride = w; j.width = ( int16_t ) w; j.height = ( int16_t ) h;
   j.vertical = ( uint8_t ) vertical; j.taps = ( uint8_t ) taps; j.isFirst = ( uint8_t ) isFirst; j.isLast = ( uint8_t ) isLast;
   for( int k = 0; k < taps; k++ ) j.coeff[k] = coeff[k];
   j.clipMin = ( int16_t ) clipMin; j.clipMax = ( int16_t ) clipMax; j.bitDepth = ( uint8_t ) bitDepth; j.biMCForDMVR = ( uint8_t ) biMC;
-  memcpy( hp + jobOffB, &j, sizeof( j ) );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, srcBytes, hipMemcpyHostToDevice, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( dp + jobOffB, hp + jobOffB, sizeof( j ), hipMemcpyHostToDevice, ctx->stream ) );
-  hipLaunchKernelGGL( if_batch_kernel, dim3( 1 ), dim3( 256 ), 0, ctx->stream, ( const int16_t * ) dp, ( int16_t * ) ( dp + dstOffB ),
-                      ( const vtmhip_if_job * ) ( dp + jobOffB ), 1 );
+  s.put( jobOffB, j );
+  VTMHIP_TRY( s.upload( srcOffB, srcBytes ) );   // the source and the job: the destination region in between is only written
+  VTMHIP_TRY( s.upload( jobOffB, sizeof( j ) ) );
+  hipLaunchKernelGGL( if_batch_kernel, dim3( 1 ), dim3( 256 ), 0, ctx->stream, s.dev<const int16_t>( 0 ), s.dev<int16_t>( dstOffB ), s.dev<const vtmhip_if_job>( jobOffB ), 1 );
   VTMHIP_LAUNCHED( ctx );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( hp + dstOffB, dp + dstOffB, dstBytes, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
-  for( int y = 0; y < h; y++ ) memcpy( dst + ( ptrdiff_t ) y * dstStride, hp + dstOffB + ( size_t ) y * w * 2, ( size_t ) w * 2 );
+  VTMHIP_TRY( s.fetch( dstOffB, dstBytes ) );
+  s.unpack( dst, dstStride, dstOffB, w, h );
   return VTMHIP_OK;
 }
 
@@ -846,10 +843,7 @@ int vtmhip_filterCopy( vtmhip_ctx *ctx, int isFirst, int isLast, const int16_t *
 
 int vtmhip_if_batch_dev( vtmhip_ctx *ctx, const int16_t *d_srcBase, int16_t *d_dstBase, const vtmhip_if_job *d_jobs, int n )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_srcBase && d_dstBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_srcBase && d_dstBase && d_jobs );
   hipLaunchKernelGGL( if_batch_kernel, dim3( ( n + 3 ) / 4 ), dim3( 256 ), 0, ctx->stream, d_srcBase, d_dstBase, d_jobs, n );
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
@@ -867,10 +861,7 @@ int vtmhip_frac_search_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, con
 int vtmhip_internal_frac_search( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_refBase, const vtmhip_frac_job *d_jobs, int n, int maxWidth, int maxHeight,
                                  int uniformSquare, vtmhip_frac_result *d_results, const MeFuse *fuse )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_orgBase && d_refBase && ( d_jobs || fuse ) && d_results, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_orgBase && d_refBase && ( d_jobs || fuse ) && d_results );
   FracFuse fu; memset( &fu, 0, sizeof( fu ) );
   if( fuse ) { fu.me = fuse->me; fu.ires = fuse->ires; fu.out = fuse->out; fu.useHadME = fuse->cfg.useHadME; fu.bitDepth = fuse->bitDepth; fu.patIsOther = fuse->patIsOther; }
   VTMHIP_REQUIRE( ctx, maxWidth >= 4 && maxWidth <= 128 && maxHeight >= 4 && maxHeight <= 128, "maxWidth / maxHeight" );
@@ -880,9 +871,7 @@ int vtmhip_internal_frac_search( vtmhip_ctx *ctx, const int16_t *d_orgBase, cons
 #define VTMHIP_FRAC_CASE( WW, HH ) case ( WW ) * 256 + ( HH ): return launch_frac_sq<WW, HH>( ctx, d_orgBase, d_refBase, d_jobs, n, d_results, fu );
     switch( maxWidth * 256 + maxHeight )
     {
-      VTMHIP_FRAC_CASE( 8, 8 ) VTMHIP_FRAC_CASE( 16, 16 ) VTMHIP_FRAC_CASE( 32, 32 ) VTMHIP_FRAC_CASE( 64, 64 ) VTMHIP_FRAC_CASE( 128, 128 )
-      VTMHIP_FRAC_CASE( 16, 8 ) VTMHIP_FRAC_CASE( 8, 16 ) VTMHIP_FRAC_CASE( 32, 8 ) VTMHIP_FRAC_CASE( 8, 32 ) VTMHIP_FRAC_CASE( 32, 16 ) VTMHIP_FRAC_CASE( 16, 32 )
-      VTMHIP_FRAC_CASE( 64, 16 ) VTMHIP_FRAC_CASE( 16, 64 ) VTMHIP_FRAC_CASE( 64, 32 ) VTMHIP_FRAC_CASE( 32, 64 )
+      VTMHIP_UNIFORM_SHAPES( VTMHIP_FRAC_CASE, VTMHIP_FRAC_CASE )
     default: break;   // other shapes: generic kernel below
     }
 #undef VTMHIP_FRAC_CASE

@@ -19,6 +19,7 @@
 //
 // Out of scope: ACT, the picture-level sign decision (the caller passes signFlag), the CABAC estimate.
 #include "ctx.hpp"
+#include "stage.hpp"
 #include "lmcs.hpp"
 #include "tu_stages.hpp"
 
@@ -452,31 +453,12 @@ int launch_uni( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_jccr_jo
   return VTMHIP_OK;
 }
 
-// host-pointer staging of the two pointer entries: both blocks compactly (stride = width) at the start of the pinned / device staging area
-void stage_pair( char *hp, const int16_t *cb, int cbStride, const int16_t *cr, int crStride, int w, int h )
-{
-  const size_t blk = ( size_t ) w * h * sizeof( int16_t );
-  for( int y = 0; y < h; y++ )
-  {
-    memcpy( hp + ( size_t ) y * w * 2, cb + ( ptrdiff_t ) y * cbStride, ( size_t ) w * 2 );
-    memcpy( hp + blk + ( size_t ) y * w * 2, cr + ( ptrdiff_t ) y * crStride, ( size_t ) w * 2 );
-  }
-}
-
-void unstage( int16_t *dst, int dstStride, const char *src, int w, int h )
-{
-  for( int y = 0; y < h; y++ ) memcpy( dst + ( ptrdiff_t ) y * dstStride, src + ( size_t ) y * w * 2, ( size_t ) w * 2 );
-}
-
 // vtmhip_jccr_chain_batch_dev (CRS == false) and vtmhip_jccr_chain_crs_batch_dev: one dispatch, the same launch paths
 template<bool CRS>
 int jccr_chain_entry( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
                       int32_t *d_levelsBase, int16_t *d_recCbBase, int16_t *d_recCrBase, vtmhip_jccr_result *d_results )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_resiBase && d_jobs && d_results, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_resiBase && d_jobs && d_results );
   VTMHIP_REQUIRE( ctx, maxWidth >= 2 && maxWidth <= 64 && maxHeight >= 2 && maxHeight <= 64, "maxWidth / maxHeight: 2..64 (2-D transforms)" );
   const bool lanePath = uniformSize && maxWidth * maxHeight <= 32 && maxWidth >= 4 && maxHeight >= 4;
   const bool uniPath  = uniformSize && maxWidth >= 8 && maxHeight >= 8;
@@ -563,27 +545,26 @@ int vtmhip_fwdTransformCbCr( vtmhip_ctx *ctx, int mode, const int16_t *cb, int c
   int16_t  *joint = am == 3 ? c2 : c1;
   const int jointStride = am == 3 ? c2Stride : c1Stride;
   VTMHIP_REQUIRE( ctx, cb && cr && dist && ( am == 0 || joint ), "null pointer" );
+  HostStage    s( ctx );
   const size_t blk = ( size_t ) width * height * sizeof( int16_t );
-  const size_t jobOff = ( 3 * blk + 63 ) & ~( size_t ) 63, outOff = jobOff + 64;   // [cb][cr][joint] job dist[4][2]
-  int st = vtmhip_internal_scratch( ctx, outOff + 64 );
-  if( st ) return st;
-  char *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
-  stage_pair( hp, cb, cbStride, cr, crStride, width, height );
+  const size_t cbOff = s.region( blk ), crOff = s.region( blk ), jointOff = s.region( blk ), jobOff = s.region( sizeof( vtmhip_ict_job ) ), outOff = s.region( 64 );   // dist[4][2]
+  VTMHIP_TRY( s.reserve() );
+  s.pack( cbOff, cb, cbStride, width, height );
+  s.pack( crOff, cr, crStride, width, height );
   vtmhip_ict_job j;
   memset( &j, 0, sizeof( j ) );
-  j.cbOff = 0; j.crOff = ( int64_t ) width * height; j.cbStride = j.crStride = width;
-  j.outOff = ( int64_t ) ( 2 - ( cbfMask ? cbfMask - 1 : 0 ) ) * width * height;   // the requested plane lands right behind the two inputs
+  j.cbOff = ( int64_t ) ( cbOff / 2 ); j.crOff = ( int64_t ) ( crOff / 2 ); j.cbStride = j.crStride = width;
+  j.outOff = ( int64_t ) ( jointOff / 2 ) - ( int64_t ) ( cbfMask ? cbfMask - 1 : 0 ) * width * height;   // the requested plane lands in the joint region
   j.width = ( int16_t ) width; j.height = ( int16_t ) height; j.signFlag = mode < 0; j.maskBits = ( uint8_t ) ( cbfMask ? 1 << cbfMask : 0 );
-  memcpy( hp + jobOff, &j, sizeof( j ) );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, outOff, hipMemcpyHostToDevice, ctx->stream ) );
-  hipLaunchKernelGGL( ict_fwd_kernel, dim3( 1 ), dim3( 256 ), 0, ctx->stream, ( const int16_t * ) dp, ( const vtmhip_ict_job * ) ( dp + jobOff ), 1, ( int16_t * ) dp,
-                      ( long long * ) ( dp + outOff ) );
+  s.put( jobOff, j );
+  VTMHIP_TRY( s.upload( 0, outOff ) );
+  hipLaunchKernelGGL( ict_fwd_kernel, dim3( 1 ), dim3( 256 ), 0, ctx->stream, s.dev<const int16_t>( 0 ), s.dev<const vtmhip_ict_job>( jobOff ), 1, s.dev<int16_t>( 0 ),
+                      s.dev<long long>( outOff ) );
   VTMHIP_LAUNCHED( ctx );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( hp + 2 * blk, dp + 2 * blk, blk, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( hp + outOff, dp + outOff, 64, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
-  memcpy( dist, hp + outOff + 16 * cbfMask, 16 );
-  if( am ) unstage( joint, jointStride, hp + 2 * blk, width, height );
+  VTMHIP_TRY( s.download( jointOff, blk ) );
+  VTMHIP_TRY( s.fetch( outOff, 64 ) );
+  memcpy( dist, s.hp + outOff + 16 * cbfMask, 16 );
+  if( am ) s.unpack( joint, jointStride, jointOff, width, height );
   return VTMHIP_OK;
 }
 
@@ -594,29 +575,25 @@ int vtmhip_invTransformCbCr( vtmhip_ctx *ctx, int mode, int16_t *cb, int cbStrid
   VTMHIP_REQUIRE( ctx, width >= 1 && width <= 64 && height >= 1 && height <= 64, "width / height: 1 .. 64" );
   VTMHIP_REQUIRE( ctx, cb && cr, "null pointer" );
   if( mode == 0 ) return VTMHIP_OK;   // invTransformCbCr<0> touches nothing
-  const size_t blk = ( size_t ) width * height * sizeof( int16_t );
-  int st = vtmhip_internal_scratch( ctx, 2 * blk );
-  if( st ) return st;
-  char *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
-  stage_pair( hp, cb, cbStride, cr, crStride, width, height );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, 2 * blk, hipMemcpyHostToDevice, ctx->stream ) );
+  HostStage    s( ctx );
+  const size_t blk = ( size_t ) width * height * sizeof( int16_t ), cbOff = s.region( blk ), crOff = s.region( blk );
+  VTMHIP_TRY( s.reserve() );
+  s.pack( cbOff, cb, cbStride, width, height );
+  s.pack( crOff, cr, crStride, width, height );
+  VTMHIP_TRY( s.upload( 0, s.total ) );
   const int count = width * height;
-  hipLaunchKernelGGL( ict_inv_kernel, dim3( ( count + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ( int16_t * ) dp, ( int16_t * ) ( dp + blk ), count,
+  hipLaunchKernelGGL( ict_inv_kernel, dim3( ( count + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, s.dev<int16_t>( cbOff ), s.dev<int16_t>( crOff ), count,
                       mode < 0 ? -mode : mode, mode < 0 ? -1 : 1 );
   VTMHIP_LAUNCHED( ctx );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( hp, dp, 2 * blk, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
-  if( mode == 3 || mode == -3 ) unstage( cb, cbStride, hp, width, height );
-  else unstage( cr, crStride, hp + blk, width, height );
+  VTMHIP_TRY( s.fetch( 0, s.total ) );
+  if( mode == 3 || mode == -3 ) s.unpack( cb, cbStride, cbOff, width, height );
+  else s.unpack( cr, crStride, crOff, width, height );
   return VTMHIP_OK;
 }
 
 int vtmhip_ict_fwd_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_ict_job *d_jobs, int n, int16_t *d_jointBase, int64_t *d_dist )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_resiBase && d_jobs && d_dist, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_resiBase && d_jobs && d_dist );
   VTMHIP_TIME_KERNEL( ctx, "ict_fwd_kernel" );
   hipLaunchKernelGGL( ict_fwd_kernel, dim3( ( n + 3 ) / 4 ), dim3( 256 ), 0, ctx->stream, d_resiBase, d_jobs, n, d_jointBase, ( long long * ) d_dist );
   VTMHIP_LAUNCHED( ctx );

@@ -10,6 +10,7 @@
 //     scan of the segment counts): 2x2 / 4x4 blocks share a wave, a 128x128 block keeps all lanes busy;
 //   - a whole segment moves as one 8-byte access (2-byte aligned: the hardware splits it only when the address asks for it), a ragged one sample by sample.
 #include "ctx.hpp"
+#include "stage.hpp"
 #include "lmcs.hpp"
 
 namespace
@@ -248,25 +249,19 @@ int vtmhip_rspSignal( vtmhip_ctx *ctx, int16_t *buf, int stride, int width, int 
   VTMHIP_REQUIRE( ctx, buf && lut, "null pointer" );
   VTMHIP_REQUIRE( ctx, width >= 1 && height >= 1 && width <= 128 && height <= 128, "block size must be 1..128" );
   VTMHIP_REQUIRE( ctx, lutSize >= 1 && lutSize <= 65536, "lutSize: 1 .. 65536" );
-  const size_t blk = ( size_t ) width * height * sizeof( int16_t ), lutOff = ( blk + 63 ) & ~( size_t ) 63, total = lutOff + ( size_t ) lutSize * sizeof( int16_t );
-  int st = vtmhip_internal_scratch( ctx, total );
-  if( st ) return st;
-  char *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
-  for( int y = 0; y < height; y++ )
-  {
-    const int16_t *s = buf + ( ptrdiff_t ) y * stride;
-    for( int x = 0; x < width; x++ ) VTMHIP_REQUIRE( ctx, s[x] >= 0 && s[x] < lutSize, "a sample lies outside the LUT" );
-    memcpy( hp + ( size_t ) y * width * 2, s, ( size_t ) width * 2 );
-  }
-  memcpy( hp + lutOff, lut, ( size_t ) lutSize * sizeof( int16_t ) );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, total, hipMemcpyHostToDevice, ctx->stream ) );
-  const int count = width * height;
+  HostStage    s( ctx );
+  const int    count = width * height;
+  const size_t blk = ( size_t ) count * sizeof( int16_t ), lutBytes = ( size_t ) lutSize * sizeof( int16_t ), bufOff = s.region( blk ), lutOff = s.region( lutBytes );
+  VTMHIP_TRY( s.reserve() );
+  s.pack( bufOff, buf, stride, width, height );
+  for( int i = 0; i < count; i++ ) VTMHIP_REQUIRE( ctx, s.host<int16_t>( bufOff )[i] >= 0 && s.host<int16_t>( bufOff )[i] < lutSize, "a sample lies outside the LUT" );
+  memcpy( s.hp + lutOff, lut, lutBytes );
+  VTMHIP_TRY( s.upload( 0, lutOff + lutBytes ) );
   VTMHIP_TIME_KERNEL( ctx, "rsp_kernel" );
-  hipLaunchKernelGGL( rsp_kernel, dim3( ( count + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ( int16_t * ) dp, count, ( const int16_t * ) ( dp + lutOff ), lutSize );
+  hipLaunchKernelGGL( rsp_kernel, dim3( ( count + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, s.dev<int16_t>( bufOff ), count, s.dev<const int16_t>( lutOff ), lutSize );
   VTMHIP_LAUNCHED( ctx );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( hp, dp, blk, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
-  for( int y = 0; y < height; y++ ) memcpy( buf + ( ptrdiff_t ) y * stride, hp + ( size_t ) y * width * 2, ( size_t ) width * 2 );
+  VTMHIP_TRY( s.fetch( bufOff, blk ) );
+  s.unpack( buf, stride, bufOff, width, height );
   return VTMHIP_OK;
 }
 
@@ -278,31 +273,26 @@ int vtmhip_scaleSignal( vtmhip_ctx *ctx, int16_t *buf, int stride, int width, in
   VTMHIP_REQUIRE( ctx, scale >= 1 && scale <= 32767, "scale: 1 .. 32767" );
   VTMHIP_REQUIRE( ctx, bitDepth >= 8 && bitDepth <= 12, "bitDepth must be 8..12" );
   VTMHIP_REQUIRE( ctx, !( dir && width == 1 ), "forward scaling of a block of width 1 (Buffer.cpp:427: THROW)" );
-  const size_t blk = ( size_t ) width * height * sizeof( int16_t ), jobOff = ( blk + 63 ) & ~( size_t ) 63, total = jobOff + 64;
-  int st = vtmhip_internal_scratch( ctx, total );
-  if( st ) return st;
-  char *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
-  for( int y = 0; y < height; y++ ) memcpy( hp + ( size_t ) y * width * 2, buf + ( ptrdiff_t ) y * stride, ( size_t ) width * 2 );
+  HostStage    s( ctx );
+  const size_t blk = ( size_t ) width * height * sizeof( int16_t ), bufOff = s.region( blk ), jobOff = s.region( sizeof( vtmhip_scale_job ) );
+  VTMHIP_TRY( s.reserve() );
+  s.pack( bufOff, buf, stride, width, height );
   vtmhip_scale_job j;
   memset( &j, 0, sizeof( j ) );
+  j.srcOff = j.dstOff = ( int64_t ) ( bufOff / 2 );
   j.srcStride = j.dstStride = width; j.width = ( int16_t ) width; j.height = ( int16_t ) height;
   j.scale = ( uint16_t ) scale; j.dir = dir ? 1 : 0; j.bitDepth = ( uint8_t ) bitDepth;
-  memcpy( hp + jobOff, &j, sizeof( j ) );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, total, hipMemcpyHostToDevice, ctx->stream ) );
-  st = lm_launch<OP_SCALE>( ctx, ( const int16_t * ) dp, nullptr, ( int16_t * ) dp, nullptr, dp + jobOff, 1, 1 );
-  if( st ) return st;
-  VTMHIP_HIP( ctx, hipMemcpyAsync( hp, dp, blk, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
-  for( int y = 0; y < height; y++ ) memcpy( buf + ( ptrdiff_t ) y * stride, hp + ( size_t ) y * width * 2, ( size_t ) width * 2 );
+  s.put( jobOff, j );
+  VTMHIP_TRY( s.upload( 0, s.total ) );
+  VTMHIP_TRY( lm_launch<OP_SCALE>( ctx, s.dev<const int16_t>( 0 ), nullptr, s.dev<int16_t>( 0 ), nullptr, s.dev<void>( jobOff ), 1, 1 ) );
+  VTMHIP_TRY( s.fetch( bufOff, blk ) );
+  s.unpack( buf, stride, bufOff, width, height );
   return VTMHIP_OK;
 }
 
 int vtmhip_scale_signal_batch_dev( vtmhip_ctx *ctx, const int16_t *d_srcBase, int16_t *d_dstBase, const vtmhip_scale_job *d_jobs, int n )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_srcBase && d_dstBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_srcBase && d_dstBase && d_jobs );
   return lm_launch<OP_SCALE>( ctx, d_srcBase, nullptr, d_dstBase, nullptr, d_jobs, n, lm_jobs_per_wave( ctx, n ) );
 }
 
@@ -311,9 +301,7 @@ int vtmhip_lmcs_resi_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const
 {
   VTMHIP_CHECK_CTX( ctx );
   VTMHIP_REQUIRE( ctx, ctx->lmcsLumaBD != 0, "vtmhip_set_lmcs_fwd_lut has not been called" );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_orgBase && d_predBase && d_resiBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ARGS( ctx, n, d_orgBase && d_predBase && d_resiBase && d_jobs );
   return lm_launch<OP_RESI>( ctx, d_orgBase, d_predBase, d_resiBase, d_dstBase, d_jobs, n, lm_jobs_per_wave( ctx, n ) );
 }
 
@@ -321,9 +309,7 @@ int vtmhip_lmcs_reco_batch_dev( vtmhip_ctx *ctx, const int16_t *d_predBase, cons
 {
   VTMHIP_CHECK_CTX( ctx );
   VTMHIP_REQUIRE( ctx, ctx->lmcsLumaBD != 0, "vtmhip_set_lmcs_fwd_lut has not been called" );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_predBase && d_resiBase && d_dstBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ARGS( ctx, n, d_predBase && d_resiBase && d_dstBase && d_jobs );
   return lm_launch<OP_RECO>( ctx, d_predBase, d_resiBase, d_dstBase, nullptr, d_jobs, n, lm_jobs_per_wave( ctx, n ) );
 }
 

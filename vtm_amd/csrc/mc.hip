@@ -6,6 +6,7 @@
 // CommonLib/Buffer.cpp removeHighFreq :475-520 (org = 2*org - pred, unclipped: ClipForBiPredMEEnabled = 0),
 // addAvg :467-507 (dst = clip((a + b + offset) >> shift) on 14-bit intermediates).
 #include "ctx.hpp"
+#include "stage.hpp"
 #include "mc_block.hpp"
 #include "mv_rules.hpp"
 
@@ -760,10 +761,7 @@ int vtmhip_mc_luma_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, int16_t
 
 int vtmhip_mc_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, int16_t *d_dstBase, const vtmhip_mc_job *d_jobs, int n, int maxWidth, int maxHeight )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_refBase && d_dstBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_refBase && d_dstBase && d_jobs );
   VTMHIP_REQUIRE( ctx, maxWidth >= 2 && maxWidth <= 128 && maxHeight >= 2 && maxHeight <= 128, "maxWidth / maxHeight" );
   const size_t lds = ( size_t ) maxWidth * ( maxHeight + 7 ) * sizeof( int16_t );
   hipLaunchKernelGGL( mc_kernel, dim3( n ), dim3( 64 ), lds, ctx->stream, d_refBase, d_dstBase, d_jobs, maxWidth, maxHeight );
@@ -774,10 +772,7 @@ int vtmhip_mc_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, int16_t *d_d
 int vtmhip_motion_compensation_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_refBase, int16_t *d_predBase, int16_t *d_outBase,
                                           const vtmhip_pred_job *d_jobs, int n, int maxWidth, int maxHeight )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_refBase && d_jobs && ( d_predBase || d_outBase ), "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_refBase && d_jobs && ( d_predBase || d_outBase ) );
   VTMHIP_REQUIRE( ctx, !d_outBase || d_orgBase, "an epilogue output needs the original plane" );
   VTMHIP_REQUIRE( ctx, maxWidth >= 2 && maxWidth <= 128 && maxHeight >= 2 && maxHeight <= 128, "maxWidth / maxHeight" );
   return vtmhip_internal_mc_launch( ctx, d_orgBase, d_refBase, d_predBase, d_outBase, d_jobs, n, maxWidth, maxHeight, nullptr );
@@ -786,10 +781,7 @@ int vtmhip_motion_compensation_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgB
 int vtmhip_remove_high_freq_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_predBase, int16_t *d_dstBase,
                                        const vtmhip_pelop_job *d_jobs, int n )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_orgBase && d_predBase && d_dstBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_orgBase && d_predBase && d_dstBase && d_jobs );
   hipLaunchKernelGGL( pelop_kernel, dim3( n ), dim3( 256 ), 0, ctx->stream, d_orgBase, d_predBase, d_dstBase, d_jobs, 0 );
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
@@ -797,10 +789,7 @@ int vtmhip_remove_high_freq_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase
 
 int vtmhip_subtract_batch_dev( vtmhip_ctx *ctx, const int16_t *d_aBase, const int16_t *d_bBase, int16_t *d_dstBase, const vtmhip_pelop_job *d_jobs, int n )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_aBase && d_bBase && d_dstBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_aBase && d_bBase && d_dstBase && d_jobs );
   hipLaunchKernelGGL( pelop_kernel, dim3( n ), dim3( 256 ), 0, ctx->stream, d_aBase, d_bBase, d_dstBase, d_jobs, 2 );
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
@@ -809,10 +798,7 @@ int vtmhip_subtract_batch_dev( vtmhip_ctx *ctx, const int16_t *d_aBase, const in
 int vtmhip_remove_weight_high_freq_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_predBase, int16_t *d_dstBase,
                                               const vtmhip_pelop_job *d_jobs, int n )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_orgBase && d_predBase && d_dstBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_orgBase && d_predBase && d_dstBase && d_jobs );
   hipLaunchKernelGGL( pelop_kernel, dim3( n ), dim3( 256 ), 0, ctx->stream, d_orgBase, d_predBase, d_dstBase, d_jobs, 3 );
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
@@ -821,10 +807,7 @@ int vtmhip_remove_weight_high_freq_batch_dev( vtmhip_ctx *ctx, const int16_t *d_
 int vtmhip_add_weighted_avg_batch_dev( vtmhip_ctx *ctx, const int16_t *d_src0Base, const int16_t *d_src1Base, int16_t *d_dstBase,
                                        const vtmhip_pelop_job *d_jobs, int n )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_src0Base && d_src1Base && d_dstBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_src0Base && d_src1Base && d_dstBase && d_jobs );
   hipLaunchKernelGGL( pelop_kernel, dim3( n ), dim3( 256 ), 0, ctx->stream, d_src0Base, d_src1Base, d_dstBase, d_jobs, 4 );
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
@@ -833,10 +816,7 @@ int vtmhip_add_weighted_avg_batch_dev( vtmhip_ctx *ctx, const int16_t *d_src0Bas
 int vtmhip_add_avg_batch_dev( vtmhip_ctx *ctx, const int16_t *d_src0Base, const int16_t *d_src1Base, int16_t *d_dstBase,
                               const vtmhip_pelop_job *d_jobs, int n )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_src0Base && d_src1Base && d_dstBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_src0Base && d_src1Base && d_dstBase && d_jobs );
   hipLaunchKernelGGL( pelop_kernel, dim3( n ), dim3( 256 ), 0, ctx->stream, d_src0Base, d_src1Base, d_dstBase, d_jobs, 1 );
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
@@ -845,10 +825,7 @@ int vtmhip_add_avg_batch_dev( vtmhip_ctx *ctx, const int16_t *d_src0Base, const 
 int vtmhip_bdof_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_refBase, int16_t *d_predBase, int16_t *d_outBase,
                            const vtmhip_pred_job *d_jobs, int n, int maxWidth, int maxHeight )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_refBase && d_jobs && ( d_predBase || d_outBase ), "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_refBase && d_jobs && ( d_predBase || d_outBase ) );
   VTMHIP_REQUIRE( ctx, !d_outBase || d_orgBase, "an epilogue output needs the original plane" );
   VTMHIP_REQUIRE( ctx, maxWidth >= 8 && maxWidth <= 128 && maxHeight >= 8 && maxHeight <= 128, "maxWidth / maxHeight (BDOF needs 8 <= w, h <= 128)" );
   const int regions = ( ( maxWidth + 15 ) / 16 ) * ( ( maxHeight + 15 ) / 16 );
@@ -865,10 +842,7 @@ int vtmhip_bdof_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int1
 int vtmhip_dmvr_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, int16_t *d_predBase,
                            int16_t *d_outBase, const vtmhip_dmvr_job *d_jobs, int n, int maxWidth, int maxHeight, int32_t *d_mvd )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, pic && d_refBase && d_jobs && ( d_predBase || d_outBase || d_mvd ), "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, pic && d_refBase && d_jobs && ( d_predBase || d_outBase || d_mvd ) );
   VTMHIP_REQUIRE( ctx, !d_outBase || d_orgBase, "an epilogue output needs the original plane" );
   VTMHIP_REQUIRE( ctx, pic->bitDepth >= 8 && pic->bitDepth <= 12 && pic->picW > 0 && pic->picH > 0 && pic->ctuSize >= 16, "picture parameters" );
   VTMHIP_REQUIRE( ctx, maxWidth >= 8 && maxWidth <= 128 && maxHeight >= 8 && maxHeight <= 128, "maxWidth / maxHeight (DMVR needs 8 <= w, h <= 128)" );
@@ -882,10 +856,7 @@ int vtmhip_dmvr_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const 
 int vtmhip_dmvr_chroma_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, int16_t *d_predBase,
                                   int16_t *d_outBase, const vtmhip_dmvr_job *d_jobs, int n, int maxWidth, int maxHeight, const int32_t *d_mvd )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, pic && d_refBase && d_jobs && d_mvd && ( d_predBase || d_outBase ), "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, pic && d_refBase && d_jobs && d_mvd && ( d_predBase || d_outBase ) );
   VTMHIP_REQUIRE( ctx, !d_outBase || d_orgBase, "an epilogue output needs the original plane" );
   VTMHIP_REQUIRE( ctx, pic->bitDepth >= 8 && pic->bitDepth <= 12 && pic->picW > 0 && pic->picH > 0 && pic->ctuSize >= 16, "picture parameters" );
   VTMHIP_REQUIRE( ctx, maxWidth >= 8 && maxWidth <= 128 && maxHeight >= 8 && maxHeight <= 128, "maxWidth / maxHeight (luma size of the PUs, 8..128)" );
@@ -908,10 +879,7 @@ static int geo_blend_params( vtmhip_ctx *ctx, int bitDepth, int clipMin, int cli
 int vtmhip_weightedGeoBlk_batch_dev( vtmhip_ctx *ctx, const int16_t *d_srcBase, int16_t *d_dstBase, const int16_t *d_weightBase,
                                      const vtmhip_geo_blend_job *d_jobs, int n, int bitDepth, int clipMin, int clipMax )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_srcBase && d_dstBase && d_weightBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_srcBase && d_dstBase && d_weightBase && d_jobs );
   int shift, offset;
   int st = geo_blend_params( ctx, bitDepth, clipMin, clipMax, &shift, &offset );
   if( st ) return st;
@@ -928,38 +896,28 @@ int vtmhip_weightedGeoBlk( vtmhip_ctx *ctx, const int16_t *src0, int src0Stride,
   VTMHIP_REQUIRE( ctx, width >= 1 && height >= 1 && width <= 128 && height <= 128, "block size must be 1..128" );
   VTMHIP_REQUIRE( ctx, stepX != 0 && stepX >= -2 && stepX <= 2, "stepX must be +-1 or +-2" );
   int shift, offset;
-  int st = geo_blend_params( ctx, bitDepth, clipMin, clipMax, &shift, &offset );
-  if( st ) return st;
-  // span of the weight plane the walk touches
-  long       lo = 0, hi = 0;
-  const long corners[4] = { 0, ( long ) ( width - 1 ) * stepX, ( long ) ( height - 1 ) * weightStride, ( long ) ( height - 1 ) * weightStride + ( long ) ( width - 1 ) * stepX };
-  for( long c : corners ) { lo = c < lo ? c : lo; hi = c > hi ? c : hi; }
-  const size_t wN = ( size_t ) ( hi - lo + 1 );
-  VTMHIP_REQUIRE( ctx, wN <= ( size_t ) 1 << 22, "weight walk spans more than 4 M samples" );
+  VTMHIP_TRY( geo_blend_params( ctx, bitDepth, clipMin, clipMax, &shift, &offset ) );
+  const StageSpan span = stage_walk_span( width, height, stepX, weightStride );   // the part of the weight plane the walk touches
+  VTMHIP_REQUIRE( ctx, span.count() <= ( size_t ) 1 << 22, "weight walk spans more than 4 M samples" );
+  HostStage    s( ctx );
   const size_t blk = ( size_t ) width * height * sizeof( int16_t );
-  const size_t dstOff = ( 2 * blk + 63 ) & ~( size_t ) 63, wOff = ( dstOff + blk + 63 ) & ~( size_t ) 63, jobOff = ( wOff + wN * 2 + 63 ) & ~( size_t ) 63, total = jobOff + 64;
-  st = vtmhip_internal_scratch( ctx, total );
-  if( st ) return st;
-  char *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
-  for( int y = 0; y < height; y++ )
-  {
-    memcpy( hp + ( size_t ) y * width * 2, src0 + ( ptrdiff_t ) y * src0Stride, ( size_t ) width * 2 );
-    memcpy( hp + blk + ( size_t ) y * width * 2, src1 + ( ptrdiff_t ) y * src1Stride, ( size_t ) width * 2 );
-  }
-  memcpy( hp + wOff, weight + lo, wN * 2 );
+  const size_t src0Off = s.region( blk ), src1Off = s.region( blk ), dstOff = s.region( blk ), wOff = s.region( span.count() * 2 ), jobOff = s.region( sizeof( vtmhip_geo_blend_job ) );
+  VTMHIP_TRY( s.reserve() );
+  s.pack( src0Off, src0, src0Stride, width, height );
+  s.pack( src1Off, src1, src1Stride, width, height );
+  memcpy( s.hp + wOff, weight + span.lo, span.count() * 2 );
   vtmhip_geo_blend_job j;
   memset( &j, 0, sizeof( j ) );
-  j.src0Off = 0; j.src1Off = ( int64_t ) width * height; j.dstOff = ( int64_t ) ( dstOff / 2 ); j.weightOff = ( int64_t ) ( wOff / 2 ) - lo;
+  j.src0Off = ( int64_t ) ( src0Off / 2 ); j.src1Off = ( int64_t ) ( src1Off / 2 ); j.dstOff = ( int64_t ) ( dstOff / 2 ); j.weightOff = ( int64_t ) ( wOff / 2 ) - span.lo;
   j.src0Stride = j.src1Stride = j.dstStride = width; j.weightStride = weightStride;
   j.width = ( int16_t ) width; j.height = ( int16_t ) height; j.stepX = ( int16_t ) stepX;
-  memcpy( hp + jobOff, &j, sizeof( j ) );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, total, hipMemcpyHostToDevice, ctx->stream ) );
-  hipLaunchKernelGGL( geo_blend_kernel, dim3( 1 ), dim3( 256 ), 0, ctx->stream, ( const int16_t * ) dp, ( int16_t * ) dp, ( const int16_t * ) dp,
-                      ( const vtmhip_geo_blend_job * ) ( dp + jobOff ), 1, shift, offset, clipMin, clipMax );
+  s.put( jobOff, j );
+  VTMHIP_TRY( s.upload( 0, s.total ) );
+  hipLaunchKernelGGL( geo_blend_kernel, dim3( 1 ), dim3( 256 ), 0, ctx->stream, s.dev<const int16_t>( 0 ), s.dev<int16_t>( 0 ), s.dev<const int16_t>( 0 ),
+                      s.dev<const vtmhip_geo_blend_job>( jobOff ), 1, shift, offset, clipMin, clipMax );
   VTMHIP_LAUNCHED( ctx );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( hp + dstOff, dp + dstOff, blk, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
-  for( int y = 0; y < height; y++ ) memcpy( dst + ( ptrdiff_t ) y * dstStride, hp + dstOff + ( size_t ) y * width * 2, ( size_t ) width * 2 );
+  VTMHIP_TRY( s.fetch( dstOff, blk ) );
+  s.unpack( dst, dstStride, dstOff, width, height );
   return VTMHIP_OK;
 }
 
@@ -1052,10 +1010,7 @@ extern "C"
 
 int vtmhip_affine_sobel_batch_dev( vtmhip_ctx *ctx, const int16_t *d_predBase, int32_t *d_derivBase, const vtmhip_affine_job *d_jobs, int n )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_predBase && d_derivBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_predBase && d_derivBase && d_jobs );
   hipLaunchKernelGGL( sobel_kernel, dim3( n ), dim3( 256 ), 0, ctx->stream, d_predBase, d_derivBase, d_jobs, 0 );
   hipLaunchKernelGGL( sobel_kernel, dim3( n ), dim3( 256 ), 0, ctx->stream, d_predBase, d_derivBase, d_jobs, 1 );
   VTMHIP_LAUNCHED( ctx );
@@ -1065,10 +1020,7 @@ int vtmhip_affine_sobel_batch_dev( vtmhip_ctx *ctx, const int16_t *d_predBase, i
 int vtmhip_affine_equal_coeff_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const int32_t *d_derivBase, const vtmhip_affine_job *d_jobs, int n,
                                          int64_t *d_equalCoeff )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_resiBase && d_derivBase && d_jobs && d_equalCoeff, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_resiBase && d_derivBase && d_jobs && d_equalCoeff );
   hipLaunchKernelGGL( equal_coeff_kernel, dim3( n ), dim3( 256 ), 0, ctx->stream, d_resiBase, d_derivBase, d_jobs, ( long long * ) d_equalCoeff );
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;

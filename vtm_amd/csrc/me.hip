@@ -2166,7 +2166,7 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
   const int wpj = pic->wavesPerJob;
   VTMHIP_REQUIRE( ctx, wpj == 0 || wpj == 1 || wpj == 2 || wpj == 4 || wpj == 8 || wpj == 16, "wavesPerJob must be 0, 1, 2, 4, 8 or 16" );
   // split search (default; VTMHIP_TZ_SPLIT=0: one launch): the raster scans of the batch run in tz_raster_cols_kernel between two launches of the search kernel
-  static const bool split = !( getenv( "VTMHIP_TZ_SPLIT" ) && atoi( getenv( "VTMHIP_TZ_SPLIT" ) ) == 0 );
+  static const bool split = env_switch( "VTMHIP_TZ_SPLIT", true );
   // the raster column kernel keeps a scan's totals in LDS: 39 x 39 points (SearchRange 96) by default, ((2 * range) / 5 + 1)^2 for the caller's maxSearchRange hint (384: 154 x 154 = 93 KB)
   // The hint never makes the call fail: the totals of one scan must fit the CU's LDS beside the kernel's static arrays (160 KB on gfx950: ( 160 KB - 1 KB ) / 4 - 1 = 40 703
   // points = a 201 x 201 scan = search range 500); scans with more points than totCap are not listed for the column kernel and run inside the search kernel (mode 1 checks totCap).
@@ -2181,7 +2181,7 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
   if( split )
   {
     // few searches (one band of a sharded picture): several workgroups per raster scan, so that the scans of a 128x128 level still fill the GPU
-    static const bool splitScan = !( getenv( "VTMHIP_RASTER_PARTS" ) && atoi( getenv( "VTMHIP_RASTER_PARTS" ) ) == 0 );
+    static const bool splitScan = env_switch( "VTMHIP_RASTER_PARTS", true );
     rasterParts = ( splitScan && n <= 640 ) ? ( 1280 / n < 8 ? 1280 / n : 8 ) : 1;
     if( totCap > RASTER_TOT_CAP && splitScan && n <= 4096 && rasterParts < 4 ) rasterParts = 4;      // big scans (one workgroup per CU by LDS): a few workgroups per scan balance the tail   // aim at the 1280 resident workgroups (5 per CU); twice that measured slower
     const size_t oList = ( ( size_t ) n * sizeof( TzSaved ) + 255 ) & ~( size_t ) 255;
@@ -2223,16 +2223,16 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
   // Uniform batches of small blocks (fused uni rows, no extended settings): four searches per wave, a lane per candidate (tz_group_kernel).  VTMHIP_TZ_GROUP=0: off;
   // VTMHIP_TZ_GROUP_ITEMS: the largest block in 8-sample segments after row sub-sampling (default 32: 8x8 .. 16x16 and the 32x16 / 16x32 split shapes -- `--partition btt` 17.57 -> 17.49 ms;
   // 32x32, 64 segments, is faster with a wave per search: 0.21 against 0.26 ms)
-  static const bool groupOn = !( getenv( "VTMHIP_TZ_GROUP" ) && atoi( getenv( "VTMHIP_TZ_GROUP" ) ) == 0 );
-  static const int  groupItems = getenv( "VTMHIP_TZ_GROUP_ITEMS" ) ? atoi( getenv( "VTMHIP_TZ_GROUP_ITEMS" ) ) : 32;
+  static const bool groupOn = env_switch( "VTMHIP_TZ_GROUP", true );
+  static const int  groupItems = env_int( "VTMHIP_TZ_GROUP_ITEMS", 32 );
   int grpItems = 0, grpSs = 0;
   // Row bands (VTMHIP_TZ_BANDS=0: off): the fused uniform rows whose shape vtmhip_tz_band_items accepts.  Job tables, mixed batches and the resume launch of a tz_group_kernel
   // level keep the by-candidate kernel
-  static const bool bandsOn = !( getenv( "VTMHIP_TZ_BANDS" ) && atoi( getenv( "VTMHIP_TZ_BANDS" ) ) == 0 );
+  static const bool bandsOn = env_switch( "VTMHIP_TZ_BANDS", true );
   int bandK = 0;
   if( groupOn && fuse && fuse->me && !fuse->cfg.extendedSettings && ( wpj == 0 || wpj == 1 ) && ( uniformW == 8 || uniformW == 16 || uniformW == 32 ) && uniformH >= 8 )
   {
-    const int ss = fuse->cfg.fastInterSearchMode13 && uniformH > 8 && uniformW <= 64 ? 1 : 0;      // mg::sub_shift
+    const int ss = mg::sub_shift( fuse->cfg, uniformW, uniformH );
     const int items = ( uniformW >> 3 ) * ( ( uniformH + ( 1 << ss ) - 1 ) >> ss );
     if( ( items & 7 ) == 0 && items <= groupItems && items <= 128 ) { grpItems = items; grpSs = ss; }
   }
@@ -2259,7 +2259,7 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
   else
   { VTMHIP_TIME_KERNEL( ctx, "tz_search_kernel" );
     if( bandsOn && fuse && fuse->me && uniformW > 0 && uniformH > 0 )
-      bandK = vtmhip_tz_band_items( uniformW, uniformH, fuse->cfg.fastInterSearchMode13 && uniformH > 8 && uniformW <= 64 ? 1 : 0 /* mg::sub_shift */, wpj );
+      bandK = vtmhip_tz_band_items( uniformW, uniformH, mg::sub_shift( fuse->cfg, uniformW, uniformH ), wpj );
     VTMHIP_TZ_SWITCH( split ? 1 : 0 )
   }
   if( split )
@@ -2283,7 +2283,7 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
 
 
 static int full_search_uniform( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, const vtmhip_full_job *d_jobs, int n,
-                                int width, int height, vtmhip_me_result *d_results, const FullFuse &fu );
+                                int width, int height, vtmhip_me_result *d_results, const FullFuse &fu, bool *handled );
 
 extern "C" int vtmhip_full_search_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase,
                                              const vtmhip_full_job *d_jobs, int n, vtmhip_me_result *d_results )
@@ -2306,8 +2306,9 @@ int vtmhip_internal_full_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, 
   if( fuse ) fu = *fuse;
   if( width && height && ( !fuse || ( fuse->noStart && fuse->bipredSearchRange <= 4 ) ) )
   {
-    int st = full_search_uniform( ctx, pic, d_orgBase, d_refBase, d_jobs, n, width, height, d_results, fu );
-    if( st != VTMHIP_E_INVALID + 1000 ) return st;      // (no lane-per-candidate kernel for this shape: the cooperative kernel below)
+    bool      handled;
+    const int st = full_search_uniform( ctx, pic, d_orgBase, d_refBase, d_jobs, n, width, height, d_results, fu, &handled );
+    if( handled ) return st;      // (otherwise no lane-per-candidate kernel for this shape: the cooperative kernel below)
   }
   VTMHIP_REQUIRE( ctx, pic->picW > 0 && pic->picH > 0 && pic->ctuSize > 0, "picture parameters" );
   const int wpj = pic->wavesPerJob;
@@ -2337,8 +2338,9 @@ extern "C" int vtmhip_full_search_uniform_batch_dev( vtmhip_ctx *ctx, const vtmh
 }
 
 static int full_search_uniform( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, const vtmhip_full_job *d_jobs, int n,
-                                int width, int height, vtmhip_me_result *d_results, const FullFuse &fu )
+                                int width, int height, vtmhip_me_result *d_results, const FullFuse &fu, bool *handled )
 {
+  *handled = true;
   VTMHIP_REQUIRE( ctx, pic->picW > 0 && pic->picH > 0 && pic->ctuSize > 0, "picture parameters" );
 #define VTMHIP_FSQ_LAUNCH( WW, HH )                                                                                                                                     \
   case ( WW ) * 256 + ( HH ):                                                                                                                                           \
@@ -2349,10 +2351,8 @@ static int full_search_uniform( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, c
     VTMHIP_TIME_KERNEL( ctx, "full_search_sq_kernel" );
     switch( width * 256 + height )
     {
-      VTMHIP_FSQ_LAUNCH( 8, 8 ) VTMHIP_FSQ_LAUNCH( 16, 16 ) VTMHIP_FSQ_LAUNCH( 32, 32 ) VTMHIP_FSQ_LAUNCH( 64, 64 )
-      VTMHIP_FSQ_LAUNCH( 16, 8 ) VTMHIP_FSQ_LAUNCH( 8, 16 ) VTMHIP_FSQ_LAUNCH( 32, 8 ) VTMHIP_FSQ_LAUNCH( 8, 32 ) VTMHIP_FSQ_LAUNCH( 32, 16 ) VTMHIP_FSQ_LAUNCH( 16, 32 )
-      VTMHIP_FSQ_LAUNCH( 64, 16 ) VTMHIP_FSQ_LAUNCH( 16, 64 ) VTMHIP_FSQ_LAUNCH( 64, 32 ) VTMHIP_FSQ_LAUNCH( 32, 64 )
-    default: return VTMHIP_E_INVALID + 1000;   // other shapes: the caller takes the cooperative kernel
+      VTMHIP_UNIFORM_SHAPES( VTMHIP_FSQ_LAUNCH, VTMHIP_SHAPE_NONE )
+    default: *handled = false; return VTMHIP_OK;   // other shapes (128x128 among them): the caller takes the cooperative kernel
     }
   }
 #undef VTMHIP_FSQ_LAUNCH

@@ -342,13 +342,10 @@ extern "C" int vtmhip_xMotionEstimation_batch_dev( vtmhip_ctx *ctx, const vtmhip
                                                    const int16_t *d_refBase, const int16_t *d_otherPredBase, const vtmhip_me_job *d_jobs, int n,
                                                    int maxWidth, int maxHeight, vtmhip_me_out *d_results )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, pic && cfg && d_orgBase && d_refBase && d_jobs && d_results, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, pic && cfg && d_orgBase && d_refBase && d_jobs && d_results );
   VTMHIP_REQUIRE( ctx, pic->bitDepth >= 8 && pic->bitDepth <= 12, "bit depth out of range" );      // (the fractional jobs' shifts and offsets, the integer search's keys)
   // mixed shapes, enough jobs to fill launches per class: bucket by shape (VTMHIP_MEST_BUCKET=0 keeps the one-wave-per-PU chain for the whole batch)
-  static const bool bucket = !( getenv( "VTMHIP_MEST_BUCKET" ) && atoi( getenv( "VTMHIP_MEST_BUCKET" ) ) == 0 );
+  static const bool bucket = env_switch( "VTMHIP_MEST_BUCKET", true );
   if( bucket && !cfg->uniformSquare && n >= 64 && bucket_allowed( ctx ) )   // (not under hipGraph capture: the bucketing synchronises the stream once)
     return mest_bucketed( ctx, pic, cfg, d_orgBase, d_refBase, d_otherPredBase, d_jobs, n, maxWidth, maxHeight, d_results );
   return mest_run( ctx, pic, cfg, d_orgBase, d_refBase, d_otherPredBase, d_jobs, n, maxWidth, maxHeight, d_results );
@@ -360,10 +357,7 @@ namespace
 int mest_run( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const vtmhip_me_cfg *cfg, const int16_t *d_orgBase, const int16_t *d_refBase,
               const int16_t *d_otherPredBase, const vtmhip_me_job *d_jobs, int n, int maxWidth, int maxHeight, vtmhip_me_out *d_results, const MestAmvp *amvp )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, pic && cfg && d_orgBase && d_refBase && d_jobs && d_results, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, pic && cfg && d_orgBase && d_refBase && d_jobs && d_results );
   VTMHIP_REQUIRE( ctx, pic->bitDepth >= 8 && pic->bitDepth <= 12, "bit depth out of range" );
   VTMHIP_REQUIRE( ctx, maxWidth >= 4 && maxWidth <= 128 && maxHeight >= 4 && maxHeight <= 128, "maxWidth / maxHeight" );
   VTMHIP_REQUIRE( ctx, cfg->uniformImv >= -1 && cfg->uniformImv <= 3, "uniformImv" );
@@ -413,7 +407,7 @@ int mest_run( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const vtmhip_me_cfg
   // FUSED forms (round 4; VTMHIP_MEST_FUSE=0 keeps the stand-alone glue launches): uniform batches whose pattern is addressed directly and whose rows all take the fractional
   // refinement -- the integer search builds its job records from the rows in its prologue (with xEstimateMvPredAMVP's selection when `amvp` is given), the fractional search
   // builds its jobs from the rows + the integer results and writes the rows' final records: no mest_prepare / mest_mid / mest_final launch, no job tables in between
-  static const bool fuseOn = !( getenv( "VTMHIP_MEST_FUSE" ) && atoi( getenv( "VTMHIP_MEST_FUSE" ) ) == 0 );
+  static const bool fuseOn = env_switch( "VTMHIP_MEST_FUSE", true );
   const bool fuseAny  = fuseOn && wk.direct && uimv != -1;      // a uniform AMVR mode: the integer stage fuses either way, then the fractional or the integer refinement
   const bool fuseFrac = fuseAny && fracOnly;
   const bool fuseAmvr = fuseAny && !fracOnly;
@@ -500,7 +494,7 @@ int vtmhip_internal_mest_with_amvp( vtmhip_ctx *ctx, const vtmhip_pic_params *pi
 }
 int vtmhip_internal_mest_fusable( const vtmhip_me_cfg *cfg )
 {
-  static const bool fuseOn = !( getenv( "VTMHIP_MEST_FUSE" ) && atoi( getenv( "VTMHIP_MEST_FUSE" ) ) == 0 );
+  static const bool fuseOn = env_switch( "VTMHIP_MEST_FUSE", true );
   return fuseOn && cfg->uniformBi == 1 && cfg->uniformImv >= 0 && cfg->uniformImv <= 3;
 }
 

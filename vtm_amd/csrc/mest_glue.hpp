@@ -20,6 +20,7 @@ __device__ __forceinline__ void clip_mv( const vtmhip_pic_params &pic, const vtm
   ver = min( verMax, max( verMin, ver ) );
 }
 __device__ __forceinline__ int sub_shift( const vtmhip_me_cfg &cfg, int w, int h ) { return cfg.fastInterSearchMode13 && h > 8 && w <= 64 ? 1 : 0; }   // RdCost.cpp:289-323, mode 2
+__host__ inline int            sub_shift( const vtmhip_me_cfg &cfg, int w, int h ) { return cfg.fastInterSearchMode13 && h > 8 && w <= 64 ? 1 : 0; }   // the host's copy (launch code)
 // CU-level BCW weight of the searched list of a bi job (0: the default pair); the default weight (4 of 8) is normalised to 0
 __device__ __forceinline__ int bcw_weight( const vtmhip_me_job &j ) { const int w = j.bi ? VTMHIP_MEJ_BCW_WEIGHT( j.flags ) : 0; return w == 4 ? 0 : w; }
 

@@ -450,10 +450,7 @@ extern "C"
 int vtmhip_xEstimateMvPredAMVP_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase,
                                           vtmhip_me_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize, int addIdxBits, uint64_t *d_distBiP )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, pic && d_orgBase && d_refBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, pic && d_orgBase && d_refBase && d_jobs );
   VTMHIP_REQUIRE( ctx, maxWidth >= 4 && maxWidth <= 128 && maxHeight >= 4 && maxHeight <= 128, "maxWidth / maxHeight" );
   AmvpWork     wk;
   size_t       off = 0;

@@ -11,6 +11,7 @@
 // matrix live in LDS; lane l of a wave produces output frequency k = l (matrix columns are contiguous in LDS, the data
 // row is a broadcast), so LDS reads are conflict-free.
 #include "ctx.hpp"
+#include "stage.hpp"
 #include "bucket.hpp"
 #include "tr_tables.hpp"
 #include "lmcs.hpp"
@@ -632,16 +633,13 @@ template<bool CRS>
 int tu_chain_entry( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
                     int32_t *d_levelsBase, int16_t *d_recBase, vtmhip_tu_result *d_results )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_resiBase && d_jobs && d_results, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_resiBase && d_jobs && d_results );
   VTMHIP_REQUIRE( ctx, maxWidth >= 2 && maxWidth <= TB && maxHeight >= 2 && maxHeight <= TB, "maxWidth / maxHeight: 2..64 (2-D transforms)" );
   int st = vtmhip_internal_tr_tables( ctx );
   if( st ) return st;
   // a mixed batch with enough TUs: bucket by shape on the device (bucket.hpp), the register-blocked kernel per {8,16,32,64} x {8,16,32,64} class, the
   // generic kernel for the rest (4-sample sides, transform skip).  VTMHIP_TU_BUCKET=0 keeps the generic kernel for the whole batch.
-  static const bool bucket = !( getenv( "VTMHIP_TU_BUCKET" ) && atoi( getenv( "VTMHIP_TU_BUCKET" ) ) == 0 );
+  static const bool bucket = env_switch( "VTMHIP_TU_BUCKET", true );
   if( bucket && !uniformSize && n >= 256 && maxWidth >= 8 && maxHeight >= 8 && bucket_allowed( ctx ) )
   {
     BucketPlan plan;
@@ -708,21 +706,17 @@ int vtmhip_fastFwdTrans( vtmhip_ctx *ctx, int type, int n, const int32_t *src, i
   VTMHIP_REQUIRE( ctx, type >= 0 && type < 3 && pow2( n ) && n >= 2 && n <= 64 && ( type == VTMHIP_DCT2 || ( n >= 4 && n <= 32 ) ),
                   "no such transform (fastFwdTrans slot is nullptr)" );
   VTMHIP_REQUIRE( ctx, line >= 1 && line <= 64 && shift >= 0 && shift < 32 && skipLine >= 0 && skipLine <= line && skipLine2 >= 0 && skipLine2 <= n, "shape" );
-  int st = vtmhip_internal_tr_tables( ctx );
-  if( st ) return st;
-  const size_t bytes = ( size_t ) n * line * 4;
-  st = vtmhip_internal_scratch( ctx, 2 * bytes + 128 );
-  if( st ) return st;
-  char *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
-  const size_t dOff = ( bytes + 63 ) & ~( size_t ) 63;
-  memcpy( hp, src, bytes );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, bytes, hipMemcpyHostToDevice, ctx->stream ) );
-  hipLaunchKernelGGL( fwd1d_kernel, dim3( ( n * line + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ( const int * ) dp, ( int * ) ( dp + dOff ),
+  VTMHIP_TRY( vtmhip_internal_tr_tables( ctx ) );
+  HostStage    s( ctx );
+  const size_t bytes = ( size_t ) n * line * 4, sOff = s.region( bytes ), dOff = s.region( bytes );
+  VTMHIP_TRY( s.reserve() );
+  memcpy( s.hp + sOff, src, bytes );
+  VTMHIP_TRY( s.upload( sOff, bytes ) );
+  hipLaunchKernelGGL( fwd1d_kernel, dim3( ( n * line + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, s.dev<const int>( sOff ), s.dev<int>( dOff ),
                       ctx->trTab[type][hlog2( n )], n, shift, line, skipLine, skipLine2 );
   VTMHIP_LAUNCHED( ctx );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( hp + dOff, dp + dOff, bytes, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
-  memcpy( dst, hp + dOff, bytes );
+  VTMHIP_TRY( s.fetch( dOff, bytes ) );
+  memcpy( dst, s.hp + dOff, bytes );
   return VTMHIP_OK;
 }
 
@@ -734,31 +728,24 @@ int vtmhip_fastInvTrans( vtmhip_ctx *ctx, int type, int n, const int32_t *src, i
   VTMHIP_REQUIRE( ctx, type >= 0 && type < 3 && pow2( n ) && n >= 2 && n <= 64 && ( type == VTMHIP_DCT2 || ( n >= 4 && n <= 32 ) ),
                   "no such transform (fastInvTrans slot is nullptr)" );
   VTMHIP_REQUIRE( ctx, line >= 1 && line <= 64 && shift >= 1 && shift < 32 && skipLine >= 0 && skipLine <= line && skipLine2 >= 0 && skipLine2 <= n, "shape" );
-  int st = vtmhip_internal_tr_tables( ctx );
-  if( st ) return st;
-  const size_t bytes = ( size_t ) n * line * 4;
-  st = vtmhip_internal_scratch( ctx, 2 * bytes + 128 );
-  if( st ) return st;
-  char *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
-  const size_t dOff = ( bytes + 63 ) & ~( size_t ) 63;
-  memcpy( hp, src, bytes );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, bytes, hipMemcpyHostToDevice, ctx->stream ) );
-  hipLaunchKernelGGL( inv1d_kernel, dim3( ( n * line + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ( const int * ) dp, ( int * ) ( dp + dOff ),
+  VTMHIP_TRY( vtmhip_internal_tr_tables( ctx ) );
+  HostStage    s( ctx );
+  const size_t bytes = ( size_t ) n * line * 4, sOff = s.region( bytes ), dOff = s.region( bytes );
+  VTMHIP_TRY( s.reserve() );
+  memcpy( s.hp + sOff, src, bytes );
+  VTMHIP_TRY( s.upload( sOff, bytes ) );
+  hipLaunchKernelGGL( inv1d_kernel, dim3( ( n * line + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, s.dev<const int>( sOff ), s.dev<int>( dOff ),
                       ctx->trTab[type][hlog2( n )], n, shift, line, skipLine, skipLine2, outputMinimum, outputMaximum );
   VTMHIP_LAUNCHED( ctx );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( hp + dOff, dp + dOff, bytes, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
-  memcpy( dst, hp + dOff, bytes );
+  VTMHIP_TRY( s.fetch( dOff, bytes ) );
+  memcpy( dst, s.hp + dOff, bytes );
   return VTMHIP_OK;
 }
 
 int vtmhip_xT_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, int32_t *d_coefBase, const vtmhip_tr_job *d_jobs, int n, int maxWidth,
                          int maxHeight, int32_t *d_sumAbs )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_resiBase && d_coefBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_resiBase && d_coefBase && d_jobs );
   VTMHIP_REQUIRE( ctx, maxWidth >= 1 && maxWidth <= TB && maxHeight >= 1 && maxHeight <= TB, "maxWidth / maxHeight (max transform size 64)" );
   int st = vtmhip_internal_tr_tables( ctx );
   if( st ) return st;
@@ -772,10 +759,7 @@ int vtmhip_xT_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, int32_t *d_
 int vtmhip_xIT_batch_dev( vtmhip_ctx *ctx, const int32_t *d_coefBase, int16_t *d_resiBase, const vtmhip_tr_job *d_jobs, int n, int maxWidth,
                           int maxHeight )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_resiBase && d_coefBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_resiBase && d_coefBase && d_jobs );
   VTMHIP_REQUIRE( ctx, maxWidth >= 1 && maxWidth <= TB && maxHeight >= 1 && maxHeight <= TB, "maxWidth / maxHeight (max transform size 64)" );
   int st = vtmhip_internal_tr_tables( ctx );
   if( st ) return st;
@@ -789,10 +773,7 @@ int vtmhip_xIT_batch_dev( vtmhip_ctx *ctx, const int32_t *d_coefBase, int16_t *d
 int vtmhip_quant_batch_dev( vtmhip_ctx *ctx, const int32_t *d_coefBase, int32_t *d_qBase, int32_t *d_deltaUBase, const vtmhip_quant_job *d_jobs, int n,
                             int32_t *d_absSum )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_coefBase && d_qBase && d_jobs && d_absSum, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_coefBase && d_qBase && d_jobs && d_absSum );
   hipLaunchKernelGGL( quant_kernel, dim3( n ), dim3( 256 ), 0, ctx->stream, d_coefBase, d_qBase, d_deltaUBase, d_jobs, d_absSum );
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
@@ -800,10 +781,7 @@ int vtmhip_quant_batch_dev( vtmhip_ctx *ctx, const int32_t *d_coefBase, int32_t 
 
 int vtmhip_dequant_batch_dev( vtmhip_ctx *ctx, const int32_t *d_qBase, int32_t *d_coefBase, const vtmhip_quant_job *d_jobs, int n )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_coefBase && d_qBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_coefBase && d_qBase && d_jobs );
   hipLaunchKernelGGL( dequant_kernel, dim3( n ), dim3( 256 ), 0, ctx->stream, d_qBase, d_coefBase, d_jobs );
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
@@ -824,10 +802,7 @@ int vtmhip_tu_chain_crs_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, c
 int vtmhip_tu_ts_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int width, int height,
                                   int32_t *d_levelsBase, int16_t *d_recBase, vtmhip_tu_result *d_results )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_resiBase && d_jobs && d_results, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_resiBase && d_jobs && d_results );
   VTMHIP_REQUIRE( ctx, pow2( width ) && pow2( height ) && width >= 4 && height >= 4 && width <= 32 && height <= 32, "transform skip: 4..32 (log2MaxTransformSkipBlockSize)" );
   VTMHIP_TIME_KERNEL( ctx, "tu_ts_kernel" );
   hipLaunchKernelGGL( tu_ts_kernel, dim3( ( n + 31 ) / 32 ), dim3( 256 ), 0, ctx->stream, d_resiBase, d_jobs, n, d_levelsBase, d_recBase, d_results, width, height );
@@ -914,10 +889,7 @@ int vtmhip_mts_select( const int32_t *sumAbs, int numCand, int width, int height
 extern "C" int vtmhip_xT_uniform_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int width, int height, int32_t *d_coefBase,
                                             vtmhip_tu_result *d_results )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_resiBase && d_jobs && d_coefBase && d_results, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_resiBase && d_jobs && d_coefBase && d_results );
   VTMHIP_REQUIRE( ctx, width >= 8 && width <= TB && height >= 8 && height <= TB && pow2( width ) && pow2( height ), "width / height: powers of two 8..64" );
   int st = vtmhip_internal_tr_tables( ctx );
   if( st ) return st;
@@ -1083,20 +1055,19 @@ static int lfnst_single( vtmhip_ctx *ctx, const int32_t *src, int32_t *dst, int 
   VTMHIP_REQUIRE( ctx, ctx->lfnstTab, "vtmhip_lfnst_set_tables has not been called" );
   VTMHIP_REQUIRE( ctx, mode >= 0 && mode < 4 && index >= 0 && index < 2 && ( size == 4 || size == 8 ) && ( zeroOutSize == 8 || zeroOutSize == 16 ), "mode / index / size / zeroOutSize" );
   const int trSize = size > 4 ? 48 : 16, nIn = inverse ? zeroOutSize : trSize;
-  int st = vtmhip_internal_scratch( ctx, 1024 );
-  if( st ) return st;
-  char *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
-  memcpy( hp, src, sizeof( int32_t ) * nIn );
+  HostStage    s( ctx );
+  const size_t srcOff = s.region( sizeof( int32_t ) * 48 ), dstOff = s.region( sizeof( int32_t ) * 48 ), jobOff = s.region( sizeof( vtmhip_lfnst_job ) );
+  VTMHIP_TRY( s.reserve() );
+  memcpy( s.hp + srcOff, src, sizeof( int32_t ) * nIn );
   vtmhip_lfnst_job j;
   memset( &j, 0, sizeof( j ) );
-  j.srcOff = 0; j.dstOff = 64; j.mode = ( uint8_t ) mode; j.index = ( uint8_t ) index; j.size = ( uint8_t ) size; j.zeroOutSize = ( uint8_t ) zeroOutSize; j.inverse = ( uint8_t ) inverse;
-  memcpy( hp + 512, &j, sizeof( j ) );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, 576, hipMemcpyHostToDevice, ctx->stream ) );
-  hipLaunchKernelGGL( lfnst_kernel, dim3( 1 ), dim3( 256 ), 0, ctx->stream, ctx->lfnstTab, ( const int * ) dp, ( int * ) dp, ( const vtmhip_lfnst_job * ) ( dp + 512 ), 1 );
+  j.srcOff = ( int64_t ) ( srcOff / 4 ); j.dstOff = ( int64_t ) ( dstOff / 4 ); j.mode = ( uint8_t ) mode; j.index = ( uint8_t ) index; j.size = ( uint8_t ) size; j.zeroOutSize = ( uint8_t ) zeroOutSize; j.inverse = ( uint8_t ) inverse;
+  s.put( jobOff, j );
+  VTMHIP_TRY( s.upload( 0, s.total ) );
+  hipLaunchKernelGGL( lfnst_kernel, dim3( 1 ), dim3( 256 ), 0, ctx->stream, ctx->lfnstTab, s.dev<const int>( 0 ), s.dev<int>( 0 ), s.dev<const vtmhip_lfnst_job>( jobOff ), 1 );
   VTMHIP_LAUNCHED( ctx );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( hp + 256, dp + 256, sizeof( int32_t ) * trSize, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
-  memcpy( dst, hp + 256, sizeof( int32_t ) * trSize );
+  VTMHIP_TRY( s.fetch( dstOff, sizeof( int32_t ) * trSize ) );
+  memcpy( dst, s.hp + dstOff, sizeof( int32_t ) * trSize );
   return VTMHIP_OK;
 }
 

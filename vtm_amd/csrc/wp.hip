@@ -15,6 +15,7 @@
 //
 // wp_pred_kernel: one wave per job, 4-sample row segments over the lanes.
 #include "ctx.hpp"
+#include "stage.hpp"
 
 namespace
 {
@@ -350,29 +351,22 @@ int wp_single( vtmhip_ctx *ctx, int kind, const int16_t *org, int orgStride, con
                   "outside the weighted-prediction sample contract (width / height 1..128, bitDepth 8..12, isBiPred 0 / 1, w in [-256, 256], shift 0..8, "
                   "offset / round in int16, even width and height on the 2x2 HAD path)" );
   // stage org and cur compactly (stride = width), then the job and the result slot
+  HostStage    s( ctx );
   const size_t blk = ( size_t ) width * height * sizeof( int16_t );
-  const size_t jobOff = ( 2 * blk + 63 ) & ~( size_t ) 63, outOff = jobOff + 64;
-  int st = vtmhip_internal_scratch( ctx, outOff + 64 );
-  if( st ) return st;
-  char *hp = ( char * ) ctx->pinned, *dp = ( char * ) ctx->scratch;
-  for( int y = 0; y < height; y++ )
-  {
-    memcpy( hp + ( size_t ) y * width * 2, org + ( ptrdiff_t ) y * orgStride, ( size_t ) width * 2 );
-    memcpy( hp + blk + ( size_t ) y * width * 2, cur + ( ptrdiff_t ) y * curStride, ( size_t ) width * 2 );
-  }
+  const size_t orgOff = s.region( blk ), curOff = s.region( blk ), jobOff = s.region( sizeof( vtmhip_wp_dist_job ) ), outOff = s.region( 8 );
+  VTMHIP_TRY( s.reserve() );
+  s.pack( orgOff, org, orgStride, width, height );
+  s.pack( curOff, cur, curStride, width, height );
   vtmhip_wp_dist_job j;
   memset( &j, 0, sizeof( j ) );
-  j.orgOff = 0; j.curOff = ( int64_t ) width * height; j.orgStride = width; j.curStride = width;
+  j.orgOff = ( int64_t ) ( orgOff / 2 ); j.curOff = ( int64_t ) ( curOff / 2 ); j.orgStride = width; j.curStride = width;
   j.width = ( int16_t ) width; j.height = ( int16_t ) height; j.kind = ( uint8_t ) kind; j.bitDepth = ( uint8_t ) bitDepth; j.isBiPred = ( uint8_t ) isBiPred;
   j.wp = *wp; j.maxDist = maxDist;
-  memcpy( hp + jobOff, &j, sizeof( j ) );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( dp, hp, outOff, hipMemcpyHostToDevice, ctx->stream ) );
-  st = wp_dist_launch( ctx, ( const int16_t * ) dp, ( const int16_t * ) dp, ( const vtmhip_wp_dist_job * ) ( dp + jobOff ), 1, 1,
-                       ( unsigned long long * ) ( dp + outOff ) );
-  if( st ) return st;
-  VTMHIP_HIP( ctx, hipMemcpyAsync( hp + outOff, dp + outOff, 8, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
-  memcpy( dist, hp + outOff, 8 );
+  s.put( jobOff, j );
+  VTMHIP_TRY( s.upload( 0, outOff ) );
+  VTMHIP_TRY( wp_dist_launch( ctx, s.dev<const int16_t>( 0 ), s.dev<const int16_t>( 0 ), s.dev<const vtmhip_wp_dist_job>( jobOff ), 1, 1, s.dev<unsigned long long>( outOff ) ) );
+  VTMHIP_TRY( s.fetch( outOff, 8 ) );
+  memcpy( dist, s.hp + outOff, 8 );
   return VTMHIP_OK;
 }
 
@@ -401,19 +395,13 @@ int vtmhip_xGetHADsw( vtmhip_ctx *ctx, const int16_t *org, int orgStride, const 
 
 int vtmhip_wp_dist_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_curBase, const vtmhip_wp_dist_job *d_jobs, int n, uint64_t *d_dist )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_orgBase && d_curBase && d_jobs && d_dist, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_orgBase && d_curBase && d_jobs && d_dist );
   return wp_dist_launch( ctx, d_orgBase, d_curBase, d_jobs, n, wp_jobs_per_wave( ctx, n ), ( unsigned long long * ) d_dist );
 }
 
 int vtmhip_wp_pred_batch_dev( vtmhip_ctx *ctx, const int16_t *d_src0Base, const int16_t *d_src1Base, int16_t *d_dstBase, const vtmhip_wp_pred_job *d_jobs, int n )
 {
-  VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, n >= 0, "n" );
-  if( n == 0 ) return VTMHIP_OK;
-  VTMHIP_REQUIRE( ctx, d_src0Base && d_src1Base && d_dstBase && d_jobs, "null pointer" );
+  VTMHIP_BATCH_ENTRY( ctx, n, d_src0Base && d_src1Base && d_dstBase && d_jobs );
   VTMHIP_TIME_KERNEL( ctx, "wp_pred_kernel" );
   hipLaunchKernelGGL( wp_pred_kernel, dim3( ( n + 3 ) / 4 ), dim3( 256 ), 0, ctx->stream, d_src0Base, d_src1Base, d_dstBase, d_jobs, n );
   VTMHIP_LAUNCHED( ctx );
