@@ -1291,6 +1291,99 @@ int vtmhip_is_uniform_shape( int width, int height );
  * kernel; so does every launch when VTMHIP_TZ_BANDS=0 is set in the environment. */
 int vtmhip_tz_band_items( int width, int height, int subShift, int wavesPerJob );
 
+/* ---- sub-block transform (SBT) of inter CUs: the mode estimator and the SBT candidates of xEstimateInterResidualQT --------------------------------
+ * (CodingUnit::checkAllowedSbt Unit.cpp:450-494; CU::getSbtMode ... numSbtModeRdo UnitTools.cpp:3516-3589; PartitionerImpl::getSbtTuTiling
+ * UnitPartitioner.cpp:1091-1148; TrQuant::getTrTypes TrQuant.cpp:728-760; InterSearch::calcMinDistSbt / skipSbtByRDCost InterSearch.cpp:6195-6438.)
+ * The rules have one definition for host and device, vtm_amd/csrc/sbt_rules.hpp:
+ *   sbtIdx 1 VER_HALF, 2 HOR_HALF, 3 VER_QUAD, 4 HOR_QUAD; sbtPos 0 / 1; sbtMode = (sbtIdx - 1) * 2 + sbtPos (0 .. 7); sbtAllowed: bit sbtIdx set.
+ *   Allowed by size: both sides <= maxTbSize, VER_HALF w >= 8, HOR_HALF h >= 8, VER_QUAD w >= 16, HOR_QUAD h >= 16 (prediction mode and CIIP: the caller's).
+ *   Coded tile of a component block cw x ch: POS0 the first 1/2 (1/4) of the split side, POS1 the last; every factor is (dim * f) >> 2 on the component's block.
+ *   Luma transform pair: vertical splits DCT2 / DCT2 when the sub-TU's height > 32, else POS0 (hor DCT8, ver DST7), POS1 (DST7, DST7); horizontal splits
+ *   DCT2 / DCT2 when its width > 32, else POS0 (DST7, DCT8), POS1 (DST7, DST7).  Chroma: DCT2 / DCT2.  No transform skip, no MTS.
+ * 4:2:0 only.  Out of scope: the level-order picture driver, JCCR or chroma residual scaling on SBT sub-TUs, the CABAC estimate, m_histBestSbt and the
+ * save / load of SBT decisions, ACT. */
+#define VTMHIP_SBT_VER_HALF 1
+#define VTMHIP_SBT_HOR_HALF 2
+#define VTMHIP_SBT_VER_QUAD 3
+#define VTMHIP_SBT_HOR_QUAD 4
+
+typedef struct
+{
+  int64_t orgOff[3], predOff[3];      /* the CU's original / prediction blocks of Y, Cb, Cr inside d_orgBase / d_predBase; a chroma offset of -1 (either one): luma only */
+  int32_t orgStride[3], predStride[3];
+  int16_t width, height;              /* the LUMA CU size, powers of two 4 .. 64; chroma blocks are width / 2 x height / 2 */
+  uint8_t bitDepth;                   /* 8 .. 12 */
+  uint8_t sbtAllowed;                 /* the CU's mask; a type the size rule above excludes makes the job invalid */
+  uint8_t pad0, pad1;
+  double  chromaWeight;               /* RdCost::getChromaWeight() */
+  double  distScale;                  /* RdCost::m_DistScaleUnadjusted: calcRdCost( bits, dist ) = distScale * dist + bits */
+} vtmhip_sbt_est_job;
+
+typedef struct
+{
+  uint64_t est[9];                    /* m_estMinDistSbt: [sbtMode] (UINT64_MAX: not tried), [8] = the CU's SSE over the partitions */
+  uint8_t  rdoOrder[8];               /* m_sbtRdoOrder, 255-filled */
+  uint32_t part[3][4][4];             /* the raw partition sums [component][j][i] BEFORE the chroma weight (zero outside numPartY x numPartX and for absent chroma) */
+  uint8_t  skipAll;                   /* m_skipSbtAll: distScale * est[8] < 12 << 15; est[0 .. 7] and rdoOrder then stay UINT64_MAX / 255 */
+  uint8_t  pad[7];
+} vtmhip_sbt_est_result;
+
+/* InterSearch::calcMinDistSbt for n CUs, one launch.  numPartX / numPartY = 4 for a luma side >= 16, 1 for 4, 2 otherwise; every component's block is divided by
+ * that count; a chroma partition sum becomes (uint64)( double( sum ) * chromaWeight ) before it joins dist[j][i].  Squared differences are added at full
+ * precision: the reference's shift DISTORTION_PRECISION_ADJUSTMENT( ( bitDepth - 8 ) << 1 ) is 0 as it is built (FULL_NBIT = 1, TypeDef.h:228-233; sbtDistShift in
+ * sbt_rules.hpp is the one place that says so).  Samples lie within the bit depth (|org - pred| <= 4095), so a partition sum -- at most 256 samples -- fits 32
+ * bits (by 2 096 896 at 12 bits: a difference outside the bit depth wraps the sum silently; the caller's contract, as for every sample entry here).  maxWidth x maxHeight (the largest luma CU of the batch)
+ * sizes the lanes a CU gets: 16 (up to 256 luma samples: four CUs share a wave), a wave (up to 1024) or a workgroup; a larger job is still computed.
+ * The jobs stay on the device: a job with a side outside 4 .. 64 or not a power of two, a bitDepth outside 8 .. 12 or a sbtAllowed the size rule (maxTbSize 64)
+ * excludes is skipped -- its result is not written.  A CU with sbtAllowed == 0 gets est[8] and part[] by the same partition rule (the reference takes
+ * getDistPart there, which rounds the chroma weight differently: keep that case on the host if the value matters). */
+int vtmhip_sbt_est_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_predBase, const vtmhip_sbt_est_job *d_jobs, int n, int maxWidth,
+                              int maxHeight, vtmhip_sbt_est_result *d_results );
+
+/* InterSearch::skipSbtByRDCost over an est[9] record (host arithmetic, no device; the double operations in the reference's order): the early-skip type 0 .. 3,
+ * or 255 to try the mode.  costSbtOff == MAX_DOUBLE (1.7e+308): no SBT-off result yet.  A NULL est or a mode outside the table returns VTMHIP_E_INVALID. */
+int vtmhip_sbt_skip_by_rdcost( const uint64_t est[9], double distScale, int sbtIdx, int sbtPos, double bestCost, uint64_t distSbtOff, double costSbtOff,
+                               int rootCbfSbtOff );
+
+typedef struct
+{
+  int64_t resiOff[3];                 /* the CU's residual of Y, Cb, Cr inside d_resiBase; a chroma offset of -1: that component is not coded */
+  int64_t outOff[3];                  /* per component: the sub-TU's levels (sub-W x sub-H contiguous) inside d_levelsBase and the CU-shaped reconstructed residual
+                                         (comp-W x comp-H contiguous) inside d_recBase */
+  int32_t resiStride[3];
+  int16_t width, height;              /* the LUMA CU size, powers of two 4 .. 64 */
+  int16_t qpPer[3], qpRem[3];         /* as vtmhip_tu_job, per component */
+  uint8_t sbtIdx, sbtPos;             /* VTMHIP_SBT_*, 0 / 1 */
+  uint8_t bitDepth, isIRAP;           /* bitDepth 8 .. 12 */
+} vtmhip_sbt_job;
+
+typedef struct
+{
+  uint64_t sseCoded[3];               /* the chain's SSE over the coded tile (vtmhip_tu_result.sse); unweighted: the caller applies the chroma distortion weight */
+  uint64_t sseZero[3];                /* sum of r * r over the uncoded tile's residual (full precision, as sseCoded: see vtmhip_sbt_est_batch_dev) */
+  int32_t  absSum[3];                 /* uiAbsSum of Quant::quant on the sub-TU */
+  int32_t  pad;
+} vtmhip_sbt_result;                  /* an absent component's fields are zero */
+
+/* One (CU, sbtIdx, sbtPos) candidate per job, no host round trip between the steps: an expansion kernel turns every job into one vtmhip_tu_job per present
+ * component (the sub-TU rectangle inside the CU's residual, the transform pair above), the fused chain runs them through the launch paths of
+ * vtmhip_tu_chain_batch_dev with uniformSize == 0 (256 or more sub-TUs: bucketed by shape), and a finish kernel completes the candidate: sseCoded / absSum from
+ * the chain, sseZero, and -- when d_recBase is given -- the CU-shaped reconstruction with the coded tile from the chain and zeros elsewhere.  d_levelsBase and
+ * d_recBase may be NULL.  The chain writes the compact sub-TU reconstruction to the head of the CU-shaped block; the finish kernel spreads it in place, so the
+ * only scratch is the expanded job table and its results (the context's workspace of the stream, no allocation once it has grown).
+ * The job table is read back (n * 80 bytes, one stream synchronisation; never under stream capture) and checked before anything is launched: a side outside
+ * 4 .. 64 or not a power of two, a mode the size rule (maxTbSize 64) does not allow, sbtPos > 1, a bitDepth outside 8 .. 12, qpRem outside 0 .. 5, qpPer < 0, a
+ * negative luma offset or a NULL pointer return VTMHIP_E_INVALID and launch nothing.  n == 0 is VTMHIP_OK. */
+int vtmhip_sbt_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_sbt_job *d_jobs, int n, int32_t *d_levelsBase, int16_t *d_recBase,
+                                vtmhip_sbt_result *d_results );
+
+/* The same expansion as host arithmetic, for callers that keep their own job tables: out[i] = the luma sub-TU of job i (i < n), the chroma sub-TUs follow from
+ * out[n] on in job order (Cb before Cr); tuIdx[3 * i + c] = the index of job i's component c inside out, -1 when absent (may be NULL).  out holds up to 3 * n
+ * jobs; *numOut receives the count.  The checks of vtmhip_sbt_chain_batch_dev apply. */
+int vtmhip_sbt_make_tu_jobs( const vtmhip_sbt_job *jobs, int n, vtmhip_tu_job *out, int *numOut, int32_t *tuIdx );
+
+int vtmhip_sbt_struct_size( int which );   /* sizeof() of 0 vtmhip_sbt_est_job, 1 vtmhip_sbt_est_result, 2 vtmhip_sbt_job, 3 vtmhip_sbt_result; -1 otherwise */
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,8 @@ inline bool env_switch( const char *name, bool dflt ) { return env_int( name, df
 
 int vtmhip_internal_scratch( vtmhip_ctx *ctx, size_t bytes );   // grows ctx->scratch / ctx->pinned
 int vtmhip_internal_tr_tables( vtmhip_ctx *ctx );               // transform.hip: fills ctx->trTab / trTabBuf on first use (under initMutex)
+int vtmhip_internal_tu_chain_launch( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
+                                     int32_t *d_levelsBase, int16_t *d_recBase, vtmhip_tu_result *d_results );   // transform.hip: the dispatch of vtmhip_tu_chain_batch_dev
 int vtmhip_internal_mc_launch( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_refBase, int16_t *d_predBase, int16_t *d_outBase, const vtmhip_pred_job *d_jobs,
                                int n, int maxWidth, int maxHeight, unsigned long long *d_sadOut );   // mc.hip: motionCompensation, optionally reduced to the SAD against the original
 int vtmhip_internal_mc_amvp_launch( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, const vtmhip_me_job *d_rows, int n,

@@ -694,6 +694,13 @@ __global__ __launch_bounds__( 256 ) void mts_select_kernel( const vtmhip_tu_resu
 
 }   // namespace
 
+// the dispatch of vtmhip_tu_chain_batch_dev for the other translation units of the library (sbt.hip runs its expanded sub-TU jobs through it)
+int vtmhip_internal_tu_chain_launch( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
+                                     int32_t *d_levelsBase, int16_t *d_recBase, vtmhip_tu_result *d_results )
+{
+  return tu_chain_entry<false>( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, uniformSize, d_levelsBase, d_recBase, d_results );
+}
+
 extern "C"
 {
 

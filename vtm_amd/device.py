@@ -9,7 +9,7 @@ import numpy as np
 
 from . import lib as _lib
 from .lib import (AffineJob, DistJob, FracJob, FracResult, FullJob, IctJob, IfJob, JccrJob, JccrResult, LmcsJob, McJob, MeResult, PelOpJob, PicParams, QuantJob,   # noqa: F401
-                  ScaleJob, TrJob, TuJob, TuResult, TzJob, VtmHipError, WpDistJob, WpParam, WpPredJob, WtdJob)
+                  SbtEstJob, SbtEstResult, SbtJob, SbtResult, ScaleJob, TrJob, TuJob, TuResult, TzJob, VtmHipError, WpDistJob, WpParam, WpPredJob, WtdJob)
 
 
 class DevBuf:
@@ -444,6 +444,14 @@ class Context:
         """jccr_chain_batch with LMCS chroma residual scaling around the joint candidate: JccrJob.chromaAdj = tu.getChromaAdj() or 0"""
         self._check(self.L.vtmhip_jccr_chain_crs_batch_dev(self.h, d_resi, d_jobs, n, max_w, max_h, int(uniform), d_levels, d_rec_cb, d_rec_cr, d_results))
 
+    def sbt_est_batch(self, d_org, d_pred, d_jobs, n, max_w, max_h, d_results):
+        """InterSearch::calcMinDistSbt for n SbtEstJob CUs -> SbtEstResult (mode estimates, RDO order, skipAll, the raw partition sums)"""
+        self._check(self.L.vtmhip_sbt_est_batch_dev(self.h, d_org, d_pred, d_jobs, n, max_w, max_h, d_results))
+
+    def sbt_chain_batch(self, d_resi, d_jobs, n, d_results, d_levels=None, d_rec=None):
+        """n SbtJob candidates (CU, sbtIdx, sbtPos): sub-TU expansion, the fused chain, completion over the whole CU -> SbtResult"""
+        self._check(self.L.vtmhip_sbt_chain_batch_dev(self.h, d_resi, d_jobs, n, d_levels, d_rec, d_results))
+
     def scale_signal_batch(self, d_src, d_dst, d_jobs, n):
         """scaleSignal of n ScaleJob blocks, each with its own scale and direction (d_dst may be d_src: in place)"""
         self._check(self.L.vtmhip_scale_signal_batch_dev(self.h, d_src, d_dst, d_jobs, n))
@@ -479,3 +487,22 @@ def ict_select(dist, is_intra):
     if st != _lib.OK:
         raise VtmHipError(st)
     return [masks[i] for i in range(num.value)]
+
+
+def sbt_skip_by_rdcost(est, dist_scale, sbt_idx, sbt_pos, best_cost, dist_sbt_off, cost_sbt_off, root_cbf_sbt_off):
+    """InterSearch::skipSbtByRDCost over an est[9] record (host arithmetic, no device): 0 .. 3 or 255"""
+    e = (C.c_uint64 * 9)(*[int(v) for v in est])
+    st = _lib.load().vtmhip_sbt_skip_by_rdcost(e, dist_scale, sbt_idx, sbt_pos, best_cost, int(dist_sbt_off), cost_sbt_off, int(root_cbf_sbt_off))
+    if st < 0:
+        raise VtmHipError(st)
+    return st
+
+
+def sbt_make_tu_jobs(jobs):
+    """The host form of the chain's expansion: (TuJob array, tuIdx int32 [n, 3]) of an SbtJob ctypes array"""
+    n = len(jobs)
+    out, idx, num = (TuJob * (3 * n))(), np.zeros((n, 3), np.int32), C.c_int()
+    st = _lib.load().vtmhip_sbt_make_tu_jobs(C.addressof(jobs), n, C.addressof(out), C.byref(num), idx.ctypes.data)
+    if st != _lib.OK:
+        raise VtmHipError(st)
+    return (TuJob * num.value).from_buffer_copy(bytes(out)[:num.value * C.sizeof(TuJob)]), idx

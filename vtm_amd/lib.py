@@ -16,6 +16,8 @@ WP_UNI, WP_BI = 0, 1              # vtmhip_wp_pred_job.mode
 DCT2, DCT8, DST7, TRSKIP = 0, 1, 2, 3
 ICT_MODES = ((0, 3, 1, 2), (0, -3, -1, -2))   # g_ictModes[signFlag][cbfMask]
 LMCS_MAP_PRED, LMCS_WRITE_MAPPED = 1, 2       # vtmhip_lmcs_job.flags
+SBT_VER_HALF, SBT_HOR_HALF, SBT_VER_QUAD, SBT_HOR_QUAD = 1, 2, 3, 4   # sbtIdx; sbtMode = (sbtIdx - 1) * 2 + sbtPos
+SBT_MAX_DIST = (1 << 64) - 1                  # vtmhip_sbt_est_result.est of a mode that is not tried
 
 
 class DistJob(C.Structure):
@@ -303,12 +305,32 @@ class ScaleJob(C.Structure):
                 ("scale", C.c_uint16), ("dir", C.c_uint8), ("bitDepth", C.c_uint8)]
 
 
+class SbtEstJob(C.Structure):
+    _fields_ = [("orgOff", C.c_int64 * 3), ("predOff", C.c_int64 * 3), ("orgStride", C.c_int32 * 3), ("predStride", C.c_int32 * 3), ("width", C.c_int16),
+                ("height", C.c_int16), ("bitDepth", C.c_uint8), ("sbtAllowed", C.c_uint8), ("pad0", C.c_uint8), ("pad1", C.c_uint8), ("chromaWeight", C.c_double),
+                ("distScale", C.c_double)]
+
+
+class SbtEstResult(C.Structure):
+    _fields_ = [("est", C.c_uint64 * 9), ("rdoOrder", C.c_uint8 * 8), ("part", ((C.c_uint32 * 4) * 4) * 3), ("skipAll", C.c_uint8), ("pad", C.c_uint8 * 7)]
+
+
+class SbtJob(C.Structure):
+    _fields_ = [("resiOff", C.c_int64 * 3), ("outOff", C.c_int64 * 3), ("resiStride", C.c_int32 * 3), ("width", C.c_int16), ("height", C.c_int16),
+                ("qpPer", C.c_int16 * 3), ("qpRem", C.c_int16 * 3), ("sbtIdx", C.c_uint8), ("sbtPos", C.c_uint8), ("bitDepth", C.c_uint8), ("isIRAP", C.c_uint8)]
+
+
+class SbtResult(C.Structure):
+    _fields_ = [("sseCoded", C.c_uint64 * 3), ("sseZero", C.c_uint64 * 3), ("absSum", C.c_int32 * 3), ("pad", C.c_int32)]
+
+
 _STRUCTS = [DistJob, TzJob, MeResult, PicParams, IfJob, FracJob, FracResult, TrJob, QuantJob, FullJob, McJob, PelOpJob,
             TuJob, TuResult, AffineJob, MeCfg, MeJob, MeOut, PredJob, MaskedSadJob, GeoBlendJob, DmvrJob, LfnstJob,
             PisRow, PisPu, PisLevel, AffineMeJob, AffineMeOut, LfnstTuJob, PisLevelRun, PisBuffers, SmvdJob, PisPuIn, WtdJob,
             WpDistJob, WpPredJob]   # order of vtmhip_struct_size(which)
 _JCCR_STRUCTS = [IctJob, JccrJob, JccrResult]   # order of vtmhip_jccr_struct_size(which)
 _LMCS_STRUCTS = [LmcsJob, ScaleJob]             # order of vtmhip_lmcs_struct_size(which)
+_SBT_STRUCTS = [SbtEstJob, SbtEstResult, SbtJob, SbtResult]   # order of vtmhip_sbt_struct_size(which)
 
 # every symbol include/vtmhip.h declares (tests/test_abi.py checks the exports against the header text)
 _PROTOS = {
@@ -381,6 +403,11 @@ _PROTOS = {
     "vtmhip_scale_signal_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "vtmhip_lmcs_resi_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "vtmhip_lmcs_reco_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "vtmhip_sbt_struct_size": (C.c_int, [C.c_int]),
+    "vtmhip_sbt_est_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vtmhip_sbt_skip_by_rdcost": (C.c_int, [C.POINTER(C.c_uint64), C.c_double, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_double, C.c_int]),
+    "vtmhip_sbt_chain_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtmhip_sbt_make_tu_jobs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "vtmhip_filterHor": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                    C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vtmhip_filterVer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
@@ -505,6 +532,10 @@ def load():
         if lib.vtmhip_lmcs_struct_size(i) != C.sizeof(s):
             raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
                               % (s.__name__, C.sizeof(s), lib.vtmhip_lmcs_struct_size(i)))
+    for i, s in enumerate(_SBT_STRUCTS):
+        if lib.vtmhip_sbt_struct_size(i) != C.sizeof(s):
+            raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
+                              % (s.__name__, C.sizeof(s), lib.vtmhip_sbt_struct_size(i)))
     _lib = lib
     return lib
 
