@@ -1291,6 +1291,35 @@ int vtmhip_is_uniform_shape( int width, int height );
  * kernel; so does every launch when VTMHIP_TZ_BANDS=0 is set in the environment. */
 int vtmhip_tz_band_items( int width, int height, int subShift, int wavesPerJob );
 
+/* ---- raster pruning: 8x8 box sums of the reference planes ---------------------------------------------------------------------------------------------
+ * The raster scan of xTZSearch (split search: tz_raster_cols_kernel) skips grid points that a block-sum lower bound rules out: over the 8x8 sub-blocks of the block,
+ * sum |sum(org sub-block) - sum(ref sub-block)| <= SAD, and a point whose bound + MV rate is not below the best cost the search holds when the scan starts can never be
+ * accepted.  A scan without such a point is skipped; otherwise the bounding rectangle of the remaining points is scanned.  Results do not change.
+ * The bound reads a SUM BUFFER congruent with the reference planes: d_sumBase[off] is the sum of the 8x8 samples whose first is d_refBase[off].
+ *   vtmhip_tz_box_sums_dev: the sums of ONE luma plane (its sample (0,0) at d_refBase + planeOff, `margin` >= ctuSize + 16 border samples on every side, as the planes of
+ *     every *_dev call carry), on the context's stream.  Written: x in [-(margin - 9), width + margin - 17], y in [-(margin - 9), height + margin - 17] -- every position
+ *     clipMv leaves to a block origin (-(ctuSize + 7) .. size + 7 with ctuSize = margin - 16) and the block's further sub-blocks; read: samples up to size + margin - 10,
+ *     nothing outside the plane's border.  Samples are unsigned and at most 10 bits deep (64 * 1023 fits 16 bits).
+ *   vtmhip_tz_attach_sums: from now on the TZ searches of this context whose d_refBase is `d_refBase` use d_sumBase (d_sumBase NULL: detach).  One buffer at a time.
+ *     width / height / margin: what the sums were computed with (every plane alike).  A search uses them only when its vtmhip_pic_params name the same picture size and
+ *     margin >= ctuSize + 16, i.e. when the sums cover every position its scan can take; any other search runs the full scan.
+ *     CONTRACT: attached sums describe the CURRENT contents of every plane the searches read, computed for the picture size the searches pass in vtmhip_pic_params; the
+ *     caller recomputes them (stream-ordered before the search) whenever a plane changes.  With nothing attached nothing changes.  Jobs the bound does not apply to
+ *     (subShift != 0, signedSamples, bitDepth > 10, a width or height that is no multiple of 8, the in-kernel scans) run the full scan.
+ *     vtmhip_pis_run_picture computes and attaches the sums of the picture's reference planes itself and, on return, puts back whatever the caller had attached
+ *     (a picture the bound does not apply to -- bitDepth > 10, no level with subShift 0, levels of different geometry -- runs with the caller's attachment untouched).
+ *     Its sum buffer is a workspace of the context, about the size of the DPB span of the referenced planes, kept per main stream.  FIRST-CALL CONTRACT, as for the
+ *     other per-stream workspaces: the first picture of a geometry on a main stream (and any later picture that needs a larger span) allocates it -- a stream
+ *     synchronise, a hipFree of the smaller block (which waits for the device, the side stream's pass included) and a hipMalloc -- so run one picture eagerly on a
+ *     stream before timing it or capturing it into a graph (bench.py --graph does exactly that).  The block is written on the first side stream and read by the
+ *     raster launches on the main stream, ordered by events inside the call.
+ *   vtmhip_tz_prune_stats: stats[6] = raster scans listed for the column kernel, scans skipped, scans reduced to a proper sub-rectangle, grid points evaluated, grid
+ *     points of all listed scans, scans whose winner was below the best cost on entry (the search accepts it) -- of this context since the last reset (stats may be NULL; reset != 0 clears).  Synchronises the context's stream.
+ * VTMHIP_TZ_PRUNE=0 in the environment: the sums are ignored (and the picture loop computes none). */
+int vtmhip_tz_box_sums_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, uint16_t *d_sumBase, int64_t planeOff, int stride, int width, int height, int margin );
+int vtmhip_tz_attach_sums( vtmhip_ctx *ctx, const int16_t *d_refBase, const uint16_t *d_sumBase, int width, int height, int margin );
+int vtmhip_tz_prune_stats( vtmhip_ctx *ctx, uint64_t *stats, int reset );
+
 /* ---- sub-block transform (SBT) of inter CUs: the mode estimator and the SBT candidates of xEstimateInterResidualQT --------------------------------
  * (CodingUnit::checkAllowedSbt Unit.cpp:450-494; CU::getSbtMode ... numSbtModeRdo UnitTools.cpp:3516-3589; PartitionerImpl::getSbtTuTiling
  * UnitPartitioner.cpp:1091-1148; TrQuant::getTrTypes TrQuant.cpp:728-760; InterSearch::calcMinDistSbt / skipSbtByRDCost InterSearch.cpp:6195-6438.)

@@ -83,7 +83,8 @@ int vtmhip_create( int device, vtmhip_ctx **out )
   if( !ctx ) return VTMHIP_E_NOMEM;
   ctx->device = device;
   if( hipSetDevice( device ) != hipSuccess || hipStreamCreateWithFlags( &ctx->ownStream, hipStreamNonBlocking ) != hipSuccess ||
-      hipEventCreate( &ctx->evStart ) != hipSuccess || hipEventCreate( &ctx->evStop ) != hipSuccess )
+      hipEventCreate( &ctx->evStart ) != hipSuccess || hipEventCreate( &ctx->evStop ) != hipSuccess ||
+      hipMalloc( ( void ** ) &ctx->tzStats, 6 * sizeof( unsigned long long ) ) != hipSuccess || hipMemset( ctx->tzStats, 0, 6 * sizeof( unsigned long long ) ) != hipSuccess )
   {
     delete ctx;
     return VTMHIP_E_HIP;
@@ -107,6 +108,7 @@ int vtmhip_destroy( vtmhip_ctx *ctx )
   if( ctx->wtdFixed ) ( void ) hipFree( ctx->wtdFixed );
   if( ctx->wtdInv ) ( void ) hipFree( ctx->wtdInv );
   if( ctx->lmcsFwd ) ( void ) hipFree( ctx->lmcsFwd );
+  if( ctx->tzStats ) ( void ) hipFree( ctx->tzStats );
   if( ctx->pinned ) ( void ) hipHostFree( ctx->pinned );
   for( auto &t : ctx->timed ) { ( void ) hipEventDestroy( t.start ); ( void ) hipEventDestroy( t.stop ); }
   for( hipEvent_t e : ctx->forkEvents ) ( void ) hipEventDestroy( e );
@@ -200,6 +202,26 @@ int vtmhip_timer_stop_ms( vtmhip_ctx *ctx, float *ms )
   VTMHIP_HIP( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
   VTMHIP_HIP( ctx, hipEventSynchronize( ctx->evStop ) );
   VTMHIP_HIP( ctx, hipEventElapsedTime( ms, ctx->evStart, ctx->evStop ) );
+  return VTMHIP_OK;
+}
+
+int vtmhip_tz_attach_sums( vtmhip_ctx *ctx, const int16_t *d_refBase, const uint16_t *d_sumBase, int width, int height, int margin )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  VTMHIP_REQUIRE( ctx, !d_sumBase || ( d_refBase && width > 0 && height > 0 && margin >= 24 ), "sums without a reference base or plane geometry" );
+  ctx->tzSumsRef = d_sumBase ? d_refBase : nullptr;
+  ctx->tzSums = d_sumBase;
+  ctx->tzSumsW = d_sumBase ? width : 0; ctx->tzSumsH = d_sumBase ? height : 0; ctx->tzSumsMargin = d_sumBase ? margin : 0;
+  ctx->tzSumsReady = nullptr;
+  return VTMHIP_OK;
+}
+
+int vtmhip_tz_prune_stats( vtmhip_ctx *ctx, uint64_t *stats, int reset )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  if( stats ) VTMHIP_HIP( ctx, hipMemcpyAsync( stats, ctx->tzStats, 6 * sizeof( unsigned long long ), hipMemcpyDeviceToHost, ctx->stream ) );
+  if( reset ) VTMHIP_HIP( ctx, hipMemsetAsync( ctx->tzStats, 0, 6 * sizeof( unsigned long long ), ctx->stream ) );
+  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
   return VTMHIP_OK;
 }
 

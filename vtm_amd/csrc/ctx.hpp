@@ -49,6 +49,13 @@ struct vtmhip_ctx
   struct TimedLaunch { const char *kernel; hipEvent_t start, stop; };
   std::vector<TimedLaunch> timed;
   std::vector<hipEvent_t>  forkEvents;   // fork / join events of vtmhip_pis_run_picture (driver.hip): created on demand, reused by every picture, freed by vtmhip_destroy
+  // raster pruning (me.hip): the 8x8 box sums attached for one reference base (vtmhip_tz_attach_sums; the picture loop attaches its own per picture)
+  const int16_t  *tzSumsRef   = nullptr;   // the d_refBase the sums are congruent with
+  const uint16_t *tzSums      = nullptr;   // nullptr: nothing attached
+  int             tzSumsW = 0, tzSumsH = 0, tzSumsMargin = 0;   // what the attached sums were computed with: a search of another picture size, or of a CTU the margin does not cover, ignores them
+  hipEvent_t      tzSumsReady = nullptr;   // picture loop: recorded behind a box-sum pass that runs on a side stream; a raster launch on another stream waits for it
+  hipStream_t     tzSumsJoined = nullptr;  // the stream that is already ordered behind tzSumsReady
+  unsigned long long *tzStats = nullptr;   // device: scans listed, skipped, reduced, grid points evaluated, grid points total, scans accepted (vtmhip_tz_prune_stats)
 };
 
 // scope guard around a kernel launch: records start / stop events on ctx->stream when timing is on (bench.py's roofline: the dominant kernel's

@@ -2,6 +2,7 @@
 // calls per partition level and the fork / join between the uni-search chain and the levels' remaining stages, issued natively (no interpreter between the
 // ~130 launches of a picture).  Every step is a public entry point of this library; nothing here computes.
 #include "ctx.hpp"
+#include "mest_glue.hpp"
 
 #include <vector>
 #include <cstring>
@@ -139,6 +140,77 @@ int run_rest( vtmhip_ctx *ctx, const vtmhip_pis_level_run &L, const vtmhip_pis_b
   return st;
 }
 
+// Raster pruning (me.hip): the 8x8 box sums of every luma plane the levels reference, computed per picture (a plane may have been rewritten since the last one) into a
+// workspace of the context congruent with the DPB, and attached for the picture.  The pass is ordered behind whatever `main` holds on entry, as the picture's first search
+// kernel is; with a side stream it runs there, beside the first level's integer search, and the first raster launch joins it (ctx->tzSumsReady).
+struct SumsAttached      // on every way out of the picture loop: the caller's own attachment (or none) is back
+{
+  vtmhip_ctx     *c;
+  bool            on;
+  const int16_t  *ref;
+  const uint16_t *sums;
+  int             w, h, margin;
+  explicit SumsAttached( vtmhip_ctx *ctx ) : c( ctx ), on( false ), ref( ctx->tzSumsRef ), sums( ctx->tzSums ), w( ctx->tzSumsW ), h( ctx->tzSumsH ), margin( ctx->tzSumsMargin ) {}
+  ~SumsAttached()
+  {
+    if( on ) { c->tzSumsRef = ref; c->tzSums = sums; c->tzSumsW = w; c->tzSumsH = h; c->tzSumsMargin = margin; c->tzSumsReady = nullptr; }
+  }
+};
+
+int picture_sums( vtmhip_ctx *ctx, const vtmhip_pis_level_run *levels, int numLevels, const vtmhip_pis_buffers &buf, hipStream_t main, hipStream_t side, EventPool &pool,
+                  bool &attached )
+{
+  static const bool pruneOn = env_switch( "VTMHIP_TZ_PRUNE", true ) && env_switch( "VTMHIP_TZ_SPLIT", true );      // (only the split search's column kernel prunes)
+  if( !pruneOn || numLevels <= 0 ) return VTMHIP_OK;
+  const vtmhip_pic_params &pic = levels[0].pic;
+  const int                stride = levels[0].pis.refStride, m = pic.ctuSize + 16;      // the border every reference plane carries at least (vtmhip.h)
+  if( pic.bitDepth > 10 || pic.picW <= 0 || pic.picH <= 0 || pic.ctuSize <= 0 || stride < pic.picW + 2 * m ) return VTMHIP_OK;
+  bool                 wanted = false;      // a level whose scans the bound applies to: every row in the SAD, whole 8x8 sub-blocks
+  std::vector<int64_t> planes;
+  for( int i = 0; i < numLevels; i++ )
+  {
+    const vtmhip_pis_level_run &L = levels[i];
+    if( L.pic.picW != pic.picW || L.pic.picH != pic.picH || L.pic.ctuSize != pic.ctuSize || L.pic.bitDepth != pic.bitDepth || L.pis.refStride != stride ) return VTMHIP_OK;
+    if( L.pis.numPU > 0 && !( ( L.width | L.height ) & 7 ) && L.width <= pic.ctuSize && L.height <= pic.ctuSize && mg::sub_shift( L.cfgUni, L.width, L.height ) == 0 ) wanted = true;
+    for( int l = 0; l < 2; l++ )
+      for( int r = 0; r < L.pis.numRef[l] && r < VTMHIP_MAX_REF; r++ )
+      {
+        const int64_t off = L.pis.refPlaneOff[l][r];
+        bool          seen = false;
+        for( int64_t o : planes ) seen = seen || o == off;
+        if( !seen ) planes.push_back( off );
+      }
+  }
+  if( !wanted || planes.empty() ) return VTMHIP_OK;
+  int64_t lo = planes[0], hi = planes[0];
+  for( int64_t o : planes ) { lo = o < lo ? o : lo; hi = o > hi ? o : hi; }
+  lo -= ( int64_t ) m * stride + m;                          // first / one past the last sample of the planes with their borders
+  hi += ( int64_t ) ( pic.picH + m ) * stride;
+  void *ws = nullptr;
+  ctx->stream = main;
+  VTMHIP_TRY( vtmhip_internal_workspace( ctx, ( size_t ) ( hi - lo ) * sizeof( uint16_t ), &ws, 4 ) );      // a slot of its own (0 .. 3 belong to the calls the picture makes on this stream); grown by the first picture of this size, then reused
+  uint16_t *sumBase = ( uint16_t * ) ws - lo;
+  hipEvent_t ready = nullptr;
+  if( side )
+  {
+    hipEvent_t fork = pool.get();
+    ready = pool.get();
+    VTMHIP_REQUIRE( ctx, fork && ready, "hipEventCreate" );
+    VTMHIP_HIP( ctx, hipEventRecord( fork, main ) );
+    VTMHIP_HIP( ctx, hipStreamWaitEvent( side, fork, 0 ) );
+    ctx->stream = side;
+  }
+  int st = VTMHIP_OK;
+  for( size_t k = 0; k < planes.size() && !st; k++ ) st = vtmhip_tz_box_sums_dev( ctx, buf.dpb, sumBase, planes[k], stride, pic.picW, pic.picH, m );
+  ctx->stream = main;
+  if( st ) return st;
+  if( side ) VTMHIP_HIP( ctx, hipEventRecord( ready, side ) );
+  ctx->tzSumsRef = buf.dpb; ctx->tzSums = sumBase; ctx->tzSumsW = pic.picW; ctx->tzSumsH = pic.picH; ctx->tzSumsMargin = m;
+  ctx->tzSumsReady = ready; ctx->tzSumsJoined = side;
+  attached = true;
+  return VTMHIP_OK;
+}
+
 }   // namespace
 
 extern "C" int vtmhip_is_uniform_shape( int w, int h )
@@ -171,6 +243,9 @@ extern "C" int vtmhip_pis_run_picture( vtmhip_ctx *ctx, const vtmhip_pis_level_r
   hipStream_t main = ( hipStream_t ) mainStream;
   int         st = VTMHIP_OK;
   ctx->stream = main;
+  SumsAttached sums( ctx );
+  st = picture_sums( ctx, levels, numLevels, *buf, main, numSide > 0 ? ( hipStream_t ) sideStreams[0] : nullptr, pool, sums.on );
+  if( st ) return st;
   if( numSide == 0 )
   {
     for( int i = 0; i < numLevels && !st; i++ ) st = run_uni( ctx, levels[i], *buf );

@@ -986,9 +986,78 @@ __device__ __forceinline__ void raster_task( const MeJob &j, const Range &r, int
   }
 }
 
+// ---- raster pruning: a block-sum lower bound rules grid points out before their SAD is formed ------------------------------------------------
+// Over the 8x8 sub-blocks of the block, sum |sum(org sub-block) - sum(ref sub-block)| <= SAD (the sum-norm inequality: successive elimination with one level of
+// sub-blocks).  xTZSearchHelp accepts only a cost strictly below the best cost the search holds when the scan starts (TzSaved::bestSad), so a grid point whose
+// bound + MV rate is not below it can never be accepted and its SAD need not be formed.  The sums of the reference sub-blocks come from a shadow plane of 8x8 box
+// sums (box_sum8_kernel, vtmhip_tz_box_sums_dev) congruent with the reference planes: sums[refOff + y * stride + x] is the sum of the 8x8 samples from
+// ref[refOff + y * stride + x] on.  A lane takes one grid point: 256 differences instead of 16 384, given up as soon as no point of the wave is still below the best.
+// tzStats: scans listed, skipped, reduced, grid points evaluated, grid points total, scans whose winner the search accepts (vtmhip_tz_prune_stats).
+template<int NSX>
+__device__ __forceinline__ bool raster_bound_alive( const uint16_t *sp, long stride, int nsxRt, int nsy, const unsigned *sOrg, unsigned long long mvc, unsigned long long best,
+                                                    bool valid )
+{
+  const int nsx = NSX ? NSX : nsxRt;
+  unsigned  acc = 0;
+  bool      alive = valid && mvc < best;
+  for( int sy = 0; sy < nsy; sy++ )
+  {
+    if( !__any( alive ) ) break;      // wave-uniform: the bound only grows
+    const uint16_t *row = sp + ( long ) ( 8 * sy ) * stride;
+    if( NSX )
+    {
+#pragma unroll
+      for( int sx = 0; sx < NSX; sx++ )
+      {
+        const unsigned a = sOrg[sy * NSX + sx], b = row[8 * sx];
+        acc += a > b ? a - b : b - a;
+      }
+    }
+    else
+      for( int sx = 0; sx < nsx; sx++ )
+      {
+        const unsigned a = sOrg[sy * nsx + sx], b = row[8 * sx];
+        acc += a > b ? a - b : b - a;
+      }
+    alive = valid && mvc + acc < best;
+  }
+  return alive;
+}
+
+// 8x8 box sums of one plane: S(x, y) = the sum of the samples (x .. x + 7, y .. y + 7), for x0 <= x <= x1, y0 <= y <= y1, stored congruent with the plane.  A thread
+// walks down one column: a row's horizontal sum is eight loads of its own (neighbouring lanes share the cache lines; no exchange, no barrier, so the loads of the
+// rows ahead are in flight while a row is summed), the last eight horizontal sums stay in registers.
+constexpr int BOX_ROWS = 32;      // output rows of one workgroup (it reads 7 more)
+__global__ __launch_bounds__( 256 ) void box_sum8_kernel( const int16_t *__restrict__ plane, uint16_t *__restrict__ sums, long stride, int x0, int x1, int y0, int y1 )
+{
+  const int x = x0 + ( int ) blockIdx.x * 256 + ( int ) threadIdx.x;
+  if( x > x1 ) return;
+  const int yb = y0 + ( int ) blockIdx.y * BOX_ROWS, yLast = min( yb + BOX_ROWS - 1, y1 );
+  unsigned  ring[8], v = 0;
+#pragma unroll
+  for( int k = 0; k < 8; k++ ) ring[k] = 0;
+  for( int y = yb; y <= yLast + 7; y += 8 )
+  {
+#pragma unroll
+    for( int k = 0; k < 8; k++ )
+    {
+      const int yy = y + k;
+      if( yy > yLast + 7 ) break;
+      const int16_t *p = plane + ( long ) yy * stride + x;
+      unsigned       h = 0;
+#pragma unroll
+      for( int i = 0; i < 8; i++ ) h += ( unsigned short ) p[i];
+      v += h - ring[k];      // the horizontal sum of row yy enters, that of row yy - 8 leaves
+      ring[k] = h;
+      if( yy - 7 >= yb ) sums[( long ) ( yy - 7 ) * stride + x] = ( uint16_t ) v;
+    }
+  }
+}
+
 __global__ __launch_bounds__( 256 ) void tz_raster_cols_kernel( vtmhip_pic_params pic, const int16_t *__restrict__ orgBase, const int16_t *__restrict__ refBase,
                                                                const vtmhip_tz_job *__restrict__ jobs, TzSaved *__restrict__ saved, const int *__restrict__ list,
-                                                               unsigned *__restrict__ gTot, int parts, int totCap )
+                                                               unsigned *__restrict__ gTot, int parts, int totCap, const uint16_t *__restrict__ sums,
+                                                               unsigned long long *__restrict__ tzStats )
 {
   // parts > 1 (few searches in the batch: one band of a picture sharded over several GPUs, the 128x128 level): `parts` workgroups share one scan -- each takes
   // every parts-th task, adds its partial totals into the scan's global totals (gTot[e][RASTER_TOT_CAP + 1], zeroed by the host; the last entry counts the
@@ -997,6 +1066,7 @@ __global__ __launch_bounds__( 256 ) void tz_raster_cols_kernel( vtmhip_pic_param
   __shared__ unsigned long long sRedCost[4];
   __shared__ unsigned           sRedIdx[4];
   __shared__ int                sLast;
+  __shared__ int                sBox[4];
   const int lane = threadIdx.x & 63, wv = uni( ( int ) ( threadIdx.x >> 6 ) );
   const int count = list[0];
   const int part = parts > 1 ? ( int ) blockIdx.x % parts : 0, eStride = parts > 1 ? ( int ) gridDim.x / parts : ( int ) gridDim.x;
@@ -1011,8 +1081,75 @@ __global__ __launch_bounds__( 256 ) void tz_raster_cols_kernel( vtmhip_pic_param
     j.predHor = jp->predHor; j.predVer = jp->predVer; j.costScale = 2; j.lambda = jp->motionLambda;
     j.bias = jp->signedSamples ? 0x80008000u : 0u;
     j.narrow = false; j.tiny = false; j.totCap = totCap;
-    const Range r = sv.sr;
-    const int   nx = ( r.right - r.left ) / 5 + 1, ny = ( r.bottom - r.top ) / 5 + 1, total = nx * ny;
+    Range r = sv.sr;
+    int   nx = ( r.right - r.left ) / 5 + 1, ny = ( r.bottom - r.top ) / 5 + 1, total = nx * ny;
+    const int fullNx = nx;
+    int       cx0 = 0, cy0 = 0;
+    // Eligible for the bound (block-uniform): sums attached, every row in the SAD, unsigned samples whose 8x8 sums fit 16 bits, whole 8x8 sub-blocks, and a scan inside the
+    // positions the box sums cover (clipMv's range of a block origin, mv_rules.hpp).  Every workgroup of a split scan derives the same rectangle.
+    const int nsx = j.w >> 3, nsy = j.h >> 3;
+    if( sums && j.ss == 0 && !j.bias && pic.bitDepth <= 10 && !( ( j.w | j.h ) & 7 ) && nsx * nsy <= 256 && j.w <= pic.ctuSize && j.h <= pic.ctuSize &&
+        jp->puX + r.left >= -( pic.ctuSize + 7 ) && jp->puX + r.right <= pic.picW + 7 && jp->puY + r.top >= -( pic.ctuSize + 7 ) && jp->puY + r.bottom <= pic.picH + 7 )
+    {
+      if( ( int ) threadIdx.x < nsx * nsy )      // the block's sub-block sums -> sTot[0 .. nsx * nsy) (the totals are not in use yet)
+      {
+        const int      sy = ( int ) threadIdx.x / nsx, sx = ( int ) threadIdx.x - sy * nsx;
+        const int16_t *po = j.org + ( long ) ( 8 * sy ) * j.orgStride + 8 * sx;
+        unsigned       s = 0;
+#pragma unroll
+        for( int rr = 0; rr < 8; rr++ )
+        {
+          const Pel8 a = *reinterpret_cast<const Pel8 *>( po + ( long ) rr * j.orgStride );
+          s = sad2( a.v[0], 0u, s ); s = sad2( a.v[1], 0u, s ); s = sad2( a.v[2], 0u, s ); s = sad2( a.v[3], 0u, s );
+        }
+        sTot[threadIdx.x] = s;
+      }
+      if( threadIdx.x < 4 ) sBox[threadIdx.x] = ( threadIdx.x & 1 ) ? -1 : 0x7fffffff;      // min / max column, min / max row of the points still below the best
+      __syncthreads();
+      const unsigned long long best = sv.bestSad;
+      const uint16_t          *sp0 = sums + jp->refOff;
+      // First a sample: one grid point per thread, spread over the whole grid.  The rectangle only grows, so when the sample's survivors already span three quarters of
+      // the grid the scan has little left to save: the bound is dropped and the whole grid scanned (what the bound costs where it rules nothing out stays one pass).
+      // Otherwise every point, 64 neighbouring points per wave: they are ruled out together, after a row or two of sub-blocks.
+      const int passes = ( total + 255 ) >> 8;
+      int       bx0 = 0, bx1 = -1, by0 = 0, by1 = -1;
+      for( int ps = passes > 1 ? -1 : 0; ps < passes; ps++ )      // block-uniform
+      {
+        const int  c = ps < 0 ? ( int ) ( ( ( long ) threadIdx.x * total ) >> 8 ) : ps * 256 + ( int ) threadIdx.x, cc = min( c, total - 1 );
+        const int  cy = cc / nx, cx = cc - cy * nx;
+        const int  x = r.left + 5 * cx, y = r.top + 5 * cy;
+        const unsigned long long mvc = mv_cost( j, x, y );
+        const uint16_t          *sp = sp0 + ( long ) y * j.refStride + x;
+        const bool alive = nsx == 16 ? raster_bound_alive<16>( sp, j.refStride, nsx, nsy, sTot, mvc, best, c < total )
+                                     : raster_bound_alive<0>( sp, j.refStride, nsx, nsy, sTot, mvc, best, c < total );
+        if( alive ) { atomicMin( &sBox[0], cx ); atomicMax( &sBox[1], cx ); atomicMin( &sBox[2], cy ); atomicMax( &sBox[3], cy ); }
+        if( ps >= 0 && ps < passes - 1 ) continue;
+        __syncthreads();
+        bx0 = sBox[0]; bx1 = sBox[1]; by0 = sBox[2]; by1 = sBox[3];
+        __syncthreads();      // (every thread has read the sample's rectangle before the passes widen it; after the last pass: sBox and the sub-block sums are free again)
+        if( ps < 0 && bx1 >= 0 && 4 * ( bx1 - bx0 + 1 ) * ( by1 - by0 + 1 ) >= 3 * total ) { bx0 = 0; bx1 = nx - 1; by0 = 0; by1 = ny - 1; break; }
+      }
+      const int kept = bx1 < 0 ? 0 : ( bx1 - bx0 + 1 ) * ( by1 - by0 + 1 );
+      if( tzStats && threadIdx.x == 0 && part == 0 )
+      {
+        atomicAdd( &tzStats[0], 1ull );
+        if( kept == 0 ) atomicAdd( &tzStats[1], 1ull );
+        else if( kept < total ) atomicAdd( &tzStats[2], 1ull );
+        if( kept ) atomicAdd( &tzStats[3], ( unsigned long long ) kept );
+        atomicAdd( &tzStats[4], ( unsigned long long ) total );
+      }
+      if( kept == 0 ) continue;      // block-uniform, in every workgroup of the scan: nothing on the grid can be accepted, rasterCost keeps the value no cost is below
+      // the scan of the survivors' bounding rectangle: row-major order inside it preserves raster order, so its (cost, index) minimum is the grid's whenever that is accepted
+      cx0 = bx0; cy0 = by0;
+      r.right = r.left + 5 * bx1; r.bottom = r.top + 5 * by1; r.left += 5 * bx0; r.top += 5 * by0;
+      nx = bx1 - bx0 + 1; ny = by1 - by0 + 1; total = kept;
+    }
+    else if( tzStats && threadIdx.x == 0 && part == 0 )
+    {
+      atomicAdd( &tzStats[0], 1ull );
+      atomicAdd( &tzStats[3], ( unsigned long long ) total );
+      atomicAdd( &tzStats[4], ( unsigned long long ) total );
+    }
     for( int i = threadIdx.x; i < total; i += 256 ) sTot[i] = 0;
     __syncthreads();
     const int segs = j.w >> 3, par = 1 << j.ss, rowStep = 5 << j.ss;
@@ -1072,7 +1209,9 @@ __global__ __launch_bounds__( 256 ) void tz_raster_cols_kernel( vtmhip_pic_param
     {
       for( int w = 1; w < 4; w++ )
         if( sRedCost[w] < bc || ( sRedCost[w] == bc && sRedIdx[w] < bi ) ) { bc = sRedCost[w]; bi = sRedIdx[w]; }
-      sv.rasterCost = bc; sv.rasterIdx = bi;
+      const unsigned ry = bi / ( unsigned ) nx, rx = bi - ry * ( unsigned ) nx;      // a reduced scan: the winner's index on the full grid
+      sv.rasterCost = bc; sv.rasterIdx = ( ry + ( unsigned ) cy0 ) * ( unsigned ) fullNx + rx + ( unsigned ) cx0;
+      if( tzStats && bc < sv.bestSad ) atomicAdd( &tzStats[5], 1ull );
     }
     __syncthreads();
   }
@@ -2142,6 +2281,23 @@ extern "C" int vtmhip_tz_band_items( int width, int height, int subShift, int wa
   return k == 1 || k == 2 || k == 4 ? k : 0;
 }
 
+// The 8x8 box sums of one luma plane for the raster pruning, on the context's stream.  Covered: every position a block origin may take (clipMv: -(ctuSize + 7) .. size + 7
+// with ctuSize = margin - 16) plus the block's further sub-blocks, i.e. x in [-(margin - 9), width + margin - 17] and y likewise; the last sum reads sample
+// size + margin - 10, inside the plane's border.
+extern "C" int vtmhip_tz_box_sums_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, uint16_t *d_sumBase, int64_t planeOff, int stride, int width, int height, int margin )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  VTMHIP_REQUIRE( ctx, d_refBase && d_sumBase, "null pointer" );
+  VTMHIP_REQUIRE( ctx, width > 0 && height > 0 && margin >= 24 && stride >= width + 2 * margin, "plane geometry" );
+  const int x0 = -( margin - 9 ), x1 = width + margin - 17, y0 = -( margin - 9 ), y1 = height + margin - 17;
+  { VTMHIP_TIME_KERNEL( ctx, "box_sum8_kernel" );
+    hipLaunchKernelGGL( box_sum8_kernel, dim3( ( x1 - x0 + 256 ) / 256, ( y1 - y0 + BOX_ROWS ) / BOX_ROWS ), dim3( 256 ), 0, ctx->stream, d_refBase + planeOff, d_sumBase + planeOff,
+                        ( long ) stride, x0, x1, y0, y1 );
+  }
+  VTMHIP_LAUNCHED( ctx );
+  return VTMHIP_OK;
+}
+
 extern "C" int vtmhip_tz_search_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase,
                                            const vtmhip_tz_job *d_jobs, int n, vtmhip_me_result *d_results )
 {
@@ -2267,8 +2423,18 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
     { VTMHIP_TIME_KERNEL( ctx, "tz_raster_cols_kernel" );
       const size_t totLds = ( size_t ) ( totCap + 1 ) * sizeof( unsigned );
       if( totLds > 32 * 1024 ) VTMHIP_HIP( ctx, hipFuncSetAttribute( reinterpret_cast<const void *>( tz_raster_cols_kernel ), hipFuncAttributeMaxDynamicSharedMemorySize, ( int ) totLds ) );
+      // raster pruning (VTMHIP_TZ_PRUNE=0: off): the box sums attached for this reference base (vtmhip_tz_attach_sums); a pass still running on another stream is joined here
+      static const bool pruneOn = env_switch( "VTMHIP_TZ_PRUNE", true );
+      // (only sums computed for this picture size with a margin that covers clipMv's range of this CTU size: the kernel's eligibility test relies on that coverage)
+      const uint16_t   *d_sums = pruneOn && ctx->tzSums && ctx->tzSumsRef == d_refBase && ctx->tzSumsW == pic->picW && ctx->tzSumsH == pic->picH &&
+                                         ctx->tzSumsMargin >= pic->ctuSize + 16 ? ctx->tzSums : nullptr;
+      if( d_sums && ctx->tzSumsReady && ctx->tzSumsJoined != ctx->stream )      // (once per stream: later launches of the stream are ordered behind this one)
+      {
+        VTMHIP_HIP( ctx, hipStreamWaitEvent( ctx->stream, ctx->tzSumsReady, 0 ) );
+        ctx->tzSumsJoined = ctx->stream;
+      }
       hipLaunchKernelGGL( tz_raster_cols_kernel, dim3( rasterParts > 1 ? n * rasterParts : ( n < 3072 ? n : 3072 ) ), dim3( 256 ), totLds, ctx->stream, *pic, d_orgBase,
-                          d_refBase, d_jobs, d_saved, d_list, d_tot, rasterParts, totCap );
+                          d_refBase, d_jobs, d_saved, d_list, d_tot, rasterParts, totCap, d_sums, ctx->tzStats );
     }
     { VTMHIP_TIME_KERNEL( ctx, "tz_search_kernel" );
       VTMHIP_TZ_SWITCH( 2 )

@@ -320,6 +320,21 @@ class Context:
         """segments per thread of the row-band integer search kernel for a fused uniform launch of this shape; 0: the by-candidate kernel"""
         return int(self.L.vtmhip_tz_band_items(w, h, sub_shift, waves_per_job))
 
+    def tz_box_sums(self, d_ref, d_sums, plane_off, stride, width, height, margin):
+        """8x8 box sums of one luma plane (sample (0,0) at d_ref + plane_off) into the congruent uint16 buffer d_sums, for the raster pruning (vtmhip_tz_box_sums_dev)"""
+        self._check(self.L.vtmhip_tz_box_sums_dev(self.h, d_ref, d_sums, plane_off, stride, width, height, margin))
+
+    def tz_attach_sums(self, d_ref, d_sums, width=0, height=0, margin=0):
+        """the TZ searches on d_ref use the box sums d_sums (computed with this width / height / margin) from now on; d_sums None: detach.  The caller keeps the sums
+        current (vtmhip_tz_attach_sums)"""
+        self._check(self.L.vtmhip_tz_attach_sums(self.h, d_ref if d_sums else None, d_sums, width, height, margin))
+
+    def tz_prune_stats(self, reset=False):
+        """raster pruning since the last reset: dict of scans listed / skipped / reduced / accepted and grid points evaluated / total (synchronises the stream)"""
+        st = (C.c_uint64 * 6)()
+        self._check(self.L.vtmhip_tz_prune_stats(self.h, st, int(reset)))
+        return dict(zip(("listed", "skipped", "reduced", "points_evaluated", "points_total", "accepted"), (int(v) for v in st)))
+
     def affine_motion_estimation_batch(self, pic, d_org, d_ref, d_other, d_jobs, n, max_w, max_h, d_results, bcw=False):
         """InterSearch::xAffineMotionEstimation per AffineMeJob (one workgroup per job); bcw: the batch may hold bi jobs under a CU-level BCW weight of -2 (32-bit variant beside)"""
         f = self.L.vtmhip_xAffineMotionEstimation_bcw_batch_dev if bcw else self.L.vtmhip_xAffineMotionEstimation_batch_dev
