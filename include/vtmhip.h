@@ -1413,6 +1413,75 @@ int vtmhip_sbt_make_tu_jobs( const vtmhip_sbt_job *jobs, int n, vtmhip_tu_job *o
 
 int vtmhip_sbt_struct_size( int which );   /* sizeof() of 0 vtmhip_sbt_est_job, 1 vtmhip_sbt_est_result, 2 vtmhip_sbt_job, 3 vtmhip_sbt_result; -1 otherwise */
 
+/* ---- intra luma prediction: IntraPrediction::predIntraAng (CommonLib/IntraPrediction.cpp:217-266) for a luma block without ISP, MIP or BDPCM, and the first-round
+ * mode pre-selection of IntraSearch::estIntraPredLumaQT (EncoderLib/IntraSearch.cpp:549-700) fused on top of it.  The rules have one definition for host and
+ * device, vtm_amd/csrc/intra_rules.hpp:
+ *   parameters        initPredIntraParams :356-444 with getModifiedWideAngle :184-204 and the MDIS thresholds m_aucIntraFilter :58-68
+ *   filtered lines    xFilterReferenceSamples :1166-1200, computed on the device from the unfiltered ones
+ *   planar, DC        xPredIntraPlanar :294-348, xGetPredValDc :153-182, their PDPC :244-265
+ *   angular           xPredIntraAng :459-643: pure horizontal / vertical with the clipped PDPC, the extension of the main reference through invAngle for negative
+ *                     angles, the replication of its last sample for positive ones, the cubic (H.266 table 28) or smoothing taps on fractional slopes, the PDPC column
+ * MIP, ISP, BDPCM, chroma, IntraSmoothingDisabled, the availability analysis that fills the reference samples (xFillReferenceSamples), the mode bits and the
+ * candidate lists stay the caller's. */
+typedef struct
+{
+  int32_t predMode;            /* the mode after the wide-angle shift: -14 .. 80 (what the angle is taken from) */
+  int32_t isModeVer;
+  int32_t intraPredAngle;
+  int32_t invAngle;
+  int32_t angularScale;        /* set for positive angles, 0 otherwise (the reference leaves it untouched there) */
+  int32_t applyPDPC;
+  int32_t refFilterFlag;       /* predict from the [1 2 1]-filtered lines */
+  int32_t interpolationFlag;   /* fractional slopes take the smoothing taps instead of the cubic ones */
+} vtmhip_intra_params;
+
+/* m_ipaParam of a width x height luma block (sides 4, 8, 16, 32, 64), mode 0 .. 66, multiRefIdx 0 .. 2 (not 0 with planar): host arithmetic, no context.
+ * Anything else returns VTMHIP_E_INVALID. */
+int vtmhip_intra_pred_params( int width, int height, int mode, int multiRefIdx, vtmhip_intra_params *out );
+
+typedef struct
+{
+  int64_t refOff;      /* top line: d_refBase[refOff .. refOff + 2W + m], index 0 = the corner sample of line m;
+                          the left line follows directly: 2H + 1 + m samples, index 0 = the same corner
+                          (the reference's unfiltered buffer with predStride = 2W + 1 + m) */
+  int64_t orgOff;      /* original block inside d_orgBase (pre-selection only) */
+  int32_t orgStride;
+  int16_t width, height;   /* 4, 8, 16, 32, 64 each; every combination */
+  uint8_t bitDepth;        /* 8 .. 12; clip range [0, (1 << bitDepth) - 1] */
+  uint8_t multiRefIdx;     /* 0, 1, 2 (MULTI_REF_LINE_IDX) */
+  uint8_t reserved[2];     /* 0 */
+} vtmhip_intra_block;
+
+typedef struct
+{
+  int64_t predOff;     /* vtmhip_intra_pred_batch_dev only: the W x H prediction (stride W) inside d_predBase */
+  int32_t block;       /* index into d_blocks */
+  uint8_t mode;        /* 0 planar, 1 DC, 2 .. 66 */
+  uint8_t reserved[3]; /* 0 */
+} vtmhip_intra_job;
+
+/* predIntraAng, PDPC included, for n (block, mode) jobs: job k writes width x height samples with stride width at d_predBase + predOff.  Only the job's own lines
+ * are read: 2W + 1 + m and 2H + 1 + m samples from refOff on; where the reference replicates the last sample of the main line, the device repeats the index.
+ * Jobs of one block that follow each other in d_jobs share one load of its lines (and of its original block below); any order is allowed.
+ * NULL pointers, n < 0, numBlocks < 0 and numBlocks == 0 with n > 0 return VTMHIP_E_INVALID; n == 0 is VTMHIP_OK.  The tables stay on the device: a job whose
+ * block index is outside [0, numBlocks), whose mode is above 66 or planar with multiRefIdx != 0, or whose block has a side outside the list, a bitDepth outside
+ * 8 .. 12 or a multiRefIdx above 2 is skipped -- nothing is read through it and its output is not written (as vtmhip_sbt_est_batch_dev skips its invalid jobs).
+ * The largest well-formed block of d_blocks decides how many lanes a job gets (vtmhip_intra_lanes_per_job); a small kernel finds it, so there is no read-back. */
+int vtmhip_intra_pred_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const vtmhip_intra_block *d_blocks, int numBlocks, const vtmhip_intra_job *d_jobs, int n,
+                                 int16_t *d_predBase );
+
+/* The same prediction formed in LDS and consumed there: d_dist[2 k] = the SAD of job k's prediction against its block's original, d_dist[2 k + 1] = the SATD under
+ * the xGetHADs tile rules (the DistParam::distFunc slots of IntraSearch.cpp:573-592).  No sample of a prediction goes to global memory; predOff is ignored.
+ * min( 2 * SAD, SATD ), the mode bits and the candidate lists stay the caller's.  Checks and skipped jobs as above (both d_dist entries of a skipped job are left). */
+int vtmhip_intra_presel_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_orgBase, const vtmhip_intra_block *d_blocks, int numBlocks,
+                                   const vtmhip_intra_job *d_jobs, int n, uint64_t *d_dist );
+
+/* lanes a job gets when the largest block of the table has maxArea = width * height samples: 16 (up to 64 samples: sixteen jobs per workgroup at once), 64 (up to
+ * 1024: a wave per job) or 256 (the workgroup per job); 0 for an area outside 16 .. 4096 */
+int vtmhip_intra_lanes_per_job( int maxArea );
+
+int vtmhip_intra_struct_size( int which );   /* sizeof() of 0 vtmhip_intra_params, 1 vtmhip_intra_block, 2 vtmhip_intra_job; -1 otherwise */
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,10 +1,13 @@
 // dist_block.hpp -- the distortion of ONE (original block, candidate block) pair by one wave: SAD with row sub-sampling (RdCost.cpp:493-1003), SSE (:1783-2133) or SATD by
-// the tile rules of xGetHADs (:2837-2931).  Shared by dist_batch_kernel (dist.hip) and the fused AMVR refinement of xMotionEstimation (mest.hip).  The result is in every lane.
+// the tile rules of xGetHADs (:2837-2931).  Shared by dist_batch_kernel (dist.hip), the fused AMVR refinement of xMotionEstimation (mest.hip) and the fused intra
+// pre-selection (intra.hip).  The result is in every lane.  lanes_block_dist<L> is the same walk by a group of L <= 64 consecutive lanes of a wave (L a power of two,
+// `lane` the index inside the group): small blocks share a wave, one block per group.
 #pragma once
 #include "ctx.hpp"
 #include "had.hpp"
 
-__device__ __forceinline__ unsigned long long wave_block_dist( int kind, const int16_t *org, int os, const int16_t *cur, int cs, int w, int h, int subShift, int lane )
+template<int L>
+__device__ __forceinline__ unsigned long long lanes_block_dist( int kind, const int16_t *org, int os, const int16_t *cur, int cs, int w, int h, int subShift, int lane )
 {
   unsigned long long acc = 0;
 
@@ -15,7 +18,7 @@ __device__ __forceinline__ unsigned long long wave_block_dist( int kind, const i
     unsigned  s = 0;
     if( ( w & 3 ) == 0 )
     {
-      for( int it = lane; it < rows * segs; it += 64 )
+      for( int it = lane; it < rows * segs; it += L )
       {
         const int      r = it / segs, x = ( it - r * segs ) << 2;
         const int16_t *o = org + ( long ) ( r << ss ) * os + x;
@@ -26,7 +29,7 @@ __device__ __forceinline__ unsigned long long wave_block_dist( int kind, const i
     }
     else
     {
-      for( int it = lane; it < rows * w; it += 64 )
+      for( int it = lane; it < rows * w; it += L )
       {
         const int r = it / w, x = it - r * w;
         s += ( unsigned ) abs( ( int ) org[( long ) ( r << ss ) * os + x] - ( int ) cur[( long ) ( r << ss ) * cs + x] );
@@ -39,7 +42,7 @@ __device__ __forceinline__ unsigned long long wave_block_dist( int kind, const i
     const int segs = w >> 2;
     if( ( w & 3 ) == 0 )
     {
-      for( int it = lane; it < h * segs; it += 64 )
+      for( int it = lane; it < h * segs; it += L )
       {
         const int      r = it / segs, x = ( it - r * segs ) << 2;
         const int16_t *o = org + ( long ) r * os + x;
@@ -54,7 +57,7 @@ __device__ __forceinline__ unsigned long long wave_block_dist( int kind, const i
     }
     else
     {
-      for( int it = lane; it < h * w; it += 64 )
+      for( int it = lane; it < h * w; it += L )
       {
         const int r = it / w, x = it - r * w;
         const int d = ( int ) org[( long ) r * os + x] - ( int ) cur[( long ) r * cs + x];
@@ -73,7 +76,7 @@ __device__ __forceinline__ unsigned long long wave_block_dist( int kind, const i
     else if( ( h & 3 ) == 0 && ( w & 3 ) == 0 ) { tw = 4; th = 4; }
     else { tw = 2; th = 2; }
     const int tx = w / tw, ty = h / th;
-    for( int it = lane; it < tx * ty; it += 64 )
+    for( int it = lane; it < tx * ty; it += L )
     {
       const int      y = ( it / tx ) * th, x = ( it % tx ) * tw;
       const int16_t *o = org + ( long ) y * os + x;
@@ -89,5 +92,12 @@ __device__ __forceinline__ unsigned long long wave_block_dist( int kind, const i
       acc += v;
     }
   }
-  return wave_reduce_add_u64( acc );
+#pragma unroll
+  for( int o = L >> 1; o > 0; o >>= 1 ) acc += __shfl_xor( acc, o, 64 );
+  return acc;
+}
+
+__device__ __forceinline__ unsigned long long wave_block_dist( int kind, const int16_t *org, int os, const int16_t *cur, int cs, int w, int h, int subShift, int lane )
+{
+  return lanes_block_dist<64>( kind, org, os, cur, cs, w, h, subShift, lane );
 }

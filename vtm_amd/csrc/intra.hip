@@ -1,0 +1,238 @@
+// intra.hip -- intra luma prediction on the device; the rules are intra_rules.hpp's.
+//   vtmhip_intra_pred_params       IntraPrediction::initPredIntraParams, host arithmetic                      (CommonLib/IntraPrediction.cpp:356-444)
+//   vtmhip_intra_pred_batch_dev    IntraPrediction::predIntraAng for a batch of (block, mode) jobs            (:217-266)
+//   vtmhip_intra_presel_batch_dev  the same prediction kept in LDS and reduced to its SAD and SATD against the original block: the first-round pre-selection
+//                                  of IntraSearch::estIntraPredLumaQT                                         (EncoderLib/IntraSearch.cpp:549-700)
+//
+// Every sample of every mode is a closed form over the two reference lines (intra_rules.hpp), so a job is W x H independent samples.
+//
+// intra_shape_kernel: one workgroup walks the block table and leaves the lanes a job gets (vtmhip_intra_lanes_per_job of the largest well-formed block) in the
+// stream's workspace -- the tables stay on the device and the host never waits for them.
+//
+// intra_kernel<FUSED>: 256 threads.  A job gets L lanes: 16 (blocks up to 64 samples: 16 jobs run side by side, 4 in a wave), 64 (up to 1024: a wave per job) or
+// 256 (the workgroup).  A workgroup takes CHUNK consecutive jobs (16 / 8 / 4) and cuts them into runs of one block index.  Per run it loads the block's two lines
+// once, forms the [1 2 1]-filtered lines and the DC value in LDS and -- fused -- stages the original block; the run's jobs then go through the lane groups.  The
+// grid is sized for the smallest CHUNK; workgroups past the table's end leave at once.
+// Fused: a group writes its prediction to its slot of sPred and takes SAD and SATD from there through lanes_block_dist (dist_block.hpp: the xGetHADs tile rule);
+// with 256 lanes per job wave 0 takes the SAD and wave 1 the SATD (64 x 64 is 64 tiles: one per lane).
+// LDS: 4 lines x 136 samples + the DC value, fused + 2 x 4096 samples (original, predictions): 1.1 KB / 17.1 KB per workgroup.
+#include "ctx.hpp"
+#include "chroma_taps.hpp"
+#include "dist_block.hpp"
+#include "intra_rules.hpp"
+
+namespace
+{
+
+__constant__ int16_t c_intraCubic[32][4] = { VTMHIP_CHROMA_FILTER_TAPS };   // InterpolationFilter::getChromaFilterTable (IntraPrediction.cpp:576)
+
+constexpr int INTRA_LINE = 136;    // 2 * 64 + 1 + 2 samples of a line, rounded up
+constexpr int INTRA_MAX_AREA = 4096;
+
+__host__ __device__ inline int intra_lanes( int maxArea ) { return maxArea < 16 || maxArea > INTRA_MAX_AREA ? 0 : maxArea <= 64 ? 16 : maxArea <= 1024 ? 64 : 256; }
+__host__ __device__ inline int intra_chunk( int lanes ) { return lanes == 16 ? 16 : lanes == 64 ? 8 : 4; }
+constexpr int INTRA_MIN_CHUNK = 4;
+
+__device__ __forceinline__ bool intra_block_ok( const vtmhip_intra_block &b ) { return intraBlockOk( b.width, b.height, b.bitDepth, b.multiRefIdx ); }
+
+__global__ __launch_bounds__( 256 ) void intra_shape_kernel( const vtmhip_intra_block *__restrict__ blocks, int numBlocks, int *__restrict__ lanes )
+{
+  __shared__ int sMax;
+  if( threadIdx.x == 0 ) sMax = 16;
+  __syncthreads();
+  int m = 0;
+  for( int i = threadIdx.x; i < numBlocks; i += 256 )
+  {
+    const vtmhip_intra_block b = blocks[i];
+    if( intra_block_ok( b ) ) m = max( m, b.width * b.height );
+  }
+  if( m ) atomicMax( &sMax, m );
+  __syncthreads();
+  if( threadIdx.x == 0 ) *lanes = intra_lanes( sMax );
+}
+
+struct IntraLds
+{
+  int16_t *line;   // [4][INTRA_LINE]: top, left, filtered top, filtered left
+  int     *dc;
+  int16_t *org, *pred;   // fused only
+};
+
+template<int L, bool FUSED>
+__device__ __forceinline__ void intra_chunk_body( const IntraLds &s, const int16_t *__restrict__ refBase, const int16_t *__restrict__ orgBase,
+                                                  const vtmhip_intra_block *__restrict__ blocks, int numBlocks, const vtmhip_intra_job *__restrict__ jobs, int n,
+                                                  int16_t *__restrict__ predBase, unsigned long long *__restrict__ dist )
+{
+  constexpr int G = 256 / L, CHUNK = L == 16 ? 16 : L == 64 ? 8 : 4;
+  const int tid = threadIdx.x, g = tid / L, l = tid % L;
+  const int jBegin = blockIdx.x * CHUNK, jEnd = min( n, jBegin + CHUNK );
+  int16_t  *sTop = s.line, *sLeft = s.line + INTRA_LINE, *sFTop = s.line + 2 * INTRA_LINE, *sFLeft = s.line + 3 * INTRA_LINE;
+
+  for( int j = jBegin; j < jEnd; )
+  {
+    // the run [j, e) of one block index (uniform over the workgroup)
+    const int blk = uni( jobs[j].block );
+    int       e   = j + 1;
+    while( e < jEnd && uni( jobs[e].block ) == blk ) e++;
+    const int first = j;
+    j = e;
+    if( blk < 0 || blk >= numBlocks ) continue;
+    const vtmhip_intra_block B = blocks[blk];
+    const int w = uni( ( int ) B.width ), h = uni( ( int ) B.height ), m = uni( ( int ) B.multiRefIdx ), bd = uni( ( int ) B.bitDepth );
+    if( !intraBlockOk( w, h, bd, m ) || w * h > ( L == 16 ? 64 : L == 64 ? 1024 : INTRA_MAX_AREA ) ) continue;   // the second part cannot happen: L comes from the largest block
+    const int area = w * h, log2W = intraLog2( w ), log2H = intraLog2( h ), nTop = 2 * w + 1 + m, nLeft = 2 * h + 1 + m;
+
+    __syncthreads();   // the previous run's readers are done
+    {
+      const int16_t *ref = refBase + B.refOff;
+      for( int i = tid; i < nTop + nLeft; i += 256 )
+      {
+        const int16_t v = ref[i];
+        if( i < nTop ) sTop[i] = v;
+        else sLeft[i - nTop] = v;
+      }
+      if( FUSED )
+      {
+        const int16_t *org = orgBase + B.orgOff;
+        for( int i = tid; i < area; i += 256 ) s.org[i] = org[( long ) ( i >> log2W ) * B.orgStride + ( i & ( w - 1 ) )];
+      }
+    }
+    __syncthreads();
+    if( m == 0 )   // the filtered lines exist for m = 0 only (refFilterFlag)
+      for( int i = tid; i < nTop + nLeft; i += 256 )
+      {
+        if( i < nTop ) sFTop[i] = intraFilteredSample( sTop, sLeft, i, 2 * w );
+        else sFLeft[i - nTop] = intraFilteredSample( sLeft, sTop, i - nTop, 2 * h );
+      }
+    IntraBlk U;
+    U.top = sTop; U.left = sLeft; U.w = w; U.h = h; U.log2W = log2W; U.log2H = log2H; U.m = m; U.maxVal = ( 1 << bd ) - 1;
+    if( tid == 255 ) *s.dc = intraDcVal( U );
+    __syncthreads();
+    const int dcVal = *s.dc;
+
+    for( int base = first; base < e; base += G )
+    {
+      const int job = base + g;
+      bool      ok  = job < e;
+      vtmhip_intra_job J;
+      if( ok )
+      {
+        J  = jobs[job];
+        ok = intraModeOk( J.mode, m );
+      }
+      int16_t *slot = FUSED ? s.pred + g * area : nullptr;
+      if( ok )
+      {
+        vtmhip_intra_params p;
+        intraPredParams( w, h, J.mode, m, p );
+        IntraBlk b = U;
+        if( p.refFilterFlag ) { b.top = sFTop; b.left = sFLeft; }
+        int16_t *out = FUSED ? slot : predBase + J.predOff;
+        for( int i = l; i < area; i += L ) out[i] = intraPredSample( p, J.mode, b, dcVal, c_intraCubic, i & ( w - 1 ), i >> log2W );
+      }
+      if( FUSED )
+      {
+        __syncthreads();
+        if( L == 256 )
+        {
+          const int wv = tid >> 6;   // wave 0: SAD, wave 1: SATD
+          if( ok && wv < 2 )
+          {
+            const unsigned long long d = wave_block_dist( wv ? VTMHIP_DIST_SATD : VTMHIP_DIST_SAD, s.org, w, slot, w, w, h, 0, tid & 63 );
+            if( ( tid & 63 ) == 0 ) dist[2 * ( long ) job + wv] = d;
+          }
+        }
+        else if( ok )
+        {
+          const unsigned long long sad  = lanes_block_dist<L>( VTMHIP_DIST_SAD, s.org, w, slot, w, w, h, 0, l );
+          const unsigned long long satd = lanes_block_dist<L>( VTMHIP_DIST_SATD, s.org, w, slot, w, w, h, 0, l );
+          if( l == 0 ) { dist[2 * ( long ) job] = sad; dist[2 * ( long ) job + 1] = satd; }
+        }
+        __syncthreads();   // before the next round overwrites the slots
+      }
+    }
+  }
+}
+
+template<bool FUSED>
+__global__ __launch_bounds__( 256 ) void intra_kernel( const int *__restrict__ lanesPtr, const int16_t *__restrict__ refBase, const int16_t *__restrict__ orgBase,
+                                                       const vtmhip_intra_block *__restrict__ blocks, int numBlocks, const vtmhip_intra_job *__restrict__ jobs, int n,
+                                                       int16_t *__restrict__ predBase, unsigned long long *__restrict__ dist )
+{
+  __shared__ int16_t sLine[4 * INTRA_LINE];
+  __shared__ int     sDc;
+  __shared__ int16_t sOrg[FUSED ? INTRA_MAX_AREA : 1], sPred[FUSED ? INTRA_MAX_AREA : 1];
+  const int lanes = uni( *lanesPtr );
+  if( ( long ) blockIdx.x * intra_chunk( lanes ) >= n ) return;
+  const IntraLds s = { sLine, &sDc, sOrg, sPred };
+  if( lanes == 16 ) intra_chunk_body<16, FUSED>( s, refBase, orgBase, blocks, numBlocks, jobs, n, predBase, dist );
+  else if( lanes == 64 ) intra_chunk_body<64, FUSED>( s, refBase, orgBase, blocks, numBlocks, jobs, n, predBase, dist );
+  else intra_chunk_body<256, FUSED>( s, refBase, orgBase, blocks, numBlocks, jobs, n, predBase, dist );
+}
+
+int intra_launch( vtmhip_ctx *ctx, bool fused, const int16_t *d_refBase, const int16_t *d_orgBase, const vtmhip_intra_block *d_blocks, int numBlocks,
+                  const vtmhip_intra_job *d_jobs, int n, int16_t *d_predBase, uint64_t *d_dist )
+{
+  void *arena = nullptr;
+  VTMHIP_TRY( vtmhip_internal_workspace( ctx, 256, &arena ) );
+  int *d_lanes = ( int * ) arena;
+  hipLaunchKernelGGL( intra_shape_kernel, dim3( 1 ), dim3( 256 ), 0, ctx->stream, d_blocks, numBlocks, d_lanes );
+  VTMHIP_LAUNCHED( ctx );
+  const dim3 grid( ( n + INTRA_MIN_CHUNK - 1 ) / INTRA_MIN_CHUNK );
+  VTMHIP_TIME_KERNEL( ctx, fused ? "intra_presel_kernel" : "intra_pred_kernel" );
+  if( fused )
+    hipLaunchKernelGGL( intra_kernel<true>, grid, dim3( 256 ), 0, ctx->stream, d_lanes, d_refBase, d_orgBase, d_blocks, numBlocks, d_jobs, n, d_predBase,
+                        ( unsigned long long * ) d_dist );
+  else
+    hipLaunchKernelGGL( intra_kernel<false>, grid, dim3( 256 ), 0, ctx->stream, d_lanes, d_refBase, d_orgBase, d_blocks, numBlocks, d_jobs, n, d_predBase,
+                        ( unsigned long long * ) d_dist );
+  VTMHIP_LAUNCHED( ctx );
+  return VTMHIP_OK;
+}
+
+}   // namespace
+
+extern "C"
+{
+
+int vtmhip_intra_struct_size( int which )
+{
+  switch( which )
+  {
+  case 0: return ( int ) sizeof( vtmhip_intra_params );
+  case 1: return ( int ) sizeof( vtmhip_intra_block );
+  case 2: return ( int ) sizeof( vtmhip_intra_job );
+  default: return -1;
+  }
+}
+
+int vtmhip_intra_lanes_per_job( int maxArea ) { return intra_lanes( maxArea ); }
+
+int vtmhip_intra_pred_params( int width, int height, int mode, int multiRefIdx, vtmhip_intra_params *out )
+{
+  if( !out || !intraBlockOk( width, height, 8, multiRefIdx ) || !intraModeOk( mode, multiRefIdx ) ) return VTMHIP_E_INVALID;
+  intraPredParams( width, height, mode, multiRefIdx, *out );
+  return VTMHIP_OK;
+}
+
+int vtmhip_intra_pred_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const vtmhip_intra_block *d_blocks, int numBlocks, const vtmhip_intra_job *d_jobs, int n,
+                                 int16_t *d_predBase )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  VTMHIP_REQUIRE( ctx, numBlocks >= 0, "numBlocks" );
+  VTMHIP_BATCH_ARGS( ctx, n, d_refBase && d_blocks && d_jobs && d_predBase );
+  VTMHIP_REQUIRE( ctx, numBlocks > 0, "jobs without blocks" );
+  return intra_launch( ctx, false, d_refBase, nullptr, d_blocks, numBlocks, d_jobs, n, d_predBase, nullptr );
+}
+
+int vtmhip_intra_presel_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_orgBase, const vtmhip_intra_block *d_blocks, int numBlocks,
+                                   const vtmhip_intra_job *d_jobs, int n, uint64_t *d_dist )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  VTMHIP_REQUIRE( ctx, numBlocks >= 0, "numBlocks" );
+  VTMHIP_BATCH_ARGS( ctx, n, d_refBase && d_orgBase && d_blocks && d_jobs && d_dist );
+  VTMHIP_REQUIRE( ctx, numBlocks > 0, "jobs without blocks" );
+  return intra_launch( ctx, true, d_refBase, d_orgBase, d_blocks, numBlocks, d_jobs, n, nullptr, d_dist );
+}
+
+}   // extern "C"

@@ -3,6 +3,7 @@
 // and smvd.hip (the symmetric-MVD search predicts two blocks per candidate).
 #pragma once
 #include "ctx.hpp"
+#include "chroma_taps.hpp"
 
 namespace
 {
@@ -62,11 +63,7 @@ __device__ __forceinline__ const int16_t *luma_taps( int frac, int w, int h, int
 }
 
 // H.266 table 28 (chroma 4-tap filter, 1/32 sample phases), InterpolationFilter.cpp:132-166
-__constant__ int16_t c_chromaFilterMc[32][4] = {
-  { 0, 64, 0, 0 },    { -1, 63, 2, 0 },   { -2, 62, 4, 0 },   { -2, 60, 7, -1 },  { -2, 58, 10, -2 }, { -3, 57, 12, -2 }, { -4, 56, 14, -2 }, { -4, 55, 15, -2 },
-  { -4, 54, 16, -2 }, { -5, 53, 18, -2 }, { -6, 52, 20, -2 }, { -6, 49, 24, -3 }, { -6, 46, 28, -4 }, { -5, 44, 29, -4 }, { -4, 42, 30, -4 }, { -4, 39, 33, -4 },
-  { -4, 36, 36, -4 }, { -4, 33, 39, -4 }, { -4, 30, 42, -4 }, { -4, 29, 44, -5 }, { -4, 28, 46, -6 }, { -3, 24, 49, -6 }, { -2, 20, 52, -6 }, { -2, 18, 53, -5 },
-  { -2, 16, 54, -4 }, { -2, 15, 55, -4 }, { -2, 14, 56, -4 }, { -2, 12, 57, -3 }, { -2, 10, 58, -2 }, { -1, 7, 60, -2 },  { 0, 4, 62, -2 },   { 0, 2, 63, -1 } };
+__constant__ int16_t c_chromaFilterMc[32][4] = { VTMHIP_CHROMA_FILTER_TAPS };   // chroma_taps.hpp
 
 // One block, one wave.  NT = 8: luma (phase = 4 fraction bits); NT = 4: a 4:2:0 chroma plane (the vector stays in luma 1/16 units, so
 // the phase has 5 bits; InterPrediction.cpp:675-676).  lds holds the (h + NT - 1) x w horizontal-pass intermediates.

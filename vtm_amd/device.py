@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib as _lib
-from .lib import (AffineJob, DistJob, FracJob, FracResult, FullJob, IctJob, IfJob, JccrJob, JccrResult, LmcsJob, McJob, MeResult, PelOpJob, PicParams, QuantJob,   # noqa: F401
+from .lib import (AffineJob, DistJob, FracJob, FracResult, FullJob, IctJob, IfJob, IntraBlock, IntraJob, IntraParams, JccrJob, JccrResult, LmcsJob, McJob, MeResult, PelOpJob, PicParams, QuantJob,   # noqa: F401
                   SbtEstJob, SbtEstResult, SbtJob, SbtResult, ScaleJob, TrJob, TuJob, TuResult, TzJob, VtmHipError, WpDistJob, WpParam, WpPredJob, WtdJob)
 
 
@@ -467,6 +467,36 @@ class Context:
         """n SbtJob candidates (CU, sbtIdx, sbtPos): sub-TU expansion, the fused chain, completion over the whole CU -> SbtResult"""
         self._check(self.L.vtmhip_sbt_chain_batch_dev(self.h, d_resi, d_jobs, n, d_levels, d_rec, d_results))
 
+    def intra_pred_batch(self, d_ref, d_blocks, num_blocks, d_jobs, n, d_pred):
+        """predIntraAng (PDPC included) of n IntraJob (block, mode) pairs over num_blocks IntraBlock entries -> W x H samples, stride W, at IntraJob.predOff"""
+        self._check(self.L.vtmhip_intra_pred_batch_dev(self.h, d_ref, d_blocks, num_blocks, d_jobs, n, d_pred))
+
+    def intra_presel_batch(self, d_ref, d_org, d_blocks, num_blocks, d_jobs, n, d_dist):
+        """the same predictions kept on chip: d_dist[2 k] = SAD, d_dist[2 k + 1] = SATD of job k against its block's original"""
+        self._check(self.L.vtmhip_intra_presel_batch_dev(self.h, d_ref, d_org, d_blocks, num_blocks, d_jobs, n, d_dist))
+
+    def intra_presel(self, blocks, org=None):
+        """Host convenience over the two entries.  blocks: a list of dicts with `top`, `left` (numpy lines of 2W + 1 + m and 2H + 1 + m samples), `w`, `h`, `bd`,
+        `m`, `modes` and -- for the pre-selection -- `org_off`, `org_stride` into the int16 plane `org`.  With `org` it returns a uint64 array [jobs, 2] of
+        (SAD, SATD) in block-then-mode order, without it the list of predictions [h, w] in the same order."""
+        tables, refs, acc = pack_intra_tables(blocks)
+        blk_arr, job_arr, n = tables
+        d_ref, d_blk, d_job = self.to_device(refs), self.to_device(struct_array_to_numpy(blk_arr)), self.to_device(struct_array_to_numpy(job_arr))
+        if org is not None:
+            d_org, d_out = self.to_device(np.ascontiguousarray(org, np.int16)), self.alloc(16 * n)
+            self.intra_presel_batch(d_ref.ptr, d_org.ptr, d_blk.ptr, len(blocks), d_job.ptr, n, d_out.ptr)
+            self.sync()
+            res = d_out.to_host(np.uint64).reshape(n, 2)
+        else:
+            d_out = self.alloc(2 * max(acc, 1))
+            self.intra_pred_batch(d_ref.ptr, d_blk.ptr, len(blocks), d_job.ptr, n, d_out.ptr)
+            self.sync()
+            flat = d_out.to_host(np.int16)
+            res = [flat[j.predOff:j.predOff + blocks[j.block]["w"] * blocks[j.block]["h"]].reshape(blocks[j.block]["h"], blocks[j.block]["w"]) for j in job_arr]
+        for b in (d_ref, d_blk, d_job, d_out) + ((d_org,) if org is not None else ()):
+            b.free()
+        return res
+
     def scale_signal_batch(self, d_src, d_dst, d_jobs, n):
         """scaleSignal of n ScaleJob blocks, each with its own scale and direction (d_dst may be d_src: in place)"""
         self._check(self.L.vtmhip_scale_signal_batch_dev(self.h, d_src, d_dst, d_jobs, n))
@@ -492,6 +522,32 @@ class Context:
 def struct_array_to_numpy(arr):
     """ctypes array of Structures -> uint8 numpy view (for upload)."""
     return np.frombuffer(arr, dtype=np.uint8)
+
+
+def intra_pred_params(w, h, mode, m=0):
+    """initPredIntraParams of a luma block as an IntraParams record (host arithmetic, no device)"""
+    p = IntraParams()
+    st = _lib.load().vtmhip_intra_pred_params(w, h, mode, m, C.byref(p))
+    if st != _lib.OK:
+        raise VtmHipError(st)
+    return p
+
+
+def pack_intra_tables(blocks):
+    """IntraBlock / IntraJob tables of a list of block dicts (see Context.intra_presel): ((blocks, jobs, n), the concatenated int16 lines, prediction samples)"""
+    blk_arr = (IntraBlock * max(len(blocks), 1))()
+    refs, jobs, ref_off, pred_off = [], [], 0, 0
+    for i, b in enumerate(blocks):
+        top, left = np.asarray(b["top"], np.int16), np.asarray(b["left"], np.int16)
+        assert top.size == 2 * b["w"] + 1 + b["m"] and left.size == 2 * b["h"] + 1 + b["m"]
+        blk_arr[i] = IntraBlock(ref_off, b.get("org_off", 0), b.get("org_stride", 0), b["w"], b["h"], b["bd"], b["m"])
+        refs += [top, left]
+        ref_off += top.size + left.size
+        for mode in b["modes"]:
+            jobs.append(IntraJob(pred_off, i, mode))
+            pred_off += b["w"] * b["h"]
+    job_arr = (IntraJob * max(len(jobs), 1))(*jobs)
+    return (blk_arr, job_arr, len(jobs)), (np.concatenate(refs) if refs else np.zeros(1, np.int16)), pred_off
 
 
 def ict_select(dist, is_intra):

@@ -324,6 +324,20 @@ class SbtResult(C.Structure):
     _fields_ = [("sseCoded", C.c_uint64 * 3), ("sseZero", C.c_uint64 * 3), ("absSum", C.c_int32 * 3), ("pad", C.c_int32)]
 
 
+class IntraParams(C.Structure):
+    _fields_ = [("predMode", C.c_int32), ("isModeVer", C.c_int32), ("intraPredAngle", C.c_int32), ("invAngle", C.c_int32), ("angularScale", C.c_int32),
+                ("applyPDPC", C.c_int32), ("refFilterFlag", C.c_int32), ("interpolationFlag", C.c_int32)]
+
+
+class IntraBlock(C.Structure):
+    _fields_ = [("refOff", C.c_int64), ("orgOff", C.c_int64), ("orgStride", C.c_int32), ("width", C.c_int16), ("height", C.c_int16), ("bitDepth", C.c_uint8),
+                ("multiRefIdx", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class IntraJob(C.Structure):
+    _fields_ = [("predOff", C.c_int64), ("block", C.c_int32), ("mode", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
 _STRUCTS = [DistJob, TzJob, MeResult, PicParams, IfJob, FracJob, FracResult, TrJob, QuantJob, FullJob, McJob, PelOpJob,
             TuJob, TuResult, AffineJob, MeCfg, MeJob, MeOut, PredJob, MaskedSadJob, GeoBlendJob, DmvrJob, LfnstJob,
             PisRow, PisPu, PisLevel, AffineMeJob, AffineMeOut, LfnstTuJob, PisLevelRun, PisBuffers, SmvdJob, PisPuIn, WtdJob,
@@ -331,6 +345,7 @@ _STRUCTS = [DistJob, TzJob, MeResult, PicParams, IfJob, FracJob, FracResult, TrJ
 _JCCR_STRUCTS = [IctJob, JccrJob, JccrResult]   # order of vtmhip_jccr_struct_size(which)
 _LMCS_STRUCTS = [LmcsJob, ScaleJob]             # order of vtmhip_lmcs_struct_size(which)
 _SBT_STRUCTS = [SbtEstJob, SbtEstResult, SbtJob, SbtResult]   # order of vtmhip_sbt_struct_size(which)
+_INTRA_STRUCTS = [IntraParams, IntraBlock, IntraJob]          # order of vtmhip_intra_struct_size(which)
 
 # every symbol include/vtmhip.h declares (tests/test_abi.py checks the exports against the header text)
 _PROTOS = {
@@ -449,6 +464,11 @@ _PROTOS = {
     "vtmhip_affine_equal_coeff_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vtmhip_dist_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vtmhip_dist_uniform_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vtmhip_intra_struct_size": (C.c_int, [C.c_int]),
+    "vtmhip_intra_lanes_per_job": (C.c_int, [C.c_int]),
+    "vtmhip_intra_pred_params": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(IntraParams)]),
+    "vtmhip_intra_pred_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "vtmhip_intra_presel_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "vtmhip_intra_cand_cost_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vtmhip_satd8_grid_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p]),
@@ -539,6 +559,10 @@ def load():
         if lib.vtmhip_sbt_struct_size(i) != C.sizeof(s):
             raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
                               % (s.__name__, C.sizeof(s), lib.vtmhip_sbt_struct_size(i)))
+    for i, s in enumerate(_INTRA_STRUCTS):
+        if lib.vtmhip_intra_struct_size(i) != C.sizeof(s):
+            raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
+                              % (s.__name__, C.sizeof(s), lib.vtmhip_intra_struct_size(i)))
     _lib = lib
     return lib
 
