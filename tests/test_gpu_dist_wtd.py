@@ -125,6 +125,68 @@ def test_batch_matches_pointer_entry_and_rule(ctx, signal):
             assert _pointer(ctx, np.ascontiguousarray(org), c.astype(np.int16), comp, luma, sx, sy) == exp
 
 
+PACKED_SMALL, PACKED_TALL = [(2, 2), (2, 4), (4, 4), (6, 4), (8, 8)], [(4, 70), (12, 40), (6, 50)]   # tall: 70 / 120 / 100 row segments, no multiple of 64
+PACKED_REJECT = [dict(compID=3), dict(width=0), dict(flags=4)]
+
+
+def _packed_batch(rng, bd, n, lut, cw, inv):
+    """n PQ jobs for groups of two: mostly small blocks of all components and chroma formats, ~6 % tall ones (i % 32 == 20: the first job of its group, == 3: the
+    second), half of the luma jobs inverse-reshaped, every 97th rejected.  The expectations are wtd_util's rule, evaluated for all jobs of one shape at a time."""
+    mx = 1 << bd
+    keys = []
+    for i in range(n):
+        w, h = PACKED_TALL[(i // 32) % 3] if i % 32 in (3, 20) else PACKED_SMALL[int(rng.integers(len(PACKED_SMALL)))]
+        comp = int(rng.integers(3))
+        sx, sy = FORMATS[int(rng.integers(3))] if comp else (0, 0)
+        keys.append((w, h, comp, sx, sy, lib.WTD_INV_RESHAPE_CUR if comp == 0 and i % 2 == (i // 2) % 2 else 0, int(rng.integers(0, 5))))
+    pools, size = {"org": [], "cur": [], "luma": []}, {"org": 0, "cur": 0, "luma": 0}
+    jobs, exp = [None] * n, [lib.WTD_INVALID_DIST] * n
+    for key in sorted(set(keys)):
+        w, h, comp, sx, sy, flags, pad = key
+        idx = [i for i in range(n) if keys[i] == key]
+        m, lw = len(idx), (w << sx) + 3
+        org, cur = (rng.integers(0, mx, (m, h, w + pad)).astype(np.int16) for _ in range(2))
+        luma = rng.integers(0, mx, (m, h << sy, lw)).astype(np.int16)
+        lv = org[:, :, :w] if comp == 0 else luma[:, (np.arange(h) << sy)[:, None], (np.arange(w) << sx)[None, :]]
+        c = inv[cur[:, :, :w]] if flags else cur[:, :, :w]
+        dist = wu.mse_samples(comp, org[:, :, :w], c, lv, lut, wu.PQ, cw).astype(np.int64).astype(np.uint64).reshape(m, -1).sum(axis=1, dtype=np.uint64)
+        for k, i in enumerate(idx):
+            jobs[i] = dict(orgOff=size["org"] + k * org[0].size, curOff=size["cur"] + k * cur[0].size, orgLumaOff=size["luma"] + k * luma[0].size, orgStride=w + pad,
+                           curStride=w + pad, orgLumaStride=lw, width=w, height=h, compID=comp, cShiftX=sx, cShiftY=sy, flags=flags)
+            if i % 97 == 96:
+                jobs[i].update(PACKED_REJECT[(i // 97) % 3])
+            else:
+                exp[i] = int(dist[k])
+            if i % 50 == 0:   # the per-block form of the rule on the same samples
+                assert int(dist[k]) == wu.sse_wtd(org[k, :, :w], cur[k, :, :w], comp, lut, wu.PQ, cw, luma[k], sx, sy, inv if flags else None)
+        for name, a in (("org", org), ("cur", cur), ("luma", luma)):
+            pools[name].append(a.reshape(-1))
+            size[name] += a.size
+    return jobs, exp, {k: np.concatenate(v) for k, v in pools.items()}
+
+
+def test_batch_with_several_jobs_per_wave(ctx):
+    """vtmhip_sse_wtd_batch_dev packs G = n / (32 * CUs) jobs per wave (at most 64): a batch large enough for G = 2 runs the cursor over two jobs per wave, a
+    lane's accumulator flushed into the right job's sum when its segments move on, tall jobs whose end falls inside a 64-segment step as the first and as the
+    second job of a group, and rejected jobs inside a group.  PQ: every chroma sample reads the co-located luma."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n, bd = 2 * 32 * cus, 10
+    assert n // (32 * cus) == 2
+    rng = np.random.default_rng(60)
+    lut, cw, inv = wu.random_table(rng, bd), 0.83, wu.random_inv_lut(rng, bd)
+    ctx.set_luma_level_weights(lut, bd, wu.PQ, cw, inv)
+    jobs, exp, pools = _packed_batch(rng, bd, n, lut, cw, inv)
+    out = _run_batch(ctx, jobs, pools)
+    bad = [i for i in range(n) if int(out[i]) != exp[i]]
+    assert not bad, (len(bad), [(i, jobs[i], int(out[i]), exp[i]) for i in bad[:3]])
+    tall = [sum(1 for i in range(first, n, 2) if (jobs[i]["width"], jobs[i]["height"]) in PACKED_TALL and exp[i] != lib.WTD_INVALID_DIST) for first in (0, 1)]
+    assert min(tall) >= n // 40 and sum(e == lib.WTD_INVALID_DIST for e in exp) == n // 97
+    luma_jobs = [j for j in jobs if j["compID"] == 0]
+    assert abs(2 * sum(j["flags"] == lib.WTD_INV_RESHAPE_CUR for j in luma_jobs) - len(luma_jobs)) < len(luma_jobs) // 10
+    assert {(j["compID"], j["cShiftX"], j["cShiftY"]) for j in jobs} >= {(0, 0, 0)} | {(c, sx, sy) for c in (1, 2) for (sx, sy) in FORMATS}
+
+
 def test_table_reset_between_batches(ctx):
     bd = 8
     rng = np.random.default_rng(30)

@@ -208,6 +208,123 @@ def test_lmcs_resi_and_reco(bd):
         assert d_out.to_host(np.int16).tolist() == [int(lut[0]), int(lut[top]), int(lut[3]), int(lut[top])]
 
 
+# ---- several jobs per wave ------------------------------------------------------------------------------------------------------------------------------
+# The batch entries pack G = n / (32 * CUs) jobs per wave (at most 64).  n = 2 * 32 * CUs gives G = 2: the cursor over two jobs per wave, mixed shapes whose
+# segment counts end inside a 64-segment step (the tall ones as the first and as the second job of a group), rejected jobs inside a group.
+PACKED_SMALL, PACKED_TALL = [(1, 1), (2, 2), (4, 4), (8, 4), (3, 5)], [(4, 70), (12, 40), (6, 50)]   # tall: 70 / 120 / 100 row segments, no multiple of 64
+_packed = {}
+
+
+def _view(a, off, stride, w, h):
+    return np.lib.stride_tricks.as_strided(a[off:], (h, w), (2 * stride, 2))
+
+
+def _packed_specs(planes):
+    """(n, [(w, h, tall, rejected, [(offset, stride)] * planes)], pool size): n = 2 * 32 * CUs jobs, ~6 % tall, every 97th rejected, odd strides and offsets"""
+    if planes not in _packed:
+        import torch
+        cus = torch.cuda.get_device_properties(0).multi_processor_count
+        n = 2 * 32 * cus
+        assert n // (32 * cus) == 2
+        rng = np.random.default_rng(700 + planes)
+        specs, cur = [], [0] * planes
+        for k in range(n):
+            tall = k % 32 in (3, 20)   # 20: the first job of its group of two, 3: the second
+            w, h = PACKED_TALL[(k // 32) % 3] if tall else PACKED_SMALL[int(rng.integers(len(PACKED_SMALL)))]
+            pl = []
+            for b in range(planes):
+                off, stride, cur[b] = _place(rng, cur[b], w, h)
+                pl.append((off, stride))
+            specs.append((w, h, tall, k % 97 == 96, pl))
+        for first in (0, 1):
+            assert sum(t and not rej for k, (_w, _h, t, rej, _pl) in enumerate(specs) if k % 2 == first) >= n // 40
+        assert sum(rej for (_w, _h, _t, rej, _pl) in specs) == n // 97
+        _packed[planes] = n, specs, max(cur) + 8
+    return _packed[planes]
+
+
+def _packed_luma(bd=10):
+    n, specs, size = _packed_specs(4)
+    rng = np.random.default_rng(710)
+    top = (1 << bd) - 1
+    return n, specs, size, lu.make_lut(77, bd), rng.integers(0, top + 1, size).astype(np.int16), rng.integers(0, top + 1, size).astype(np.int16), \
+        rng.integers(-top, top + 1, size).astype(np.int16)
+
+
+def test_lmcs_resi_with_several_jobs_per_wave(ctx, bd=10):
+    """all four flag combinations; rejected inside groups: width 0, an unknown flag bit.  Outside the blocks and in a rejected job's block the sentinels stay."""
+    n, specs, size, lut, org, pred, _rin = _packed_luma(bd)
+    jobs = (LmcsJob * n)()
+    exp_resi, exp_dst = np.full(size, 0x3333, np.int16), np.full(size, 0x4444, np.int16)
+    for k, (w, h, _tall, rej, pl) in enumerate(specs):
+        j, flags = jobs[k], (k // 2 + k) % 4
+        (j.orgOff, j.orgStride), (j.predOff, j.predStride), (j.resiOff, j.resiStride), (j.dstOff, j.dstStride) = pl
+        j.width, j.height, j.bitDepth, j.flags = w, h, bd, flags
+        if rej:
+            j.width, j.flags = (0, flags) if (k // 97) % 2 else (w, flags | 4)
+            continue
+        r, mapped = lu.resi_expect(_view(org, *pl[0], w, h), _view(pred, *pl[1], w, h), lut, flags & lu.MAP_PRED)
+        _view(exp_resi, *pl[2], w, h)[:] = r
+        if flags & lu.WRITE_MAPPED:
+            _view(exp_dst, *pl[3], w, h)[:] = mapped
+    assert {(j.flags, k % 2) for k, j in enumerate(jobs) if j.flags < 4} == {(f, p) for f in range(4) for p in range(2)}
+    ctx.set_lmcs_fwd_lut(lut, bd)
+    d_resi, d_dst = ctx.to_device(np.full(size, 0x3333, np.int16)), ctx.to_device(np.full(size, 0x4444, np.int16))
+    bufs = [ctx.to_device(org), ctx.to_device(pred), ctx.to_device(np.frombuffer(jobs, np.uint8)), d_resi, d_dst]
+    ctx.lmcs_resi_batch(bufs[0].ptr, bufs[1].ptr, d_resi.ptr, bufs[2].ptr, n, d_dst.ptr)
+    assert np.array_equal(d_resi.to_host(np.int16), exp_resi)
+    assert np.array_equal(d_dst.to_host(np.int16), exp_dst)
+    for b in bufs:
+        b.free()
+
+
+def test_lmcs_reco_with_several_jobs_per_wave(ctx, bd=10):
+    """both MAP_PRED settings; rejected inside groups: width 0, a flag bit the reconstruction does not know (WRITE_MAPPED, bit 2)"""
+    n, specs, size, lut, _org, pred, rin = _packed_luma(bd)
+    jobs = (LmcsJob * n)()
+    exp = np.full(size, 0x6666, np.int16)
+    for k, (w, h, _tall, rej, pl) in enumerate(specs):
+        j, flags = jobs[k], ((k // 2 + k) % 2) * lu.MAP_PRED
+        (j.predOff, j.predStride), (j.resiOff, j.resiStride), (j.dstOff, j.dstStride) = pl[1:]
+        j.width, j.height, j.bitDepth, j.flags = w, h, bd, flags
+        if rej:
+            j.width, j.flags = [(0, flags), (w, flags | lu.WRITE_MAPPED), (w, flags | 4)][(k // 97) % 3]
+            continue
+        _view(exp, *pl[3], w, h)[:] = lu.reco_expect(_view(pred, *pl[1], w, h), _view(rin, *pl[2], w, h), lut, flags, bd)
+    ctx.set_lmcs_fwd_lut(lut, bd)
+    d_reco = ctx.to_device(np.full(size, 0x6666, np.int16))
+    bufs = [ctx.to_device(pred), ctx.to_device(rin), ctx.to_device(np.frombuffer(jobs, np.uint8)), d_reco]
+    ctx.lmcs_reco_batch(bufs[0].ptr, bufs[1].ptr, d_reco.ptr, bufs[2].ptr, n)
+    assert np.array_equal(d_reco.to_host(np.int16), exp)
+    for b in bufs:
+        b.free()
+
+
+def test_scale_signal_batch_with_several_jobs_per_wave(ctx):
+    """both directions, the edge scales, 8 / 10 / 12 bits; rejected inside groups: scale 0, forward scaling of width 1 (a 1x1 block is otherwise scaled inversely)"""
+    n, specs, size = _packed_specs(2)
+    rng = np.random.default_rng(720)
+    src, exp = rng.integers(-32768, 32768, size).astype(np.int16), np.full(size, 0x5555, np.int16)
+    jobs = (ScaleJob * n)()
+    for k, (w, h, _tall, rej, pl) in enumerate(specs):
+        j = jobs[k]
+        (j.srcOff, j.srcStride), (j.dstOff, j.dstStride) = pl
+        scale, fwd, bd = lu.EDGE_SCALES[int(rng.integers(len(lu.EDGE_SCALES)))], (k // 2 + k) % 2 if w > 1 else 0, 8 + 2 * (k % 3)
+        j.width, j.height, j.scale, j.dir, j.bitDepth = w, h, scale, fwd, bd
+        if rej:
+            if (k // 97) % 2:
+                j.scale = 0
+            else:
+                j.width, j.dir = 1, 1
+            continue
+        _view(exp, *pl[1], w, h)[:] = lu.scale_signal(_view(src, *pl[0], w, h), scale, fwd, bd)
+    bufs = [ctx.to_device(src), ctx.to_device(np.full(size, 0x5555, np.int16)), ctx.to_device(np.frombuffer(jobs, np.uint8))]
+    ctx.scale_signal_batch(bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, n)
+    assert np.array_equal(bufs[1].to_host(np.int16), exp)
+    for b in bufs:
+        b.free()
+
+
 # ---- the plain chain with CRS ------------------------------------------------------------------------------------------------------------------------
 _tu, _jc = {}, {}
 TU_SHAPES = {"generic": [(2, 2), (2, 4), (4, 2), (4, 16), (16, 4), (8, 8), (32, 32), (4, 4), (32, 32)],   # the last two: transform skip

@@ -1,0 +1,20 @@
+"""The jobs-per-wave skeleton of the per-block batch kernels (the HIP-free part of vtm_amd/csrc/wave_pack.hpp: FastDiv, the item cursor, the group indexing
+and the launch rules) as a stand-alone program under AddressSanitizer and UBSan."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "host", "test_wave_pack")
+
+
+def _build():
+    srcs = [os.path.join(ROOT, "host", "test_wave_pack.cpp"), os.path.join(ROOT, "vtm_amd", "csrc", "wave_pack.hpp")]
+    if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(s) for s in srcs):
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", EXE, srcs[0]])
+
+
+def test_wave_pack_under_sanitizers():
+    _build()
+    r = subprocess.run([EXE], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "192 cursor cases" in r.stdout and "\n0 failures" in r.stdout

@@ -13,6 +13,7 @@
 #include "ctx.hpp"
 #include "had.hpp"
 #include "mv_rules.hpp"
+#include "pel_pack.hpp"
 
 #include <cmath>
 
@@ -112,7 +113,6 @@ __device__ __forceinline__ void subblock_4x4( const int16_t *r0, int rs, int mh,
   }
 }
 
-struct __attribute__( ( packed, aligned( 2 ) ) ) Pel8u { unsigned v[4]; };   // 8 samples from a 2-byte aligned address
 
 // One COLUMN of a 4x4 sub-block at vector (mh, mv): o[4] = rows 0..3 of column q, rounded + clipped (last) or 14-bit intermediates (!last); the same
 // arithmetic as subblock_4x4, split so that the four lanes of a quad share one sub-block without talking to each other: a lane filters the 11 rows of
@@ -134,7 +134,7 @@ __device__ __forceinline__ void subblock_column( const int16_t *r0, int rs, int 
 #pragma unroll
     for( int y = 0; y < 4; y++ )
     {
-      const Pel8u v = *reinterpret_cast<const Pel8u *>( src + ( long ) y * rs - 3 );
+      const Pel8 v = *reinterpret_cast<const Pel8 *>( src + ( long ) y * rs - 3 );
       int         sum = 0;
 #pragma unroll
       for( int k = 0; k < 4; k++ ) sum += ( int ) ( short ) v.v[k] * ( int ) c[2 * k] + ( ( int ) v.v[k] >> 16 ) * ( int ) c[2 * k + 1];
@@ -169,7 +169,7 @@ __device__ __forceinline__ void subblock_column( const int16_t *r0, int rs, int 
 #pragma unroll
   for( int r = 0; r < 11; r++ )
   {
-    const Pel8u v = *reinterpret_cast<const Pel8u *>( src + ( long ) ( r - 3 ) * rs - 3 );
+    const Pel8 v = *reinterpret_cast<const Pel8 *>( src + ( long ) ( r - 3 ) * rs - 3 );
     int         sum = 0;
 #pragma unroll
     for( int k = 0; k < 4; k++ ) sum += ( int ) ( short ) v.v[k] * ( int ) ch[2 * k] + ( ( int ) v.v[k] >> 16 ) * ( int ) ch[2 * k + 1];

@@ -15,6 +15,7 @@
 #include "stage.hpp"
 #include "had.hpp"
 #include "dist_block.hpp"
+#include "pel_pack.hpp"
 
 namespace
 {
@@ -137,7 +138,6 @@ __global__ __launch_bounds__( THREADS ) void satd8_grid_kernel( const int16_t *_
 // dist_batch_kernel gives a wave to every job, so an 8x8 SATD (one tile) keeps 1 lane of 64 busy and an 8x8 SAD 16.  When the
 // caller can promise one block size per launch (the merge / AMVP candidates of one CU size, hooks B7 / B10), LPJ = the power of two
 // >= the job's work items (8-sample row segments, Hadamard tiles) lanes form a job and 64 / LPJ jobs share a wave.
-struct __attribute__( ( packed, aligned( 2 ) ) ) DPel8 { unsigned v[4]; };
 
 __global__ __launch_bounds__( 256 ) void dist_uniform_kernel( const int16_t *__restrict__ orgBase, const int16_t *__restrict__ curBase,
                                                              const vtmhip_dist_job *__restrict__ jobs, int n, int kind, int w, int h, int ss, int lpjShift,
@@ -186,8 +186,8 @@ __global__ __launch_bounds__( 256 ) void dist_uniform_kernel( const int16_t *__r
     for( int it = sub; live && it < rows * segs; it += lpj )
     {
       const int   r = it / segs, x = ( it - r * segs ) << 3;
-      const DPel8 a = *reinterpret_cast<const DPel8 *>( org + ( long ) ( r << rs ) * os + x );
-      const DPel8 b = *reinterpret_cast<const DPel8 *>( cur + ( long ) ( r << rs ) * cs + x );
+      const Pel8 a = *reinterpret_cast<const Pel8 *>( org + ( long ) ( r << rs ) * os + x );
+      const Pel8 b = *reinterpret_cast<const Pel8 *>( cur + ( long ) ( r << rs ) * cs + x );
       if( kind == VTMHIP_DIST_SAD )
       {
 #pragma unroll

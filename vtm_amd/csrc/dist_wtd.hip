@@ -2,15 +2,15 @@
 // per-sample rule RdCost::getWeightedMSE :3055-3086), the CU-level final distortion of LMCS / WCG encodes.  Bit-exact with the reference under the sample
 // contract of include/vtmhip.h (org, cur, orgLuma in [0, 2^bitDepth), bitDepth <= 12), including the truncation of the weighted square to 32 bits.
 //
-// sse_wtd_kernel (wave = 64 lanes, 4 waves per workgroup):
+// sse_wtd_kernel (4 waves per workgroup) packs jobs into waves as wave_pack.hpp lays out; an item is a 4-sample row segment, walked lane-strided:
 //   - the fixed-point weight table (<= 4096 x int32) and the inverse reshape LUT (<= 4096 x int16) are staged in LDS once per workgroup with 16-byte loads;
 //     every per-sample weight / inverse-LUT lookup is an LDS read;
-//   - a wave takes G consecutive jobs (G <= 64, chosen by the host from n) and spreads the 4-sample row segments of all of them over its 64 lanes
-//     (wave prefix scan of the segment counts): 2x2 / 4x4 chroma blocks share a wave, a 128x128 luma block keeps all lanes busy;
 //   - a lane accumulates in 64 bits while its segments belong to one job and adds the partial into the job's LDS slot when it moves on (integer sum:
 //     order-free); the 64-bit weighted square is one 32 x 32 -> 64 multiply (fixed < 2^31, d * d < 2^24), never a generic 64 x 64 one.
 #include "ctx.hpp"
 #include "stage.hpp"
+#include "wave_pack.hpp"
+#include "pel_pack.hpp"
 
 namespace
 {
@@ -22,12 +22,10 @@ struct WtdJobL   // a job as the kernel uses it (LDS, one per lane of a group)
 {
   const int16_t *org, *cur, *luma;
   int os, cs, ls;
-  int w, segs;
-  unsigned magic;   // floor((2^32 - 1) / segs): segment index -> (row, segment) without a division
+  int w;
+  FastDiv segs;     // segment index -> (row, segment)
   int mode;         // bit 0: inverse-reshape cur; bit 1: chroma with the constant weight; bit 2: chroma weighted by the co-located luma; bits 8..: cShiftX | cShiftY << 1
 };
-
-struct __attribute__( ( packed, aligned( 2 ) ) ) WPel4 { unsigned v[2]; };
 
 __device__ __forceinline__ unsigned long long wmse( int fixed, int o, int c )
 {
@@ -54,17 +52,16 @@ __global__ __launch_bounds__( 64 * WTD_WAVES ) void sse_wtd_kernel( const int16_
     for( int i = threadIdx.x; i < ( tabN >> 3 ); i += blockDim.x ) reinterpret_cast<int4 *>( sInv )[i] = reinterpret_cast<const int4 *>( invTab )[i];
 
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, top = tabN - 1;
-  const int nGroups = ( n + G - 1 ) / G;
+  const int nGroups = wave_groups( n, G );
   // every wave of a workgroup runs the same number of rounds (the barriers below)
   for( int round = blockIdx.x * WTD_WAVES; round < nGroups; round += gridDim.x * WTD_WAVES )
   {
-    const int grp = round + wv, base = grp * G, job = base + lane;
-    const bool mine = grp < nGroups && lane < G && job < n;
+    const WaveGroup g( round, wv, lane, n, G, nGroups );
     int  items = 0;
     bool valid = false;
-    if( mine )
+    if( g.mine )
     {
-      const vtmhip_wtd_job j = jobs[job];
+      const vtmhip_wtd_job j = jobs[g.job];
       const int  w = j.width, h = j.height, comp = j.compID, sx = j.cShiftX, sy = j.cShiftY, fl = j.flags;
       const bool inv = ( fl & VTMHIP_WTD_INV_RESHAPE_CUR ) != 0;
       valid = w >= 1 && w <= 128 && h >= 1 && h <= 128 && comp <= 2 && sx <= 1 && sy <= 1 && ( comp != 0 || ( sx | sy ) == 0 ) &&
@@ -74,62 +71,33 @@ __global__ __launch_bounds__( 64 * WTD_WAVES ) void sse_wtd_kernel( const int16_
         WtdJobL &L = sJob[wv][lane];
         L.org = orgBase + j.orgOff; L.cur = curBase + j.curOff; L.luma = lumaBase + j.orgLumaOff;
         L.os = j.orgStride; L.cs = j.curStride; L.ls = j.orgLumaStride;
-        L.w = w; L.segs = ( w + 3 ) >> 2; L.magic = 0xffffffffu / ( unsigned ) L.segs;
+        L.w = w; L.segs = FastDiv( ( w + 3 ) >> 2 );
         L.mode = ( inv ? 1 : 0 ) | ( comp != 0 ? ( chromaConst ? 2 : 4 ) : 0 ) | ( ( sx | sy << 1 ) << 8 );
-        items = h * L.segs;
+        items = h * L.segs.d;
       }
     }
-    int incl = items;
-#pragma unroll
-    for( int o = 1; o < 64; o <<= 1 )
-    {
-      const int t = __shfl_up( incl, o, 64 );
-      if( lane >= o ) incl += t;
-    }
-    const int total = __shfl( incl, 63, 64 );
-    sEnd[wv][lane] = incl;
+    const int total = wave_scan_items( lane, items, sEnd[wv] );
     sSum[wv][lane] = 0;
     __syncthreads();   // also orders the table staging of the first round
 
     // lane walks the group's segments t = lane, lane + 64, ...: its job index only grows
-    int                cj = -1, start = 0, end = 0;
+    WaveCursor         cur;
     WtdJobL            L {};
     unsigned long long acc = 0;
     for( int t = lane; t < total; t += 64 )
     {
-      if( t >= end )
+      if( cur.beyond( t ) )
       {
-        if( cj >= 0 ) atomicAdd( &sSum[wv][cj], acc );
+        if( cur.cj >= 0 ) atomicAdd( &sSum[wv][cur.cj], acc );
         acc = 0;
-        do { start = end; end = sEnd[wv][++cj]; } while( t >= end );   // skips jobs without segments (rejected ones)
-        L = sJob[wv][cj];
+        cur.advance( t, sEnd[wv] );
+        L = sJob[wv][cur.cj];
       }
-      const int local = t - start;
-      int       r     = ( int ) __umulhi( ( unsigned ) local, L.magic );
-      r += ( r + 1 ) * L.segs <= local ? 1 : 0;
-      const int x = ( local - r * L.segs ) << 2;
+      const int local = t - cur.start, r = L.segs( local ), x = ( local - r * L.segs.d ) << 2, cnt = min( 4, L.w - x );
       const int16_t *o = L.org + ( long ) r * L.os + x, *c = L.cur + ( long ) r * L.cs + x;
-      int ov[4], cv[4];
-      if( x + 4 <= L.w )
-      {
-        const WPel4 a = *reinterpret_cast<const WPel4 *>( o ), b = *reinterpret_cast<const WPel4 *>( c );
-#pragma unroll
-        for( int k = 0; k < 2; k++ )
-        {
-          ov[2 * k] = ( short ) ( a.v[k] & 0xffffu ); ov[2 * k + 1] = ( int ) a.v[k] >> 16;
-          cv[2 * k] = ( short ) ( b.v[k] & 0xffffu ); cv[2 * k + 1] = ( int ) b.v[k] >> 16;
-        }
-      }
-      else
-      {
-#pragma unroll
-        for( int k = 0; k < 4; k++ )
-        {
-          const bool in = x + k < L.w;   // past the block's right edge: d = 0 adds 0
-          ov[k] = in ? o[k] : 0;
-          cv[k] = in ? c[k] : 0;
-        }
-      }
+      int            ov[4], cv[4];   // past the block's right edge org = cur = 0: d = 0 adds 0
+      if( cnt == 4 ) { unpack4( *reinterpret_cast<const Pel4 *>( o ), ov ); unpack4( *reinterpret_cast<const Pel4 *>( c ), cv ); }   // one branch: both loads go out together
+      else { ld4( o, cnt, ov ); ld4( c, cnt, cv ); }
       if( L.mode & 1 )
       {
 #pragma unroll
@@ -158,18 +126,11 @@ __global__ __launch_bounds__( 64 * WTD_WAVES ) void sse_wtd_kernel( const int16_
         for( int k = 0; k < 4; k++ ) acc += wmse( sTab[min( max( ov[k], 0 ), top )], ov[k], cv[k] );
       }
     }
-    if( cj >= 0 ) atomicAdd( &sSum[wv][cj], acc );
+    if( cur.cj >= 0 ) atomicAdd( &sSum[wv][cur.cj], acc );
     __syncthreads();
-    if( mine ) out[job] = valid ? sSum[wv][lane] : ~0ull;
+    if( g.mine ) out[g.job] = valid ? sSum[wv][lane] : ~0ull;
     __syncthreads();   // sJob / sEnd / sSum are rewritten by the next round
   }
-}
-
-// jobs per wave: pack as many as still leave ~32 waves per CU (8 per SIMD, what the latency of the sample loads needs), at most 64
-int wtd_jobs_per_wave( const vtmhip_ctx *ctx, int n )
-{
-  const int g = n / ( ctx->numCUs * 32 );
-  return g < 1 ? 1 : g > 64 ? 64 : g;
 }
 
 int wtd_launch( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_curBase, const int16_t *d_lumaBase, const vtmhip_wtd_job *d_jobs, int n, int G,
@@ -177,9 +138,7 @@ int wtd_launch( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_curB
 {
   const int    tabN    = 1 << ctx->wtdLumaBD;
   const size_t lds     = ( size_t ) tabN * sizeof( int32_t ) + ( ctx->wtdHasInv ? ( size_t ) tabN * sizeof( int16_t ) : 0 );
-  const int    nGroups = ( n + G - 1 ) / G;
-  int          blocks  = ( nGroups + WTD_WAVES - 1 ) / WTD_WAVES;
-  if( blocks > ctx->numCUs * 8 ) blocks = ctx->numCUs * 8;   // the rest loop: the tables are staged once per workgroup
+  const int    blocks  = wave_blocks( n, G, WTD_WAVES, ctx->numCUs * 8 );   // the tables are staged once per workgroup
   const int chromaConst = ctx->wtdSignalType == 0 || ctx->wtdSignalType == 2;   // RESHAPE_SIGNAL_SDR / _HLG: m_chromaWeight (RdCost.cpp:3066-3076)
   VTMHIP_TIME_KERNEL( ctx, "sse_wtd_kernel" );
   hipLaunchKernelGGL( sse_wtd_kernel, dim3( blocks ), dim3( 64 * WTD_WAVES ), lds, ctx->stream, d_orgBase, d_curBase, d_lumaBase, d_jobs, n, G, ctx->wtdFixed,
@@ -225,7 +184,7 @@ int vtmhip_sse_wtd_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const i
   VTMHIP_CHECK_CTX( ctx );
   VTMHIP_REQUIRE( ctx, ctx->wtdLumaBD != 0, "vtmhip_set_luma_level_weights has not been called" );
   VTMHIP_BATCH_ARGS( ctx, n, d_orgBase && d_curBase && d_orgLumaBase && d_jobs && d_dist );
-  return wtd_launch( ctx, d_orgBase, d_curBase, d_orgLumaBase, d_jobs, n, wtd_jobs_per_wave( ctx, n ), ( unsigned long long * ) d_dist );
+  return wtd_launch( ctx, d_orgBase, d_curBase, d_orgLumaBase, d_jobs, n, wave_jobs_per_wave( ctx->numCUs, n ), ( unsigned long long * ) d_dist );
 }
 
 int vtmhip_xGetSSE_WTD( vtmhip_ctx *ctx, const int16_t *org, int orgStride, const int16_t *cur, int curStride, int width, int height, int compID,

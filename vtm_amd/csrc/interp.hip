@@ -18,6 +18,7 @@
 #include "mest_glue.hpp"
 #include "mv_rules.hpp"
 #include "had.hpp"
+#include "pel_pack.hpp"
 
 #include <type_traits>
 
@@ -30,8 +31,6 @@ __constant__ int16_t c_lumaFilter[16][8] = {
   { -1, 4, -11, 40, 40, -11, 4, -1 },{ -1, 4, -10, 34, 45, -11, 4, -1 },{ -1, 4, -10, 31, 47, -9, 3, -1 }, { -1, 3, -8, 26, 52, -11, 4, -1 },
   { 0, 1, -5, 17, 58, -10, 4, -1 },  { 0, 1, -4, 13, 60, -8, 3, -1 },   { 0, 1, -3, 8, 62, -5, 2, -1 },    { 0, 1, -2, 4, 63, -3, 1, 0 } };
 __constant__ int16_t c_lumaAltHpel[8] = { 0, 3, 9, 20, 20, 9, 3, 0 };
-
-struct __attribute__( ( packed, aligned( 2 ) ) ) Pel8u { unsigned v[4]; };   // 8 samples from a 2-byte aligned address
 
 struct IfParams { int shift, offset, clip, cmin, cmax; };
 
@@ -70,12 +69,6 @@ __device__ __forceinline__ int16_t if_finish( int sum, const IfParams &p )
 
 // ---- generic batched filter: one WAVE per job (four jobs per workgroup); 8 outputs per lane with 16-byte loads / stores when the width is
 //      a multiple of 8, one output per lane otherwise ------------------------------------------------------------------------------------
-__device__ __forceinline__ void if_unpack8( const Pel8u &t, int a[8] )
-{
-#pragma unroll
-  for( int k = 0; k < 4; k++ ) { a[2 * k] = ( int ) ( short ) ( t.v[k] & 0xffffu ); a[2 * k + 1] = ( int ) t.v[k] >> 16; }
-}
-
 __global__ __launch_bounds__( 256 ) void if_batch_kernel( const int16_t *__restrict__ srcBase, int16_t *__restrict__ dstBase,
                                                          const vtmhip_if_job *__restrict__ jobs, int n )
 {
@@ -129,7 +122,7 @@ __global__ __launch_bounds__( 256 ) void if_batch_kernel( const int16_t *__restr
         for( int t = 0; t < taps; t++ )
         {
           int row[8];
-          if_unpack8( *reinterpret_cast<const Pel8u *>( src + ( long ) ( y + t - halo ) * j.srcStride + x0 ), row );
+          unpack8( *reinterpret_cast<const Pel8 *>( src + ( long ) ( y + t - halo ) * j.srcStride + x0 ), row );
 #pragma unroll
           for( int k = 0; k < 8; k++ ) sum[k] += row[k] * c[t];
         }
@@ -138,8 +131,8 @@ __global__ __launch_bounds__( 256 ) void if_batch_kernel( const int16_t *__restr
       {
         int            a[16];
         const int16_t *s0 = src + ( long ) y * j.srcStride + x0 - halo;
-        if_unpack8( *reinterpret_cast<const Pel8u *>( s0 ), a );
-        if_unpack8( *reinterpret_cast<const Pel8u *>( s0 + 8 ), a + 8 );
+        unpack8( *reinterpret_cast<const Pel8 *>( s0 ), a );
+        unpack8( *reinterpret_cast<const Pel8 *>( s0 + 8 ), a + 8 );
 #pragma unroll
         for( int k = 0; k < 8; k++ )
         {
@@ -147,11 +140,11 @@ __global__ __launch_bounds__( 256 ) void if_batch_kernel( const int16_t *__restr
           for( int t = 0; t < 8; t++ ) sum[k] += a[k + t] * c[t];   // taps < 8: the remaining coefficients are zero
         }
       }
-      Pel8u o;
+      Pel8 o;
 #pragma unroll
       for( int k = 0; k < 4; k++ )
         o.v[k] = ( ( unsigned ) ( unsigned short ) if_finish( sum[2 * k], p ) ) | ( ( unsigned ) ( unsigned short ) if_finish( sum[2 * k + 1], p ) << 16 );
-      *reinterpret_cast<Pel8u *>( dst + ( long ) y * j.dstStride + x0 ) = o;
+      *reinterpret_cast<Pel8 *>( dst + ( long ) y * j.dstStride + x0 ) = o;
     }
     return;
   }
@@ -433,7 +426,7 @@ __global__ __launch_bounds__( ( FracSq<W, H>::BLOCK ), ( FracSq<W, H>::MINW ) ) 
       const int               jl = i / ( ( H + 8 ) * CH ), rem = i - jl * ( H + 8 ) * CH, r = rem / CH, c = ( rem - r * CH ) * 8;
       const vtmhip_frac_job &j  = jb[jl];
       const int16_t         *ref = refBase + j.refOff + ( long ) ( j.intY + r - 4 ) * j.refStride + ( j.intX + c - 4 );
-      const Pel8u            v   = *reinterpret_cast<const Pel8u *>( ref );
+      const Pel8             v   = *reinterpret_cast<const Pel8 *>( ref );
       *reinterpret_cast<int4 *>( lds + jl * C::PERJOB + r * C::WLD + c ) = make_int4( ( int ) v.v[0], ( int ) v.v[1], ( int ) v.v[2], ( int ) v.v[3] );
     }
   }
@@ -657,7 +650,7 @@ __global__ __launch_bounds__( ( FracSq<W, H>::BLOCK ), ( FracSq<W, H>::MINW ) ) 
 #pragma unroll
         for( int y = 0; y < 8; y++ )
         {
-          const Pel8u o = *reinterpret_cast<const Pel8u *>( org + ( long ) y * j.orgStride );
+          const Pel8 o = *reinterpret_cast<const Pel8 *>( org + ( long ) y * j.orgStride );
 #pragma unroll
           for( int k = 0; k < 4; k++ )
           {
@@ -676,7 +669,7 @@ __global__ __launch_bounds__( ( FracSq<W, H>::BLOCK ), ( FracSq<W, H>::MINW ) ) 
 #pragma unroll
         for( int y = 0; y < 8; y++ )
         {
-          const Pel8u o = *reinterpret_cast<const Pel8u *>( org + ( long ) y * j.orgStride );
+          const Pel8 o = *reinterpret_cast<const Pel8 *>( org + ( long ) y * j.orgStride );
 #pragma unroll
           for( int x = 0; x < 8; x++ )
           {
@@ -711,7 +704,7 @@ __global__ __launch_bounds__( ( FracSq<W, H>::BLOCK ), ( FracSq<W, H>::MINW ) ) 
 #pragma unroll
         for( int y = 0; y < 8; y++ )
         {
-          const Pel8u o = *reinterpret_cast<const Pel8u *>( org + ( long ) y * j.orgStride );
+          const Pel8 o = *reinterpret_cast<const Pel8 *>( org + ( long ) y * j.orgStride );
 #pragma unroll
           for( int x = 0; x < 8; x++ )
           {

@@ -4,13 +4,12 @@
 //   and the reconstruction           reco = clip( fwdLUT[pred] + resi )        (InterSearch.cpp:7540-7551).
 // The scaling arithmetic is lmcs.hpp's; the chains with the scaling fused in are in transform.hip / jccr.hip.
 //
-// lmcs_op_kernel (wave = 64 lanes, 4 waves per workgroup), the layout of dist_wtd.hip's kernel:
-//   - the forward LUT (<= 4096 x int16) is staged in LDS once per workgroup with 16-byte loads; every lookup is an LDS read with the index clamped into the table;
-//   - a wave takes G consecutive jobs (G <= 64, chosen by the host from n) and spreads the 4-sample row segments of all of them over its 64 lanes (wave prefix
-//     scan of the segment counts): 2x2 / 4x4 blocks share a wave, a 128x128 block keeps all lanes busy;
-//   - a whole segment moves as one 8-byte access (2-byte aligned: the hardware splits it only when the address asks for it), a ragged one sample by sample.
+// lmcs_op_kernel (4 waves per workgroup) packs jobs into waves as wave_pack.hpp lays out; an item is a 4-sample row segment (pel_pack.hpp's ld4 / st4), walked
+// lane-strided.  The forward LUT (<= 4096 x int16) is staged in LDS once per workgroup with 16-byte loads; every lookup is an LDS read with the index clamped.
 #include "ctx.hpp"
 #include "stage.hpp"
+#include "wave_pack.hpp"
+#include "pel_pack.hpp"
 #include "lmcs.hpp"
 
 namespace
@@ -25,44 +24,12 @@ struct LmJobL   // a job as the kernel uses it (LDS, one per lane of a group)
   const int16_t *a, *b;   // SCALE: src, -;  RESI: org, pred;  RECO: pred, resi
   int16_t       *o, *o2;  // SCALE: dst, -;  RESI: resi, mapped prediction;  RECO: reco, -
   int       as, bs, os, o2s;
-  int       w, segs;
-  unsigned  magic;        // floor((2^32 - 1) / segs): segment index -> (row, segment) without a division
+  int       w;
+  FastDiv   segs;         // segment index -> (row, segment)
   int       mode;         // SCALE: dir;  RESI / RECO: VTMHIP_LMCS_* flags
   LmcsScale sc;
   int       maxAbs;       // SCALE: (1 << bitDepth) - 1;  RECO: the clip's upper bound
 };
-
-struct __attribute__( ( packed, aligned( 2 ) ) ) LPel4 { unsigned v[2]; };
-
-__device__ __forceinline__ void ld4( const int16_t *p, int cnt, int v[4] )
-{
-  if( cnt == 4 )
-  {
-    const LPel4 a = *reinterpret_cast<const LPel4 *>( p );
-    v[0] = ( short ) ( a.v[0] & 0xffffu ); v[1] = ( int ) a.v[0] >> 16; v[2] = ( short ) ( a.v[1] & 0xffffu ); v[3] = ( int ) a.v[1] >> 16;
-  }
-  else
-  {
-#pragma unroll
-    for( int k = 0; k < 4; k++ ) v[k] = k < cnt ? p[k] : 0;
-  }
-}
-
-__device__ __forceinline__ void st4( int16_t *p, int cnt, const int v[4] )
-{
-  if( cnt == 4 )
-  {
-    LPel4 a;
-    a.v[0] = ( ( unsigned ) v[0] & 0xffffu ) | ( ( unsigned ) v[1] << 16 ); a.v[1] = ( ( unsigned ) v[2] & 0xffffu ) | ( ( unsigned ) v[3] << 16 );
-    *reinterpret_cast<LPel4 *>( p ) = a;
-  }
-  else
-  {
-#pragma unroll
-    for( int k = 0; k < 4; k++ )
-      if( k < cnt ) p[k] = ( int16_t ) v[k];
-  }
-}
 
 template<int OP>
 __device__ __forceinline__ bool lm_job( const void *jobs, int job, const int16_t *aBase, const int16_t *bBase, int16_t *oBase, int16_t *o2Base, LmJobL &L, int &h )
@@ -110,48 +77,33 @@ __global__ __launch_bounds__( 64 * LM_WAVES ) void lmcs_op_kernel( const int16_t
     for( int i = threadIdx.x; i < ( tabN >> 3 ); i += blockDim.x ) reinterpret_cast<int4 *>( sLut )[i] = reinterpret_cast<const int4 *>( lut )[i];
 
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, top = tabN - 1;
-  const int nGroups = ( n + G - 1 ) / G;
+  const int nGroups = wave_groups( n, G );
   // every wave of a workgroup runs the same number of rounds (the barriers below)
   for( int round = blockIdx.x * LM_WAVES; round < nGroups; round += gridDim.x * LM_WAVES )
   {
-    const int grp = round + wv, job = grp * G + lane;
-    int       items = 0;
-    if( grp < nGroups && lane < G && job < n )
+    const WaveGroup g( round, wv, lane, n, G, nGroups );
+    int             items = 0;
+    if( g.mine )
     {
       LmJobL L;
       int    h = 0;
-      if( lm_job<OP>( jobs, job, aBase, bBase, oBase, o2Base, L, h ) )
+      if( lm_job<OP>( jobs, g.job, aBase, bBase, oBase, o2Base, L, h ) )
       {
-        L.segs = ( L.w + 3 ) >> 2; L.magic = 0xffffffffu / ( unsigned ) L.segs;
+        L.segs = FastDiv( ( L.w + 3 ) >> 2 );
         sJob[wv][lane] = L;
-        items = h * L.segs;
+        items = h * L.segs.d;
       }
     }
-    int incl = items;
-#pragma unroll
-    for( int o = 1; o < 64; o <<= 1 )
-    {
-      const int t = __shfl_up( incl, o, 64 );
-      if( lane >= o ) incl += t;
-    }
-    const int total = __shfl( incl, 63, 64 );
-    sEnd[wv][lane] = incl;
+    const int total = wave_scan_items( lane, items, sEnd[wv] );
     __syncthreads();   // also orders the table staging of the first round
 
     // lane walks the group's segments t = lane, lane + 64, ...: its job index only grows
-    int    cj = -1, start = 0, end = 0;
-    LmJobL L {};
+    WaveCursor cur;
+    LmJobL     L {};
     for( int t = lane; t < total; t += 64 )
     {
-      if( t >= end )
-      {
-        do { start = end; end = sEnd[wv][++cj]; } while( t >= end );   // skips jobs without segments (rejected ones)
-        L = sJob[wv][cj];
-      }
-      const int local = t - start;
-      int       r     = ( int ) __umulhi( ( unsigned ) local, L.magic );
-      r += ( r + 1 ) * L.segs <= local ? 1 : 0;
-      const int x = ( local - r * L.segs ) << 2, cnt = min( 4, L.w - x );
+      if( cur.beyond( t ) ) { cur.advance( t, sEnd[wv] ); L = sJob[wv][cur.cj]; }
+      const int local = t - cur.start, r = L.segs( local ), x = ( local - r * L.segs.d ) << 2, cnt = min( 4, L.w - x );
       int       av[4], bv[4], ov[4];
       ld4( L.a + ( long ) r * L.as + x, cnt, av );
       if( OP == OP_SCALE )
@@ -194,21 +146,12 @@ __global__ __launch_bounds__( 256 ) void rsp_kernel( int16_t *__restrict__ buf, 
   if( i < count ) buf[i] = lut[min( max( ( int ) buf[i], 0 ), lutSize - 1 )];
 }
 
-// jobs per wave: pack as many as still leave ~32 waves per CU, at most 64 (dist_wtd.hip's rule)
-int lm_jobs_per_wave( const vtmhip_ctx *ctx, int n )
-{
-  const int g = n / ( ctx->numCUs * 32 );
-  return g < 1 ? 1 : g > 64 ? 64 : g;
-}
-
 template<int OP>
 int lm_launch( vtmhip_ctx *ctx, const int16_t *a, const int16_t *b, int16_t *o, int16_t *o2, const void *d_jobs, int n, int G )
 {
   const int    tabN    = OP == OP_SCALE ? 0 : 1 << ctx->lmcsLumaBD;
   const size_t lds     = ( size_t ) tabN * sizeof( int16_t );
-  const int    nGroups = ( n + G - 1 ) / G;
-  int          blocks  = ( nGroups + LM_WAVES - 1 ) / LM_WAVES;
-  if( blocks > ctx->numCUs * 8 ) blocks = ctx->numCUs * 8;   // the rest loop: the table is staged once per workgroup
+  const int    blocks  = wave_blocks( n, G, LM_WAVES, ctx->numCUs * 8 );   // the table is staged once per workgroup
   VTMHIP_TIME_KERNEL( ctx, "lmcs_op_kernel" );
   hipLaunchKernelGGL( lmcs_op_kernel<OP>, dim3( blocks ), dim3( 64 * LM_WAVES ), lds, ctx->stream, a, b, o, o2, d_jobs, n, G, ( const int16_t * ) ctx->lmcsFwd, tabN );
   VTMHIP_LAUNCHED( ctx );
@@ -293,7 +236,7 @@ int vtmhip_scaleSignal( vtmhip_ctx *ctx, int16_t *buf, int stride, int width, in
 int vtmhip_scale_signal_batch_dev( vtmhip_ctx *ctx, const int16_t *d_srcBase, int16_t *d_dstBase, const vtmhip_scale_job *d_jobs, int n )
 {
   VTMHIP_BATCH_ENTRY( ctx, n, d_srcBase && d_dstBase && d_jobs );
-  return lm_launch<OP_SCALE>( ctx, d_srcBase, nullptr, d_dstBase, nullptr, d_jobs, n, lm_jobs_per_wave( ctx, n ) );
+  return lm_launch<OP_SCALE>( ctx, d_srcBase, nullptr, d_dstBase, nullptr, d_jobs, n, wave_jobs_per_wave( ctx->numCUs, n ) );
 }
 
 int vtmhip_lmcs_resi_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_predBase, int16_t *d_resiBase, int16_t *d_dstBase,
@@ -302,7 +245,7 @@ int vtmhip_lmcs_resi_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const
   VTMHIP_CHECK_CTX( ctx );
   VTMHIP_REQUIRE( ctx, ctx->lmcsLumaBD != 0, "vtmhip_set_lmcs_fwd_lut has not been called" );
   VTMHIP_BATCH_ARGS( ctx, n, d_orgBase && d_predBase && d_resiBase && d_jobs );
-  return lm_launch<OP_RESI>( ctx, d_orgBase, d_predBase, d_resiBase, d_dstBase, d_jobs, n, lm_jobs_per_wave( ctx, n ) );
+  return lm_launch<OP_RESI>( ctx, d_orgBase, d_predBase, d_resiBase, d_dstBase, d_jobs, n, wave_jobs_per_wave( ctx->numCUs, n ) );
 }
 
 int vtmhip_lmcs_reco_batch_dev( vtmhip_ctx *ctx, const int16_t *d_predBase, const int16_t *d_resiBase, int16_t *d_dstBase, const vtmhip_lmcs_job *d_jobs, int n )
@@ -310,7 +253,7 @@ int vtmhip_lmcs_reco_batch_dev( vtmhip_ctx *ctx, const int16_t *d_predBase, cons
   VTMHIP_CHECK_CTX( ctx );
   VTMHIP_REQUIRE( ctx, ctx->lmcsLumaBD != 0, "vtmhip_set_lmcs_fwd_lut has not been called" );
   VTMHIP_BATCH_ARGS( ctx, n, d_predBase && d_resiBase && d_dstBase && d_jobs );
-  return lm_launch<OP_RECO>( ctx, d_predBase, d_resiBase, d_dstBase, nullptr, d_jobs, n, lm_jobs_per_wave( ctx, n ) );
+  return lm_launch<OP_RECO>( ctx, d_predBase, d_resiBase, d_dstBase, nullptr, d_jobs, n, wave_jobs_per_wave( ctx->numCUs, n ) );
 }
 
 }   // extern "C"

@@ -4,6 +4,8 @@
 #pragma once
 #include "ctx.hpp"
 #include "chroma_taps.hpp"
+#include "wave_pack.hpp"
+#include "pel_pack.hpp"
 
 namespace
 {
@@ -21,19 +23,6 @@ __constant__ int16_t c_lumaFilter4x4Mc[16][8] = {
 __constant__ int16_t c_altHpelMc[8] = { 0, 3, 9, 20, 20, 9, 3, 0 };
 
 struct Fir { int shift, offset, clip, cmax; };
-
-// p / d for 0 <= p with p * d < 2^32: multiply-high by floor(2^32 / d) and one correction step (4 instructions) instead of the generic ~25-instruction
-// integer division sequence; the constructor's division is wave-uniform, once per block
-struct FastDiv
-{
-  unsigned magic; int d;
-  __device__ __forceinline__ explicit FastDiv( int dd ) : magic( 0xffffffffu / ( unsigned ) dd ), d( dd ) {}
-  __device__ __forceinline__ int operator()( int p ) const
-  {
-    const int q = ( int ) __umulhi( ( unsigned ) p, magic );
-    return q + ( ( q + 1 ) * d <= p ? 1 : 0 );
-  }
-};
 
 // InterpolationFilter::filter shift/offset rules (:577-602); integer phases use taps {0,0,0,64,0,0,0,0}, which is
 // arithmetically identical to filterCopy (:398-525) for every (isFirst, isLast) pair that occurs here except
@@ -146,13 +135,6 @@ __device__ __forceinline__ void mc_block( const vtmhip_mc_job &j, const int16_t 
 
 
 // ---- 8 outputs per lane (blocks whose width is a multiple of 8): 16-byte loads / stores, each input sample fetched once per lane --------
-struct __attribute__( ( packed, aligned( 2 ) ) ) Pel8u { unsigned v[4]; };   // 8 samples at a 2-byte aligned address (global memory)
-
-__device__ __forceinline__ void unpack8( const unsigned u[4], int a[8] )
-{
-#pragma unroll
-  for( int k = 0; k < 4; k++ ) { a[2 * k] = ( int ) ( short ) ( u[k] & 0xffffu ); a[2 * k + 1] = ( int ) u[k] >> 16; }
-}
 __device__ __forceinline__ uint4 pack8( const int v[8] )
 {
   uint4 u;
@@ -162,15 +144,15 @@ __device__ __forceinline__ uint4 pack8( const int v[8] )
 }
 __device__ __forceinline__ void load8g( const int16_t *p, int a[8] )    // global, 2-byte aligned
 {
-  const Pel8u t = *reinterpret_cast<const Pel8u *>( p );
+  const Pel8 t = *reinterpret_cast<const Pel8 *>( p );
   unpack8( t.v, a );
 }
 __device__ __forceinline__ void store8g( int16_t *p, const int v[8] )
 {
   const uint4 u = pack8( v );
-  Pel8u       t;
+  Pel8       t;
   t.v[0] = u.x; t.v[1] = u.y; t.v[2] = u.z; t.v[3] = u.w;
-  *reinterpret_cast<Pel8u *>( p ) = t;
+  *reinterpret_cast<Pel8 *>( p ) = t;
 }
 __device__ __forceinline__ void load8s( const int16_t *p, int a[8] )    // LDS, 16-byte aligned
 {

@@ -13,6 +13,7 @@
 #include "ctx.hpp"
 #include "mest_glue.hpp"
 #include "mv_rules.hpp"
+#include "pel_pack.hpp"
 
 #include <cstdlib>
 
@@ -71,16 +72,10 @@ __device__ __forceinline__ Range search_range( const MeJob &j, int predHor, int 
   return sr;
 }
 
-// 8 / 4 consecutive samples from a 2-byte aligned address (gfx950 global memory handles the misalignment in hardware)
-struct __attribute__( ( packed, aligned( 2 ) ) ) Pel8 { unsigned v[4]; };
-struct __attribute__( ( packed, aligned( 2 ) ) ) Pel4 { unsigned v[2]; };
-
 // 8 (4) reference samples at a candidate's sample offset.  A multi-dword load whose address is only 2-byte aligned runs at 0.28x the rate of a 4-byte aligned one
 // on gfx950 (scripts/unaligned_load.hip: 9.2 vs 33 TB/s out of L2 / TCP), and half of all candidates sit at odd sample offsets -- so the segment is always
 // fetched from the dword below (one 16- / 8-byte load + the next dword, both 4-byte aligned) and funnel-shifted by 0 or 16 bits: no branch, the loads of an
 // unrolled trip still go out together.  Reads at most 2 bytes before and 4 bytes after the segment (inside the plane's margin rows / the next segment).
-struct __attribute__( ( packed, aligned( 4 ) ) ) Dw4 { unsigned v[4]; };
-struct __attribute__( ( packed, aligned( 4 ) ) ) Dw2 { unsigned v[2]; };
 __device__ __forceinline__ Pel8 ld8( const int16_t *p )
 {
   const unsigned  sh = ( ( unsigned ) reinterpret_cast<uintptr_t>( p ) & 2u ) << 3;

@@ -13,11 +13,10 @@
 // stages it in LDS, then writes the whole block (coded tile from LDS, zero elsewhere) and sums the uncoded tile's residual on the way.
 #include "ctx.hpp"
 #include "sbt_rules.hpp"
+#include "pel_pack.hpp"
 
 namespace
 {
-
-struct __attribute__( ( packed, aligned( 2 ) ) ) SPel2 { unsigned v; };
 
 __host__ __device__ inline bool sbt_side_ok( int s ) { return s >= 4 && s <= 64 && ( s & ( s - 1 ) ) == 0; }
 __host__ __device__ inline int  sbt_log2( int v ) { int r = 0; while( ( 1 << r ) < v ) r++; return r; }
@@ -62,7 +61,7 @@ __global__ __launch_bounds__( 256 ) void sbt_est_kernel( const int16_t *__restri
       {
         const int y = idx >> lgHalf, x = ( idx & ( ( 1 << lgHalf ) - 1 ) ) << 1;
         const int part = ( ( y >> lgLenY ) << 2 ) + ( x >> lgLenX );
-        const unsigned a = reinterpret_cast<const SPel2 *>( o + ( long ) y * os + x )->v, b = reinterpret_cast<const SPel2 *>( p + ( long ) y * ps + x )->v;
+        const unsigned a = reinterpret_cast<const Pel2 *>( o + ( long ) y * os + x )->v, b = reinterpret_cast<const Pel2 *>( p + ( long ) y * ps + x )->v;
         const int d0 = ( short ) ( a & 0xffffu ) - ( short ) ( b & 0xffffu ), d1 = ( ( int ) a >> 16 ) - ( ( int ) b >> 16 );
         if( part != cur )
         {

@@ -349,16 +349,16 @@ __device__ __forceinline__ void pred_tile( const int16_t *__restrict__ ref, int 
 #if VTMHIP_SMVD_PREFETCH
   // the next input row's two loads are issued BEFORE this row's filter work (the scheduling barrier at the end of a row keeps the compiler from hoisting all fifteen rows' loads --
   // registers -- but it also kept every row's loads behind the previous row's arithmetic: a full memory latency per row at two waves per SIMD)
-  Pel8u na = *reinterpret_cast<const Pel8u *>( src ), nb = *reinterpret_cast<const Pel8u *>( src + 8 );
+  Pel8 na = *reinterpret_cast<const Pel8 *>( src ), nb = *reinterpret_cast<const Pel8 *>( src + 8 );
 #endif
 #pragma unroll
   for( int r = 0; r < 15; r++ )
   {
 #if VTMHIP_SMVD_PREFETCH
-    const Pel8u a = na, b = nb;
-    if( r < 14 ) { na = *reinterpret_cast<const Pel8u *>( src + ( long ) ( r + 1 ) * stride ); nb = *reinterpret_cast<const Pel8u *>( src + ( long ) ( r + 1 ) * stride + 8 ); }
+    const Pel8 a = na, b = nb;
+    if( r < 14 ) { na = *reinterpret_cast<const Pel8 *>( src + ( long ) ( r + 1 ) * stride ); nb = *reinterpret_cast<const Pel8 *>( src + ( long ) ( r + 1 ) * stride + 8 ); }
 #else
-    const Pel8u a = *reinterpret_cast<const Pel8u *>( src + ( long ) r * stride ), b = *reinterpret_cast<const Pel8u *>( src + ( long ) r * stride + 8 );
+    const Pel8 a = *reinterpret_cast<const Pel8 *>( src + ( long ) r * stride ), b = *reinterpret_cast<const Pel8 *>( src + ( long ) r * stride + 8 );
 #endif
     const unsigned d[8] = { a.v[0], a.v[1], a.v[2], a.v[3], b.v[0], b.v[1], b.v[2], b.v[3] };   // d[m] = samples (2m, 2m + 1)
     unsigned e[7];                                                                             // e[m] = samples (2m + 1, 2m + 2)
@@ -487,15 +487,15 @@ __device__ __forceinline__ unsigned tile_eval( const TileJob &t, int tx, int ty,
   const int16_t *org = t.org + ( long ) ( ty * 8 ) * t.orgStride + tx * 8;
   v2s D[8][4];
 #if VTMHIP_SMVD_PREFETCH
-  Pel8u onx = *reinterpret_cast<const Pel8u *>( org );      // the original block's rows arrive one output row ahead, like the reference rows in pred_tile
+  Pel8 onx = *reinterpret_cast<const Pel8 *>( org );      // the original block's rows arrive one output row ahead, like the reference rows in pred_tile
 #endif
   pred_tile( t.refA + ( long ) ( ty * 8 ) * t.strideA + tx * 8, t.strideA, ax, ay, t.alt, t.f, [&]( int y, const unsigned w[4] )
   {
 #if VTMHIP_SMVD_PREFETCH
-    const Pel8u o = onx;
-    if( y < 7 ) onx = *reinterpret_cast<const Pel8u *>( org + ( long ) ( y + 1 ) * t.orgStride );
+    const Pel8 o = onx;
+    if( y < 7 ) onx = *reinterpret_cast<const Pel8 *>( org + ( long ) ( y + 1 ) * t.orgStride );
 #else
-    const Pel8u o = *reinterpret_cast<const Pel8u *>( org + ( long ) y * t.orgStride );
+    const Pel8 o = *reinterpret_cast<const Pel8 *>( org + ( long ) y * t.orgStride );
 #endif
 #pragma unroll
     for( int k = 0; k < 4; k++ )

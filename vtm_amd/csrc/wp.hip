@@ -3,9 +3,8 @@
 // addWeightBi (WeightPrediction.cpp:46-64, 157-226, 288-392).  Bit-exact with the scalar reference under the sample contract of include/vtmhip.h.
 // DISTORTION_PRECISION_ADJUSTMENT is 0 (FULL_NBIT, TypeDef.h:225-237): the reference's final `>> distortionShift` is a no-op and is left out.
 //
-// wp_dist_kernel (wave = 64 lanes, 4 waves per workgroup):
-//   - a wave takes G consecutive jobs (G <= 64, chosen by the host from n) and spreads their ITEMS over its lanes (wave prefix scan of the item counts):
-//     an item is one row of a SAD / SSE job, one Hadamard tile of a HAD job (8x8, 4x4, or one step of the 2x2 row walk); small blocks share a wave;
+// wp_dist_kernel (4 waves per workgroup) packs jobs into waves as wave_pack.hpp lays out, walked in wave-uniform steps of 64 items:
+//   - an item is one row of a SAD / SSE job, one Hadamard tile of a HAD job (8x8, 4x4, or one step of the 2x2 row walk);
 //   - the weighting is applied as the samples are loaded; a lane produces one 64-bit sum per item;
 //   - the items of a job lie on consecutive lanes in increasing row / tile order, so a segmented inclusive scan over the lanes (keyed by the job), carried
 //     from one 64-item step to the next through lane 63, gives every item the prefix sum of its job.  SADw's per-row early exit returns the FIRST prefix
@@ -16,6 +15,8 @@
 // wp_pred_kernel: one wave per job, 4-sample row segments over the lanes.
 #include "ctx.hpp"
 #include "stage.hpp"
+#include "wave_pack.hpp"
+#include "pel_pack.hpp"
 
 namespace
 {
@@ -58,12 +59,10 @@ struct WpJobL   // a job as the kernel uses it (LDS, one per lane of a group)
   int os, cs;
   int w, kind, mode, cmax;
   int wt, off, sh, rnd;
-  int tile, tpr;        // HAD: tile size 8 / 4 / 2 and tiles per row
-  unsigned magic;       // HAD: floor((2^32 - 1) / tpr): item -> (tile row, tile column) without a division
+  int tile;             // HAD: tile size 8 / 4 / 2
+  FastDiv tpr;          // HAD: tiles per row: item -> (tile row, tile column)
   unsigned long long maxDist;
 };
-
-struct __attribute__( ( packed, aligned( 2 ) ) ) WPel4 { unsigned v[2]; };
 
 __device__ __forceinline__ int wp_pred( const WpJobL &L, int c )
 {
@@ -78,14 +77,6 @@ __device__ __forceinline__ int wp_pred( const WpJobL &L, int c )
   }
 }
 
-// four consecutive samples of a row; the WPel4 load needs x + 4 <= width (2-byte aligned, like dist_wtd.hip)
-__device__ __forceinline__ void load4( const int16_t *p, int v[4] )
-{
-  const WPel4 a = *reinterpret_cast<const WPel4 *>( p );
-  v[0] = ( short ) ( a.v[0] & 0xffffu ); v[1] = ( int ) a.v[0] >> 16;
-  v[2] = ( short ) ( a.v[1] & 0xffffu ); v[3] = ( int ) a.v[1] >> 16;
-}
-
 // one row of SADw / SSEw
 __device__ __forceinline__ unsigned long long wp_row( const WpJobL &L, int r )
 {
@@ -96,8 +87,8 @@ __device__ __forceinline__ unsigned long long wp_row( const WpJobL &L, int r )
   for( ; x + 4 <= L.w; x += 4 )
   {
     int ov[4], cv[4];
-    load4( o + x, ov );
-    load4( c + x, cv );
+    ld4( o + x, 4, ov );
+    ld4( c + x, 4, cv );
 #pragma unroll
     for( int k = 0; k < 4; k++ )
     {
@@ -150,8 +141,8 @@ template<int N> __device__ __forceinline__ unsigned long long wp_had_tile( const
     for( int k = 0; k < N; k += 4 )
     {
       int ov[4], cv[4];
-      load4( o + k, ov );
-      load4( c + k, cv );
+      ld4( o + k, 4, ov );
+      ld4( c + k, 4, cv );
 #pragma unroll
       for( int i = 0; i < 4; i++ ) d[y * N + k + i] = ov[i] - ( int16_t ) ( ( ( L.wt * cv[i] + L.rnd ) >> L.sh ) + L.off );   // Pel pred, never clipped
     }
@@ -183,15 +174,13 @@ __device__ __forceinline__ unsigned long long wp_had_2x2( const WpJobL &L, int k
 __device__ __forceinline__ unsigned long long wp_item( const WpJobL &L, int local )
 {
   if( L.kind != VTMHIP_DIST_SATD ) return wp_row( L, local );
-  int ty = ( int ) __umulhi( ( unsigned ) local, L.magic );
-  ty += ( ty + 1 ) * L.tpr <= local ? 1 : 0;
-  const int tx = local - ty * L.tpr;
+  const int ty = L.tpr( local ), tx = local - ty * L.tpr.d;
   if( L.tile == 8 ) return wp_had_tile<8>( L, ty << 3, tx << 3 );
   if( L.tile == 4 ) return wp_had_tile<4>( L, ty << 2, tx << 2 );
   return wp_had_2x2( L, ty, tx << 1 );
 }
 
-// 4 waves per SIMD: the 8x8 tile's 64 differences fit in 125 VGPRs without scratch (unbounded, the compiler takes 135; at 5 it spills)
+// 4 waves per SIMD: the 8x8 tile's 64 differences fit in 124 VGPRs without scratch (unbounded, the compiler takes 135; at 5 it spills)
 __global__ __launch_bounds__( 64 * WP_WAVES, 4 ) void wp_dist_kernel( const int16_t *__restrict__ orgBase, const int16_t *__restrict__ curBase,
                                                                   const vtmhip_wp_dist_job *__restrict__ jobs, int n, int G, unsigned long long *__restrict__ out )
 {
@@ -199,16 +188,15 @@ __global__ __launch_bounds__( 64 * WP_WAVES, 4 ) void wp_dist_kernel( const int1
   __shared__ int    sEnd[WP_WAVES][64];   // inclusive prefix of the group's item counts
 
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int nGroups = ( n + G - 1 ) / G;
+  const int nGroups = wave_groups( n, G );
   // every wave of a workgroup runs the same number of rounds (the barriers below)
   for( int round = blockIdx.x * WP_WAVES; round < nGroups; round += gridDim.x * WP_WAVES )
   {
-    const int grp = round + wv, base = grp * G, job = base + lane;
-    const bool mine = grp < nGroups && lane < G && job < n;
+    const WaveGroup g( round, wv, lane, n, G, nGroups );
     int items = 0;
-    if( mine )
+    if( g.mine )
     {
-      const vtmhip_wp_dist_job j = jobs[job];
+      const vtmhip_wp_dist_job j = jobs[g.job];
       const int w = j.width, h = j.height, kind = j.kind;
       if( wp_dist_ok( w, h, kind, j.bitDepth, j.isBiPred, j.wp ) )
       {
@@ -224,27 +212,18 @@ __global__ __launch_bounds__( 64 * WP_WAVES, 4 ) void wp_dist_kernel( const int1
         if( kind == VTMHIP_DIST_SATD )
         {
           L.tile = ( ( w | h ) & 7 ) == 0 ? 8 : ( ( w | h ) & 3 ) == 0 ? 4 : 2;
-          L.tpr = w / L.tile;
-          L.magic = 0xffffffffu / ( unsigned ) L.tpr;
-          items = ( h / L.tile ) * L.tpr;
+          L.tpr = FastDiv( w / L.tile );
+          items = ( h / L.tile ) * L.tpr.d;
         }
         else items = h;
       }
-      else out[job] = VTMHIP_WP_INVALID_DIST;
+      else out[g.job] = VTMHIP_WP_INVALID_DIST;
     }
-    int incl = items;
-#pragma unroll
-    for( int o = 1; o < 64; o <<= 1 )
-    {
-      const int t = __shfl_up( incl, o, 64 );
-      if( lane >= o ) incl += t;
-    }
-    const int total = __shfl( incl, 63, 64 );
-    sEnd[wv][lane] = incl;
+    const int total = wave_scan_items( lane, items, sEnd[wv] );
     __syncthreads();
 
     // the wave walks the group's items 64 at a time; lane's item t = b + lane: its job index only grows
-    int                cj = -1, start = 0, end = 0;
+    WaveCursor         cur;
     WpJobL             L {};
     int                carryJob = -1;   // the job of lane 63 in the previous step and its prefix there
     unsigned long long carrySum = 0;
@@ -256,13 +235,9 @@ __global__ __launch_bounds__( 64 * WP_WAVES, 4 ) void wp_dist_kernel( const int1
       unsigned long long v   = 0;
       if( act )
       {
-        if( t >= end )
-        {
-          do { start = end; end = sEnd[wv][++cj]; } while( t >= end );   // skips jobs without items (rejected ones)
-          L = sJob[wv][cj];
-        }
-        v   = wp_item( L, t - start );
-        key = cj;
+        if( cur.beyond( t ) ) { cur.advance( t, sEnd[wv] ); L = sJob[wv][cur.cj]; }
+        v   = wp_item( L, t - cur.start );
+        key = cur.cj;
       }
       // segmented inclusive scan: the items of one job are consecutive lanes
 #pragma unroll
@@ -279,7 +254,7 @@ __global__ __launch_bounds__( 64 * WP_WAVES, 4 ) void wp_dist_kernel( const int1
       if( act )
       {
         const bool over = L.maxDist < prefix, wasOver = L.maxDist < prev;   // SADw: `if( maximumDistortionForEarlyExit < uiSum ) return uiSum` per row
-        if( ( over && !wasOver ) || ( !over && t == end - 1 ) ) out[base + cj] = prefix;
+        if( ( over && !wasOver ) || ( !over && t == cur.end - 1 ) ) out[g.base + cur.cj] = prefix;
       }
       carryJob = __shfl( key, 63, 64 );
       carrySum = __shfl( prefix, 63, 64 );
@@ -288,18 +263,9 @@ __global__ __launch_bounds__( 64 * WP_WAVES, 4 ) void wp_dist_kernel( const int1
   }
 }
 
-// jobs per wave: pack as many as still leave ~32 waves per CU (8 per SIMD), at most 64 (as dist_wtd.hip)
-int wp_jobs_per_wave( const vtmhip_ctx *ctx, int n )
-{
-  const int g = n / ( ctx->numCUs * 32 );
-  return g < 1 ? 1 : g > 64 ? 64 : g;
-}
-
 int wp_dist_launch( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_curBase, const vtmhip_wp_dist_job *d_jobs, int n, int G, unsigned long long *d_out )
 {
-  const int nGroups = ( n + G - 1 ) / G;
-  int       blocks  = ( nGroups + WP_WAVES - 1 ) / WP_WAVES;
-  if( blocks > ctx->numCUs * 64 ) blocks = ctx->numCUs * 64;   // the rest loop
+  const int blocks = wave_blocks( n, G, WP_WAVES, ctx->numCUs * 64 );
   VTMHIP_TIME_KERNEL( ctx, "wp_dist_kernel" );
   hipLaunchKernelGGL( wp_dist_kernel, dim3( blocks ), dim3( 64 * WP_WAVES ), 0, ctx->stream, d_orgBase, d_curBase, d_jobs, n, G, d_out );
   VTMHIP_LAUNCHED( ctx );
@@ -396,7 +362,7 @@ int vtmhip_xGetHADsw( vtmhip_ctx *ctx, const int16_t *org, int orgStride, const 
 int vtmhip_wp_dist_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_curBase, const vtmhip_wp_dist_job *d_jobs, int n, uint64_t *d_dist )
 {
   VTMHIP_BATCH_ENTRY( ctx, n, d_orgBase && d_curBase && d_jobs && d_dist );
-  return wp_dist_launch( ctx, d_orgBase, d_curBase, d_jobs, n, wp_jobs_per_wave( ctx, n ), ( unsigned long long * ) d_dist );
+  return wp_dist_launch( ctx, d_orgBase, d_curBase, d_jobs, n, wave_jobs_per_wave( ctx->numCUs, n ), ( unsigned long long * ) d_dist );
 }
 
 int vtmhip_wp_pred_batch_dev( vtmhip_ctx *ctx, const int16_t *d_src0Base, const int16_t *d_src1Base, int16_t *d_dstBase, const vtmhip_wp_pred_job *d_jobs, int n )
