@@ -1421,8 +1421,8 @@ int vtmhip_sbt_struct_size( int which );   /* sizeof() of 0 vtmhip_sbt_est_job, 
  *   planar, DC        xPredIntraPlanar :294-348, xGetPredValDc :153-182, their PDPC :244-265
  *   angular           xPredIntraAng :459-643: pure horizontal / vertical with the clipped PDPC, the extension of the main reference through invAngle for negative
  *                     angles, the replication of its last sample for positive ones, the cubic (H.266 table 28) or smoothing taps on fractional slopes, the PDPC column
- * MIP, ISP, BDPCM, chroma, IntraSmoothingDisabled, the availability analysis that fills the reference samples (xFillReferenceSamples), the mode bits and the
- * candidate lists stay the caller's. */
+ * MIP, ISP, BDPCM, IntraSmoothingDisabled, the availability analysis that fills the reference samples (xFillReferenceSamples), the mode bits and the
+ * candidate lists stay the caller's.  Chroma has entries of its own below (vtmhip_intra_chroma_*). */
 typedef struct
 {
   int32_t predMode;            /* the mode after the wide-angle shift: -14 .. 80 (what the angle is taken from) */
@@ -1481,6 +1481,71 @@ int vtmhip_intra_presel_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, co
 int vtmhip_intra_lanes_per_job( int maxArea );
 
 int vtmhip_intra_struct_size( int which );   /* sizeof() of 0 vtmhip_intra_params, 1 vtmhip_intra_block, 2 vtmhip_intra_job; -1 otherwise */
+
+/* ---- intra chroma prediction for 4:2:0, Cb and Cr together, without BDPCM: the regular modes of a chroma block and the cross-component linear model
+ * (LM 67, MDLM_L 68, MDLM_T 69; CommonDef.h:256-260), and the mode pre-selection of IntraSearch::estIntraPredChromaQT (EncoderLib/IntraSearch.cpp:1308-1414)
+ * fused on top of them.  One definition for host and device, vtm_amd/csrc/cclm_rules.hpp and intra_rules.hpp:
+ *   regular modes     predIntraAng with !isLuma: no reference filter, no smoothing taps, the two-tap rule on fractional slopes (IntraPrediction.cpp:592-604); wide
+ *                     angles, PDPC and DC from the chroma block's own width and height.  The mode is the final one (DM resolved by the caller).
+ *   down-sampling     xGetLumaRecPixels :1324-1579: the 6-tap default, the 5-tap cross (sps_cclm_colocated_chroma_flag), the one-row 3-tap of the top neighbour
+ *                     row in the first row of a CTU, leftPadding / abovePadding, the left column from luma columns -3 .. -1
+ *   model             xGetLMParameters :1580-1795: template lengths, the four picked pairs, the min / max grouping, the division by the significand table
+ *   prediction        clip( ( ( a * ds ) >> shift ) + b ), predIntraChromaLM :268-288
+ * The availability analysis stays the caller's: it hands over the flags and counts below with the unfiltered Cb and Cr reference lines (as for luma, multiRefIdx 0)
+ * and the luma reconstruction.  Chroma sides are 4, 8, 16 and 32; a side of 2 (the chroma of a 4-wide or 4-high luma CU) is NOT covered and such a block is
+ * skipped as malformed.  BDPCM, 4:2:2 / 4:4:4, the mode bits and the candidate lists stay the caller's. */
+typedef struct
+{
+  int64_t cbRefOff, crRefOff;   /* the component's top line d_refBase[off .. off + 2W], index 0 = the corner; its left line follows directly: 2H + 1 samples */
+  int64_t cbOrgOff, crOrgOff;   /* original blocks inside d_orgBase (pre-selection only) */
+  int64_t lumaOff;              /* inside d_lumaBase: the luma reconstruction sample under chroma (0, 0).  Read around it (LM modes only): columns 0 .. 2W - 1 of
+                                   rows 0 .. 2H - 1; with above, rows -3 .. -1 of columns (left ? -3 : 0) .. 2 (W + aboveRight) - 1; with left, columns -3 .. -1 of
+                                   rows (above ? -3 : 0) .. 2 (H + belowLeft) - 1 */
+  int32_t orgStride, lumaStride;
+  int16_t width, height;            /* 4, 8, 16, 32 each; every combination */
+  int16_t aboveRight, belowLeft;    /* available chroma samples beyond the block: multiples of 2, at most width / height, 0 without above / left */
+  uint8_t bitDepth;                 /* 8 .. 12 */
+  uint8_t above, left;              /* 0 / 1: the whole above row / left column of the block is available */
+  uint8_t firstRow;                 /* 0 / 1: the block lies in the first luma row of its CTU */
+  uint8_t colocated;                /* 0 / 1: sps_cclm_colocated_chroma_flag */
+  uint8_t reserved[3];              /* 0 */
+} vtmhip_intra_chroma_block;
+
+typedef struct
+{
+  int64_t cbPredOff, crPredOff;   /* vtmhip_intra_chroma_pred_batch_dev only: the W x H predictions (stride W) inside d_predBase */
+  int32_t block;                  /* index into d_blocks */
+  uint8_t mode;                   /* 0 .. 66 regular, 67 LM, 68 MDLM_L, 69 MDLM_T */
+  uint8_t reserved[3];            /* 0 */
+} vtmhip_intra_chroma_job;
+
+typedef struct
+{
+  int32_t a, b, shift;
+} vtmhip_cclm_model;
+
+/* xGetLMParameters of one (block, component 0 Cb / 1 Cr, mode 67 .. 69): host arithmetic on host pointers, no context -- the block's offsets index refBase and
+ * lumaBase as they index the device buffers below.  A malformed block, another mode or component, or a NULL pointer returns VTMHIP_E_INVALID. */
+int vtmhip_cclm_params( const vtmhip_intra_chroma_block *block, const int16_t *refBase, const int16_t *lumaBase, int component, int mode, vtmhip_cclm_model *out );
+
+/* The Cb and Cr predictions of n (block, mode) jobs: job k writes width x height samples with stride width at d_predBase + cbPredOff and + crPredOff.  Jobs of
+ * one block that follow each other in d_jobs share one load of its lines and -- when one of them is an LM mode -- one down-sampling of its luma block; any order
+ * is allowed.  d_lumaBase is read only through blocks that an LM job names.
+ * NULL pointers, n < 0, numBlocks < 0 and numBlocks == 0 with n > 0 return VTMHIP_E_INVALID; n == 0 is VTMHIP_OK.  The tables stay on the device: a job whose
+ * block index is outside [0, numBlocks) or whose mode is above 69, and every job of a block with a side outside 4 / 8 / 16 / 32, a bitDepth outside 8 .. 12, a
+ * flag above 1 or inconsistent availability (aboveRight without above, belowLeft without left, a count that is odd, negative or beyond the side) is skipped --
+ * nothing is read through it and its output is not written.  The largest well-formed block decides how many lanes a job gets (vtmhip_intra_lanes_per_job: 16 or
+ * 64 here); a small kernel finds it, so there is no read-back. */
+int vtmhip_intra_chroma_pred_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_lumaBase, const vtmhip_intra_chroma_block *d_blocks, int numBlocks,
+                                        const vtmhip_intra_chroma_job *d_jobs, int n, int16_t *d_predBase );
+
+/* The same predictions formed in LDS and consumed there: d_dist[4 k + 0 .. 3] = SAD Cb, SATD Cb, SAD Cr, SATD Cr of job k against its block's originals, the SATD
+ * under the xGetHADs tile rules.  No sample of a prediction goes to global memory; the prediction offsets are ignored.  min( 2 * SAD, SATD ) per component, their
+ * sum, the sort and the mode bits stay the caller's.  Checks and skipped jobs as above (all four entries of a skipped job are left). */
+int vtmhip_intra_chroma_presel_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_lumaBase, const int16_t *d_orgBase,
+                                          const vtmhip_intra_chroma_block *d_blocks, int numBlocks, const vtmhip_intra_chroma_job *d_jobs, int n, uint64_t *d_dist );
+
+int vtmhip_intra_chroma_struct_size( int which );   /* sizeof() of 0 vtmhip_intra_chroma_block, 1 vtmhip_intra_chroma_job, 2 vtmhip_cclm_model; -1 otherwise */
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,4 @@
-// intra_rules.hpp -- the luma intra prediction rules of the reference (no ISP, MIP or BDPCM), defined once for host and device: plain integer functions without a HIP
+// intra_rules.hpp -- the intra prediction rules of the reference for the regular modes (no ISP, MIP or BDPCM; luma, and chroma through the `chroma` argument), defined once for host and device: plain integer functions without a HIP
 // dependency, so host/test_intra.cpp compiles them with g++ and the kernels of intra.hip use the same text.
 //   intraWideAngle          IntraPrediction::getModifiedWideAngle                              CommonLib/IntraPrediction.cpp:184-204
 //   intraPredParams         IntraPrediction::initPredIntraParams, m_aucIntraFilter             :356-444, :58-68
@@ -49,7 +49,8 @@ INTRA_HD int intraWideAngle( int w, int h, int mode )
   return mode;
 }
 
-INTRA_HD void intraPredParams( int w, int h, int mode, int m, vtmhip_intra_params &p )
+// chroma: a chroma block (m = 0) -- no filter of either kind (:409); everything else, wide angles and PDPC included, from the block's own width and height
+INTRA_HD void intraPredParams( int w, int h, int mode, int m, vtmhip_intra_params &p, bool chroma = false )
 {
   const int angTable[32]    = { 0, 1, 2, 3, 4, 6, 8, 10, 12, 14, 16, 18, 20, 23, 26, 29, 32, 35, 39, 45, 51, 57, 64, 73, 86, 102, 128, 171, 256, 341, 512, 1024 };
   const int invAngTable[32] = { 0,   16384, 8192, 5461, 4096, 2731, 2048, 1638, 1365, 1170, 1024, 910, 819, 712, 630, 565,
@@ -80,7 +81,7 @@ INTRA_HD void intraPredParams( int w, int h, int mode, int m, vtmhip_intra_param
       if( p.angularScale < 0 ) p.applyPDPC = 0;
     }
   }
-  if( m != 0 || mode == INTRA_DC ) return;
+  if( m != 0 || mode == INTRA_DC || chroma ) return;
   if( mode == INTRA_PLANAR ) { p.refFilterFlag = w * h > 32; return; }
   const int diff = intraMin( intraAbs( predMode - INTRA_HOR ), intraAbs( predMode - INTRA_VER ) );
   if( diff > mdisThreshold[( intraLog2( w ) + intraLog2( h ) ) >> 1] )
@@ -156,7 +157,8 @@ INTRA_HD int intraRefMain( const int16_t *mainLine, const int16_t *sideLine, int
 }
 
 // cubic: the 32 x 4 taps of chroma_taps.hpp.  Horizontal modes are the vertical rule on the transposed block: (r, c) = (row, column) of that block.
-INTRA_HD int16_t intraAngularSample( const vtmhip_intra_params &p, const IntraBlk &b, const int16_t ( *cubic )[4], int x, int y )
+// chroma: a fractional slope takes the two-tap rule without a clip (:592-604) and cubic is not read.
+INTRA_HD int16_t intraAngularSample( const vtmhip_intra_params &p, const IntraBlk &b, const int16_t ( *cubic )[4], int x, int y, bool chroma = false )
 {
   const bool ver = p.isModeVer != 0;
   const int  r = ver ? y : x, c = ver ? x : y, mainSize = ver ? b.w : b.h, sideSize = ver ? b.h : b.w;
@@ -178,7 +180,12 @@ INTRA_HD int16_t intraAngularSample( const vtmhip_intra_params &p, const IntraBl
   }
   const int deltaPos = angle * ( r + 1 + b.m ), deltaInt = deltaPos >> 5, deltaFract = deltaPos & 31, i0 = b.m + deltaInt + c;
   int v;
-  if( !intraIntegerSlope( intraAbs( angle ) ) )
+  if( chroma && !intraIntegerSlope( intraAbs( angle ) ) )
+  {
+    const int p0 = intraRefMain( mainLine, sideLine, i0 + 1, p.invAngle, mainLast, sideSize, sideLast ), p1 = intraRefMain( mainLine, sideLine, i0 + 2, p.invAngle, mainLast, sideSize, sideLast );
+    v = ( int16_t ) ( p0 + ( ( deltaFract * ( p1 - p0 ) + 16 ) >> 5 ) );
+  }
+  else if( !intraIntegerSlope( intraAbs( angle ) ) )
   {
     const int half = deltaFract >> 1;
     int f0, f1, f2, f3;
@@ -199,9 +206,9 @@ INTRA_HD int16_t intraAngularSample( const vtmhip_intra_params &p, const IntraBl
 }
 
 // b: the lines already chosen by p.refFilterFlag; dcVal: intraDcVal( b ), needed for mode 1 only
-INTRA_HD int16_t intraPredSample( const vtmhip_intra_params &p, int mode, const IntraBlk &b, int dcVal, const int16_t ( *cubic )[4], int x, int y )
+INTRA_HD int16_t intraPredSample( const vtmhip_intra_params &p, int mode, const IntraBlk &b, int dcVal, const int16_t ( *cubic )[4], int x, int y, bool chroma = false )
 {
-  if( mode > INTRA_DC ) return intraAngularSample( p, b, cubic, x, y );
+  if( mode > INTRA_DC ) return intraAngularSample( p, b, cubic, x, y, chroma );
   const int v = mode == INTRA_PLANAR ? intraPlanarSample( b, x, y ) : dcVal;
   return p.applyPDPC ? intraPdpcSample( b, x, y, v ) : ( int16_t ) v;
 }

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib as _lib
-from .lib import (AffineJob, DistJob, FracJob, FracResult, FullJob, IctJob, IfJob, IntraBlock, IntraJob, IntraParams, JccrJob, JccrResult, LmcsJob, McJob, MeResult, PelOpJob, PicParams, QuantJob,   # noqa: F401
+from .lib import (AffineJob, DistJob, FracJob, FracResult, FullJob, IctJob, IfJob, IntraBlock, IntraChromaBlock, IntraChromaJob, IntraJob, IntraParams, CclmModel, JccrJob, JccrResult, LmcsJob, McJob, MeResult, PelOpJob, PicParams, QuantJob,   # noqa: F401
                   SbtEstJob, SbtEstResult, SbtJob, SbtResult, ScaleJob, TrJob, TuJob, TuResult, TzJob, VtmHipError, WpDistJob, WpParam, WpPredJob, WtdJob)
 
 
@@ -497,6 +497,40 @@ class Context:
             b.free()
         return res
 
+    def intra_chroma_pred_batch(self, d_ref, d_luma, d_blocks, num_blocks, d_jobs, n, d_pred):
+        """the Cb and Cr predictions (regular modes 0 .. 66, LM 67, MDLM_L 68, MDLM_T 69) of n IntraChromaJob pairs over num_blocks IntraChromaBlock entries"""
+        self._check(self.L.vtmhip_intra_chroma_pred_batch_dev(self.h, d_ref, d_luma, d_blocks, num_blocks, d_jobs, n, d_pred))
+
+    def intra_chroma_presel_batch(self, d_ref, d_luma, d_org, d_blocks, num_blocks, d_jobs, n, d_dist):
+        """the same predictions kept on chip: d_dist[4 k ..] = SAD Cb, SATD Cb, SAD Cr, SATD Cr of job k against its block's originals"""
+        self._check(self.L.vtmhip_intra_chroma_presel_batch_dev(self.h, d_ref, d_luma, d_org, d_blocks, num_blocks, d_jobs, n, d_dist))
+
+    def intra_chroma_presel(self, blocks, luma, org=None):
+        """Host convenience over the two entries.  blocks: a list of dicts with `lines` = ((Cb top, Cb left), (Cr top, Cr left)) (numpy, 2W + 1 and 2H + 1 samples),
+        `w`, `h`, `bd`, `above`, `left`, `ar`, `bl`, `first_row`, `coloc`, `luma_off`, `luma_stride` into the int16 array `luma`, `modes` and -- for the
+        pre-selection -- `org_off` = (Cb, Cr), `org_stride` into the int16 array `org`.  With `org` it returns a uint64 array [jobs, 4] of (SAD Cb, SATD Cb, SAD Cr,
+        SATD Cr) in block-then-mode order, without it the list of predictions [2, h, w] in the same order."""
+        tables, refs, acc = pack_intra_chroma_tables(blocks)
+        blk_arr, job_arr, n = tables
+        bufs = [self.to_device(refs), self.to_device(np.ascontiguousarray(luma, np.int16).reshape(-1)), self.to_device(struct_array_to_numpy(blk_arr)),
+                self.to_device(struct_array_to_numpy(job_arr))]
+        d_ref, d_luma, d_blk, d_job = bufs
+        if org is not None:
+            bufs += [self.to_device(np.ascontiguousarray(org, np.int16).reshape(-1)), self.alloc(32 * max(n, 1))]
+            self.intra_chroma_presel_batch(d_ref.ptr, d_luma.ptr, bufs[4].ptr, d_blk.ptr, len(blocks), d_job.ptr, n, bufs[5].ptr)
+            self.sync()
+            res = bufs[5].to_host(np.uint64).reshape(-1, 4)[:n]
+        else:
+            bufs.append(self.alloc(2 * max(acc, 1)))
+            self.intra_chroma_pred_batch(d_ref.ptr, d_luma.ptr, d_blk.ptr, len(blocks), d_job.ptr, n, bufs[4].ptr)
+            self.sync()
+            flat = bufs[4].to_host(np.int16)
+            res = [flat[j.cbPredOff:j.cbPredOff + 2 * blocks[j.block]["w"] * blocks[j.block]["h"]].reshape(2, blocks[j.block]["h"], blocks[j.block]["w"])
+                   for j in job_arr[:n]]
+        for b in bufs:
+            b.free()
+        return res
+
     def scale_signal_batch(self, d_src, d_dst, d_jobs, n):
         """scaleSignal of n ScaleJob blocks, each with its own scale and direction (d_dst may be d_src: in place)"""
         self._check(self.L.vtmhip_scale_signal_batch_dev(self.h, d_src, d_dst, d_jobs, n))
@@ -548,6 +582,45 @@ def pack_intra_tables(blocks):
             pred_off += b["w"] * b["h"]
     job_arr = (IntraJob * max(len(jobs), 1))(*jobs)
     return (blk_arr, job_arr, len(jobs)), (np.concatenate(refs) if refs else np.zeros(1, np.int16)), pred_off
+
+
+def chroma_block_record(b, cb_ref_off, cr_ref_off):
+    """the IntraChromaBlock of a block dict (see Context.intra_chroma_presel) whose lines start at the two offsets"""
+    org = b.get("org_off", (0, 0))
+    return IntraChromaBlock(cb_ref_off, cr_ref_off, org[0], org[1], b["luma_off"], b.get("org_stride", 0), b["luma_stride"], b["w"], b["h"], b["ar"], b["bl"], b["bd"],
+                            int(b["above"]), int(b["left"]), int(b["first_row"]), int(b["coloc"]))
+
+
+def pack_intra_chroma_tables(blocks):
+    """IntraChromaBlock / IntraChromaJob tables of a list of block dicts: ((blocks, jobs, n), the concatenated int16 lines, prediction samples); the Cr prediction
+    of a job follows its Cb prediction"""
+    blk_arr = (IntraChromaBlock * max(len(blocks), 1))()
+    refs, jobs, ref_off, pred_off = [], [], 0, 0
+    for i, b in enumerate(blocks):
+        offs = []
+        for top, left in b["lines"]:
+            top, left = np.asarray(top, np.int16), np.asarray(left, np.int16)
+            assert top.size == 2 * b["w"] + 1 and left.size == 2 * b["h"] + 1
+            offs.append(ref_off)
+            refs += [top, left]
+            ref_off += top.size + left.size
+        blk_arr[i] = chroma_block_record(b, offs[0], offs[1])
+        for mode in b["modes"]:
+            jobs.append(IntraChromaJob(pred_off, pred_off + b["w"] * b["h"], i, mode))
+            pred_off += 2 * b["w"] * b["h"]
+    job_arr = (IntraChromaJob * max(len(jobs), 1))(*jobs)
+    return (blk_arr, job_arr, len(jobs)), (np.concatenate(refs) if refs else np.zeros(1, np.int16)), pred_off
+
+
+def cclm_params(block, ref, luma, component, mode):
+    """xGetLMParameters of one (block dict, component 0 Cb / 1 Cr, mode 67 .. 69) as (a, b, shift): host arithmetic on numpy arrays, no device.  The block's lines
+    are taken from the int16 array `ref` at `ref_off` = (Cb, Cr), its luma from the int16 array `luma`."""
+    ref, luma = np.ascontiguousarray(ref, np.int16), np.ascontiguousarray(luma, np.int16)
+    rec, out = chroma_block_record(block, block["ref_off"][0], block["ref_off"][1]), CclmModel()
+    st = _lib.load().vtmhip_cclm_params(C.byref(rec), ref.ctypes.data, luma.ctypes.data, component, mode, C.byref(out))
+    if st != _lib.OK:
+        raise VtmHipError(st)
+    return out.a, out.b, out.shift
 
 
 def ict_select(dist, is_intra):
