@@ -1065,6 +1065,7 @@ __global__ __launch_bounds__( 256 ) void tz_raster_cols_kernel( vtmhip_pic_param
   const int lane = threadIdx.x & 63, wv = uni( ( int ) ( threadIdx.x >> 6 ) );
   const int count = list[0];
   const int part = parts > 1 ? ( int ) blockIdx.x % parts : 0, eStride = parts > 1 ? ( int ) gridDim.x / parts : ( int ) gridDim.x;
+  // (more than one pass per workgroup, i.e. more listed scans than the grid: tests/test_gpu_tz_batch_sizes.py)
   for( int e = parts > 1 ? ( int ) blockIdx.x / parts : ( int ) blockIdx.x; e < count; e += eStride )
   {
     const int            jobIdx = list[1 + e];
@@ -1556,6 +1557,7 @@ void tz_search_kernel( vtmhip_pic_params pic, const int16_t *__restrict__ orgBas
     // the resume launch of a level of small blocks: only the listed searches run (a few per cent of the level), and a grid of one workgroup per four searches of the LEVEL would be
     // 130 000 workgroups that leave at once -- 50 us of a launch for nothing.  A bounded grid walks the list instead (the waves of a workgroup are independent searches here)
     const int listed = uni( list[0] );
+    // (more than one pass per workgroup, i.e. more than 4 * 2048 listed searches: tests/test_gpu_tz_batch_sizes.py)
     for( int b = ( int ) blockIdx.x; b * 4 < listed; b += ( int ) gridDim.x )
       tz_search_one<WPJ, K>( pic, orgBase, refBase, jobs, numJobs, results, mode, saved, list, totCap, fu, b, ( int ) gridDim.x );
     return;
@@ -2333,6 +2335,7 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
   {
     // few searches (one band of a sharded picture): several workgroups per raster scan, so that the scans of a 128x128 level still fill the GPU
     static const bool splitScan = env_switch( "VTMHIP_RASTER_PARTS", true );
+    // (every value of rasterParts, the hint's 4 and the 64 MB bound below: tests/test_gpu_tz_batch_sizes.py, raster_parts)
     rasterParts = ( splitScan && n <= 640 ) ? ( 1280 / n < 8 ? 1280 / n : 8 ) : 1;
     if( totCap > RASTER_TOT_CAP && splitScan && n <= 4096 && rasterParts < 4 ) rasterParts = 4;      // big scans (one workgroup per CU by LDS): a few workgroups per scan balance the tail   // aim at the 1280 resident workgroups (5 per CU); twice that measured slower
     const size_t oList = ( ( size_t ) n * sizeof( TzSaved ) + 255 ) & ~( size_t ) 255;
@@ -2369,6 +2372,7 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
   case 4: VTMHIP_TZ_LAUNCH( 4, n, MODE ); break;                    \
   case 8: VTMHIP_TZ_LAUNCH( 8, n, MODE ); break;                    \
   case 16: VTMHIP_TZ_LAUNCH( 16, n, MODE ); break;                  \
+  /* (the bounded resume grid, RESUME_GRID of tests/test_gpu_tz_batch_sizes.py) */ \
   default: VTMHIP_TZ_LAUNCH( 1, ( ( MODE ) == 2 && ( n + 3 ) / 4 > 2048 ? 2048 : ( n + 3 ) / 4 ), MODE ); break; \
   }
   // Uniform batches of small blocks (fused uni rows, no extended settings): four searches per wave, a lane per candidate (tz_group_kernel).  VTMHIP_TZ_GROUP=0: off;
@@ -2428,6 +2432,7 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
         VTMHIP_HIP( ctx, hipStreamWaitEvent( ctx->stream, ctx->tzSumsReady, 0 ) );
         ctx->tzSumsJoined = ctx->stream;
       }
+      // (the grid of one workgroup per scan, COLS_GRID of tests/test_gpu_tz_batch_sizes.py)
       hipLaunchKernelGGL( tz_raster_cols_kernel, dim3( rasterParts > 1 ? n * rasterParts : ( n < 3072 ? n : 3072 ) ), dim3( 256 ), totLds, ctx->stream, *pic, d_orgBase,
                           d_refBase, d_jobs, d_saved, d_list, d_tot, rasterParts, totCap, d_sums, ctx->tzStats );
     }
