@@ -1315,10 +1315,17 @@ int vtmhip_tz_band_items( int width, int height, int subShift, int wavesPerJob )
  *     raster launches on the main stream, ordered by events inside the call.
  *   vtmhip_tz_prune_stats: stats[6] = raster scans listed for the column kernel, scans skipped, scans reduced to a proper sub-rectangle, grid points evaluated, grid
  *     points of all listed scans, scans whose winner was below the best cost on entry (the search accepts it) -- of this context since the last reset (stats may be NULL; reset != 0 clears).  Synchronises the context's stream.
- * VTMHIP_TZ_PRUNE=0 in the environment: the sums are ignored (and the picture loop computes none). */
+ * ROUND BOUND: the same sums rule out candidates of the diamond, star and two-point rounds in the fused uniform launches of 128x128 and 128x64 rows at
+ * wavesPerJob 8 (subShift 0, bitDepth <= 10, unsigned samples): a round first forms each candidate's bound (512 B against the 32 KB of its samples) and evaluates only
+ * the candidates whose bound + MV rate is below the best cost the search holds.  Results, nEval and vtmhip_tz_prune_stats do not change.
+ *   vtmhip_tz_round_stats: stats[7] = rounds bounded, candidates listed in them, candidates skipped of the first launches (modes 0 / 1), the same three of the resume
+ *     launches (mode 2), and `violations`: evaluated candidates whose exact SAD came out below their bound -- the kernel's own check that sums and planes are
+ *     congruent, 0 unless the CONTRACT above is broken.  Of this context since the last reset (stats may be NULL; reset != 0 clears).  Synchronises the context's stream.
+ * VTMHIP_TZ_PRUNE=0 in the environment: the sums are ignored (and the picture loop computes none).  VTMHIP_TZ_ROUND_BOUND=0: the list rounds ignore them. */
 int vtmhip_tz_box_sums_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, uint16_t *d_sumBase, int64_t planeOff, int stride, int width, int height, int margin );
 int vtmhip_tz_attach_sums( vtmhip_ctx *ctx, const int16_t *d_refBase, const uint16_t *d_sumBase, int width, int height, int margin );
 int vtmhip_tz_prune_stats( vtmhip_ctx *ctx, uint64_t *stats, int reset );
+int vtmhip_tz_round_stats( vtmhip_ctx *ctx, uint64_t *stats, int reset );
 
 /* ---- sub-block transform (SBT) of inter CUs: the mode estimator and the SBT candidates of xEstimateInterResidualQT --------------------------------
  * (CodingUnit::checkAllowedSbt Unit.cpp:450-494; CU::getSbtMode ... numSbtModeRdo UnitTools.cpp:3516-3589; PartitionerImpl::getSbtTuTiling

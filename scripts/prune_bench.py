@@ -1,7 +1,8 @@
 """Raster pruning on content the bound does not favour: the uniform 128x128 uni batch (vtmhip_xMotionEstimation_batch_dev, zero predictors, search range 96) of a
 3840x2160 picture of the hard clip (synth.gen_frames_hard, two textures moving in opposite directions + sigma-10 noise) at dPOC 2 and 4, and of the benchmark's clip
 (synth.gen_frames, a pure pan; dPOC 4 -- at dPOC 2 the diamond reaches the motion and no search comes to a scan) for contrast -- with the box sums attached and without.  Prints, per clip: ms of the batch and of its tz_raster_cols_kernel launch (HIP
-events), ms of the box-sum pass, the statistic (share of scans skipped / reduced, grid points evaluated / total) and a checksum of the records (equal on and off)."""
+events), ms of the two tz_search launches together (first and resume; VTMHIP_TZ_ROUND_BOUND=0 in the environment: without the round bound), the round
+statistic (vtmhip_tz_round_stats of one batch), ms of the box-sum pass, the statistic (share of scans skipped / reduced, grid points evaluated / total) and a checksum of the records (equal on and off)."""
 import ctypes as C
 import json
 import os
@@ -51,6 +52,7 @@ def main():
             torch.cuda.synchronize()
             reps = 5
             ctx.tz_prune_stats(reset=True)
+            ctx.tz_round_stats(reset=True)
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
             ev[0].record()
             for _ in range(reps):
@@ -58,13 +60,15 @@ def main():
             ev[1].record()
             torch.cuda.synchronize()
             st = ctx.tz_prune_stats()
+            rs = {k: v // reps for k, v in ctx.tz_round_stats().items()}
             ctx.kernel_timing(True)
             once()
             raster_ms, _ = ctx.kernel_timing_read("tz_raster_cols_kernel")
             box_ms, _ = ctx.kernel_timing_read("box_sum8_kernel")
+            search_ms, search_n = ctx.kernel_timing_read("tz_search_kernel")
             ctx.kernel_timing(False)
             res = np.frombuffer(d_res.to_host(np.uint8).tobytes(), np.dtype(MeOut))
-            row[mode] = dict(batch_ms=round(ev[0].elapsed_time(ev[1]) / reps, 3), raster_ms=round(raster_ms, 3), box_sum_ms=round(box_ms, 3),
+            row[mode] = dict(batch_ms=round(ev[0].elapsed_time(ev[1]) / reps, 3), raster_ms=round(raster_ms, 3), search_ms=round(search_ms, 3), search_launches=search_n, round_stats=rs, box_sum_ms=round(box_ms, 3),
                              listed=st["listed"] // reps, skipped_share=round(st["skipped"] / max(1, st["listed"]), 3), reduced_share=round(st["reduced"] / max(1, st["listed"]), 3),
                              accepted_share=round(st["accepted"] / max(1, st["listed"]), 3), points_evaluated=st["points_evaluated"] // reps, points_total=st["points_total"] // reps,
                              checksum=int(res["cost"].astype(np.uint64).sum() % (1 << 31)))

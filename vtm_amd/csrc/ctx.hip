@@ -84,7 +84,8 @@ int vtmhip_create( int device, vtmhip_ctx **out )
   ctx->device = device;
   if( hipSetDevice( device ) != hipSuccess || hipStreamCreateWithFlags( &ctx->ownStream, hipStreamNonBlocking ) != hipSuccess ||
       hipEventCreate( &ctx->evStart ) != hipSuccess || hipEventCreate( &ctx->evStop ) != hipSuccess ||
-      hipMalloc( ( void ** ) &ctx->tzStats, 6 * sizeof( unsigned long long ) ) != hipSuccess || hipMemset( ctx->tzStats, 0, 6 * sizeof( unsigned long long ) ) != hipSuccess )
+      hipMalloc( ( void ** ) &ctx->tzStats, 6 * sizeof( unsigned long long ) ) != hipSuccess || hipMemset( ctx->tzStats, 0, 6 * sizeof( unsigned long long ) ) != hipSuccess ||
+      hipMalloc( ( void ** ) &ctx->tzRoundStats, 7 * sizeof( unsigned long long ) ) != hipSuccess || hipMemset( ctx->tzRoundStats, 0, 7 * sizeof( unsigned long long ) ) != hipSuccess )
   {
     delete ctx;
     return VTMHIP_E_HIP;
@@ -109,6 +110,7 @@ int vtmhip_destroy( vtmhip_ctx *ctx )
   if( ctx->wtdInv ) ( void ) hipFree( ctx->wtdInv );
   if( ctx->lmcsFwd ) ( void ) hipFree( ctx->lmcsFwd );
   if( ctx->tzStats ) ( void ) hipFree( ctx->tzStats );
+  if( ctx->tzRoundStats ) ( void ) hipFree( ctx->tzRoundStats );
   if( ctx->pinned ) ( void ) hipHostFree( ctx->pinned );
   for( auto &t : ctx->timed ) { ( void ) hipEventDestroy( t.start ); ( void ) hipEventDestroy( t.stop ); }
   for( hipEvent_t e : ctx->forkEvents ) ( void ) hipEventDestroy( e );
@@ -221,6 +223,15 @@ int vtmhip_tz_prune_stats( vtmhip_ctx *ctx, uint64_t *stats, int reset )
   VTMHIP_CHECK_CTX( ctx );
   if( stats ) VTMHIP_HIP( ctx, hipMemcpyAsync( stats, ctx->tzStats, 6 * sizeof( unsigned long long ), hipMemcpyDeviceToHost, ctx->stream ) );
   if( reset ) VTMHIP_HIP( ctx, hipMemsetAsync( ctx->tzStats, 0, 6 * sizeof( unsigned long long ), ctx->stream ) );
+  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
+  return VTMHIP_OK;
+}
+
+int vtmhip_tz_round_stats( vtmhip_ctx *ctx, uint64_t *stats, int reset )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  if( stats ) VTMHIP_HIP( ctx, hipMemcpyAsync( stats, ctx->tzRoundStats, 7 * sizeof( unsigned long long ), hipMemcpyDeviceToHost, ctx->stream ) );
+  if( reset ) VTMHIP_HIP( ctx, hipMemsetAsync( ctx->tzRoundStats, 0, 7 * sizeof( unsigned long long ), ctx->stream ) );
   VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
   return VTMHIP_OK;
 }

@@ -56,6 +56,7 @@ struct vtmhip_ctx
   hipEvent_t      tzSumsReady = nullptr;   // picture loop: recorded behind a box-sum pass that runs on a side stream; a raster launch on another stream waits for it
   hipStream_t     tzSumsJoined = nullptr;  // the stream that is already ordered behind tzSumsReady
   unsigned long long *tzStats = nullptr;   // device: scans listed, skipped, reduced, grid points evaluated, grid points total, scans accepted (vtmhip_tz_prune_stats)
+  unsigned long long *tzRoundStats = nullptr;   // device: rounds bounded, candidates listed in them, candidates skipped -- first launches, then resume launches -- and violations (vtmhip_tz_round_stats)
 };
 
 // scope guard around a kernel launch: records start / stop events on ctx->stream when timing is on (bench.py's roofline: the dominant kernel's

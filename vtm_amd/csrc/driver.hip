@@ -142,7 +142,10 @@ int run_rest( vtmhip_ctx *ctx, const vtmhip_pis_level_run &L, const vtmhip_pis_b
 
 // Raster pruning (me.hip): the 8x8 box sums of every luma plane the levels reference, computed per picture (a plane may have been rewritten since the last one) into a
 // workspace of the context congruent with the DPB, and attached for the picture.  The pass is ordered behind whatever `main` holds on entry, as the picture's first search
-// kernel is; with a side stream it runs there, beside the first level's integer search, and the first raster launch joins it (ctx->tzSumsReady).
+// kernel is; with side streams it runs there, beside the template SADs of the first level, and the first launch that reads the sums -- the first level's bounded integer
+// search, else the first raster launch -- joins it (ctx->tzSumsReady).  The planes' passes all run on the first side stream.  VTMHIP_SUMS_SPREAD=1: one side stream
+// each, meeting on the first, so that the pass ends behind the longest of them instead of their sum -- measured 0.04 ms of the picture SLOWER (the later forks of those
+// streams queue behind the passes; profiles/roundbound_bench_ab.txt), so it is not the default.
 struct SumsAttached      // on every way out of the picture loop: the caller's own attachment (or none) is back
 {
   vtmhip_ctx     *c;
@@ -157,9 +160,12 @@ struct SumsAttached      // on every way out of the picture loop: the caller's o
   }
 };
 
-int picture_sums( vtmhip_ctx *ctx, const vtmhip_pis_level_run *levels, int numLevels, const vtmhip_pis_buffers &buf, hipStream_t main, hipStream_t side, EventPool &pool,
-                  bool &attached )
+int picture_sums( vtmhip_ctx *ctx, const vtmhip_pis_level_run *levels, int numLevels, const vtmhip_pis_buffers &buf, hipStream_t main, void *const *sides, int numSide,
+                  EventPool &pool, bool &attached )
 {
+  static const bool spread = env_switch( "VTMHIP_SUMS_SPREAD", false );
+  hipStream_t side = numSide > 0 ? ( hipStream_t ) sides[0] : nullptr;
+  if( !spread && numSide > 1 ) numSide = 1;
   static const bool pruneOn = env_switch( "VTMHIP_TZ_PRUNE", true ) && env_switch( "VTMHIP_TZ_SPLIT", true );      // (only the split search's column kernel prunes)
   if( !pruneOn || numLevels <= 0 ) return VTMHIP_OK;
   const vtmhip_pic_params &pic = levels[0].pic;
@@ -197,13 +203,23 @@ int picture_sums( vtmhip_ctx *ctx, const vtmhip_pis_level_run *levels, int numLe
     ready = pool.get();
     VTMHIP_REQUIRE( ctx, fork && ready, "hipEventCreate" );
     VTMHIP_HIP( ctx, hipEventRecord( fork, main ) );
-    VTMHIP_HIP( ctx, hipStreamWaitEvent( side, fork, 0 ) );
-    ctx->stream = side;
+    for( int s = 0; s < numSide && s < ( int ) planes.size(); s++ ) VTMHIP_HIP( ctx, hipStreamWaitEvent( ( hipStream_t ) sides[s], fork, 0 ) );
   }
   int st = VTMHIP_OK;
-  for( size_t k = 0; k < planes.size() && !st; k++ ) st = vtmhip_tz_box_sums_dev( ctx, buf.dpb, sumBase, planes[k], stride, pic.picW, pic.picH, m );
+  for( size_t k = 0; k < planes.size() && !st; k++ )
+  {
+    if( side ) ctx->stream = ( hipStream_t ) sides[k % ( size_t ) numSide];
+    st = vtmhip_tz_box_sums_dev( ctx, buf.dpb, sumBase, planes[k], stride, pic.picW, pic.picH, m );
+  }
   ctx->stream = main;
   if( st ) return st;
+  for( int s = 1; s < numSide && s < ( int ) planes.size(); s++ )      // the other side streams' passes meet on the first
+  {
+    hipEvent_t e = pool.get();
+    VTMHIP_REQUIRE( ctx, e, "hipEventCreate" );
+    VTMHIP_HIP( ctx, hipEventRecord( e, ( hipStream_t ) sides[s] ) );
+    VTMHIP_HIP( ctx, hipStreamWaitEvent( side, e, 0 ) );
+  }
   if( side ) VTMHIP_HIP( ctx, hipEventRecord( ready, side ) );
   ctx->tzSumsRef = buf.dpb; ctx->tzSums = sumBase; ctx->tzSumsW = pic.picW; ctx->tzSumsH = pic.picH; ctx->tzSumsMargin = m;
   ctx->tzSumsReady = ready; ctx->tzSumsJoined = side;
@@ -244,7 +260,7 @@ extern "C" int vtmhip_pis_run_picture( vtmhip_ctx *ctx, const vtmhip_pis_level_r
   int         st = VTMHIP_OK;
   ctx->stream = main;
   SumsAttached sums( ctx );
-  st = picture_sums( ctx, levels, numLevels, *buf, main, numSide > 0 ? ( hipStream_t ) sideStreams[0] : nullptr, pool, sums.on );
+  st = picture_sums( ctx, levels, numLevels, *buf, main, sideStreams, numSide, pool, sums.on );
   if( st ) return st;
   if( numSide == 0 )
   {

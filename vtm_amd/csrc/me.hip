@@ -466,6 +466,18 @@ template<int K> struct Band
   unsigned offB, stepB;           // byte offset of its first segment from a candidate's top-left reference sample; segment m lies m * stepB further
 };
 
+// Round bound (BOUND instantiations: 128x128 and 128x64 at eight waves, every row in the SAD, unsigned samples of at most 10 bits): the sum-norm bound of the raster pruning
+// (below: sum over the 8x8 sub-blocks of |sum(org) - sum(ref)| <= SAD) inside the list rounds.  The sums of the original block's K * 64 sub-blocks sit in LDS for the
+// whole search; a round first forms every candidate's bound from the shadow plane of box sums (512 B a candidate against the 32 KB of its samples) and loads only the
+// candidates whose bound + MV rate is below the best cost the search holds: tz_round accepts strictly, so none of the others can be accepted.
+struct RoundBound
+{
+  const uint16_t *sums;       // the box sums congruent with j.ref (nullptr: this search is not bounded)
+  unsigned       *org;        // LDS [K * 64]: the sums of the original block's sub-blocks, row-major
+  unsigned       *red;        // LDS [16][K]: a round's bounds, one partial per wave and candidate
+  unsigned        rounds, listed, skipped, violations;   // vtmhip_tz_round_stats, of this search
+};
+
 template<int K>
 __device__ __forceinline__ void band_load_org( const MeJob &j, Band<K> &bd, int tid, int threads )
 {
@@ -486,29 +498,40 @@ __device__ __forceinline__ void band_load_org( const MeJob &j, Band<K> &bd, int 
 
 // the thread's partial SADs of the round's n candidates, summed over the 16 lanes of its DPP row; lane (16 row + c) returns the row total of candidate c
 // (px, py: lane c holds candidate c's position)
-template<int K, bool SGN>
-__device__ __forceinline__ unsigned band_partials( const MeJob &j, const Band<K> &bd, int px, int py, int n, int lane )
+// (MASKED: only the candidates whose bit is set in `mask`, wave-uniform -- the round bound; the other lanes' return value is undefined)
+template<int K, bool SGN, bool MASKED = false>
+__device__ __forceinline__ unsigned band_partials( const MeJob &j, const Band<K> &bd, int px, int py, int n, int lane, unsigned mask = 0 )
 {
   // candidates whose loads are in flight together.  Four segments per thread: one candidate -- eight loads with the extra dword of the aligned form do not fit 128 registers.
   // (Eight loads WITHOUT that form, odd candidates fetched by 2-byte aligned loads, measured the same: 0.558 against 0.564 ms per launch of the 128x128 level, 0.596 by
   // candidates.  That level moves 32 KB per candidate through the CU's vector memory path and is bound by it, not by the number of loads in flight: DESIGN.md 4.2)
-  constexpr int  CH = K == 4 ? 1 : BAND_LOADS / K;
+  // (MASKED, two segments: two candidates -- with four, the chunk's candidate numbers and the search's bound state push the kernel one register over the budget; four
+  // loads in flight is what the 128x128 level runs with)
+  constexpr int  CH = K == 4 ? 1 : MASKED && K == 2 ? 2 : BAND_LOADS / K;
   const bool   evenStride = !( ( j.refStride << j.ss ) & 1 );
   const size_t stepB = uni( bd.stepB );
   const int    slot = lane & 15;
   unsigned     mine = 0;
-  for( int c0 = 0; c0 < n; c0 += CH )
+  for( int c0 = 0; MASKED ? mask != 0 : c0 < n; c0 += CH )
   {
     Pel8     b[CH][K];
     unsigned e[CH][K];
     bool     odd[CH];
+    int      cq[CH];      // the chunk's candidates: c0 .. c0 + CH - 1, MASKED: the next CH set bits (-1: none left)
+#pragma unroll
+    for( int q = 0; q < CH; q++ )
+    {
+      cq[q] = 0;
+      if( MASKED ) { cq[q] = mask ? __builtin_ctz( mask ) : -1; mask &= mask - 1; }
+    }
 #pragma unroll
     for( int q = 0; q < CH; q++ )
     {
       odd[q] = false;
-      if( c0 + q < n )      // (uniform)
+      if( MASKED ? cq[q] >= 0 : c0 + q < n )      // (uniform)
       {
-        const int16_t *cp = j.ref + ( long ) __builtin_amdgcn_readlane( py, c0 + q ) * j.refStride + __builtin_amdgcn_readlane( px, c0 + q );
+        const int      c  = MASKED ? cq[q] : c0 + q;
+        const int16_t *cp = j.ref + ( long ) __builtin_amdgcn_readlane( py, c ) * j.refStride + __builtin_amdgcn_readlane( px, c );
         // a candidate at an odd sample offset (every lane's address has its parity when the row step is even): the dword-aligned form of ld8
         odd[q] = evenStride && ( reinterpret_cast<uintptr_t>( cp ) & 2 ) != 0;
         const char *cb = reinterpret_cast<const char *>( cp ) - ( odd[q] ? 2 : 0 );
@@ -523,7 +546,7 @@ __device__ __forceinline__ unsigned band_partials( const MeJob &j, const Band<K>
     }
 #pragma unroll
     for( int q = 0; q < CH; q++ )
-      if( c0 + q < n )
+      if( MASKED ? cq[q] >= 0 : c0 + q < n )
       {
         if( odd[q] )
         {
@@ -544,20 +567,75 @@ __device__ __forceinline__ unsigned band_partials( const MeJob &j, const Band<K>
         s += dpp_u32<DPP_XOR2>( s );
         s += dpp_u32<DPP_HALF_MIRROR>( s );
         s += dpp_u32<DPP_MIRROR>( s );      // every lane of the row holds the row's total
-        mine = slot == c0 + q ? s : mine;
+        mine = slot == ( MASKED ? cq[q] : c0 + q ) ? s : mine;
       }
   }
   return mine;
 }
 
 // a list round of n (1 .. 16) candidates in pts[]: the first strict minimum in list order as (cost, index), the same in every wave
+// the round's candidates whose bound + MV rate is below `best` as a wave-uniform mask, the same in every wave; lane c (and c + 16, ..) gets candidate c's bound.
+// K waves take the K * 64 sub-blocks of one candidate, WPJ / K candidates at a time; one barrier (rb.red is free again behind the round's next barrier)
 template<int WPJ, int K>
-__device__ __forceinline__ void band_round( const MeJob &j, const Band<K> &bd, const int4 *pts, int n, const Coop &co, unsigned long long &bestCost, unsigned &bestIdx )
+__device__ __forceinline__ unsigned round_bound_mask( const MeJob &j, const RoundBound &rb, const int4 &p, int n, const Coop &co, unsigned long long best, unsigned &bound )
+{
+  constexpr int CG = WPJ / K;      // candidates in flight
+  const int     sub = ( int ) threadIdx.x & ( K * 64 - 1 ), sy = sub >> j.sprShift, sx = sub & ( j.segsPerRow - 1 );
+  const unsigned  a = rb.org[sub];
+  const uint16_t *sp = rb.sums + ( long ) ( 8 * sy ) * j.refStride + 8 * sx;
+  unsigned        v[16 / CG];
+#pragma unroll
+  for( int q = 0; q < 16 / CG; q++ )
+  {
+    const int c = co.wave / K + q * CG;      // (wave-uniform)
+    v[q] = a;
+    if( c < n )
+    {
+      const int x = __builtin_amdgcn_readlane( p.x, c ), y = __builtin_amdgcn_readlane( p.y, c );
+      // a position the box sums do not cover (never one clipMv admits): bound 0, the candidate is evaluated unless its rate alone rules it out
+      // (the box sums cover clipMv's range of the block origin, mv_rules.hpp)
+      if( ( x << 4 ) >= j.horMin && ( x << 4 ) <= j.horMax && ( y << 4 ) >= j.verMin && ( y << 4 ) <= j.verMax ) v[q] = sp[( long ) y * j.refStride + x];
+    }
+  }
+#pragma unroll
+  for( int q = 0; q < 16 / CG; q++ )
+  {
+    const int c = co.wave / K + q * CG;
+    if( c < n )
+    {
+      const unsigned d = group_sum( a > v[q] ? a - v[q] : v[q] - a, 64 );
+      if( co.lane == 0 ) rb.red[c * K + co.wave % K] = d;
+    }
+  }
+  job_sync<WPJ>();
+  bound = 0;
+#pragma unroll
+  for( int k = 0; k < K; k++ ) bound += rb.red[( co.lane & 15 ) * K + k];
+  const bool alive = ( co.lane & 15 ) < n && bound + mv_cost( j, p.x, p.y ) < best;
+  return uni( ( unsigned ) __ballot( alive ) & 0xffffu );
+}
+
+template<int WPJ, int K, bool BOUND = false>
+__device__ __forceinline__ void band_round( const MeJob &j, const Band<K> &bd, const int4 *pts, int n, const Coop &co, unsigned long long &bestCost, unsigned &bestIdx,
+                                            RoundBound *rb = nullptr, unsigned long long best = 0 )
 {
   const int lane = co.lane;
   unsigned *part = co.part + ( pts == co.ptsBase ? 0 : 16 * 4 * WPJ );
   const int4     p    = pts[lane & 15];      // lane c (and c + 16, ..): candidate c; entries from n on are stale and unused
-  const unsigned mine = j.bias ? band_partials<K, true>( j, bd, p.x, p.y, n, lane ) : band_partials<K, false>( j, bd, p.x, p.y, n, lane );
+  // round bound: every round but the first of a search, whatever its length -- a candidate's bound moves 1 / 64 of its bytes, so even the two points of the last
+  // round pay when one in sixty-four is ruled out.  A skipped candidate enters the minimum with cost ~0: it is never the round's strict minimum below `best`
+  bool     bounded = false;
+  unsigned mask = 0, bound = 0;
+  if constexpr( BOUND ) bounded = rb->sums && best != ~0ull;      // (uniform over the job)
+  if constexpr( BOUND )
+    if( bounded )
+    {
+      mask = round_bound_mask<WPJ, K>( j, *rb, p, n, co, best, bound );
+      rb->rounds += 1u; rb->listed += ( unsigned ) n; rb->skipped += ( unsigned ) ( n - __popc( mask ) );
+    }
+  unsigned mine;
+  if( BOUND && bounded ) mine = band_partials<K, false, true>( j, bd, p.x, p.y, n, lane, mask );      // (bounded searches have no sign bias)
+  else mine = j.bias ? band_partials<K, true>( j, bd, p.x, p.y, n, lane ) : band_partials<K, false>( j, bd, p.x, p.y, n, lane );
   if( ( lane & 15 ) < n ) part[( lane & 15 ) * ( 4 * WPJ ) + co.wave * 4 + ( lane >> 4 )] = mine;
   job_sync<WPJ>();
   // candidate c's 4 * WPJ partials: from four waves on, the four DPP rows add a quarter each (lane 16 g + c) and the quarters meet by two cross-row steps
@@ -569,7 +647,9 @@ __device__ __forceinline__ void band_round( const MeJob &j, const Band<K> &bd, c
     for( int w = 0; w < WPJ / G; w++ ) { const uint4 t = pp[w]; tot += t.x + t.y + t.z + t.w; }
     if( G == 4 ) { tot += __shfl_xor( tot, 16, 64 ); tot += __shfl_xor( tot, 32, 64 ); }
   }
-  const bool valid = lane < n;
+  const bool valid = BOUND && bounded ? lane < n && ( ( mask >> ( lane & 15 ) ) & 1u ) : lane < n;
+  if constexpr( BOUND )      // the in-kernel check of the sums' addressing: an exact SAD below its bound (wave 0 counts, lane c holds both numbers of candidate c)
+    if( bounded && co.wave == 0 ) rb->violations += ( unsigned ) __popcll( __ballot( valid && tot < bound ) );
   bestCost = ~0ull;
   bestIdx  = valid ? ( unsigned ) lane : 0xffffffffu;
   if( valid ) bestCost = ( ( unsigned long long ) tot << j.ss ) + mv_cost( j, p.x, p.y );
@@ -599,14 +679,15 @@ __device__ __forceinline__ void band_round( const MeJob &j, const Band<K> &bd, c
 
 // evaluate the n (<= 16) candidates whose (x, y, nr, dist) sit in pts[] and replay the accept rule
 // (K > 0, row bands: pts moves on to the other half of the list buffer)
-template<int WPJ, int K>
-__device__ __forceinline__ void tz_round( const MeJob &j, const Band<K> &bd, TzState &s, int4 *&pts, int n, const Coop &co, bool touchMeta )
+template<int WPJ, int K, bool BOUND = false>
+__device__ __forceinline__ void tz_round( const MeJob &j, const Band<K> &bd, TzState &s, int4 *&pts, int n, const Coop &co, bool touchMeta, RoundBound *rb = nullptr )
 {
   if( K > 0 && n == 0 ) return;      // (uniform over the job: nothing was written, nobody meets)
   job_sync<WPJ>();   // pts[] was written by the job's leader thread
   unsigned long long cost;
   unsigned           idx;
-  if constexpr( K > 0 ) band_round<WPJ, K>( j, bd, pts, n, co, cost, idx );
+  if constexpr( K > 0 && BOUND ) band_round<WPJ, K, true>( j, bd, pts, n, co, cost, idx, rb, s.bestSad );
+  else if constexpr( K > 0 ) band_round<WPJ, K>( j, bd, pts, n, co, cost, idx );
   else eval_candidates<false, WPJ>( j, pts, n, 0, 0, 1, 1, co, cost, idx );
   s.nEval += ( unsigned ) n;
   if( n > 0 && cost < s.bestSad )
@@ -708,16 +789,16 @@ __device__ int diamond_points( const Range &sr, int sx, int sy, int d, bool corn
   return n;
 }
 
-template<int WPJ, int K>
-__device__ __forceinline__ void tz_diamond( const MeJob &j, const Band<K> &bd, TzState &s, int sx, int sy, int d, bool corners, int4 *&pts, const Coop &co )
+template<int WPJ, int K, bool BOUND = false>
+__device__ __forceinline__ void tz_diamond( const MeJob &j, const Band<K> &bd, TzState &s, int sx, int sy, int d, bool corners, int4 *&pts, const Coop &co, RoundBound *rb = nullptr )
 {
   const int n = diamond_points( s.sr, sx, sy, d, corners, pts, co );
   s.bestRound += 1;
-  tz_round<WPJ, K>( j, bd, s, pts, n, co, true );
+  tz_round<WPJ, K, BOUND>( j, bd, s, pts, n, co, true, rb );
 }
 
-template<int WPJ, int K>
-__device__ __forceinline__ void tz_two_point( const MeJob &j, const Band<K> &bd, TzState &s, int4 *&pts, const Coop &co )
+template<int WPJ, int K, bool BOUND = false>
+__device__ __forceinline__ void tz_two_point( const MeJob &j, const Band<K> &bd, TzState &s, int4 *&pts, const Coop &co, RoundBound *rb = nullptr )
 {
   // untested neighbours of the best point, by the point number of the dist-1 round (xTZ2PointSearch :426-446);
   // packed as 2-bit fields (value + 1) per point number 0..8
@@ -731,7 +812,7 @@ __device__ __forceinline__ void tz_two_point( const MeJob &j, const Band<K> &bd,
   int       n  = 0;
   if( x1 >= s.sr.left && x1 <= s.sr.right && y1 >= s.sr.top && y1 <= s.sr.bottom ) PUSH( x1, y1, 0, 2 );
   if( x2 >= s.sr.left && x2 <= s.sr.right && y2 >= s.sr.top && y2 <= s.sr.bottom ) PUSH( x2, y2, 0, 2 );
-  tz_round<WPJ, K>( j, bd, s, pts, n, co, true );
+  tz_round<WPJ, K, BOUND>( j, bd, s, pts, n, co, true, rb );
 }
 
 // Raster scan when a whole wave shares one candidate (lpc == 64, 8-sample segments, power-of-two row length): the lane's IPL
@@ -1214,10 +1295,11 @@ __global__ __launch_bounds__( 256 ) void tz_raster_cols_kernel( vtmhip_pic_param
 }
 
 // WPJ = 1: 256 threads = 4 independent jobs.  WPJ > 1: 64 * WPJ threads = 1 job.
-template<int WPJ, int K>
+template<int WPJ, int K, bool BOUND = false>
 __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, const int16_t *__restrict__ orgBase, const int16_t *__restrict__ refBase,
                                                const vtmhip_tz_job *__restrict__ jobs, int numJobs, vtmhip_me_result *__restrict__ results, int mode, TzSaved *__restrict__ saved,
-                                               int *__restrict__ list, int totCap, const MeFuse &fu, int blockIdxX, int gridDimX )
+                                               int *__restrict__ list, int totCap, const MeFuse &fu, int blockIdxX, int gridDimX,
+                                               const uint16_t *__restrict__ sums = nullptr, unsigned long long *__restrict__ roundStats = nullptr )
 {
   // mode 0: the whole search.  Split launches: mode 1 stops at the raster decision of jobs tz_raster_cols_kernel can take (state -> saved[], job
   // index -> list[]; every other job runs to the end here); mode 2 resumes the listed jobs after the scan.
@@ -1362,6 +1444,34 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
     else band_load_org<K>( j, bd, WPJ == 1 ? lane : ( int ) threadIdx.x, 64 * WPJ );
   }
   else stage_org<WPJ, ( WPJ >= 4 ? ORG_LDS_CAP : ORG_LDS_CAP2 )>( j, sOrgLds, ( int ) threadIdx.x );
+  RoundBound rb, *rbp = nullptr;      // (BOUND only)
+  if constexpr( BOUND )
+  {
+    rbp = &rb;
+    rb.sums = nullptr; rb.rounds = rb.listed = rb.skipped = rb.violations = 0;
+    // the launch promised every row in the SAD, at most 10 bits and sums that cover clipMv's range for this picture; a job of signed samples is not bounded (uniform over the job)
+    __shared__ unsigned sSubOrg[K * 64], sBoundRed[16 * K];
+    rb.org = sSubOrg; rb.red = sBoundRed;
+    if( sums && !j.bias && j.ss == 0 && j.w <= pic.ctuSize && j.h <= pic.ctuSize )
+    {
+      rb.sums = sums + jp->refOff;
+      // the sub-block sums from the segments the threads hold: segment m of thread t lies in row ( t >> sprShift ) + m * rows and column segment t & ( segsPerRow - 1 ), so the
+      // eight threads segsPerRow apart whose rows share r >> 3 add their segment sums into one 8x8 sub-block
+      if( ( int ) threadIdx.x < K * 64 ) sSubOrg[threadIdx.x] = 0;
+      job_sync<WPJ>();
+      const int r = ( int ) threadIdx.x >> j.sprShift, rows = ( 64 * WPJ ) >> j.sprShift;
+#pragma unroll
+      for( int m = 0; m < K; m++ )
+      {
+        unsigned t = 0;
+#pragma unroll
+        for( int k = 0; k < 4; k++ ) t = sad2( bd.o[m][k], 0u, t );
+        atomicAdd( &sSubOrg[( ( r + m * rows ) >> 3 ) * j.segsPerRow + ( ( int ) threadIdx.x & ( j.segsPerRow - 1 ) )], t );
+      }
+      // (no barrier here: every round starts with the job_sync of tz_round, which orders these LDS atomics before round_bound_mask reads the sums -- also in a
+      // resume launch, whose first round is already bounded)
+    }
+  }
 
   const bool ext = jp->extendedSettings != 0, fast = jp->fastSettings != 0, firstStop = jp->firstSearchStop != 0;
   const int  iRaster = fast ? 8 : 5, searchRange = jp->searchRange;
@@ -1393,7 +1503,7 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
       clip_mv( j, ex, ey );
       PUSH( mvr::prec_down( ex, 4 ), mvr::prec_down( ey, 4 ), 0, 0 );
     }
-    tz_round<WPJ, K>( j, bd, s, pts, n, co, true );
+    tz_round<WPJ, K, BOUND>( j, bd, s, pts, n, co, true, rbp );
     if( numExtra > 14 )   // 15th candidate: the list holds 16 points
     {
       int m = 0;
@@ -1404,7 +1514,7 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
         PUSH( mvr::prec_down( ex, 4 ), mvr::prec_down( ey, 4 ), 0, 0 );
         m = n;
       }
-      tz_round<WPJ, K>( j, bd, s, pts, m, co, false );
+      tz_round<WPJ, K, BOUND>( j, bd, s, pts, m, co, false, rbp );
     }
   }
   else
@@ -1412,13 +1522,13 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
     {
       int n = 0;
       PUSH( mx, my, 0, 0 );
-      tz_round<WPJ, K>( j, bd, s, pts, n, co, true );
+      tz_round<WPJ, K, BOUND>( j, bd, s, pts, n, co, true, rbp );
     }
     if( !fast && ( mx != 0 || my != 0 ) && ( s.bestX != 0 || s.bestY != 0 ) )
     {
       int n = 0;
       PUSH( 0, 0, 0, 0 );
-      tz_round<WPJ, K>( j, bd, s, pts, n, co, true );
+      tz_round<WPJ, K, BOUND>( j, bd, s, pts, n, co, true, rbp );
     }
     int ix = jp->intMv2Nx2NPredHor << 4, iy = jp->intMv2Nx2NPredVer << 4;
     clip_mv( j, ix, iy );
@@ -1428,7 +1538,7 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
     {
       int n = 0;
       PUSH( ix, iy, 0, 0 );
-      tz_round<WPJ, K>( j, bd, s, pts, n, co, true );
+      tz_round<WPJ, K, BOUND>( j, bd, s, pts, n, co, true, rbp );
     }
     // m_uniMvList start candidates (:3725-3762): one parallel round, same first-strict-minimum semantics
     int       n  = 0;
@@ -1439,7 +1549,7 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
       clip_mv( j, ex, ey );
       PUSH( mvr::prec_down( ex, 4 ), mvr::prec_down( ey, 4 ), 0, 0 );
     }
-    tz_round<WPJ, K>( j, bd, s, pts, n, co, false );
+    tz_round<WPJ, K, BOUND>( j, bd, s, pts, n, co, false, rbp );
   }
 
   s.sr = search_range( j, s.bestX << 4, s.bestY << 4, searchRange >> ( fast ? 1 : 0 ) );
@@ -1449,17 +1559,17 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
 
   for( int d = 1; d <= searchRange; d *= 2 )
   {
-    tz_diamond<WPJ, K>( j, bd, s, startX, startY, d, ext, pts, co );
+    tz_diamond<WPJ, K, BOUND>( j, bd, s, startX, startY, d, ext, pts, co, rbp );
     if( firstStop && s.bestRound >= 3 ) break;
   }
   if( ext && !bestCandidateZero )
   {
-    for( int d = 1; d <= ( searchRange >> 1 ); d *= 2 ) tz_diamond<WPJ, K>( j, bd, s, 0, 0, d, false, pts, co );
+    for( int d = 1; d <= ( searchRange >> 1 ); d *= 2 ) tz_diamond<WPJ, K, BOUND>( j, bd, s, 0, 0, d, false, pts, co, rbp );
   }
   if( s.bestDist == 1 )
   {
     s.bestDist = 0;
-    tz_two_point<WPJ, K>( j, bd, s, pts, co );
+    tz_two_point<WPJ, K, BOUND>( j, bd, s, pts, co, rbp );
   }
   if( ext )
   {
@@ -1481,6 +1591,13 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
     {
       if( co.leader )
       {
+        if constexpr( BOUND )
+        if( roundStats && rb.rounds )
+        {
+          unsigned long long *st = roundStats + ( mode == 2 ? 3 : 0 );
+          atomicAdd( &st[0], ( unsigned long long ) rb.rounds ); atomicAdd( &st[1], ( unsigned long long ) rb.listed ); atomicAdd( &st[2], ( unsigned long long ) rb.skipped );
+          if( rb.violations ) atomicAdd( &roundStats[6], ( unsigned long long ) rb.violations );
+        }
         TzSaved sv;
         sv.sr = s.sr; sv.bestSad = s.bestSad; sv.bestX = s.bestX; sv.bestY = s.bestY; sv.pointNr = s.pointNr; sv.bestDist = s.bestDist;
         sv.bestRound = s.bestRound; sv.nEval = s.nEval; sv.rasterCost = ~0ull; sv.rasterIdx = 0; sv.pad = 0;
@@ -1526,18 +1643,25 @@ __device__ __forceinline__ void tz_search_one( const vtmhip_pic_params &pic, con
     s.pointNr  = 0;
     for( int d = 1; d < searchRange + 1; d *= 2 )
     {
-      tz_diamond<WPJ, K>( j, bd, s, startX, startY, d, ext, pts, co );
+      tz_diamond<WPJ, K, BOUND>( j, bd, s, startX, startY, d, ext, pts, co, rbp );
       if( fast && s.bestRound >= 2 ) break;
     }
     if( s.bestDist == 1 )
     {
       s.bestDist = 0;
-      if( s.pointNr != 0 ) tz_two_point<WPJ, K>( j, bd, s, pts, co );
+      if( s.pointNr != 0 ) tz_two_point<WPJ, K, BOUND>( j, bd, s, pts, co, rbp );
     }
   }
 
   if( co.leader )
   {
+    if constexpr( BOUND )
+    if( roundStats && rb.rounds )
+    {
+      unsigned long long *st = roundStats + ( mode == 2 ? 3 : 0 );
+      atomicAdd( &st[0], ( unsigned long long ) rb.rounds ); atomicAdd( &st[1], ( unsigned long long ) rb.listed ); atomicAdd( &st[2], ( unsigned long long ) rb.skipped );
+      if( rb.violations ) atomicAdd( &roundStats[6], ( unsigned long long ) rb.violations );
+    }
     vtmhip_me_result r;
     r.mvX = s.bestX; r.mvY = s.bestY; r.nEval = s.nEval; r.reserved = 0;
     r.cost = s.bestSad;
@@ -1565,6 +1689,17 @@ void tz_search_kernel( vtmhip_pic_params pic, const int16_t *__restrict__ orgBas
   tz_search_one<WPJ, K>( pic, orgBase, refBase, jobs, numJobs, results, mode, saved, list, totCap, fu, ( int ) blockIdx.x, ( int ) gridDim.x );
 }
 
+// The bounded form of the row-band search (RoundBound): <8, 4> (128x128) and <8, 2> (128x64).  A kernel of its own rather than a flag of tz_search_kernel: the two further
+// arguments would move the hidden arguments of every other instantiation, and those keep the code they had
+template<int WPJ, int K>
+__global__ __launch_bounds__( 64 * WPJ ) __attribute__( ( amdgpu_waves_per_eu( 4 ) ) )
+void tz_search_bound_kernel( vtmhip_pic_params pic, const int16_t *__restrict__ orgBase, const int16_t *__restrict__ refBase, const vtmhip_tz_job *__restrict__ jobs, int numJobs,
+                             vtmhip_me_result *__restrict__ results, int mode, TzSaved *__restrict__ saved, int *__restrict__ list, int totCap, MeFuse fu,
+                             const uint16_t *__restrict__ sums, unsigned long long *__restrict__ roundStats )
+{
+  static_assert( WPJ == 8 && ( K == 4 || K == 2 ), "the bounded instantiations" );
+  tz_search_one<WPJ, K, true>( pic, orgBase, refBase, jobs, numJobs, results, mode, saved, list, totCap, fu, ( int ) blockIdx.x, ( int ) gridDim.x, sums, roundStats );
+}
 
 // ---- small blocks: FOUR searches per wave ---------------------------------------------------------------------------------------------------------
 // tz_group_kernel: a search owns one DPP row (16 lanes) and a lane is one CANDIDATE of the round -- a round of xTZ8PointDiamondSearch has at most 16 points, and lane `slot` takes the
@@ -2391,6 +2526,31 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
     const int items = ( uniformW >> 3 ) * ( ( uniformH + ( 1 << ss ) - 1 ) >> ss );
     if( ( items & 7 ) == 0 && items <= groupItems && items <= 128 ) { grpItems = items; grpSs = ss; }
   }
+  // raster pruning and round bound (VTMHIP_TZ_PRUNE=0: both off): the box sums attached for this reference base (vtmhip_tz_attach_sums)
+  static const bool pruneOn = env_switch( "VTMHIP_TZ_PRUNE", true );
+  // (only sums computed for this picture size with a margin that covers clipMv's range of this CTU size: the kernels' eligibility tests rely on that coverage)
+  const uint16_t   *d_sums = pruneOn && ctx->tzSums && ctx->tzSumsRef == d_refBase && ctx->tzSumsW == pic->picW && ctx->tzSumsH == pic->picH &&
+                                     ctx->tzSumsMargin >= pic->ctuSize + 16 ? ctx->tzSums : nullptr;
+  auto join_sums = [&]() -> int      // a box-sum pass still running on another stream is joined before the first launch that reads the sums
+  {
+    if( d_sums && ctx->tzSumsReady && ctx->tzSumsJoined != ctx->stream )      // (once per stream: later launches of the stream are ordered behind this one)
+    {
+      VTMHIP_HIP( ctx, hipStreamWaitEvent( ctx->stream, ctx->tzSumsReady, 0 ) );
+      ctx->tzSumsJoined = ctx->stream;
+    }
+    return VTMHIP_OK;
+  };
+  // Round bound (VTMHIP_TZ_ROUND_BOUND=0: off): the fused uniform 128x128 / 128x64 launches at eight waves per search whose SAD takes every row, of samples whose 8x8
+  // sums fit 16 bits, take tz_search_bound_kernel for the first launch and for the resume launch
+  static const bool roundBoundOn = env_switch( "VTMHIP_TZ_ROUND_BOUND", true );
+  bool roundBound = false;
+#define VTMHIP_TZ_BOUND_LAUNCH( KK, MODE ) \
+  hipLaunchKernelGGL( ( tz_search_bound_kernel<8, KK> ), dim3( n ), dim3( 512 ), 0, ctx->stream, *pic, d_orgBase, d_refBase, d_jobs, n, d_results, MODE, d_saved, d_list, totCap, \
+                      ( MODE ) == 2 ? fuNone : fuFirst, d_sums, ctx->tzRoundStats )
+#define VTMHIP_TZ_SEARCH( MODE )                                                   \
+  if( roundBound && bandK == 4 ) VTMHIP_TZ_BOUND_LAUNCH( 4, MODE );                \
+  else if( roundBound ) VTMHIP_TZ_BOUND_LAUNCH( 2, MODE );                         \
+  else { VTMHIP_TZ_SWITCH( MODE ) }
   if( grpItems )
   {
     VTMHIP_TIME_KERNEL( ctx, "tz_group_kernel" );
@@ -2415,31 +2575,28 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
   { VTMHIP_TIME_KERNEL( ctx, "tz_search_kernel" );
     if( bandsOn && fuse && fuse->me && uniformW > 0 && uniformH > 0 )
       bandK = vtmhip_tz_band_items( uniformW, uniformH, mg::sub_shift( fuse->cfg, uniformW, uniformH ), wpj );
-    VTMHIP_TZ_SWITCH( split ? 1 : 0 )
+    // (128 wide only: 64x128 has bandK 2 at eight waves as well, and the kernel's indexing would take it, but no test runs the bound at that shape)
+    roundBound = roundBoundOn && d_sums && wpj == 8 && uniformW == 128 && ( bandK == 4 || bandK == 2 ) && mg::sub_shift( fuse->cfg, uniformW, uniformH ) == 0 && pic->bitDepth <= 10 &&
+                 uniformW <= pic->ctuSize && uniformH <= pic->ctuSize;
+    if( roundBound ) { const int st = join_sums(); if( st ) return st; }
+    VTMHIP_TZ_SEARCH( split ? 1 : 0 )
   }
   if( split )
   {
     { VTMHIP_TIME_KERNEL( ctx, "tz_raster_cols_kernel" );
       const size_t totLds = ( size_t ) ( totCap + 1 ) * sizeof( unsigned );
       if( totLds > 32 * 1024 ) VTMHIP_HIP( ctx, hipFuncSetAttribute( reinterpret_cast<const void *>( tz_raster_cols_kernel ), hipFuncAttributeMaxDynamicSharedMemorySize, ( int ) totLds ) );
-      // raster pruning (VTMHIP_TZ_PRUNE=0: off): the box sums attached for this reference base (vtmhip_tz_attach_sums); a pass still running on another stream is joined here
-      static const bool pruneOn = env_switch( "VTMHIP_TZ_PRUNE", true );
-      // (only sums computed for this picture size with a margin that covers clipMv's range of this CTU size: the kernel's eligibility test relies on that coverage)
-      const uint16_t   *d_sums = pruneOn && ctx->tzSums && ctx->tzSumsRef == d_refBase && ctx->tzSumsW == pic->picW && ctx->tzSumsH == pic->picH &&
-                                         ctx->tzSumsMargin >= pic->ctuSize + 16 ? ctx->tzSums : nullptr;
-      if( d_sums && ctx->tzSumsReady && ctx->tzSumsJoined != ctx->stream )      // (once per stream: later launches of the stream are ordered behind this one)
-      {
-        VTMHIP_HIP( ctx, hipStreamWaitEvent( ctx->stream, ctx->tzSumsReady, 0 ) );
-        ctx->tzSumsJoined = ctx->stream;
-      }
+      { const int st = join_sums(); if( st ) return st; }
       // (the grid of one workgroup per scan, COLS_GRID of tests/test_gpu_tz_batch_sizes.py)
       hipLaunchKernelGGL( tz_raster_cols_kernel, dim3( rasterParts > 1 ? n * rasterParts : ( n < 3072 ? n : 3072 ) ), dim3( 256 ), totLds, ctx->stream, *pic, d_orgBase,
                           d_refBase, d_jobs, d_saved, d_list, d_tot, rasterParts, totCap, d_sums, ctx->tzStats );
     }
     { VTMHIP_TIME_KERNEL( ctx, "tz_search_kernel" );
-      VTMHIP_TZ_SWITCH( 2 )
+      VTMHIP_TZ_SEARCH( 2 )
     }
   }
+#undef VTMHIP_TZ_SEARCH
+#undef VTMHIP_TZ_BOUND_LAUNCH
 #undef VTMHIP_TZ_SWITCH
 #undef VTMHIP_TZ_LAUNCH
 #undef VTMHIP_TZ_LAUNCH_K

@@ -335,6 +335,13 @@ class Context:
         self._check(self.L.vtmhip_tz_prune_stats(self.h, st, int(reset)))
         return dict(zip(("listed", "skipped", "reduced", "points_evaluated", "points_total", "accepted"), (int(v) for v in st)))
 
+    def tz_round_stats(self, reset=False):
+        """round bound since the last reset: dict of rounds bounded / candidates listed / candidates skipped of the first and of the resume launches, and violations
+        (evaluated candidates whose SAD was below their bound: 0) (synchronises the stream)"""
+        st = (C.c_uint64 * 7)()
+        self._check(self.L.vtmhip_tz_round_stats(self.h, st, int(reset)))
+        return dict(zip(("first_rounds", "first_listed", "first_skipped", "resume_rounds", "resume_listed", "resume_skipped", "violations"), (int(v) for v in st)))
+
     def affine_motion_estimation_batch(self, pic, d_org, d_ref, d_other, d_jobs, n, max_w, max_h, d_results, bcw=False):
         """InterSearch::xAffineMotionEstimation per AffineMeJob (one workgroup per job); bcw: the batch may hold bi jobs under a CU-level BCW weight of -2 (32-bit variant beside)"""
         f = self.L.vtmhip_xAffineMotionEstimation_bcw_batch_dev if bcw else self.L.vtmhip_xAffineMotionEstimation_batch_dev
