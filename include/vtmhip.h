@@ -1428,8 +1428,8 @@ int vtmhip_sbt_struct_size( int which );   /* sizeof() of 0 vtmhip_sbt_est_job, 
  *   planar, DC        xPredIntraPlanar :294-348, xGetPredValDc :153-182, their PDPC :244-265
  *   angular           xPredIntraAng :459-643: pure horizontal / vertical with the clipped PDPC, the extension of the main reference through invAngle for negative
  *                     angles, the replication of its last sample for positive ones, the cubic (H.266 table 28) or smoothing taps on fractional slopes, the PDPC column
- * MIP, ISP, BDPCM, IntraSmoothingDisabled, the availability analysis that fills the reference samples (xFillReferenceSamples), the mode bits and the
- * candidate lists stay the caller's.  Chroma has entries of its own below (vtmhip_intra_chroma_*). */
+ * ISP, BDPCM, IntraSmoothingDisabled, the availability analysis that fills the reference samples (xFillReferenceSamples), the mode bits and the
+ * candidate lists stay the caller's.  Chroma and MIP have entries of their own below (vtmhip_intra_chroma_*, vtmhip_mip_*). */
 typedef struct
 {
   int32_t predMode;            /* the mode after the wide-angle shift: -14 .. 80 (what the angle is taken from) */
@@ -1553,6 +1553,52 @@ int vtmhip_intra_chroma_presel_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refB
                                           const vtmhip_intra_chroma_block *d_blocks, int numBlocks, const vtmhip_intra_chroma_job *d_jobs, int n, uint64_t *d_dist );
 
 int vtmhip_intra_chroma_struct_size( int which );   /* sizeof() of 0 vtmhip_intra_chroma_block, 1 vtmhip_intra_chroma_job, 2 vtmhip_cclm_model; -1 otherwise */
+
+/* ---- matrix-based intra prediction (MIP) of a luma block: MatrixIntraPrediction::prepareInputForPred / predBlock (CommonLib/MatrixIntraPrediction.cpp:62-137) and
+ * the MIP candidates of IntraSearch::estIntraPredLumaQT (EncoderLib/IntraSearch.cpp:749-793: one initIntraMip per block, then predIntraMip and min( 2 * SAD, SATD )
+ * for 2 * getNumModesMip (mode, transposed) pairs) fused on top of it.  One definition for host and device, vtm_amd/csrc/mip_rules.hpp:
+ *   shape             getMipSizeId / getNumModesMip UnitTools.cpp:3873-3900 (4x4: 16 modes; a side of 4 or 8x8: 8; everything else: 6), initPredBlockParams :140-159
+ *   reduced boundary  boundaryDownsampling1D :163-191 on top[1 .. W] and left[1 .. H], the two input orders and the rebasing of :94-117
+ *   reduced block     computeReducedPred :283-335 with the caller's trained matrices (vtmhip_mip_set_tables), the clip and the transposition
+ *   up-sampling       predictionUpsampling :194-267 as a closed form per sample (horizontal pass on the anchor rows, then vertical, each rounded)
+ * Blocks are vtmhip_intra_block records with multiRefIdx 0, so one block table (and one pair of reference lines per block) serves the regular modes and MIP; of the
+ * lines only top[1 .. W] and left[1 .. H] are read.  Every width x height of 4, 8, 16, 32, 64 is accepted.  MIP for chroma (4:4:4), the mode bits and the
+ * candidate lists stay the caller's. */
+typedef struct
+{
+  int64_t predOff;     /* vtmhip_mip_pred_batch_dev only: the W x H prediction (stride W) inside d_predBase */
+  int32_t block;       /* index into d_blocks */
+  uint8_t mode;        /* 0 .. getNumModesMip - 1: below 16 (4x4), 8 (a side of 4, or 8x8) or 6 */
+  uint8_t transposed;  /* 0 / 1: the input is left | top and the reduced block is transposed (PredictionUnit::mipTransposedFlag) */
+  uint8_t reserved[2]; /* 0 */
+} vtmhip_mip_job;
+
+/* The trained matrices mipMatrix4x4[16][16][4], mipMatrix8x8[8][16][8] and mipMatrix16x16[6][64][7] (CommonLib/MipData.h; 4 736 bytes) are the caller's data, as
+ * LFNST's are: copied to the context's device once; the host arrays may go away afterwards.  The batched entries below return VTMHIP_E_INVALID until it was called. */
+int vtmhip_mip_set_tables( vtmhip_ctx *ctx, const uint8_t *m4x4, const uint8_t *m8x8, const uint8_t *m16x16 );
+
+/* predBlock for n (block, mode, transposed) jobs: job k writes width x height samples with stride width at d_predBase + predOff.  Jobs of one block that follow
+ * each other in d_jobs share one load of its lines and one pair of reduced boundaries; any order is allowed.
+ * NULL pointers, n < 0, numBlocks < 0 and numBlocks == 0 with n > 0 return VTMHIP_E_INVALID; n == 0 is VTMHIP_OK.  The tables stay on the device: a job whose
+ * block index is outside [0, numBlocks), whose mode is not below getNumModesMip of its block, whose transposed is above 1, or whose block has a side outside the
+ * list, a bitDepth outside 8 .. 12 or multiRefIdx != 0 is skipped -- nothing is read through it and its output is not written.  Lanes per job as for
+ * vtmhip_intra_pred_batch_dev (vtmhip_intra_lanes_per_job of the largest well-formed block; no read-back). */
+int vtmhip_mip_pred_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const vtmhip_intra_block *d_blocks, int numBlocks, const vtmhip_mip_job *d_jobs, int n,
+                               int16_t *d_predBase );
+
+/* The same prediction formed in LDS and consumed there: d_dist[2 k] = the SAD of job k's prediction against its block's original, d_dist[2 k + 1] = the SATD under
+ * the xGetHADs tile rules.  No sample of a prediction goes to global memory; predOff is ignored.  min( 2 * SAD, SATD ), the mode bits and reduceHadCandList stay
+ * the caller's.  Checks and skipped jobs as above (both d_dist entries of a skipped job are left). */
+int vtmhip_mip_presel_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_orgBase, const vtmhip_intra_block *d_blocks, int numBlocks,
+                                 const vtmhip_mip_job *d_jobs, int n, uint64_t *d_dist );
+
+/* The same rules on the host, no context: top and left are indexed as the lines of a vtmhip_intra_block are (top[1 .. width] and left[1 .. height] are read, index 0
+ * -- the corner -- is not), the matrices as for vtmhip_mip_set_tables, pred receives width x height samples with stride width.  Anything the device would skip, or
+ * a NULL pointer, returns VTMHIP_E_INVALID. */
+int vtmhip_mip_pred_host( int width, int height, int bitDepth, int mode, int transposed, const int16_t *top, const int16_t *left, const uint8_t *m4x4,
+                          const uint8_t *m8x8, const uint8_t *m16x16, int16_t *pred );
+
+int vtmhip_mip_struct_size( int which );   /* sizeof() of 0 vtmhip_mip_job; -1 otherwise */
 
 #ifdef __cplusplus
 }

@@ -105,6 +105,7 @@ int vtmhip_destroy( vtmhip_ctx *ctx )
   if( ctx->scratch ) ( void ) hipFree( ctx->scratch );
   for( auto &kv : ctx->work ) if( kv.second.ptr ) ( void ) hipFree( kv.second.ptr );
   if( ctx->lfnstTab ) ( void ) hipFree( ctx->lfnstTab );
+  if( ctx->mipTab ) ( void ) hipFree( ctx->mipTab );
   if( ctx->trTabBuf ) ( void ) hipFree( ctx->trTabBuf );
   if( ctx->wtdFixed ) ( void ) hipFree( ctx->wtdFixed );
   if( ctx->wtdInv ) ( void ) hipFree( ctx->wtdInv );

@@ -6,7 +6,7 @@
 //
 // Every sample of every mode is a closed form over the two reference lines (intra_rules.hpp), so a job is W x H independent samples.
 //
-// intra_shape_kernel: one workgroup walks the block table and leaves the lanes a job gets (vtmhip_intra_lanes_per_job of the largest well-formed block) in the
+// intra_shape_kernel (intra_lanes.hpp): one workgroup walks the block table and leaves the lanes a job gets (vtmhip_intra_lanes_per_job of the largest well-formed block) in the
 // stream's workspace -- the tables stay on the device and the host never waits for them.
 //
 // intra_kernel<FUSED>: 256 threads.  A job gets L lanes: 16 (blocks up to 64 samples: 16 jobs run side by side, 4 in a wave), 64 (up to 1024: a wave per job) or
@@ -19,6 +19,7 @@
 #include "ctx.hpp"
 #include "chroma_taps.hpp"
 #include "dist_block.hpp"
+#include "intra_lanes.hpp"   // intra_lanes, intra_chunk, intra_shape_kernel: shared with mip.hip
 #include "intra_rules.hpp"
 
 namespace
@@ -27,29 +28,6 @@ namespace
 __constant__ int16_t c_intraCubic[32][4] = { VTMHIP_CHROMA_FILTER_TAPS };   // InterpolationFilter::getChromaFilterTable (IntraPrediction.cpp:576)
 
 constexpr int INTRA_LINE = 136;    // 2 * 64 + 1 + 2 samples of a line, rounded up
-constexpr int INTRA_MAX_AREA = 4096;
-
-__host__ __device__ inline int intra_lanes( int maxArea ) { return maxArea < 16 || maxArea > INTRA_MAX_AREA ? 0 : maxArea <= 64 ? 16 : maxArea <= 1024 ? 64 : 256; }
-__host__ __device__ inline int intra_chunk( int lanes ) { return lanes == 16 ? 16 : lanes == 64 ? 8 : 4; }
-constexpr int INTRA_MIN_CHUNK = 4;
-
-__device__ __forceinline__ bool intra_block_ok( const vtmhip_intra_block &b ) { return intraBlockOk( b.width, b.height, b.bitDepth, b.multiRefIdx ); }
-
-__global__ __launch_bounds__( 256 ) void intra_shape_kernel( const vtmhip_intra_block *__restrict__ blocks, int numBlocks, int *__restrict__ lanes )
-{
-  __shared__ int sMax;
-  if( threadIdx.x == 0 ) sMax = 16;
-  __syncthreads();
-  int m = 0;
-  for( int i = threadIdx.x; i < numBlocks; i += 256 )
-  {
-    const vtmhip_intra_block b = blocks[i];
-    if( intra_block_ok( b ) ) m = max( m, b.width * b.height );
-  }
-  if( m ) atomicMax( &sMax, m );
-  __syncthreads();
-  if( threadIdx.x == 0 ) *lanes = intra_lanes( sMax );
-}
 
 struct IntraLds
 {

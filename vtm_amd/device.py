@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib as _lib
-from .lib import (AffineJob, DistJob, FracJob, FracResult, FullJob, IctJob, IfJob, IntraBlock, IntraChromaBlock, IntraChromaJob, IntraJob, IntraParams, CclmModel, JccrJob, JccrResult, LmcsJob, McJob, MeResult, PelOpJob, PicParams, QuantJob,   # noqa: F401
+from .lib import (AffineJob, DistJob, FracJob, FracResult, FullJob, IctJob, IfJob, IntraBlock, IntraChromaBlock, IntraChromaJob, IntraJob, IntraParams, CclmModel, JccrJob, JccrResult, LmcsJob, McJob, MeResult, MipJob, PelOpJob, PicParams, QuantJob,   # noqa: F401
                   SbtEstJob, SbtEstResult, SbtJob, SbtResult, ScaleJob, TrJob, TuJob, TuResult, TzJob, VtmHipError, WpDistJob, WpParam, WpPredJob, WtdJob)
 
 
@@ -408,6 +408,12 @@ class Context:
         assert a.size == 4 * 2 * 16 * 48 and b.size == 4 * 2 * 16 * 16
         self._check(self.L.vtmhip_lfnst_set_tables(self.h, a.ctypes.data, b.ctypes.data))
 
+    def mip_set_tables(self, m4x4, m8x8, m16x16):
+        """The caller's MIP matrices (uint8 mipMatrix4x4 [16][16][4], mipMatrix8x8 [8][16][8], mipMatrix16x16 [6][64][7]), once per context."""
+        a, b, c = (np.ascontiguousarray(m, np.uint8) for m in (m4x4, m8x8, m16x16))
+        assert a.size == 16 * 16 * 4 and b.size == 8 * 16 * 8 and c.size == 6 * 64 * 7
+        self._check(self.L.vtmhip_mip_set_tables(self.h, a.ctypes.data, b.ctypes.data, c.ctypes.data))
+
     def lfnst(self, inverse, src, mode, index, size, zero_out):
         """TrQuant::fwdLfnstNxN / invLfnstNxN on a host vector; returns the trSize outputs."""
         src = np.ascontiguousarray(src, np.int32)
@@ -504,6 +510,14 @@ class Context:
             b.free()
         return res
 
+    def mip_pred_batch(self, d_ref, d_blocks, num_blocks, d_jobs, n, d_pred):
+        """predBlock (MIP) of n MipJob (block, mode, transposed) triples over num_blocks IntraBlock entries -> W x H samples, stride W, at MipJob.predOff"""
+        self._check(self.L.vtmhip_mip_pred_batch_dev(self.h, d_ref, d_blocks, num_blocks, d_jobs, n, d_pred))
+
+    def mip_presel_batch(self, d_ref, d_org, d_blocks, num_blocks, d_jobs, n, d_dist):
+        """the same predictions kept on chip: d_dist[2 k] = SAD, d_dist[2 k + 1] = SATD of job k against its block's original"""
+        self._check(self.L.vtmhip_mip_presel_batch_dev(self.h, d_ref, d_org, d_blocks, num_blocks, d_jobs, n, d_dist))
+
     def intra_chroma_pred_batch(self, d_ref, d_luma, d_blocks, num_blocks, d_jobs, n, d_pred):
         """the Cb and Cr predictions (regular modes 0 .. 66, LM 67, MDLM_L 68, MDLM_T 69) of n IntraChromaJob pairs over num_blocks IntraChromaBlock entries"""
         self._check(self.L.vtmhip_intra_chroma_pred_batch_dev(self.h, d_ref, d_luma, d_blocks, num_blocks, d_jobs, n, d_pred))
@@ -572,6 +586,19 @@ def intra_pred_params(w, h, mode, m=0):
     if st != _lib.OK:
         raise VtmHipError(st)
     return p
+
+
+def mip_pred_host(w, h, bd, mode, transposed, top, left, m4x4, m8x8, m16x16):
+    """MIP prediction [h, w] of one block on the host (no device): top / left indexed as the lines of an IntraBlock (top[1 .. w], left[1 .. h] are read)"""
+    top, left = np.ascontiguousarray(top, np.int16), np.ascontiguousarray(left, np.int16)
+    a, b, c = (np.ascontiguousarray(m, np.uint8) for m in (m4x4, m8x8, m16x16))
+    if top.size < w + 1 or left.size < h + 1 or a.size != 16 * 16 * 4 or b.size != 8 * 16 * 8 or c.size != 6 * 64 * 7:
+        raise VtmHipError(_lib.E_INVALID)
+    pred = np.zeros((max(h, 1), max(w, 1)), np.int16)
+    st = _lib.load().vtmhip_mip_pred_host(w, h, bd, mode, transposed, top.ctypes.data, left.ctypes.data, a.ctypes.data, b.ctypes.data, c.ctypes.data, pred.ctypes.data)
+    if st != _lib.OK:
+        raise VtmHipError(st)
+    return pred
 
 
 def pack_intra_tables(blocks):

@@ -338,6 +338,10 @@ class IntraJob(C.Structure):
     _fields_ = [("predOff", C.c_int64), ("block", C.c_int32), ("mode", C.c_uint8), ("reserved", C.c_uint8 * 3)]
 
 
+class MipJob(C.Structure):
+    _fields_ = [("predOff", C.c_int64), ("block", C.c_int32), ("mode", C.c_uint8), ("transposed", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
 class IntraChromaBlock(C.Structure):
     _fields_ = [("cbRefOff", C.c_int64), ("crRefOff", C.c_int64), ("cbOrgOff", C.c_int64), ("crOrgOff", C.c_int64), ("lumaOff", C.c_int64), ("orgStride", C.c_int32),
                 ("lumaStride", C.c_int32), ("width", C.c_int16), ("height", C.c_int16), ("aboveRight", C.c_int16), ("belowLeft", C.c_int16), ("bitDepth", C.c_uint8),
@@ -361,6 +365,7 @@ _LMCS_STRUCTS = [LmcsJob, ScaleJob]             # order of vtmhip_lmcs_struct_si
 _SBT_STRUCTS = [SbtEstJob, SbtEstResult, SbtJob, SbtResult]   # order of vtmhip_sbt_struct_size(which)
 _INTRA_STRUCTS = [IntraParams, IntraBlock, IntraJob]          # order of vtmhip_intra_struct_size(which)
 _INTRA_CHROMA_STRUCTS = [IntraChromaBlock, IntraChromaJob, CclmModel]   # order of vtmhip_intra_chroma_struct_size(which)
+_MIP_STRUCTS = [MipJob]                                       # order of vtmhip_mip_struct_size(which)
 
 # every symbol include/vtmhip.h declares (tests/test_abi.py checks the exports against the header text)
 _PROTOS = {
@@ -488,6 +493,11 @@ _PROTOS = {
     "vtmhip_cclm_params": (C.c_int, [C.POINTER(IntraChromaBlock), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(CclmModel)]),
     "vtmhip_intra_chroma_pred_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "vtmhip_intra_chroma_presel_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "vtmhip_mip_struct_size": (C.c_int, [C.c_int]),
+    "vtmhip_mip_set_tables": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtmhip_mip_pred_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtmhip_mip_pred_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "vtmhip_mip_presel_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "vtmhip_intra_cand_cost_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vtmhip_satd8_grid_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p]),
@@ -587,6 +597,10 @@ def load():
         if lib.vtmhip_intra_chroma_struct_size(i) != C.sizeof(s):
             raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
                               % (s.__name__, C.sizeof(s), lib.vtmhip_intra_chroma_struct_size(i)))
+    for i, s in enumerate(_MIP_STRUCTS):
+        if lib.vtmhip_mip_struct_size(i) != C.sizeof(s):
+            raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
+                              % (s.__name__, C.sizeof(s), lib.vtmhip_mip_struct_size(i)))
     _lib = lib
     return lib
 
