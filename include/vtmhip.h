@@ -1451,7 +1451,7 @@ typedef struct
   int64_t refOff;      /* top line: d_refBase[refOff .. refOff + 2W + m], index 0 = the corner sample of line m;
                           the left line follows directly: 2H + 1 + m samples, index 0 = the same corner
                           (the reference's unfiltered buffer with predStride = 2W + 1 + m) */
-  int64_t orgOff;      /* original block inside d_orgBase (pre-selection only) */
+  int64_t orgOff;      /* original block inside d_orgBase (the pre-selection entries and vtmhip_intra_chain_batch_dev) */
   int32_t orgStride;
   int16_t width, height;   /* 4, 8, 16, 32, 64 each; every combination */
   uint8_t bitDepth;        /* 8 .. 12; clip range [0, (1 << bitDepth) - 1] */
@@ -1461,7 +1461,8 @@ typedef struct
 
 typedef struct
 {
-  int64_t predOff;     /* vtmhip_intra_pred_batch_dev only: the W x H prediction (stride W) inside d_predBase */
+  int64_t predOff;     /* vtmhip_intra_pred_batch_dev and vtmhip_intra_chain_batch_dev: the W x H prediction (stride W) inside d_predBase; the latter writes the
+                          residual at the same offset inside d_resiBase */
   int32_t block;       /* index into d_blocks */
   uint8_t mode;        /* 0 planar, 1 DC, 2 .. 66 */
   uint8_t reserved[3]; /* 0 */
@@ -1566,7 +1567,8 @@ int vtmhip_intra_chroma_struct_size( int which );   /* sizeof() of 0 vtmhip_intr
  * candidate lists stay the caller's. */
 typedef struct
 {
-  int64_t predOff;     /* vtmhip_mip_pred_batch_dev only: the W x H prediction (stride W) inside d_predBase */
+  int64_t predOff;     /* vtmhip_mip_pred_batch_dev and vtmhip_intra_chain_batch_dev: the W x H prediction (stride W) inside d_predBase; the latter writes the
+                          residual at the same offset inside d_resiBase */
   int32_t block;       /* index into d_blocks */
   uint8_t mode;        /* 0 .. getNumModesMip - 1: below 16 (4x4), 8 (a side of 4, or 8x8) or 6 */
   uint8_t transposed;  /* 0 / 1: the input is left | top and the reduced block is transposed (PredictionUnit::mipTransposedFlag) */
@@ -1599,6 +1601,58 @@ int vtmhip_mip_pred_host( int width, int height, int bitDepth, int mode, int tra
                           const uint8_t *m8x8, const uint8_t *m16x16, int16_t *pred );
 
 int vtmhip_mip_struct_size( int which );   /* sizeof() of 0 vtmhip_mip_job; -1 otherwise */
+
+/* ---- intra luma residual chain: one full-RD level of IntraSearch::estIntraPredLumaQT in one call -- per (mode, transform candidate) the steps of
+ * xIntraCodingTUBlock (EncoderLib/IntraSearch.cpp:2989-3320): prediction, piResi.subtract( piPred ), transformNxN / invTransformNxN,
+ * piReco.reconstruct( piPred, piResi, clpRng ) and getDistPart( piOrg, piReco, DF_SSE ).  The predictions are the two job tables above with the meaning they have
+ * there, over one vtmhip_intra_block table (orgOff / orgStride are used here); the chain is the fused chain of vtmhip_tu_chain_batch_dev.  The only upload of a
+ * level is its reference lines and the tables; nothing goes through the host between the steps.
+ * NOT covered, the caller's or a later change: LFNST between xT and quant; ISP and BDPCM; the chroma and JCCR intra chains; DF_SSE_WTD / LMCS (the caller hands
+ * the original in the domain it codes in); RDOQ / dependent quantisation (the chain is Quant::quant, as everywhere in this library); the CABAC bit estimate, the
+ * RD decision and the candidate lists; the encoder hook. */
+typedef struct
+{
+  int64_t outOff;            /* W x H contiguous: the levels inside d_levelsBase, the reconstruction inside d_recoBase */
+  int32_t pred;              /* 0 .. nIntra - 1: d_intraJobs[pred];  nIntra .. nIntra + nMip - 1: d_mipJobs[pred - nIntra] */
+  int16_t qpPer, qpRem;      /* as vtmhip_tu_job */
+  uint8_t typeHor, typeVer;  /* VTMHIP_DCT2 / DCT8 / DST7, or both VTMHIP_TRSKIP */
+  uint8_t isIRAP, reserved;  /* reserved: 0 */
+  int32_t pad;               /* 0 */
+} vtmhip_intra_tu_job;
+
+typedef struct
+{
+  uint64_t sse;              /* DF_SSE of the original block against the clipped reconstruction (xIntraCodingTUBlock :3313) */
+  uint64_t sseResi;          /* the chain's own vtmhip_tu_result.sse: residual against reconstructed residual (differs from sse once the clip acts) */
+  int32_t  sumAbs, absSum;   /* as vtmhip_tu_result */
+} vtmhip_intra_tu_result;
+
+/* Prediction p (p < nIntra: d_intraJobs[p], else d_mipJobs[p - nIntra]) writes its W x H samples with stride W at d_predBase + predOff and the residual
+ * original - prediction, same layout, at d_resiBase + predOff -- from the same registers, the original staged on chip; a prediction no TU job names is formed too.
+ * TU job k is one transform candidate of prediction `pred`: the block's shape and bit depth, that residual, the job's transform pair and QP.  The chain writes its
+ * levels to d_levelsBase + outOff (d_levelsBase may be NULL) and the reconstructed residual to d_recoBase + outOff, which a finish kernel overwrites in place with
+ * Clip( prediction + reconstructed residual, 0, ( 1 << bitDepth ) - 1 ); d_results[k].sse is what vtmhip_dist_batch_dev( VTMHIP_DIST_SSE ) gives for the original
+ * block and that reconstruction.  Several TU jobs may name one prediction (the MTS candidates of a mode); either prediction table may be empty; nTu == 0 is the
+ * prediction + residual pass alone (d_recoBase and d_results may then be NULL).  All counts 0 is VTMHIP_OK.
+ * The four tables are read back (one stream synchronisation; never call this under stream capture) and checked on the host before anything is launched; from the
+ * same pass come the chain's largest sides, whether every TU job has one size and a real transform (the one-lane and register-blocked chain kernels are then
+ * reached without a promise from the caller) and the lanes a prediction gets.  UNLIKE the prediction entries above, which skip a malformed job, this entry
+ * REJECTS THE WHOLE CALL -- the chain kernels trust their jobs -- with VTMHIP_E_INVALID and nothing launched: a required pointer NULL, a negative count, MIP jobs
+ * before vtmhip_mip_set_tables; any block with a side outside 4 / 8 / 16 / 32 / 64, a bitDepth outside 8 .. 12 or multiRefIdx > 2; a block index outside the
+ * table, a mode above 66, planar off line 0; a MIP mode at or above getNumModesMip, transposed > 1, MIP on a block with multiRefIdx != 0; pred outside
+ * [0, nIntra + nMip); qpRem outside 0 .. 5, qpPer < 0; a transform pair that is neither two of DCT2 / DCT8 / DST7 nor both VTMHIP_TRSKIP; DST7 / DCT8 on a side
+ * above 32, transform skip on a block with a side above 32; a non-zero reserved / pad field in any of the four tables. */
+int vtmhip_intra_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_orgBase, const vtmhip_intra_block *d_blocks, int numBlocks,
+                                  const vtmhip_intra_job *d_intraJobs, int nIntra, const vtmhip_mip_job *d_mipJobs, int nMip, const vtmhip_intra_tu_job *d_tuJobs,
+                                  int nTu, int16_t *d_predBase, int16_t *d_resiBase, int32_t *d_levelsBase, int16_t *d_recoBase, vtmhip_intra_tu_result *d_results );
+
+/* The same checks and the same expansion as host arithmetic on host tables, no context: out[k] = TU job k as the fused chain sees it (resiOff = the prediction's
+ * predOff inside d_resiBase, resiStride = W).  out holds nTu records and is left untouched when a table is rejected (VTMHIP_E_INVALID).  *maxWidth / *maxHeight: the
+ * largest sides over the TU jobs (0 without any); *uniform: 1 when every TU job has one size and a real transform; each of the three may be NULL. */
+int vtmhip_intra_chain_make_tu_jobs( const vtmhip_intra_block *blocks, int numBlocks, const vtmhip_intra_job *intraJobs, int nIntra, const vtmhip_mip_job *mipJobs,
+                                     int nMip, const vtmhip_intra_tu_job *tuJobs, int nTu, vtmhip_tu_job *out, int *maxWidth, int *maxHeight, int *uniform );
+
+int vtmhip_intra_chain_struct_size( int which );   /* sizeof() of 0 vtmhip_intra_tu_job, 1 vtmhip_intra_tu_result; -1 otherwise */
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,8 @@ struct vtmhip_ctx
   // ordered and reuse their arena
   struct WorkArena { void *ptr = nullptr; size_t size = 0; };
   std::map<std::pair<hipStream_t, int>, WorkArena> work;   // key: (stream, slot) -- slot 0: the multi-stage calls, slot 1: calls they nest (the split TZ search)
+                                                            // slot 2: the chain's shape bucketing (bucket.hpp) and the AMVP SADs (pis.hip), 3: the SBT chain (sbt.hip), 4: the picture loop's box sums
+                                                            // (driver.hip; attached for a whole picture), 5: the intra residual chain (intra_chain.hip)
   int8_t     *lfnstTab    = nullptr;   // the caller's LFNST core matrices: g_lfnst8x8 [4][2][16][48] then g_lfnst4x4 [4][2][16][16] (vtmhip_lfnst_set_tables)
   uint8_t    *mipTab      = nullptr;   // the caller's MIP matrices: mipMatrix4x4 [16][16][4], mipMatrix8x8 [8][16][8], mipMatrix16x16 [6][64][7] (vtmhip_mip_set_tables, under initMutex)
   int32_t    *wtdFixed    = nullptr;   // DF_SSE_WTD: fixed-point luma-level weights (int64_t)( w * 65536.0 ), 1 << wtdLumaBD entries (vtmhip_set_luma_level_weights)

@@ -16,121 +16,16 @@
 // Fused: a group writes its prediction to its slot of sPred and takes SAD and SATD from there through lanes_block_dist (dist_block.hpp: the xGetHADs tile rule);
 // with 256 lanes per job wave 0 takes the SAD and wave 1 the SATD (64 x 64 is 64 tiles: one per lane).
 // LDS: 4 lines x 136 samples + the DC value, fused + 2 x 4096 samples (original, predictions): 1.1 KB / 17.1 KB per workgroup.
+// intra_chunk_body lives in intra_body.hpp: intra_chain.hip instantiates its third mode (prediction + residual) in a kernel of its own.
 #include "ctx.hpp"
 #include "chroma_taps.hpp"
 #include "dist_block.hpp"
 #include "intra_lanes.hpp"   // intra_lanes, intra_chunk, intra_shape_kernel: shared with mip.hip
 #include "intra_rules.hpp"
+#include "intra_body.hpp"    // intra_chunk_body: shared with intra_chain.hip
 
 namespace
 {
-
-__constant__ int16_t c_intraCubic[32][4] = { VTMHIP_CHROMA_FILTER_TAPS };   // InterpolationFilter::getChromaFilterTable (IntraPrediction.cpp:576)
-
-constexpr int INTRA_LINE = 136;    // 2 * 64 + 1 + 2 samples of a line, rounded up
-
-struct IntraLds
-{
-  int16_t *line;   // [4][INTRA_LINE]: top, left, filtered top, filtered left
-  int     *dc;
-  int16_t *org, *pred;   // fused only
-};
-
-template<int L, bool FUSED>
-__device__ __forceinline__ void intra_chunk_body( const IntraLds &s, const int16_t *__restrict__ refBase, const int16_t *__restrict__ orgBase,
-                                                  const vtmhip_intra_block *__restrict__ blocks, int numBlocks, const vtmhip_intra_job *__restrict__ jobs, int n,
-                                                  int16_t *__restrict__ predBase, unsigned long long *__restrict__ dist )
-{
-  constexpr int G = 256 / L, CHUNK = L == 16 ? 16 : L == 64 ? 8 : 4;
-  const int tid = threadIdx.x, g = tid / L, l = tid % L;
-  const int jBegin = blockIdx.x * CHUNK, jEnd = min( n, jBegin + CHUNK );
-  int16_t  *sTop = s.line, *sLeft = s.line + INTRA_LINE, *sFTop = s.line + 2 * INTRA_LINE, *sFLeft = s.line + 3 * INTRA_LINE;
-
-  for( int j = jBegin; j < jEnd; )
-  {
-    // the run [j, e) of one block index (uniform over the workgroup)
-    const int blk = uni( jobs[j].block );
-    int       e   = j + 1;
-    while( e < jEnd && uni( jobs[e].block ) == blk ) e++;
-    const int first = j;
-    j = e;
-    if( blk < 0 || blk >= numBlocks ) continue;
-    const vtmhip_intra_block B = blocks[blk];
-    const int w = uni( ( int ) B.width ), h = uni( ( int ) B.height ), m = uni( ( int ) B.multiRefIdx ), bd = uni( ( int ) B.bitDepth );
-    if( !intraBlockOk( w, h, bd, m ) || w * h > ( L == 16 ? 64 : L == 64 ? 1024 : INTRA_MAX_AREA ) ) continue;   // the second part cannot happen: L comes from the largest block
-    const int area = w * h, log2W = intraLog2( w ), log2H = intraLog2( h ), nTop = 2 * w + 1 + m, nLeft = 2 * h + 1 + m;
-
-    __syncthreads();   // the previous run's readers are done
-    {
-      const int16_t *ref = refBase + B.refOff;
-      for( int i = tid; i < nTop + nLeft; i += 256 )
-      {
-        const int16_t v = ref[i];
-        if( i < nTop ) sTop[i] = v;
-        else sLeft[i - nTop] = v;
-      }
-      if( FUSED )
-      {
-        const int16_t *org = orgBase + B.orgOff;
-        for( int i = tid; i < area; i += 256 ) s.org[i] = org[( long ) ( i >> log2W ) * B.orgStride + ( i & ( w - 1 ) )];
-      }
-    }
-    __syncthreads();
-    if( m == 0 )   // the filtered lines exist for m = 0 only (refFilterFlag)
-      for( int i = tid; i < nTop + nLeft; i += 256 )
-      {
-        if( i < nTop ) sFTop[i] = intraFilteredSample( sTop, sLeft, i, 2 * w );
-        else sFLeft[i - nTop] = intraFilteredSample( sLeft, sTop, i - nTop, 2 * h );
-      }
-    IntraBlk U;
-    U.top = sTop; U.left = sLeft; U.w = w; U.h = h; U.log2W = log2W; U.log2H = log2H; U.m = m; U.maxVal = ( 1 << bd ) - 1;
-    if( tid == 255 ) *s.dc = intraDcVal( U );
-    __syncthreads();
-    const int dcVal = *s.dc;
-
-    for( int base = first; base < e; base += G )
-    {
-      const int job = base + g;
-      bool      ok  = job < e;
-      vtmhip_intra_job J;
-      if( ok )
-      {
-        J  = jobs[job];
-        ok = intraModeOk( J.mode, m );
-      }
-      int16_t *slot = FUSED ? s.pred + g * area : nullptr;
-      if( ok )
-      {
-        vtmhip_intra_params p;
-        intraPredParams( w, h, J.mode, m, p );
-        IntraBlk b = U;
-        if( p.refFilterFlag ) { b.top = sFTop; b.left = sFLeft; }
-        int16_t *out = FUSED ? slot : predBase + J.predOff;
-        for( int i = l; i < area; i += L ) out[i] = intraPredSample( p, J.mode, b, dcVal, c_intraCubic, i & ( w - 1 ), i >> log2W );
-      }
-      if( FUSED )
-      {
-        __syncthreads();
-        if( L == 256 )
-        {
-          const int wv = tid >> 6;   // wave 0: SAD, wave 1: SATD
-          if( ok && wv < 2 )
-          {
-            const unsigned long long d = wave_block_dist( wv ? VTMHIP_DIST_SATD : VTMHIP_DIST_SAD, s.org, w, slot, w, w, h, 0, tid & 63 );
-            if( ( tid & 63 ) == 0 ) dist[2 * ( long ) job + wv] = d;
-          }
-        }
-        else if( ok )
-        {
-          const unsigned long long sad  = lanes_block_dist<L>( VTMHIP_DIST_SAD, s.org, w, slot, w, w, h, 0, l );
-          const unsigned long long satd = lanes_block_dist<L>( VTMHIP_DIST_SATD, s.org, w, slot, w, w, h, 0, l );
-          if( l == 0 ) { dist[2 * ( long ) job] = sad; dist[2 * ( long ) job + 1] = satd; }
-        }
-        __syncthreads();   // before the next round overwrites the slots
-      }
-    }
-  }
-}
 
 template<bool FUSED>
 __global__ __launch_bounds__( 256 ) void intra_kernel( const int *__restrict__ lanesPtr, const int16_t *__restrict__ refBase, const int16_t *__restrict__ orgBase,
@@ -143,9 +38,10 @@ __global__ __launch_bounds__( 256 ) void intra_kernel( const int *__restrict__ l
   const int lanes = uni( *lanesPtr );
   if( ( long ) blockIdx.x * intra_chunk( lanes ) >= n ) return;
   const IntraLds s = { sLine, &sDc, sOrg, sPred };
-  if( lanes == 16 ) intra_chunk_body<16, FUSED>( s, refBase, orgBase, blocks, numBlocks, jobs, n, predBase, dist );
-  else if( lanes == 64 ) intra_chunk_body<64, FUSED>( s, refBase, orgBase, blocks, numBlocks, jobs, n, predBase, dist );
-  else intra_chunk_body<256, FUSED>( s, refBase, orgBase, blocks, numBlocks, jobs, n, predBase, dist );
+  constexpr IntraOut OUT = FUSED ? INTRA_OUT_DIST : INTRA_OUT_PRED;
+  if( lanes == 16 ) intra_chunk_body<16, OUT>( s, refBase, orgBase, blocks, numBlocks, jobs, n, predBase, dist );
+  else if( lanes == 64 ) intra_chunk_body<64, OUT>( s, refBase, orgBase, blocks, numBlocks, jobs, n, predBase, dist );
+  else intra_chunk_body<256, OUT>( s, refBase, orgBase, blocks, numBlocks, jobs, n, predBase, dist );
 }
 
 int intra_launch( vtmhip_ctx *ctx, bool fused, const int16_t *d_refBase, const int16_t *d_orgBase, const vtmhip_intra_block *d_blocks, int numBlocks,

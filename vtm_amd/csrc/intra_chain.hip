@@ -1,0 +1,218 @@
+// intra_chain.hip -- one full-RD level of the intra luma search on the device; the table rules are intra_chain_rules.hpp's.
+//   vtmhip_intra_chain_batch_dev     per (mode, transform candidate) the steps of IntraSearch::xIntraCodingTUBlock: prediction, residual, xT -> quant -> dequant -> xIT,
+//                                    clipped reconstruction and its SSE against the original                     (EncoderLib/IntraSearch.cpp:2989-3320)
+//   vtmhip_intra_chain_make_tu_jobs  the same checks and expansion as host arithmetic
+//
+// The launches of a call, all on the context's stream, nothing through the host between them:
+//   intra_resi_kernel / mip_resi_kernel   the bodies of intra_body.hpp / mip_body.hpp in their third mode: every prediction and original - prediction
+//   intra_chain_expand_kernel   one thread per TU job: the vtmhip_tu_job of the fused chain (the residual of the named prediction at stride W, shape and bit depth of
+//                               its block) and the block index, both in the stream's workspace
+//   the fused chain             vtmhip_internal_tu_chain_launch (transform.hip), unchanged: levels and the reconstructed residual at outOff
+//   intra_chain_finish_kernel<L>  a TU job gets L lanes (16 up to 256 samples: sixteen jobs per workgroup; 64 above: a wave per job), chosen by the host from the largest
+//                               TU.  A lane walks 4-sample row segments: prediction and reconstructed residual are W x H contiguous, the original has its own stride; all
+//                               three come as one 8-byte access at a 2-byte aligned address (pel_pack.hpp).  It overwrites the reconstructed residual with
+//                               clip( prediction + residual ) and sums ( original - reconstruction )^2 with the per-addend 32-bit product of dist_block.hpp's SSE; the
+//                               group's lanes are added by shuffles.  No LDS, no barrier.
+// The entry reads the four tables back and checks them (one stream synchronisation), so the kernels here trust what they are given.
+#include "ctx.hpp"
+#include "intra_body.hpp"   // intra_chunk_body, as intra.hip's kernels use it
+#include "mip_body.hpp"     // mip_chunk_body, as mip.hip's
+#include "intra_chain_rules.hpp"
+#include "pel_pack.hpp"
+
+namespace
+{
+
+// The third mode of the two prediction bodies (INTRA_OUT_RESI / MIP_OUT_RESI): the original is staged in LDS as for the fused pre-selection, and a lane writes its
+// sample to predBase + predOff and original - sample to resiBase + predOff from the same register -- no Hadamard stage, no prediction slot in LDS (9.1 / 10.4 KB).
+// The entry has read the block table, so the lanes per job come by value and the grid is exact.
+__global__ __launch_bounds__( 256 ) void intra_resi_kernel( int lanes, const int16_t *__restrict__ refBase, const int16_t *__restrict__ orgBase,
+                                                            const vtmhip_intra_block *__restrict__ blocks, int numBlocks, const vtmhip_intra_job *__restrict__ jobs, int n,
+                                                            int16_t *__restrict__ predBase, int16_t *__restrict__ resiBase )
+{
+  __shared__ int16_t sLine[4 * INTRA_LINE];
+  __shared__ int     sDc;
+  __shared__ int16_t sOrg[INTRA_MAX_AREA];
+  const IntraLds s = { sLine, &sDc, sOrg, nullptr };
+  if( lanes == 16 ) intra_chunk_body<16, INTRA_OUT_RESI>( s, refBase, orgBase, blocks, numBlocks, jobs, n, predBase, nullptr, resiBase );
+  else if( lanes == 64 ) intra_chunk_body<64, INTRA_OUT_RESI>( s, refBase, orgBase, blocks, numBlocks, jobs, n, predBase, nullptr, resiBase );
+  else intra_chunk_body<256, INTRA_OUT_RESI>( s, refBase, orgBase, blocks, numBlocks, jobs, n, predBase, nullptr, resiBase );
+}
+
+__global__ __launch_bounds__( 256 ) void mip_resi_kernel( int lanes, const uint8_t *__restrict__ tab, const int16_t *__restrict__ refBase, const int16_t *__restrict__ orgBase,
+                                                          const vtmhip_intra_block *__restrict__ blocks, int numBlocks, const vtmhip_mip_job *__restrict__ jobs, int n,
+                                                          int16_t *__restrict__ predBase, int16_t *__restrict__ resiBase )
+{
+  __shared__ int16_t sLine[2 * MIP_LINE];
+  __shared__ int     sBdry[8], sIn[2 * MIP_MAX_INPUT];
+  __shared__ int16_t sRed[16 * MIP_MAX_REDUCED];
+  __shared__ int16_t sOrg[INTRA_MAX_AREA];
+  const MipLds s = { sLine, sBdry, sIn, sRed, sOrg, nullptr };
+  if( lanes == 16 ) mip_chunk_body<16, MIP_OUT_RESI>( s, tab, refBase, orgBase, blocks, numBlocks, jobs, n, predBase, nullptr, resiBase );
+  else if( lanes == 64 ) mip_chunk_body<64, MIP_OUT_RESI>( s, tab, refBase, orgBase, blocks, numBlocks, jobs, n, predBase, nullptr, resiBase );
+  else mip_chunk_body<256, MIP_OUT_RESI>( s, tab, refBase, orgBase, blocks, numBlocks, jobs, n, predBase, nullptr, resiBase );
+}
+
+__global__ __launch_bounds__( 256 ) void intra_chain_expand_kernel( const vtmhip_intra_block *__restrict__ blocks, const vtmhip_intra_job *__restrict__ intraJobs, int nIntra,
+                                                                    const vtmhip_mip_job *__restrict__ mipJobs, const vtmhip_intra_tu_job *__restrict__ tuJobs, int n,
+                                                                    vtmhip_tu_job *__restrict__ out, int *__restrict__ tuBlock )
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if( i >= n ) return;
+  const vtmhip_intra_tu_job t = tuJobs[i];
+  int     blk;
+  int64_t predOff;
+  intraChainPred( intraJobs, nIntra, mipJobs, t.pred, blk, predOff );
+  intraChainExpand( t, blocks[blk], predOff, out[i] );
+  tuBlock[i] = blk;
+}
+
+template<int L>
+__global__ __launch_bounds__( 256 ) void intra_chain_finish_kernel( const int16_t *__restrict__ orgBase, const int16_t *__restrict__ predBase,
+                                                                    const vtmhip_intra_block *__restrict__ blocks, const int *__restrict__ tuBlock,
+                                                                    const vtmhip_tu_job *__restrict__ xJobs, const vtmhip_tu_result *__restrict__ xRes, int n,
+                                                                    int16_t *recoBase, vtmhip_intra_tu_result *__restrict__ results )
+{
+  constexpr int G = 256 / L;
+  const int g = threadIdx.x / L, l = threadIdx.x % L, i = blockIdx.x * G + g;
+  unsigned long long acc = 0;
+  if( i < n )
+  {
+    const vtmhip_tu_job      T = xJobs[i];
+    const vtmhip_intra_block B = blocks[tuBlock[i]];
+    const int      lgSegs = intraLog2( T.width ) - 2, items = ( T.width * T.height ) >> 2, maxVal = ( 1 << T.bitDepth ) - 1;
+    const int16_t *pred = predBase + T.resiOff, *org = orgBase + B.orgOff;   // the job's residual lies where its prediction does
+    int16_t       *reco = recoBase + T.outOff;
+    for( int it = l; it < items; it += L )
+    {
+      const int y = it >> lgSegs, x = ( it & ( ( 1 << lgSegs ) - 1 ) ) << 2;
+      int p[4], r[4], o[4];
+      ld4( pred + 4 * it, 4, p );
+      ld4( reco + 4 * it, 4, r );
+      ld4( org + ( long ) y * B.orgStride + x, 4, o );
+#pragma unroll
+      for( int k = 0; k < 4; k++ )
+      {
+        r[k] = min( max( p[k] + r[k], 0 ), maxVal );
+        const int d = o[k] - r[k];
+        acc += ( unsigned long long ) ( ( unsigned ) d * ( unsigned ) d );
+      }
+      st4( reco + 4 * it, 4, r );
+    }
+  }
+#pragma unroll
+  for( int o = L >> 1; o > 0; o >>= 1 ) acc += __shfl_xor( acc, o, 64 );   // a group is L consecutive lanes of one wave, all of them here
+  if( i < n && l == 0 )
+  {
+    const vtmhip_tu_result t = xRes[i];
+    vtmhip_intra_tu_result r;
+    r.sse = acc; r.sseResi = t.sse; r.sumAbs = t.sumAbs; r.absSum = t.absSum;
+    results[i] = r;
+  }
+}
+
+size_t align256( size_t v ) { return ( v + 255 ) & ~( size_t ) 255; }
+
+}   // namespace
+
+extern "C"
+{
+
+int vtmhip_intra_chain_struct_size( int which )
+{
+  switch( which )
+  {
+  case 0: return ( int ) sizeof( vtmhip_intra_tu_job );
+  case 1: return ( int ) sizeof( vtmhip_intra_tu_result );
+  default: return -1;
+  }
+}
+
+int vtmhip_intra_chain_make_tu_jobs( const vtmhip_intra_block *blocks, int numBlocks, const vtmhip_intra_job *intraJobs, int nIntra, const vtmhip_mip_job *mipJobs,
+                                     int nMip, const vtmhip_intra_tu_job *tuJobs, int nTu, vtmhip_tu_job *out, int *maxWidth, int *maxHeight, int *uniform )
+{
+  if( numBlocks < 0 || nIntra < 0 || nMip < 0 || nTu < 0 ) return VTMHIP_E_INVALID;
+  if( ( numBlocks && !blocks ) || ( nIntra && !intraJobs ) || ( nMip && !mipJobs ) || ( nTu && ( !tuJobs || !out ) ) ) return VTMHIP_E_INVALID;
+  IntraChainPlan plan;
+  if( !intraChainMakeTuJobs( blocks, numBlocks, intraJobs, nIntra, mipJobs, nMip, tuJobs, nTu, out, plan ) ) return VTMHIP_E_INVALID;
+  if( maxWidth ) *maxWidth = plan.maxWidth;
+  if( maxHeight ) *maxHeight = plan.maxHeight;
+  if( uniform ) *uniform = plan.uniform;
+  return VTMHIP_OK;
+}
+
+int vtmhip_intra_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_orgBase, const vtmhip_intra_block *d_blocks, int numBlocks,
+                                  const vtmhip_intra_job *d_intraJobs, int nIntra, const vtmhip_mip_job *d_mipJobs, int nMip, const vtmhip_intra_tu_job *d_tuJobs,
+                                  int nTu, int16_t *d_predBase, int16_t *d_resiBase, int32_t *d_levelsBase, int16_t *d_recoBase, vtmhip_intra_tu_result *d_results )
+{
+  VTMHIP_CHECK_CTX( ctx );
+  VTMHIP_REQUIRE( ctx, numBlocks >= 0 && nIntra >= 0 && nMip >= 0 && nTu >= 0, "negative count" );
+  if( nIntra + nMip + nTu == 0 ) return VTMHIP_OK;
+  VTMHIP_REQUIRE( ctx, d_refBase && d_orgBase && d_blocks && d_predBase && d_resiBase && ( !nIntra || d_intraJobs ) && ( !nMip || d_mipJobs ), "null pointer" );
+  VTMHIP_REQUIRE( ctx, !nTu || ( d_tuJobs && d_recoBase && d_results ), "null pointer" );
+  VTMHIP_REQUIRE( ctx, !nMip || ctx->mipTab, "vtmhip_mip_set_tables has not been called" );
+
+  // the tables decide the launches and the chain kernels trust their jobs: read back and checked before anything runs
+  const size_t bBlk = ( size_t ) numBlocks * sizeof( vtmhip_intra_block ), bIntra = ( size_t ) nIntra * sizeof( vtmhip_intra_job ),
+               bMip = ( size_t ) nMip * sizeof( vtmhip_mip_job ), bTu = ( size_t ) nTu * sizeof( vtmhip_intra_tu_job );   // every record size is a multiple of 8
+  VTMHIP_TRY( vtmhip_internal_scratch( ctx, bBlk + bIntra + bMip + bTu ) );
+  char *host = ( char * ) ctx->pinned;
+  if( bBlk ) VTMHIP_HIP( ctx, hipMemcpyAsync( host, d_blocks, bBlk, hipMemcpyDeviceToHost, ctx->stream ) );
+  if( bIntra ) VTMHIP_HIP( ctx, hipMemcpyAsync( host + bBlk, d_intraJobs, bIntra, hipMemcpyDeviceToHost, ctx->stream ) );
+  if( bMip ) VTMHIP_HIP( ctx, hipMemcpyAsync( host + bBlk + bIntra, d_mipJobs, bMip, hipMemcpyDeviceToHost, ctx->stream ) );
+  if( bTu ) VTMHIP_HIP( ctx, hipMemcpyAsync( host + bBlk + bIntra + bMip, d_tuJobs, bTu, hipMemcpyDeviceToHost, ctx->stream ) );
+  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
+  IntraChainPlan plan;
+  VTMHIP_REQUIRE( ctx,
+                  intraChainScan( ( const vtmhip_intra_block * ) host, numBlocks, ( const vtmhip_intra_job * ) ( host + bBlk ), nIntra,
+                                  ( const vtmhip_mip_job * ) ( host + bBlk + bIntra ), nMip, ( const vtmhip_intra_tu_job * ) ( host + bBlk + bIntra + bMip ), nTu, plan ),
+                  "intra chain tables: sides 4..64, bitDepth 8..12, multiRefIdx 0..2 (MIP: 0), block index, mode, pred inside the tables, qpRem 0..5, qpPer >= 0, "
+                  "two of DCT2 / DCT8 / DST7 (DCT2 above 32) or both TRSKIP (sides up to 32), reserved fields 0" );
+
+  const int lanes = intra_lanes( plan.maxBlockArea ), chunk = intra_chunk( lanes );   // what intra_shape_kernel would leave: here the host knows it
+  if( nIntra )
+  {
+    VTMHIP_TIME_KERNEL( ctx, "intra_resi_kernel" );
+    hipLaunchKernelGGL( intra_resi_kernel, dim3( ( nIntra + chunk - 1 ) / chunk ), dim3( 256 ), 0, ctx->stream, lanes, d_refBase, d_orgBase, d_blocks, numBlocks, d_intraJobs,
+                        nIntra, d_predBase, d_resiBase );
+    VTMHIP_LAUNCHED( ctx );
+  }
+  if( nMip )
+  {
+    VTMHIP_TIME_KERNEL( ctx, "mip_resi_kernel" );
+    hipLaunchKernelGGL( mip_resi_kernel, dim3( ( nMip + chunk - 1 ) / chunk ), dim3( 256 ), 0, ctx->stream, lanes, ctx->mipTab, d_refBase, d_orgBase, d_blocks, numBlocks,
+                        d_mipJobs, nMip, d_predBase, d_resiBase );
+    VTMHIP_LAUNCHED( ctx );
+  }
+  if( nTu == 0 ) return VTMHIP_OK;
+
+  // workspace (slot 5, unused until now -- ctx.hpp lists the slots: 0 the prediction entries, 2 the chain's bucketing, 3 SBT, 4 the picture loop's box sums, which stay
+  // attached across the calls a picture makes): the block index per TU job, the expanded jobs, their results
+  const size_t oJobs = align256( ( size_t ) nTu * sizeof( int ) ), oRes = align256( oJobs + ( size_t ) nTu * sizeof( vtmhip_tu_job ) );
+  void *arena = nullptr;
+  VTMHIP_TRY( vtmhip_internal_workspace( ctx, oRes + ( size_t ) nTu * sizeof( vtmhip_tu_result ), &arena, 5 ) );
+  char *base = ( char * ) arena;
+  int              *d_tuBlock = ( int * ) base;
+  vtmhip_tu_job    *d_xJobs   = ( vtmhip_tu_job * ) ( base + oJobs );
+  vtmhip_tu_result *d_xRes    = ( vtmhip_tu_result * ) ( base + oRes );
+  {
+    VTMHIP_TIME_KERNEL( ctx, "intra_chain_expand_kernel" );
+    hipLaunchKernelGGL( intra_chain_expand_kernel, dim3( ( nTu + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, d_blocks, d_intraJobs, nIntra, d_mipJobs, d_tuJobs, nTu, d_xJobs,
+                        d_tuBlock );
+    VTMHIP_LAUNCHED( ctx );
+  }
+  VTMHIP_TRY( vtmhip_internal_tu_chain_launch( ctx, d_resiBase, d_xJobs, nTu, plan.maxWidth, plan.maxHeight, plan.uniform, d_levelsBase, d_recoBase, d_xRes ) );
+  {
+    VTMHIP_TIME_KERNEL( ctx, "intra_chain_finish_kernel" );
+    if( plan.maxTuArea <= 256 )
+      hipLaunchKernelGGL( intra_chain_finish_kernel<16>, dim3( ( nTu + 15 ) / 16 ), dim3( 256 ), 0, ctx->stream, d_orgBase, d_predBase, d_blocks, d_tuBlock, d_xJobs, d_xRes, nTu,
+                          d_recoBase, d_results );
+    else
+      hipLaunchKernelGGL( intra_chain_finish_kernel<64>, dim3( ( nTu + 3 ) / 4 ), dim3( 256 ), 0, ctx->stream, d_orgBase, d_predBase, d_blocks, d_tuBlock, d_xJobs, d_xRes, nTu,
+                          d_recoBase, d_results );
+    VTMHIP_LAUNCHED( ctx );
+  }
+  return VTMHIP_OK;
+}
+
+}   // extern "C"

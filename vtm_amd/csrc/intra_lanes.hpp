@@ -4,15 +4,10 @@
 #pragma once
 #include "ctx.hpp"
 #include "intra_rules.hpp"
+#include "intra_lane_rule.hpp"   // intra_lanes, intra_chunk, INTRA_MAX_AREA, INTRA_MIN_CHUNK: the rule without the kernel
 
 namespace
 {
-
-constexpr int INTRA_MAX_AREA = 4096;
-
-__host__ __device__ inline int intra_lanes( int maxArea ) { return maxArea < 16 || maxArea > INTRA_MAX_AREA ? 0 : maxArea <= 64 ? 16 : maxArea <= 1024 ? 64 : 256; }
-__host__ __device__ inline int intra_chunk( int lanes ) { return lanes == 16 ? 16 : lanes == 64 ? 8 : 4; }
-constexpr int INTRA_MIN_CHUNK = 4;
 
 __device__ __forceinline__ bool intra_block_ok( const vtmhip_intra_block &b ) { return intraBlockOk( b.width, b.height, b.bitDepth, b.multiRefIdx ); }
 

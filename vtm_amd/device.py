@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib as _lib
-from .lib import (AffineJob, DistJob, FracJob, FracResult, FullJob, IctJob, IfJob, IntraBlock, IntraChromaBlock, IntraChromaJob, IntraJob, IntraParams, CclmModel, JccrJob, JccrResult, LmcsJob, McJob, MeResult, MipJob, PelOpJob, PicParams, QuantJob,   # noqa: F401
+from .lib import (AffineJob, DistJob, FracJob, FracResult, FullJob, IctJob, IfJob, IntraBlock, IntraChromaBlock, IntraChromaJob, IntraJob, IntraParams, IntraTuJob, IntraTuResult, CclmModel, JccrJob, JccrResult, LmcsJob, McJob, MeResult, MipJob, PelOpJob, PicParams, QuantJob,   # noqa: F401
                   SbtEstJob, SbtEstResult, SbtJob, SbtResult, ScaleJob, TrJob, TuJob, TuResult, TzJob, VtmHipError, WpDistJob, WpParam, WpPredJob, WtdJob)
 
 
@@ -518,6 +518,13 @@ class Context:
         """the same predictions kept on chip: d_dist[2 k] = SAD, d_dist[2 k + 1] = SATD of job k against its block's original"""
         self._check(self.L.vtmhip_mip_presel_batch_dev(self.h, d_ref, d_org, d_blocks, num_blocks, d_jobs, n, d_dist))
 
+    def intra_chain_batch(self, d_ref, d_org, d_blocks, num_blocks, d_intra_jobs, n_intra, d_mip_jobs, n_mip, d_tu_jobs, n_tu, d_pred, d_resi, d_reco, d_results,
+                          d_levels=None):
+        """one intra RD level: every prediction of the two job tables and its residual, then per IntraTuJob the fused chain, the clipped reconstruction (in place
+        at outOff inside d_reco) and an IntraTuResult.  A malformed table is rejected whole (VtmHipError, nothing launched)."""
+        self._check(self.L.vtmhip_intra_chain_batch_dev(self.h, d_ref, d_org, d_blocks, num_blocks, d_intra_jobs, n_intra, d_mip_jobs, n_mip, d_tu_jobs, n_tu,
+                                                        d_pred, d_resi, d_levels, d_reco, d_results))
+
     def intra_chroma_pred_batch(self, d_ref, d_luma, d_blocks, num_blocks, d_jobs, n, d_pred):
         """the Cb and Cr predictions (regular modes 0 .. 66, LM 67, MDLM_L 68, MDLM_T 69) of n IntraChromaJob pairs over num_blocks IntraChromaBlock entries"""
         self._check(self.L.vtmhip_intra_chroma_pred_batch_dev(self.h, d_ref, d_luma, d_blocks, num_blocks, d_jobs, n, d_pred))
@@ -684,3 +691,14 @@ def sbt_make_tu_jobs(jobs):
     if st != _lib.OK:
         raise VtmHipError(st)
     return (TuJob * num.value).from_buffer_copy(bytes(out)[:num.value * C.sizeof(TuJob)]), idx
+
+
+def intra_chain_make_tu_jobs(blocks, intra_jobs, mip_jobs, tu_jobs):
+    """The host form of the intra chain's checks and expansion over ctypes arrays (None: an empty table): (TuJob array, maxWidth, maxHeight, uniform)"""
+    n = [0 if a is None else len(a) for a in (blocks, intra_jobs, mip_jobs, tu_jobs)]
+    ptr = [None if a is None else C.addressof(a) for a in (blocks, intra_jobs, mip_jobs, tu_jobs)]
+    out, mw, mh, uni = (TuJob * max(n[3], 1))(), C.c_int(), C.c_int(), C.c_int()
+    st = _lib.load().vtmhip_intra_chain_make_tu_jobs(ptr[0], n[0], ptr[1], n[1], ptr[2], n[2], ptr[3], n[3], C.addressof(out), C.byref(mw), C.byref(mh), C.byref(uni))
+    if st != _lib.OK:
+        raise VtmHipError(st)
+    return (TuJob * n[3]).from_buffer_copy(bytes(out)[:n[3] * C.sizeof(TuJob)]), mw.value, mh.value, uni.value

@@ -342,6 +342,15 @@ class MipJob(C.Structure):
     _fields_ = [("predOff", C.c_int64), ("block", C.c_int32), ("mode", C.c_uint8), ("transposed", C.c_uint8), ("reserved", C.c_uint8 * 2)]
 
 
+class IntraTuJob(C.Structure):
+    _fields_ = [("outOff", C.c_int64), ("pred", C.c_int32), ("qpPer", C.c_int16), ("qpRem", C.c_int16), ("typeHor", C.c_uint8), ("typeVer", C.c_uint8),
+                ("isIRAP", C.c_uint8), ("reserved", C.c_uint8), ("pad", C.c_int32)]
+
+
+class IntraTuResult(C.Structure):
+    _fields_ = [("sse", C.c_uint64), ("sseResi", C.c_uint64), ("sumAbs", C.c_int32), ("absSum", C.c_int32)]
+
+
 class IntraChromaBlock(C.Structure):
     _fields_ = [("cbRefOff", C.c_int64), ("crRefOff", C.c_int64), ("cbOrgOff", C.c_int64), ("crOrgOff", C.c_int64), ("lumaOff", C.c_int64), ("orgStride", C.c_int32),
                 ("lumaStride", C.c_int32), ("width", C.c_int16), ("height", C.c_int16), ("aboveRight", C.c_int16), ("belowLeft", C.c_int16), ("bitDepth", C.c_uint8),
@@ -366,6 +375,7 @@ _SBT_STRUCTS = [SbtEstJob, SbtEstResult, SbtJob, SbtResult]   # order of vtmhip_
 _INTRA_STRUCTS = [IntraParams, IntraBlock, IntraJob]          # order of vtmhip_intra_struct_size(which)
 _INTRA_CHROMA_STRUCTS = [IntraChromaBlock, IntraChromaJob, CclmModel]   # order of vtmhip_intra_chroma_struct_size(which)
 _MIP_STRUCTS = [MipJob]                                       # order of vtmhip_mip_struct_size(which)
+_INTRA_CHAIN_STRUCTS = [IntraTuJob, IntraTuResult]            # order of vtmhip_intra_chain_struct_size(which)
 
 # every symbol include/vtmhip.h declares (tests/test_abi.py checks the exports against the header text)
 _PROTOS = {
@@ -498,6 +508,11 @@ _PROTOS = {
     "vtmhip_mip_pred_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtmhip_mip_pred_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "vtmhip_mip_presel_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "vtmhip_intra_chain_struct_size": (C.c_int, [C.c_int]),
+    "vtmhip_intra_chain_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtmhip_intra_chain_make_tu_jobs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int),
+                                                  C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vtmhip_intra_cand_cost_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vtmhip_satd8_grid_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p]),
@@ -601,6 +616,10 @@ def load():
         if lib.vtmhip_mip_struct_size(i) != C.sizeof(s):
             raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
                               % (s.__name__, C.sizeof(s), lib.vtmhip_mip_struct_size(i)))
+    for i, s in enumerate(_INTRA_CHAIN_STRUCTS):
+        if lib.vtmhip_intra_chain_struct_size(i) != C.sizeof(s):
+            raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
+                              % (s.__name__, C.sizeof(s), lib.vtmhip_intra_chain_struct_size(i)))
     _lib = lib
     return lib
 
