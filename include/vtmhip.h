@@ -556,6 +556,11 @@ typedef struct
 int vtmhip_motion_compensation_batch_dev( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_refBase, int16_t *d_predBase, int16_t *d_outBase,
                                           const vtmhip_pred_job *d_jobs, int n, int maxWidth, int maxHeight );
 
+/* lanes a block gets in vtmhip_motion_compensation_batch_dev and in the template-cost pass of vtmhip_xEstimateMvPredAMVP_batch_dev under the hint maxWidth x maxHeight:
+ * 8 (up to 64 samples: eight blocks per wave), 16 (up to 256: four per wave), 64 (up to 1024: a wave per block) or 256 (the workgroup per block); 0 when a side is
+ * outside 2 .. 128.  Host arithmetic, no device needed. */
+int vtmhip_mc_lanes_per_block( int maxWidth, int maxHeight );
+
 typedef struct
 {
   int64_t aOff, bOff, dstOff;

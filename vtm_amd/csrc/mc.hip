@@ -704,21 +704,23 @@ int vtmhip_internal_mc_launch( vtmhip_ctx *ctx, const int16_t *d_orgBase, const 
   // lanes per block by its number of 8-sample items (a lane filters 8 samples per step; the samples of a block are independent, only the H -> V hand-over syncs):
   // 8 lanes up to 64 samples (8 blocks per wave), 16 up to 16x16 (4 per wave), one wave up to 32x32, four waves above.  Measured on the bench picture (AMVP stage +
   // all predictions): 16 / 32 / 256 / 256 lanes 0.90 ms, 16 / 32 / 64 / 256: 0.83, 8 / 32 / 64 / 256: 0.72, 8 / 16 / 64 / 256: 0.70, 8 / 16 / 32 / 256: 0.71
+  const int lanes = vtmhip_mc_lanes_per_block( maxWidth, maxHeight );   // the one definition of the thresholds
+  VTMHIP_REQUIRE( ctx, lanes != 0, "maxWidth / maxHeight" );
   VTMHIP_TIME_KERNEL( ctx, "motion_comp_kernel" );
-  if( maxWidth * maxHeight > 1024 )
+  if( lanes == 256 )
   {
     if( lds > 64 * 1024 )
       VTMHIP_HIP( ctx, hipFuncSetAttribute( reinterpret_cast<const void *>( motion_comp_kernel<256, 1> ), hipFuncAttributeMaxDynamicSharedMemorySize, ( int ) lds ) );
     hipLaunchKernelGGL( ( motion_comp_kernel<256, 1> ), dim3( n ), dim3( 256 ), lds, ctx->stream, d_orgBase, d_refBase, d_predBase, d_outBase, d_jobs, n, maxWidth, maxHeight,
                         d_sadOut );
   }
-  else if( maxWidth * maxHeight > 256 )   // (see the threshold above) up to 32x32 samples: one wave per block -- the H -> V hand-over is a wave barrier, not a workgroup one
+  else if( lanes == 64 )   // (see the threshold above) up to 32x32 samples: one wave per block -- the H -> V hand-over is a wave barrier, not a workgroup one
     hipLaunchKernelGGL( ( motion_comp_kernel<64, 1> ), dim3( n ), dim3( 64 ), lds, ctx->stream, d_orgBase, d_refBase, d_predBase, d_outBase, d_jobs, n, maxWidth, maxHeight,
                         d_sadOut );
-  else if( maxWidth * maxHeight > 64 )
+  else if( lanes == 16 )
     hipLaunchKernelGGL( ( motion_comp_kernel<16, 4> ), dim3( ( n + 3 ) / 4 ), dim3( 64 ), 4 * lds, ctx->stream, d_orgBase, d_refBase, d_predBase, d_outBase, d_jobs, n, maxWidth,
                         maxHeight, d_sadOut );
-  else
+  else if( lanes == 8 )
     hipLaunchKernelGGL( ( motion_comp_kernel<8, 8> ), dim3( ( n + 7 ) / 8 ), dim3( 64 ), 8 * lds, ctx->stream, d_orgBase, d_refBase, d_predBase, d_outBase, d_jobs, n, maxWidth,
                         maxHeight, d_sadOut );
   VTMHIP_LAUNCHED( ctx );
@@ -731,19 +733,21 @@ int vtmhip_internal_mc_amvp_launch( vtmhip_ctx *ctx, const vtmhip_pic_params *pi
 {
   const size_t lds = ( ( ( size_t ) maxWidth * ( maxHeight + 7 ) + ( size_t ) maxWidth * maxHeight + 7 ) & ~( size_t ) 7 ) * sizeof( int16_t );
   const int    n2  = 2 * n;
+  const int lanes = vtmhip_mc_lanes_per_block( maxWidth, maxHeight );
+  VTMHIP_REQUIRE( ctx, lanes != 0, "maxWidth / maxHeight" );
   VTMHIP_TIME_KERNEL( ctx, "motion_comp_kernel" );
-  if( maxWidth * maxHeight > 1024 )
+  if( lanes == 256 )
   {
     if( lds > 64 * 1024 )
       VTMHIP_HIP( ctx, hipFuncSetAttribute( reinterpret_cast<const void *>( motion_comp_amvp_kernel<256, 1> ), hipFuncAttributeMaxDynamicSharedMemorySize, ( int ) lds ) );
     hipLaunchKernelGGL( ( motion_comp_amvp_kernel<256, 1> ), dim3( n2 ), dim3( 256 ), lds, ctx->stream, *pic, d_orgBase, d_refBase, d_rows, n2, maxWidth, maxHeight, d_sadOut );
   }
-  else if( maxWidth * maxHeight > 256 )
+  else if( lanes == 64 )
     hipLaunchKernelGGL( ( motion_comp_amvp_kernel<64, 1> ), dim3( n2 ), dim3( 64 ), lds, ctx->stream, *pic, d_orgBase, d_refBase, d_rows, n2, maxWidth, maxHeight, d_sadOut );
-  else if( maxWidth * maxHeight > 64 )
+  else if( lanes == 16 )
     hipLaunchKernelGGL( ( motion_comp_amvp_kernel<16, 4> ), dim3( ( n2 + 3 ) / 4 ), dim3( 64 ), 4 * lds, ctx->stream, *pic, d_orgBase, d_refBase, d_rows, n2, maxWidth, maxHeight,
                         d_sadOut );
-  else
+  else if( lanes == 8 )
     hipLaunchKernelGGL( ( motion_comp_amvp_kernel<8, 8> ), dim3( ( n2 + 7 ) / 8 ), dim3( 64 ), 8 * lds, ctx->stream, *pic, d_orgBase, d_refBase, d_rows, n2, maxWidth, maxHeight,
                         d_sadOut );
   VTMHIP_LAUNCHED( ctx );
@@ -752,6 +756,14 @@ int vtmhip_internal_mc_amvp_launch( vtmhip_ctx *ctx, const vtmhip_pic_params *pi
 
 extern "C"
 {
+
+// lanes per block by its number of 8-sample items: the thresholds of the two launch helpers above (their measurements are beside the first)
+int vtmhip_mc_lanes_per_block( int maxWidth, int maxHeight )
+{
+  if( maxWidth < 2 || maxWidth > 128 || maxHeight < 2 || maxHeight > 128 ) return 0;
+  const int area = maxWidth * maxHeight;
+  return area > 1024 ? 256 : area > 256 ? 64 : area > 64 ? 16 : 8;
+}
 
 int vtmhip_mc_luma_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, int16_t *d_dstBase, const vtmhip_mc_job *d_jobs, int n, int maxWidth,
                               int maxHeight )
