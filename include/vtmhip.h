@@ -1510,7 +1510,7 @@ int vtmhip_intra_struct_size( int which );   /* sizeof() of 0 vtmhip_intra_param
 typedef struct
 {
   int64_t cbRefOff, crRefOff;   /* the component's top line d_refBase[off .. off + 2W], index 0 = the corner; its left line follows directly: 2H + 1 samples */
-  int64_t cbOrgOff, crOrgOff;   /* original blocks inside d_orgBase (pre-selection only) */
+  int64_t cbOrgOff, crOrgOff;   /* original blocks inside d_orgBase (pre-selection and the chain, vtmhip_intra_chroma_chain_batch_dev) */
   int64_t lumaOff;              /* inside d_lumaBase: the luma reconstruction sample under chroma (0, 0).  Read around it (LM modes only): columns 0 .. 2W - 1 of
                                    rows 0 .. 2H - 1; with above, rows -3 .. -1 of columns (left ? -3 : 0) .. 2 (W + aboveRight) - 1; with left, columns -3 .. -1 of
                                    rows (above ? -3 : 0) .. 2 (H + belowLeft) - 1 */
@@ -1526,7 +1526,8 @@ typedef struct
 
 typedef struct
 {
-  int64_t cbPredOff, crPredOff;   /* vtmhip_intra_chroma_pred_batch_dev only: the W x H predictions (stride W) inside d_predBase */
+  int64_t cbPredOff, crPredOff;   /* vtmhip_intra_chroma_pred_batch_dev and vtmhip_intra_chroma_chain_batch_dev: the W x H predictions (stride W) inside d_predBase;
+                                     the latter writes the residuals at the same offsets inside d_resiBase */
   int32_t block;                  /* index into d_blocks */
   uint8_t mode;                   /* 0 .. 66 regular, 67 LM, 68 MDLM_L, 69 MDLM_T */
   uint8_t reserved[3];            /* 0 */
@@ -1612,9 +1613,9 @@ int vtmhip_mip_struct_size( int which );   /* sizeof() of 0 vtmhip_mip_job; -1 o
  * piReco.reconstruct( piPred, piResi, clpRng ) and getDistPart( piOrg, piReco, DF_SSE ).  The predictions are the two job tables above with the meaning they have
  * there, over one vtmhip_intra_block table (orgOff / orgStride are used here); the chain is the fused chain of vtmhip_tu_chain_batch_dev.  The only upload of a
  * level is its reference lines and the tables; nothing goes through the host between the steps.
- * NOT covered, the caller's or a later change: LFNST between xT and quant; ISP and BDPCM; the chroma and JCCR intra chains; DF_SSE_WTD / LMCS (the caller hands
+ * NOT covered, the caller's or a later change: LFNST between xT and quant; ISP and BDPCM; DF_SSE_WTD / LMCS (the caller hands
  * the original in the domain it codes in); RDOQ / dependent quantisation (the chain is Quant::quant, as everywhere in this library); the CABAC bit estimate, the
- * RD decision and the candidate lists; the encoder hook. */
+ * RD decision and the candidate lists; the encoder hook.  The chroma and JCCR intra chains have an entry of their own below (vtmhip_intra_chroma_chain_batch_dev). */
 typedef struct
 {
   int64_t outOff;            /* W x H contiguous: the levels inside d_levelsBase, the reconstruction inside d_recoBase */
@@ -1658,6 +1659,82 @@ int vtmhip_intra_chain_make_tu_jobs( const vtmhip_intra_block *blocks, int numBl
                                      int nMip, const vtmhip_intra_tu_job *tuJobs, int nTu, vtmhip_tu_job *out, int *maxWidth, int *maxHeight, int *uniform );
 
 int vtmhip_intra_chain_struct_size( int which );   /* sizeof() of 0 vtmhip_intra_tu_job, 1 vtmhip_intra_tu_result; -1 otherwise */
+
+/* ---- intra chroma residual chain: one full-RD level of IntraSearch::xRecurIntraChromaCodingQT in one call (EncoderLib/IntraSearch.cpp:4934-5260) -- the Cb and Cr
+ * predictions of a level and their residuals, then per candidate the chroma branch of xIntraCodingTUBlock (:3196-3318): for a single component scaleSignal( adj, 1 ),
+ * transformNxN / invTransformNxN, scaleSignal( adj, 0 ), piReco.reconstruct( piPred, piResi, clpRng ), getDistPart( piOrg, piReco, DF_SSE ); for a joint Cb-Cr
+ * candidate scale both, forward ICT, the chain on the coded component, inverse ICT, inverse scaling of both, both reconstructions and both distortions.  The
+ * predictions are vtmhip_intra_chroma_job records over a vtmhip_intra_chroma_block table with the meaning they have above (cbOrgOff / crOrgOff / orgStride are used
+ * here); the chains are vtmhip_tu_chain_crs_batch_dev and vtmhip_jccr_chain_crs_batch_dev (the plain forms when no job carries an adj).  The reference inverse-scales
+ * only when uiAbsSum > 0; a zero block maps to zero, so always doing it is identical.  The only upload of a level is its lines and the tables; nothing goes through
+ * the host between the steps.
+ * What stays the caller's: the lambda adjustments (:3125-3156); Reshape::calculateChromaAdjVpduNei (the adj comes per job); the cbf-dependent candidate pruning
+ * (:5061, :5087, :5179-5224) and selectICTCandidates -- the caller runs the joint candidates speculatively and discards on the host, as for MTS candidates -- ; the
+ * discard of a joint candidate whose coded cbf is 0 (:3250-3254: absSum == 0 in the result; the outputs are still written); the CABAC estimate; DF_SSE_WTD under LMCS
+ * (the reconstruction is left in global memory, so vtmhip_sse_wtd_batch_dev can follow); BDPCM, LFNST, lossless, ACT; chroma sides of 2; 4:2:2 / 4:4:4. */
+typedef struct
+{
+  int64_t  outOff;          /* W x H contiguous: the levels inside d_levelsBase, the reconstruction inside d_recoBase */
+  int32_t  pred;            /* 0 .. nPred - 1: d_jobs[pred] (both components of it were predicted) */
+  int16_t  qpPer, qpRem;    /* QpParam( tu, compID ).per / rem; transform skip: per( true ) / rem( true ) */
+  uint8_t  component;       /* 0 Cb, 1 Cr */
+  uint8_t  typeHor;         /* VTMHIP_DCT2 (DCT2 / DCT2) or VTMHIP_TRSKIP */
+  uint8_t  isIRAP, reserved;   /* reserved: 0 */
+  uint16_t chromaAdj;       /* tu.getChromaAdj(), 0 = no scaling; at most 32767 */
+  uint16_t pad;             /* 0 */
+} vtmhip_intra_chroma_tu_job;   /* its result: vtmhip_intra_tu_result */
+
+typedef struct
+{
+  int64_t  outOff;          /* W x H contiguous: the Cb reconstruction inside d_recoBase, the Cr reconstruction inside d_recoCrBase, the levels of the coded component
+                               inside d_levelsBase */
+  int32_t  pred;            /* as above */
+  int16_t  qpPer, qpRem;    /* QpParam( tu, codeCompId ).per / rem as for vtmhip_jccr_job: the device does not derive it */
+  uint8_t  typeHor, isIRAP; /* typeHor: VTMHIP_DCT2 or VTMHIP_TRSKIP */
+  uint8_t  cbfMask;         /* tu.jointCbCr: 1 .. 3 */
+  uint8_t  signFlag;        /* picHeader.getJointCbCrSignFlag(): 0 / 1 */
+  uint16_t chromaAdj, pad;  /* as above */
+} vtmhip_intra_chroma_joint_job;
+
+typedef struct
+{
+  uint64_t sseCb, sseCr;          /* DF_SSE of the original blocks against the clipped reconstructions (:3313-3316) */
+  uint64_t sseResiCb, sseResiCr;  /* the joint chain's own vtmhip_jccr_result.sseCb / sseCr: residual against reconstructed residual */
+  int64_t  fwdDist;               /* as vtmhip_jccr_result */
+  int32_t  sumAbs, absSum;        /* as vtmhip_jccr_result; absSum == 0: the reference discards this candidate (:3250) */
+} vtmhip_intra_chroma_joint_result;
+
+/* Prediction p (d_jobs[p]) writes its Cb and Cr samples with stride W at d_predBase + cbPredOff / crPredOff and the UNSCALED residuals original - prediction, same
+ * layout, at the same offsets inside d_resiBase (the chains scale on load) -- from the same registers, the two originals staged on chip; a prediction no job names
+ * is formed too.  Single job k is one transform candidate of one component of prediction `pred`; joint job k one (cbfMask, transform) candidate of it.  Several jobs
+ * may name one prediction (Cb DCT2, Cb TS, Cr DCT2, Cr TS, three masks times two transforms).  The chains write the levels to d_levelsBase + outOff (d_levelsBase may
+ * be NULL) and the reconstructed residuals to d_recoBase / d_recoCrBase + outOff, which a finish kernel overwrites in place with
+ * Clip( prediction + reconstructed residual, 0, ( 1 << bitDepth ) - 1 ); sse / sseCb / sseCr are what vtmhip_dist_batch_dev( VTMHIP_DIST_SSE ) gives for the original
+ * block and that reconstruction.  nTu == nJoint == 0 is the prediction + residual pass alone; a table that is empty needs none of its pointers (d_recoBase serves
+ * both job tables, d_recoCrBase the joint one); d_lumaBase may be NULL when no job of d_jobs is an LM mode.  All of nPred, nTu, nJoint 0 is VTMHIP_OK.
+ * The four tables are read back (one stream synchronisation; never call this under stream capture) and checked on the host before anything is launched; from the
+ * same pass come the lanes a prediction gets, per job table the largest sides and whether all its jobs have one size and VTMHIP_DCT2 (the one-lane and
+ * register-blocked chain kernels are then reached without a promise from the caller), and whether any job carries an adj.  As vtmhip_intra_chain_batch_dev, and
+ * UNLIKE the prediction entries above, this entry REJECTS THE WHOLE CALL with VTMHIP_E_INVALID and nothing launched: a required pointer NULL, a negative count; a
+ * block the prediction entries would skip (a side outside 4 / 8 / 16 / 32, a bitDepth outside 8 .. 12, a flag above 1, inconsistent availability); a block index
+ * outside the table, a mode above 69, an LM mode without d_lumaBase; pred outside [0, nPred); component > 1; typeHor other than VTMHIP_DCT2 / VTMHIP_TRSKIP; qpRem
+ * outside 0 .. 5, qpPer < 0; chromaAdj > 32767; cbfMask outside 1 .. 3; signFlag > 1; a non-zero reserved / pad field in any of the four tables. */
+int vtmhip_intra_chroma_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_lumaBase, const int16_t *d_orgBase,
+                                         const vtmhip_intra_chroma_block *d_blocks, int numBlocks, const vtmhip_intra_chroma_job *d_jobs, int nPred,
+                                         const vtmhip_intra_chroma_tu_job *d_tuJobs, int nTu, const vtmhip_intra_chroma_joint_job *d_jointJobs, int nJoint,
+                                         int16_t *d_predBase, int16_t *d_resiBase, int32_t *d_levelsBase, int16_t *d_recoBase, int16_t *d_recoCrBase,
+                                         vtmhip_intra_tu_result *d_results, vtmhip_intra_chroma_joint_result *d_jointResults );
+
+/* The same checks and the same expansion as host arithmetic on host tables, no context: outTu[k] = single job k as vtmhip_tu_chain_crs_batch_dev sees it (resiOff =
+ * the component's prediction offset inside d_resiBase, resiStride = W), outJoint[k] = joint job k as vtmhip_jccr_chain_crs_batch_dev sees it (cbOff / crOff = the two
+ * prediction offsets).  outTu holds nTu and outJoint nJoint records; both are left untouched when a table is rejected (VTMHIP_E_INVALID).  maxWidth / maxHeight:
+ * int[2] each -- [0] over the single jobs, [1] over the joint jobs: the largest sides (0 without any job); *uniformTu / *uniformJoint: 1 when every job of that
+ * table has one size and VTMHIP_DCT2; *crs: 1 when some job of either table has a non-zero chromaAdj.  Each of the five may be NULL. */
+int vtmhip_intra_chroma_chain_make_jobs( const vtmhip_intra_chroma_block *blocks, int numBlocks, const vtmhip_intra_chroma_job *jobs, int nPred,
+                                         const vtmhip_intra_chroma_tu_job *tuJobs, int nTu, const vtmhip_intra_chroma_joint_job *jointJobs, int nJoint,
+                                         vtmhip_tu_job *outTu, vtmhip_jccr_job *outJoint, int *maxWidth, int *maxHeight, int *uniformTu, int *uniformJoint, int *crs );
+
+int vtmhip_intra_chroma_chain_struct_size( int which );   /* sizeof() of 0 vtmhip_intra_chroma_tu_job, 1 vtmhip_intra_chroma_joint_job, 2 vtmhip_intra_chroma_joint_result; -1 otherwise */
 
 #ifdef __cplusplus
 }

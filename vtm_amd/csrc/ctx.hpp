@@ -32,6 +32,7 @@ struct vtmhip_ctx
   std::map<std::pair<hipStream_t, int>, WorkArena> work;   // key: (stream, slot) -- slot 0: the multi-stage calls, slot 1: calls they nest (the split TZ search)
                                                             // slot 2: the chain's shape bucketing (bucket.hpp) and the AMVP SADs (pis.hip), 3: the SBT chain (sbt.hip), 4: the picture loop's box sums
                                                             // (driver.hip; attached for a whole picture), 5: the intra residual chain (intra_chain.hip)
+                                                            // 6: the intra chroma residual chain (intra_chroma_chain.hip)
   int8_t     *lfnstTab    = nullptr;   // the caller's LFNST core matrices: g_lfnst8x8 [4][2][16][48] then g_lfnst4x4 [4][2][16][16] (vtmhip_lfnst_set_tables)
   uint8_t    *mipTab      = nullptr;   // the caller's MIP matrices: mipMatrix4x4 [16][16][4], mipMatrix8x8 [8][16][8], mipMatrix16x16 [6][64][7] (vtmhip_mip_set_tables, under initMutex)
   int32_t    *wtdFixed    = nullptr;   // DF_SSE_WTD: fixed-point luma-level weights (int64_t)( w * 65536.0 ), 1 << wtdLumaBD entries (vtmhip_set_luma_level_weights)
@@ -144,6 +145,10 @@ int vtmhip_internal_scratch( vtmhip_ctx *ctx, size_t bytes );   // grows ctx->sc
 int vtmhip_internal_tr_tables( vtmhip_ctx *ctx );               // transform.hip: fills ctx->trTab / trTabBuf on first use (under initMutex)
 int vtmhip_internal_tu_chain_launch( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
                                      int32_t *d_levelsBase, int16_t *d_recBase, vtmhip_tu_result *d_results );   // transform.hip: the dispatch of vtmhip_tu_chain_batch_dev
+int vtmhip_internal_tu_chain_crs_launch( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
+                                         int32_t *d_levelsBase, int16_t *d_recBase, vtmhip_tu_result *d_results );   // transform.hip: the dispatch of vtmhip_tu_chain_crs_batch_dev
+int vtmhip_internal_jccr_chain_launch( vtmhip_ctx *ctx, bool crs, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int maxWidth, int maxHeight,
+                                       int uniformSize, int32_t *d_levelsBase, int16_t *d_recCbBase, int16_t *d_recCrBase, vtmhip_jccr_result *d_results );   // jccr.hip: the joint chain's dispatch alone, its jobs checked by the caller
 int vtmhip_internal_mc_launch( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_refBase, int16_t *d_predBase, int16_t *d_outBase, const vtmhip_pred_job *d_jobs,
                                int n, int maxWidth, int maxHeight, unsigned long long *d_sadOut );   // mc.hip: motionCompensation, optionally reduced to the SAD against the original
 int vtmhip_internal_mc_amvp_launch( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, const vtmhip_me_job *d_rows, int n,

@@ -453,15 +453,19 @@ int launch_uni( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_jccr_jo
   return VTMHIP_OK;
 }
 
-// vtmhip_jccr_chain_batch_dev (CRS == false) and vtmhip_jccr_chain_crs_batch_dev: one dispatch, the same launch paths
+// vtmhip_jccr_chain_batch_dev (CRS == false) and vtmhip_jccr_chain_crs_batch_dev: the host check of the job table (jccr_chain_entry), then one dispatch with the
+// same launch paths (jccr_chain_dispatch: it launches and nothing else, for a caller whose jobs are checked already)
+template<bool CRS>
+int jccr_chain_dispatch( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
+                         int32_t *d_levelsBase, int16_t *d_recCbBase, int16_t *d_recCrBase, vtmhip_jccr_result *d_results );
+
 template<bool CRS>
 int jccr_chain_entry( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
                       int32_t *d_levelsBase, int16_t *d_recCbBase, int16_t *d_recCrBase, vtmhip_jccr_result *d_results )
 {
   VTMHIP_BATCH_ENTRY( ctx, n, d_resiBase && d_jobs && d_results );
   VTMHIP_REQUIRE( ctx, maxWidth >= 2 && maxWidth <= 64 && maxHeight >= 2 && maxHeight <= 64, "maxWidth / maxHeight: 2..64 (2-D transforms)" );
-  const bool lanePath = uniformSize && maxWidth * maxHeight <= 32 && maxWidth >= 4 && maxHeight >= 4;
-  const bool uniPath  = uniformSize && maxWidth >= 8 && maxHeight >= 8;
+  const bool uniPath = uniformSize && maxWidth >= 8 && maxHeight >= 8;
   if( uniPath ) VTMHIP_REQUIRE( ctx, pow2( maxWidth ) && pow2( maxHeight ), "uniformSize: width / height must be powers of two (TU sizes are)" );
   int st = vtmhip_internal_tr_tables( ctx );
   if( st ) return st;
@@ -487,6 +491,15 @@ int jccr_chain_entry( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_j
       VTMHIP_REQUIRE( ctx, !uniformSize || ( !ts && j.width == maxWidth && j.height == maxHeight ), "uniformSize: every job maxWidth x maxHeight with VTMHIP_DCT2" );
     }
   }
+  return jccr_chain_dispatch<CRS>( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, uniformSize, d_levelsBase, d_recCbBase, d_recCrBase, d_results );
+}
+
+template<bool CRS>
+int jccr_chain_dispatch( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
+                         int32_t *d_levelsBase, int16_t *d_recCbBase, int16_t *d_recCrBase, vtmhip_jccr_result *d_results )
+{
+  const bool lanePath = uniformSize && maxWidth * maxHeight <= 32 && maxWidth >= 4 && maxHeight >= 4;
+  const bool uniPath  = uniformSize && maxWidth >= 8 && maxHeight >= 8;
   if( lanePath )
   {
     if( maxWidth == 4 && maxHeight == 4 ) return launch_lane<4, 4, CRS>( ctx, d_resiBase, d_jobs, n, d_levelsBase, d_recCbBase, d_recCrBase, d_results );
@@ -637,3 +650,14 @@ int vtmhip_jccr_chain_crs_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase,
 }
 
 }   // extern "C"
+
+// the dispatch of vtmhip_jccr_chain_batch_dev (crs: of vtmhip_jccr_chain_crs_batch_dev) without the read-back of the job table, for intra_chroma_chain.hip: its jobs
+// are expanded on the device from tables the entry has checked (power-of-two sides 4 .. 32, cbfMask 1 .. 3, DCT2 or transform skip, uniformSize as found).
+// It stands behind the public entries and names the plain instantiation first: the order of first use is the order of the kernels in the object.
+int vtmhip_internal_jccr_chain_launch( vtmhip_ctx *ctx, bool crs, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int maxWidth, int maxHeight,
+                                       int uniformSize, int32_t *d_levelsBase, int16_t *d_recCbBase, int16_t *d_recCrBase, vtmhip_jccr_result *d_results )
+{
+  VTMHIP_TRY( vtmhip_internal_tr_tables( ctx ) );
+  if( !crs ) return jccr_chain_dispatch<false>( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, uniformSize, d_levelsBase, d_recCbBase, d_recCrBase, d_results );
+  return jccr_chain_dispatch<true>( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, uniformSize, d_levelsBase, d_recCbBase, d_recCrBase, d_results );
+}

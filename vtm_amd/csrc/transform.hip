@@ -701,6 +701,13 @@ int vtmhip_internal_tu_chain_launch( vtmhip_ctx *ctx, const int16_t *d_resiBase,
   return tu_chain_entry<false>( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, uniformSize, d_levelsBase, d_recBase, d_results );
 }
 
+// the same for vtmhip_tu_chain_crs_batch_dev (intra_chroma_chain.hip: jobs that carry a chroma adj)
+int vtmhip_internal_tu_chain_crs_launch( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_job *d_jobs, int n, int maxWidth, int maxHeight, int uniformSize,
+                                         int32_t *d_levelsBase, int16_t *d_recBase, vtmhip_tu_result *d_results )
+{
+  return tu_chain_entry<true>( ctx, d_resiBase, d_jobs, n, maxWidth, maxHeight, uniformSize, d_levelsBase, d_recBase, d_results );
+}
+
 extern "C"
 {
 

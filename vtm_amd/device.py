@@ -559,6 +559,14 @@ class Context:
             b.free()
         return res
 
+    def intra_chroma_chain_batch(self, d_ref, d_luma, d_org, d_blocks, num_blocks, d_jobs, n_pred, d_tu_jobs, n_tu, d_joint_jobs, n_joint, d_pred, d_resi, d_reco,
+                                 d_reco_cr, d_results, d_joint_results, d_levels=None):
+        """one intra chroma RD level: both predictions of every IntraChromaJob and their residuals, then per IntraChromaTuJob (one component) and per
+        IntraChromaJointJob (joint Cb-Cr) the chain with chroma residual scaling, the clipped reconstruction (in place at outOff inside d_reco / d_reco_cr) and an
+        IntraTuResult / IntraChromaJointResult.  A malformed table is rejected whole (VtmHipError, nothing launched)."""
+        self._check(self.L.vtmhip_intra_chroma_chain_batch_dev(self.h, d_ref, d_luma, d_org, d_blocks, num_blocks, d_jobs, n_pred, d_tu_jobs, n_tu, d_joint_jobs, n_joint,
+                                                               d_pred, d_resi, d_levels, d_reco, d_reco_cr, d_results, d_joint_results))
+
     def scale_signal_batch(self, d_src, d_dst, d_jobs, n):
         """scaleSignal of n ScaleJob blocks, each with its own scale and direction (d_dst may be d_src: in place)"""
         self._check(self.L.vtmhip_scale_signal_batch_dev(self.h, d_src, d_dst, d_jobs, n))
@@ -702,3 +710,18 @@ def intra_chain_make_tu_jobs(blocks, intra_jobs, mip_jobs, tu_jobs):
     if st != _lib.OK:
         raise VtmHipError(st)
     return (TuJob * n[3]).from_buffer_copy(bytes(out)[:n[3] * C.sizeof(TuJob)]), mw.value, mh.value, uni.value
+
+
+def intra_chroma_chain_make_jobs(blocks, jobs, tu_jobs, joint_jobs):
+    """The host form of the intra chroma chain's checks and expansion over ctypes arrays (None: an empty table):
+    (TuJob array, JccrJob array, (maxWidth, maxHeight, uniform) of the single jobs, the same of the joint jobs, crs)"""
+    n = [0 if a is None else len(a) for a in (blocks, jobs, tu_jobs, joint_jobs)]
+    ptr = [None if a is None else C.addressof(a) for a in (blocks, jobs, tu_jobs, joint_jobs)]
+    out_tu, out_joint = (TuJob * max(n[2], 1))(), (JccrJob * max(n[3], 1))()
+    mw, mh, uni_tu, uni_joint, crs = (C.c_int * 2)(), (C.c_int * 2)(), C.c_int(), C.c_int(), C.c_int()
+    st = _lib.load().vtmhip_intra_chroma_chain_make_jobs(ptr[0], n[0], ptr[1], n[1], ptr[2], n[2], ptr[3], n[3], C.addressof(out_tu), C.addressof(out_joint), mw, mh,
+                                                         C.byref(uni_tu), C.byref(uni_joint), C.byref(crs))
+    if st != _lib.OK:
+        raise VtmHipError(st)
+    return ((TuJob * n[2]).from_buffer_copy(bytes(out_tu)[:n[2] * C.sizeof(TuJob)]), (JccrJob * n[3]).from_buffer_copy(bytes(out_joint)[:n[3] * C.sizeof(JccrJob)]),
+            (mw[0], mh[0], uni_tu.value), (mw[1], mh[1], uni_joint.value), crs.value)

@@ -365,6 +365,21 @@ class CclmModel(C.Structure):
     _fields_ = [("a", C.c_int32), ("b", C.c_int32), ("shift", C.c_int32)]
 
 
+class IntraChromaTuJob(C.Structure):
+    _fields_ = [("outOff", C.c_int64), ("pred", C.c_int32), ("qpPer", C.c_int16), ("qpRem", C.c_int16), ("component", C.c_uint8), ("typeHor", C.c_uint8),
+                ("isIRAP", C.c_uint8), ("reserved", C.c_uint8), ("chromaAdj", C.c_uint16), ("pad", C.c_uint16)]
+
+
+class IntraChromaJointJob(C.Structure):
+    _fields_ = [("outOff", C.c_int64), ("pred", C.c_int32), ("qpPer", C.c_int16), ("qpRem", C.c_int16), ("typeHor", C.c_uint8), ("isIRAP", C.c_uint8),
+                ("cbfMask", C.c_uint8), ("signFlag", C.c_uint8), ("chromaAdj", C.c_uint16), ("pad", C.c_uint16)]
+
+
+class IntraChromaJointResult(C.Structure):
+    _fields_ = [("sseCb", C.c_uint64), ("sseCr", C.c_uint64), ("sseResiCb", C.c_uint64), ("sseResiCr", C.c_uint64), ("fwdDist", C.c_int64), ("sumAbs", C.c_int32),
+                ("absSum", C.c_int32)]
+
+
 _STRUCTS = [DistJob, TzJob, MeResult, PicParams, IfJob, FracJob, FracResult, TrJob, QuantJob, FullJob, McJob, PelOpJob,
             TuJob, TuResult, AffineJob, MeCfg, MeJob, MeOut, PredJob, MaskedSadJob, GeoBlendJob, DmvrJob, LfnstJob,
             PisRow, PisPu, PisLevel, AffineMeJob, AffineMeOut, LfnstTuJob, PisLevelRun, PisBuffers, SmvdJob, PisPuIn, WtdJob,
@@ -376,6 +391,7 @@ _INTRA_STRUCTS = [IntraParams, IntraBlock, IntraJob]          # order of vtmhip_
 _INTRA_CHROMA_STRUCTS = [IntraChromaBlock, IntraChromaJob, CclmModel]   # order of vtmhip_intra_chroma_struct_size(which)
 _MIP_STRUCTS = [MipJob]                                       # order of vtmhip_mip_struct_size(which)
 _INTRA_CHAIN_STRUCTS = [IntraTuJob, IntraTuResult]            # order of vtmhip_intra_chain_struct_size(which)
+_INTRA_CHROMA_CHAIN_STRUCTS = [IntraChromaTuJob, IntraChromaJointJob, IntraChromaJointResult]   # order of vtmhip_intra_chroma_chain_struct_size(which)
 
 # every symbol include/vtmhip.h declares (tests/test_abi.py checks the exports against the header text)
 _PROTOS = {
@@ -514,6 +530,11 @@ _PROTOS = {
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtmhip_intra_chain_make_tu_jobs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int),
                                                   C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vtmhip_intra_chroma_chain_struct_size": (C.c_int, [C.c_int]),
+    "vtmhip_intra_chroma_chain_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtmhip_intra_chroma_chain_make_jobs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                      C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vtmhip_intra_cand_cost_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vtmhip_satd8_grid_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p]),
@@ -621,6 +642,10 @@ def load():
         if lib.vtmhip_intra_chain_struct_size(i) != C.sizeof(s):
             raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
                               % (s.__name__, C.sizeof(s), lib.vtmhip_intra_chain_struct_size(i)))
+    for i, s in enumerate(_INTRA_CHROMA_CHAIN_STRUCTS):
+        if lib.vtmhip_intra_chroma_chain_struct_size(i) != C.sizeof(s):
+            raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
+                              % (s.__name__, C.sizeof(s), lib.vtmhip_intra_chroma_chain_struct_size(i)))
     _lib = lib
     return lib
 
