@@ -1613,7 +1613,8 @@ int vtmhip_mip_struct_size( int which );   /* sizeof() of 0 vtmhip_mip_job; -1 o
  * piReco.reconstruct( piPred, piResi, clpRng ) and getDistPart( piOrg, piReco, DF_SSE ).  The predictions are the two job tables above with the meaning they have
  * there, over one vtmhip_intra_block table (orgOff / orgStride are used here); the chain is the fused chain of vtmhip_tu_chain_batch_dev.  The only upload of a
  * level is its reference lines and the tables; nothing goes through the host between the steps.
- * NOT covered, the caller's or a later change: LFNST between xT and quant; ISP and BDPCM; DF_SSE_WTD / LMCS (the caller hands
+ * The lfnstIdx 1 / 2 candidates of a level go through vtmhip_intra_chain_lfnst_batch_dev below.
+ * NOT covered, the caller's or a later change: ISP and BDPCM; DF_SSE_WTD / LMCS (the caller hands
  * the original in the domain it codes in); RDOQ / dependent quantisation (the chain is Quant::quant, as everywhere in this library); the CABAC bit estimate, the
  * RD decision and the candidate lists; the encoder hook.  The chroma and JCCR intra chains have an entry of their own below (vtmhip_intra_chroma_chain_batch_dev). */
 typedef struct
@@ -1659,6 +1660,72 @@ int vtmhip_intra_chain_make_tu_jobs( const vtmhip_intra_block *blocks, int numBl
                                      int nMip, const vtmhip_intra_tu_job *tuJobs, int nTu, vtmhip_tu_job *out, int *maxWidth, int *maxHeight, int *uniform );
 
 int vtmhip_intra_chain_struct_size( int which );   /* sizeof() of 0 vtmhip_intra_tu_job, 1 vtmhip_intra_tu_result; -1 otherwise */
+
+/* ---- LFNST residual chain: the lfnstIdx 1 / 2 candidates of an intra luma TU in one kernel -- TrQuant::transformNxN / invTransformNxN with cu.lfnstIdx != 0:
+ * xT restricted to the kept region (TrQuant.cpp:792-804), xFwdLfnst (:436-526), Quant::quant over the first 8 / 16 scan positions (Quant.cpp:1003-1009),
+ * Quant::dequant, xInvLfnst (:339-434), xIT with the same zero-out (:872-884), and the SSE of the residual against the reconstructed residual.  DCT2 in both
+ * directions, no transform skip.  The kept primary region is 4x4 when a side is 4 and 8x8 otherwise; 8 scan positions are coded for 4x4 and 8x8 blocks, 16 for
+ * every other shape; the bottom-right 4x4 of an 8x8 region carries primary coefficients Quant::quant never reads: zero from there on.  The core matrices are the
+ * caller's (vtmhip_lfnst_set_tables).
+ * Out of scope: chroma LFNST (separate tree); ISP with LFNST; RDOQ, sign hiding and scaling lists; the CABAC bit estimate; the reference's own LFNST constraints on
+ * the coded block (the last-position rule, rapidLFNST); the encoder hook. */
+typedef struct
+{
+  int64_t resiOff, outOff;   /* the residual inside d_resiBase; W x H contiguous: the levels inside d_levelsBase, the reconstructed residual inside d_recBase */
+  int32_t resiStride;        /* >= width */
+  int16_t width, height;     /* 4, 8, 16, 32, 64 */
+  int16_t qpPer, qpRem;      /* as vtmhip_tu_job */
+  uint8_t bitDepth, isIRAP;  /* 8 .. 12 */
+  uint8_t setIdx, index;     /* lfnstTrSetIdx 0 .. 3 (vtmhip_lfnst_mode_host), lfnstIdx - 1 (0 .. 1) */
+  uint8_t transpose;         /* 0 / 1 */
+  uint8_t pad[7];            /* 0 */
+} vtmhip_lfnst_chain_job;
+
+/* Set index and transpose flag of a prediction on a width x height luma block: PU::getWideAngle, TrQuant::getLFNSTIntraMode / getTransposeFlag and g_lfnstLut for a
+ * regular mode 0 .. 66; planar (set 0, no transpose) for a MIP prediction, which needs both sides >= 16 (allowLfnstWithMip); intraMode is ignored then.  Host-only.
+ * VTMHIP_E_INVALID: a side outside 4 / 8 / 16 / 32 / 64, a mode outside 0 .. 66, MIP below 16, a NULL pointer. */
+int vtmhip_lfnst_mode_host( int width, int height, int intraMode, int isMip, int *setIdx, int *transpose );
+
+/* Per job: d_results[k].sse as vtmhip_tu_chain_batch_dev; sumAbs = sum |coefficient| over the quantised scan positions after the forward LFNST; absSum = uiAbsSum.
+ * Levels are W x H contiguous and zero outside the coded positions (d_levelsBase may be NULL); d_recBase may be NULL.  A job gets 16 lanes when the largest job of
+ * the table has up to 256 samples and a wave above (vtmhip_lfnst_chain_lanes_per_job).  The table is read back (one stream synchronisation; never under stream
+ * capture) and a malformed one REJECTS THE WHOLE CALL with VTMHIP_E_INVALID and nothing launched: a side outside the list, resiStride < width, bitDepth outside
+ * 8 .. 12, qpRem outside 0 .. 5, qpPer < 0, setIdx > 3, index > 1, transpose > 1, a non-zero pad byte; also a NULL table, residual or result pointer, n < 0, and
+ * a context that has not seen vtmhip_lfnst_set_tables.  n == 0 is VTMHIP_OK. */
+int vtmhip_lfnst_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_lfnst_chain_job *d_jobs, int n, int32_t *d_levelsBase, int16_t *d_recBase,
+                                  vtmhip_tu_result *d_results );
+int vtmhip_lfnst_chain_lanes_per_job( int maxArea );   /* host-only: 16 or 64 */
+
+/* The LFNST candidates of an intra level beside the plain ones: shape and bit depth come from the block, set index and transpose from the prediction. */
+typedef struct
+{
+  int64_t outOff;            /* as vtmhip_intra_tu_job */
+  int32_t pred;              /* as vtmhip_intra_tu_job */
+  int16_t qpPer, qpRem;      /* as vtmhip_tu_job */
+  uint8_t lfnstIdx, isIRAP;  /* 1 .. 2 */
+  uint8_t reserved[2];       /* 0 */
+  int32_t pad;               /* 0 */
+} vtmhip_intra_lfnst_tu_job;   /* its result: vtmhip_intra_tu_result */
+
+/* vtmhip_intra_chain_batch_dev with a second candidate table: the prediction + residual pass runs once, the plain TU jobs go through the fused chain and the LFNST
+ * jobs, expanded on the device, through the LFNST chain above; the finish kernel then runs over each result table (clipped reconstruction in place, SSE against the
+ * original).  Plain and LFNST jobs may name one prediction; nTu == 0 with nLfnst > 0 is valid, and the reverse; nLfnst == 0 is vtmhip_intra_chain_batch_dev.  All
+ * five tables are read back and checked before anything is launched: besides what vtmhip_intra_chain_batch_dev rejects, lfnstIdx outside 1 .. 2, a MIP prediction on
+ * a block with a side below 16, pred outside the tables, qpRem outside 0 .. 5, qpPer < 0, a non-zero reserved / pad field, nLfnst < 0, a NULL d_lfnstJobs /
+ * d_recoBase / d_lfnstResults with nLfnst > 0, and LFNST jobs before vtmhip_lfnst_set_tables reject the whole call with nothing written. */
+int vtmhip_intra_chain_lfnst_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_orgBase, const vtmhip_intra_block *d_blocks, int numBlocks,
+                                        const vtmhip_intra_job *d_intraJobs, int nIntra, const vtmhip_mip_job *d_mipJobs, int nMip, const vtmhip_intra_tu_job *d_tuJobs,
+                                        int nTu, const vtmhip_intra_lfnst_tu_job *d_lfnstJobs, int nLfnst, int16_t *d_predBase, int16_t *d_resiBase,
+                                        int32_t *d_levelsBase, int16_t *d_recoBase, vtmhip_intra_tu_result *d_results, vtmhip_intra_tu_result *d_lfnstResults );
+
+/* The same checks and expansion as host arithmetic, no context: outTu[k] as vtmhip_intra_chain_make_tu_jobs, outLfnst[k] = LFNST job k as the LFNST chain sees
+ * it.  Both are left untouched when a table is rejected (VTMHIP_E_INVALID).  *maxWidth / *maxHeight / *uniform: over the plain jobs; *lfnstLanes: the lanes an LFNST
+ * job gets (0 without any); each of the four may be NULL. */
+int vtmhip_intra_chain_lfnst_make_jobs( const vtmhip_intra_block *blocks, int numBlocks, const vtmhip_intra_job *intraJobs, int nIntra, const vtmhip_mip_job *mipJobs,
+                                        int nMip, const vtmhip_intra_tu_job *tuJobs, int nTu, const vtmhip_intra_lfnst_tu_job *lfnstJobs, int nLfnst, vtmhip_tu_job *outTu,
+                                        vtmhip_lfnst_chain_job *outLfnst, int *maxWidth, int *maxHeight, int *uniform, int *lfnstLanes );
+
+int vtmhip_lfnst_chain_struct_size( int which );   /* sizeof() of 0 vtmhip_lfnst_chain_job, 1 vtmhip_intra_lfnst_tu_job; -1 otherwise */
 
 /* ---- intra chroma residual chain: one full-RD level of IntraSearch::xRecurIntraChromaCodingQT in one call (EncoderLib/IntraSearch.cpp:4934-5260) -- the Cb and Cr
  * predictions of a level and their residuals, then per candidate the chroma branch of xIntraCodingTUBlock (:3196-3318): for a single component scaleSignal( adj, 1 ),

@@ -1,0 +1,21 @@
+"""The rules of vtm_amd/csrc/lfnst_rules.hpp (HIP-free: the LFNST mode and shape rules, the table checks and the expansion of the LFNST residual chain) as a
+stand-alone program under AddressSanitizer and UBSan, every table in a heap array of exactly its length."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "host", "test_lfnst_chain")
+
+
+def _build():
+    csrc = os.path.join(ROOT, "vtm_amd", "csrc")
+    srcs = [os.path.join(ROOT, "host", "test_lfnst_chain.cpp")] + [os.path.join(csrc, h) for h in ("lfnst_rules.hpp", "intra_chain_rules.hpp", "intra_rules.hpp", "mip_rules.hpp")]
+    if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(s) for s in srcs):
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", EXE, srcs[0]])
+
+
+def test_lfnst_rules_under_sanitizers():
+    _build()
+    r = subprocess.run([EXE], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "0 failures" in r.stdout and "26 of 26 malformed tables rejected" in r.stdout

@@ -149,6 +149,10 @@ int vtmhip_internal_tu_chain_crs_launch( vtmhip_ctx *ctx, const int16_t *d_resiB
                                          int32_t *d_levelsBase, int16_t *d_recBase, vtmhip_tu_result *d_results );   // transform.hip: the dispatch of vtmhip_tu_chain_crs_batch_dev
 int vtmhip_internal_jccr_chain_launch( vtmhip_ctx *ctx, bool crs, const int16_t *d_resiBase, const vtmhip_jccr_job *d_jobs, int n, int maxWidth, int maxHeight,
                                        int uniformSize, int32_t *d_levelsBase, int16_t *d_recCbBase, int16_t *d_recCrBase, vtmhip_jccr_result *d_results );   // jccr.hip: the joint chain's dispatch alone, its jobs checked by the caller
+int vtmhip_internal_lfnst_expand_launch( vtmhip_ctx *ctx, const vtmhip_intra_block *d_blocks, const vtmhip_intra_job *d_intraJobs, int nIntra, const vtmhip_mip_job *d_mipJobs,
+                                         const vtmhip_intra_lfnst_tu_job *d_lfnstJobs, int n, vtmhip_lfnst_chain_job *d_out, vtmhip_tu_job *d_mirror, int *d_tuBlock );   // lfnst_chain.hip
+int vtmhip_internal_lfnst_chain_launch( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_lfnst_chain_job *d_jobs, int n, int maxArea, int jobInts,
+                                        int32_t *d_levelsBase, int16_t *d_recBase, vtmhip_tu_result *d_results );   // lfnst_chain.hip: the LFNST chain's launch alone, its jobs checked by the caller
 int vtmhip_internal_mc_launch( vtmhip_ctx *ctx, const int16_t *d_orgBase, const int16_t *d_refBase, int16_t *d_predBase, int16_t *d_outBase, const vtmhip_pred_job *d_jobs,
                                int n, int maxWidth, int maxHeight, unsigned long long *d_sadOut );   // mc.hip: motionCompensation, optionally reduced to the SAD against the original
 int vtmhip_internal_mc_amvp_launch( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, const vtmhip_me_job *d_rows, int n,

@@ -2,6 +2,9 @@
 //   vtmhip_intra_chain_batch_dev     per (mode, transform candidate) the steps of IntraSearch::xIntraCodingTUBlock: prediction, residual, xT -> quant -> dequant -> xIT,
 //                                    clipped reconstruction and its SSE against the original                     (EncoderLib/IntraSearch.cpp:2989-3320)
 //   vtmhip_intra_chain_make_tu_jobs  the same checks and expansion as host arithmetic
+//   vtmhip_intra_chain_lfnst_batch_dev   the same level with a second candidate table, the lfnstIdx 1 / 2 candidates: expanded by lfnst_chain.hip's lfnst_expand_kernel
+//                                    behind the plain jobs in the workspace, run by its lfnst_chain_kernel, finished by a second launch of intra_chain_finish_kernel
+//   vtmhip_intra_chain_lfnst_make_jobs   its checks and both expansions as host arithmetic
 //
 // The launches of a call, all on the context's stream, nothing through the host between them:
 //   intra_resi_kernel / mip_resi_kernel   the bodies of intra_body.hpp / mip_body.hpp in their third mode: every prediction and original - prediction
@@ -18,6 +21,7 @@
 #include "intra_body.hpp"   // intra_chunk_body, as intra.hip's kernels use it
 #include "mip_body.hpp"     // mip_chunk_body, as mip.hip's
 #include "intra_chain_rules.hpp"
+#include "lfnst_rules.hpp"
 #include "pel_pack.hpp"
 
 namespace
@@ -141,26 +145,34 @@ int vtmhip_intra_chain_make_tu_jobs( const vtmhip_intra_block *blocks, int numBl
   return VTMHIP_OK;
 }
 
-int vtmhip_intra_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_orgBase, const vtmhip_intra_block *d_blocks, int numBlocks,
-                                  const vtmhip_intra_job *d_intraJobs, int nIntra, const vtmhip_mip_job *d_mipJobs, int nMip, const vtmhip_intra_tu_job *d_tuJobs,
-                                  int nTu, int16_t *d_predBase, int16_t *d_resiBase, int32_t *d_levelsBase, int16_t *d_recoBase, vtmhip_intra_tu_result *d_results )
+}   // extern "C"
+
+// both level entries: vtmhip_intra_chain_batch_dev is nLfnst == 0
+static int intra_chain_level( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_orgBase, const vtmhip_intra_block *d_blocks, int numBlocks,
+                              const vtmhip_intra_job *d_intraJobs, int nIntra, const vtmhip_mip_job *d_mipJobs, int nMip, const vtmhip_intra_tu_job *d_tuJobs, int nTu,
+                              const vtmhip_intra_lfnst_tu_job *d_lfnstJobs, int nLfnst, int16_t *d_predBase, int16_t *d_resiBase, int32_t *d_levelsBase, int16_t *d_recoBase,
+                              vtmhip_intra_tu_result *d_results, vtmhip_intra_tu_result *d_lfnstResults )
 {
   VTMHIP_CHECK_CTX( ctx );
-  VTMHIP_REQUIRE( ctx, numBlocks >= 0 && nIntra >= 0 && nMip >= 0 && nTu >= 0, "negative count" );
-  if( nIntra + nMip + nTu == 0 ) return VTMHIP_OK;
+  VTMHIP_REQUIRE( ctx, numBlocks >= 0 && nIntra >= 0 && nMip >= 0 && nTu >= 0 && nLfnst >= 0, "negative count" );
+  if( nIntra + nMip + nTu + nLfnst == 0 ) return VTMHIP_OK;
   VTMHIP_REQUIRE( ctx, d_refBase && d_orgBase && d_blocks && d_predBase && d_resiBase && ( !nIntra || d_intraJobs ) && ( !nMip || d_mipJobs ), "null pointer" );
   VTMHIP_REQUIRE( ctx, !nTu || ( d_tuJobs && d_recoBase && d_results ), "null pointer" );
+  VTMHIP_REQUIRE( ctx, !nLfnst || ( d_lfnstJobs && d_recoBase && d_lfnstResults ), "null pointer" );
   VTMHIP_REQUIRE( ctx, !nMip || ctx->mipTab, "vtmhip_mip_set_tables has not been called" );
+  VTMHIP_REQUIRE( ctx, !nLfnst || ctx->lfnstTab, "vtmhip_lfnst_set_tables has not been called" );
 
   // the tables decide the launches and the chain kernels trust their jobs: read back and checked before anything runs
   const size_t bBlk = ( size_t ) numBlocks * sizeof( vtmhip_intra_block ), bIntra = ( size_t ) nIntra * sizeof( vtmhip_intra_job ),
-               bMip = ( size_t ) nMip * sizeof( vtmhip_mip_job ), bTu = ( size_t ) nTu * sizeof( vtmhip_intra_tu_job );   // every record size is a multiple of 8
-  VTMHIP_TRY( vtmhip_internal_scratch( ctx, bBlk + bIntra + bMip + bTu ) );
+               bMip = ( size_t ) nMip * sizeof( vtmhip_mip_job ), bTu = ( size_t ) nTu * sizeof( vtmhip_intra_tu_job ),
+               bLf = ( size_t ) nLfnst * sizeof( vtmhip_intra_lfnst_tu_job );   // every record size is a multiple of 8
+  VTMHIP_TRY( vtmhip_internal_scratch( ctx, bBlk + bIntra + bMip + bTu + bLf ) );
   char *host = ( char * ) ctx->pinned;
   if( bBlk ) VTMHIP_HIP( ctx, hipMemcpyAsync( host, d_blocks, bBlk, hipMemcpyDeviceToHost, ctx->stream ) );
   if( bIntra ) VTMHIP_HIP( ctx, hipMemcpyAsync( host + bBlk, d_intraJobs, bIntra, hipMemcpyDeviceToHost, ctx->stream ) );
   if( bMip ) VTMHIP_HIP( ctx, hipMemcpyAsync( host + bBlk + bIntra, d_mipJobs, bMip, hipMemcpyDeviceToHost, ctx->stream ) );
   if( bTu ) VTMHIP_HIP( ctx, hipMemcpyAsync( host + bBlk + bIntra + bMip, d_tuJobs, bTu, hipMemcpyDeviceToHost, ctx->stream ) );
+  if( bLf ) VTMHIP_HIP( ctx, hipMemcpyAsync( host + bBlk + bIntra + bMip + bTu, d_lfnstJobs, bLf, hipMemcpyDeviceToHost, ctx->stream ) );
   VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
   IntraChainPlan plan;
   VTMHIP_REQUIRE( ctx,
@@ -168,6 +180,11 @@ int vtmhip_intra_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, con
                                   ( const vtmhip_mip_job * ) ( host + bBlk + bIntra ), nMip, ( const vtmhip_intra_tu_job * ) ( host + bBlk + bIntra + bMip ), nTu, plan ),
                   "intra chain tables: sides 4..64, bitDepth 8..12, multiRefIdx 0..2 (MIP: 0), block index, mode, pred inside the tables, qpRem 0..5, qpPer >= 0, "
                   "two of DCT2 / DCT8 / DST7 (DCT2 above 32) or both TRSKIP (sides up to 32), reserved fields 0" );
+  LfnstPlan lplan;
+  VTMHIP_REQUIRE( ctx,
+                  lfnstLevelScan( ( const vtmhip_intra_block * ) host, ( const vtmhip_intra_job * ) ( host + bBlk ), nIntra, ( const vtmhip_mip_job * ) ( host + bBlk + bIntra ), nMip,
+                                  ( const vtmhip_intra_lfnst_tu_job * ) ( host + bBlk + bIntra + bMip + bTu ), nLfnst, lplan ),
+                  "intra chain LFNST table: lfnstIdx 1..2, pred inside the tables, MIP on sides >= 16 only, qpRem 0..5, qpPer >= 0, reserved fields 0" );
 
   const int lanes = intra_lanes( plan.maxBlockArea ), chunk = intra_chunk( lanes );   // what intra_shape_kernel would leave: here the host knows it
   if( nIntra )
@@ -184,24 +201,35 @@ int vtmhip_intra_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, con
                         d_mipJobs, nMip, d_predBase, d_resiBase );
     VTMHIP_LAUNCHED( ctx );
   }
-  if( nTu == 0 ) return VTMHIP_OK;
+  if( nTu + nLfnst == 0 ) return VTMHIP_OK;
 
   // workspace (slot 5, unused until now -- ctx.hpp lists the slots: 0 the prediction entries, 2 the chain's bucketing, 3 SBT, 4 the picture loop's box sums, which stay
   // attached across the calls a picture makes): the block index per TU job, the expanded jobs, their results
-  const size_t oJobs = align256( ( size_t ) nTu * sizeof( int ) ), oRes = align256( oJobs + ( size_t ) nTu * sizeof( vtmhip_tu_job ) );
+  // the LFNST jobs follow the plain ones in all three arrays (their vtmhip_tu_job is the mirror the finish kernel reads); the LFNST chain's own jobs come last
+  const int    nAll = nTu + nLfnst;
+  const size_t oJobs = align256( ( size_t ) nAll * sizeof( int ) ), oRes = align256( oJobs + ( size_t ) nAll * sizeof( vtmhip_tu_job ) ),
+               oLf = align256( oRes + ( size_t ) nAll * sizeof( vtmhip_tu_result ) );
   void *arena = nullptr;
-  VTMHIP_TRY( vtmhip_internal_workspace( ctx, oRes + ( size_t ) nTu * sizeof( vtmhip_tu_result ), &arena, 5 ) );
+  VTMHIP_TRY( vtmhip_internal_workspace( ctx, oLf + ( size_t ) nLfnst * sizeof( vtmhip_lfnst_chain_job ), &arena, 5 ) );
   char *base = ( char * ) arena;
   int              *d_tuBlock = ( int * ) base;
   vtmhip_tu_job    *d_xJobs   = ( vtmhip_tu_job * ) ( base + oJobs );
   vtmhip_tu_result *d_xRes    = ( vtmhip_tu_result * ) ( base + oRes );
+  vtmhip_lfnst_chain_job *d_cJobs = ( vtmhip_lfnst_chain_job * ) ( base + oLf );
+  if( nTu )
   {
     VTMHIP_TIME_KERNEL( ctx, "intra_chain_expand_kernel" );
     hipLaunchKernelGGL( intra_chain_expand_kernel, dim3( ( nTu + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, d_blocks, d_intraJobs, nIntra, d_mipJobs, d_tuJobs, nTu, d_xJobs,
                         d_tuBlock );
     VTMHIP_LAUNCHED( ctx );
   }
-  VTMHIP_TRY( vtmhip_internal_tu_chain_launch( ctx, d_resiBase, d_xJobs, nTu, plan.maxWidth, plan.maxHeight, plan.uniform, d_levelsBase, d_recoBase, d_xRes ) );
+  if( nTu ) VTMHIP_TRY( vtmhip_internal_tu_chain_launch( ctx, d_resiBase, d_xJobs, nTu, plan.maxWidth, plan.maxHeight, plan.uniform, d_levelsBase, d_recoBase, d_xRes ) );
+  if( nLfnst )
+  {
+    VTMHIP_TRY( vtmhip_internal_lfnst_expand_launch( ctx, d_blocks, d_intraJobs, nIntra, d_mipJobs, d_lfnstJobs, nLfnst, d_cJobs, d_xJobs + nTu, d_tuBlock + nTu ) );
+    VTMHIP_TRY( vtmhip_internal_lfnst_chain_launch( ctx, d_resiBase, d_cJobs, nLfnst, lplan.maxArea, lplan.jobInts, d_levelsBase, d_recoBase, d_xRes + nTu ) );
+  }
+  if( nTu )
   {
     VTMHIP_TIME_KERNEL( ctx, "intra_chain_finish_kernel" );
     if( plan.maxTuArea <= 256 )
@@ -212,6 +240,54 @@ int vtmhip_intra_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, con
                           d_recoBase, d_results );
     VTMHIP_LAUNCHED( ctx );
   }
+  if( nLfnst )   // the same finish kernel over the second result table
+  {
+    VTMHIP_TIME_KERNEL( ctx, "intra_chain_finish_kernel" );
+    if( lplan.maxArea <= 256 )
+      hipLaunchKernelGGL( intra_chain_finish_kernel<16>, dim3( ( nLfnst + 15 ) / 16 ), dim3( 256 ), 0, ctx->stream, d_orgBase, d_predBase, d_blocks, d_tuBlock + nTu, d_xJobs + nTu,
+                          d_xRes + nTu, nLfnst, d_recoBase, d_lfnstResults );
+    else
+      hipLaunchKernelGGL( intra_chain_finish_kernel<64>, dim3( ( nLfnst + 3 ) / 4 ), dim3( 256 ), 0, ctx->stream, d_orgBase, d_predBase, d_blocks, d_tuBlock + nTu, d_xJobs + nTu,
+                          d_xRes + nTu, nLfnst, d_recoBase, d_lfnstResults );
+    VTMHIP_LAUNCHED( ctx );
+  }
+  return VTMHIP_OK;
+}
+
+extern "C"
+{
+
+int vtmhip_intra_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_orgBase, const vtmhip_intra_block *d_blocks, int numBlocks,
+                                  const vtmhip_intra_job *d_intraJobs, int nIntra, const vtmhip_mip_job *d_mipJobs, int nMip, const vtmhip_intra_tu_job *d_tuJobs,
+                                  int nTu, int16_t *d_predBase, int16_t *d_resiBase, int32_t *d_levelsBase, int16_t *d_recoBase, vtmhip_intra_tu_result *d_results )
+{
+  return intra_chain_level( ctx, d_refBase, d_orgBase, d_blocks, numBlocks, d_intraJobs, nIntra, d_mipJobs, nMip, d_tuJobs, nTu, nullptr, 0, d_predBase, d_resiBase, d_levelsBase,
+                            d_recoBase, d_results, nullptr );
+}
+
+int vtmhip_intra_chain_lfnst_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_orgBase, const vtmhip_intra_block *d_blocks, int numBlocks,
+                                        const vtmhip_intra_job *d_intraJobs, int nIntra, const vtmhip_mip_job *d_mipJobs, int nMip, const vtmhip_intra_tu_job *d_tuJobs,
+                                        int nTu, const vtmhip_intra_lfnst_tu_job *d_lfnstJobs, int nLfnst, int16_t *d_predBase, int16_t *d_resiBase,
+                                        int32_t *d_levelsBase, int16_t *d_recoBase, vtmhip_intra_tu_result *d_results, vtmhip_intra_tu_result *d_lfnstResults )
+{
+  return intra_chain_level( ctx, d_refBase, d_orgBase, d_blocks, numBlocks, d_intraJobs, nIntra, d_mipJobs, nMip, d_tuJobs, nTu, d_lfnstJobs, nLfnst, d_predBase, d_resiBase,
+                            d_levelsBase, d_recoBase, d_results, d_lfnstResults );
+}
+
+int vtmhip_intra_chain_lfnst_make_jobs( const vtmhip_intra_block *blocks, int numBlocks, const vtmhip_intra_job *intraJobs, int nIntra, const vtmhip_mip_job *mipJobs,
+                                        int nMip, const vtmhip_intra_tu_job *tuJobs, int nTu, const vtmhip_intra_lfnst_tu_job *lfnstJobs, int nLfnst, vtmhip_tu_job *outTu,
+                                        vtmhip_lfnst_chain_job *outLfnst, int *maxWidth, int *maxHeight, int *uniform, int *lanesOut )
+{
+  if( numBlocks < 0 || nIntra < 0 || nMip < 0 || nTu < 0 || nLfnst < 0 ) return VTMHIP_E_INVALID;
+  if( ( numBlocks && !blocks ) || ( nIntra && !intraJobs ) || ( nMip && !mipJobs ) || ( nTu && ( !tuJobs || !outTu ) ) || ( nLfnst && ( !lfnstJobs || !outLfnst ) ) )
+    return VTMHIP_E_INVALID;
+  IntraChainPlan plan;
+  LfnstPlan      lplan;
+  if( !lfnstLevelMakeJobs( blocks, numBlocks, intraJobs, nIntra, mipJobs, nMip, tuJobs, nTu, lfnstJobs, nLfnst, outTu, outLfnst, plan, lplan ) ) return VTMHIP_E_INVALID;
+  if( maxWidth ) *maxWidth = plan.maxWidth;
+  if( maxHeight ) *maxHeight = plan.maxHeight;
+  if( uniform ) *uniform = plan.uniform;
+  if( lanesOut ) *lanesOut = nLfnst ? lfnstLanes( lplan.maxArea ) : 0;
   return VTMHIP_OK;
 }
 

@@ -525,6 +525,17 @@ class Context:
         self._check(self.L.vtmhip_intra_chain_batch_dev(self.h, d_ref, d_org, d_blocks, num_blocks, d_intra_jobs, n_intra, d_mip_jobs, n_mip, d_tu_jobs, n_tu,
                                                         d_pred, d_resi, d_levels, d_reco, d_results))
 
+    def intra_chain_lfnst_batch(self, d_ref, d_org, d_blocks, num_blocks, d_intra_jobs, n_intra, d_mip_jobs, n_mip, d_tu_jobs, n_tu, d_lfnst_jobs, n_lfnst, d_pred, d_resi,
+                                d_reco, d_results, d_lfnst_results, d_levels=None):
+        """intra_chain_batch with a second candidate table: the IntraLfnstTuJob candidates (lfnstIdx 1 / 2) go through the LFNST chain on the same predictions and
+        residuals, their IntraTuResult records to d_lfnst_results.  A malformed table is rejected whole (VtmHipError, nothing launched)."""
+        self._check(self.L.vtmhip_intra_chain_lfnst_batch_dev(self.h, d_ref, d_org, d_blocks, num_blocks, d_intra_jobs, n_intra, d_mip_jobs, n_mip, d_tu_jobs, n_tu,
+                                                              d_lfnst_jobs, n_lfnst, d_pred, d_resi, d_levels, d_reco, d_results, d_lfnst_results))
+
+    def lfnst_chain_batch(self, d_resi, d_jobs, n, d_results, d_levels=None, d_rec=None):
+        """the LFNST candidate of n LfnstChainJob TUs: kept-region xT -> forward LFNST -> quant of 8 / 16 positions -> dequant -> inverse LFNST -> xIT -> SSE (TuResult)"""
+        self._check(self.L.vtmhip_lfnst_chain_batch_dev(self.h, d_resi, d_jobs, n, d_levels, d_rec, d_results))
+
     def intra_chroma_pred_batch(self, d_ref, d_luma, d_blocks, num_blocks, d_jobs, n, d_pred):
         """the Cb and Cr predictions (regular modes 0 .. 66, LM 67, MDLM_L 68, MDLM_T 69) of n IntraChromaJob pairs over num_blocks IntraChromaBlock entries"""
         self._check(self.L.vtmhip_intra_chroma_pred_batch_dev(self.h, d_ref, d_luma, d_blocks, num_blocks, d_jobs, n, d_pred))
@@ -710,6 +721,31 @@ def intra_chain_make_tu_jobs(blocks, intra_jobs, mip_jobs, tu_jobs):
     if st != _lib.OK:
         raise VtmHipError(st)
     return (TuJob * n[3]).from_buffer_copy(bytes(out)[:n[3] * C.sizeof(TuJob)]), mw.value, mh.value, uni.value
+
+
+def lfnst_mode(width, height, intra_mode, is_mip=False):
+    """(set index, transpose flag) of a prediction on a width x height luma block (vtmhip_lfnst_mode_host)"""
+    s, t = C.c_int(), C.c_int()
+    st = _lib.load().vtmhip_lfnst_mode_host(width, height, intra_mode, int(is_mip), C.byref(s), C.byref(t))
+    if st != _lib.OK:
+        raise VtmHipError(st)
+    return s.value, t.value
+
+
+def intra_chain_lfnst_make_jobs(blocks, intra_jobs, mip_jobs, tu_jobs, lfnst_jobs):
+    """The host form of the LFNST level entry's checks and expansions over ctypes arrays (None: an empty table):
+    (TuJob array, LfnstChainJob array, maxWidth, maxHeight, uniform, lanes per LFNST job)"""
+    tabs = (blocks, intra_jobs, mip_jobs, tu_jobs, lfnst_jobs)
+    n = [0 if a is None else len(a) for a in tabs]
+    ptr = [None if a is None else C.addressof(a) for a in tabs]
+    out, lout = (TuJob * max(n[3], 1))(), (_lib.LfnstChainJob * max(n[4], 1))()
+    mw, mh, uni, lanes = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    st = _lib.load().vtmhip_intra_chain_lfnst_make_jobs(ptr[0], n[0], ptr[1], n[1], ptr[2], n[2], ptr[3], n[3], ptr[4], n[4], C.addressof(out), C.addressof(lout),
+                                                        C.byref(mw), C.byref(mh), C.byref(uni), C.byref(lanes))
+    if st != _lib.OK:
+        raise VtmHipError(st)
+    return ((TuJob * n[3]).from_buffer_copy(bytes(out)[:n[3] * C.sizeof(TuJob)]),
+            (_lib.LfnstChainJob * n[4]).from_buffer_copy(bytes(lout)[:n[4] * C.sizeof(_lib.LfnstChainJob)]), mw.value, mh.value, uni.value, lanes.value)
 
 
 def intra_chroma_chain_make_jobs(blocks, jobs, tu_jobs, joint_jobs):

@@ -347,6 +347,17 @@ class IntraTuJob(C.Structure):
                 ("isIRAP", C.c_uint8), ("reserved", C.c_uint8), ("pad", C.c_int32)]
 
 
+class LfnstChainJob(C.Structure):
+    _fields_ = [("resiOff", C.c_int64), ("outOff", C.c_int64), ("resiStride", C.c_int32), ("width", C.c_int16), ("height", C.c_int16), ("qpPer", C.c_int16),
+                ("qpRem", C.c_int16), ("bitDepth", C.c_uint8), ("isIRAP", C.c_uint8), ("setIdx", C.c_uint8), ("index", C.c_uint8), ("transpose", C.c_uint8),
+                ("pad", C.c_uint8 * 7)]
+
+
+class IntraLfnstTuJob(C.Structure):
+    _fields_ = [("outOff", C.c_int64), ("pred", C.c_int32), ("qpPer", C.c_int16), ("qpRem", C.c_int16), ("lfnstIdx", C.c_uint8), ("isIRAP", C.c_uint8),
+                ("reserved", C.c_uint8 * 2), ("pad", C.c_int32)]
+
+
 class IntraTuResult(C.Structure):
     _fields_ = [("sse", C.c_uint64), ("sseResi", C.c_uint64), ("sumAbs", C.c_int32), ("absSum", C.c_int32)]
 
@@ -391,6 +402,7 @@ _INTRA_STRUCTS = [IntraParams, IntraBlock, IntraJob]          # order of vtmhip_
 _INTRA_CHROMA_STRUCTS = [IntraChromaBlock, IntraChromaJob, CclmModel]   # order of vtmhip_intra_chroma_struct_size(which)
 _MIP_STRUCTS = [MipJob]                                       # order of vtmhip_mip_struct_size(which)
 _INTRA_CHAIN_STRUCTS = [IntraTuJob, IntraTuResult]            # order of vtmhip_intra_chain_struct_size(which)
+_LFNST_CHAIN_STRUCTS = [LfnstChainJob, IntraLfnstTuJob]       # order of vtmhip_lfnst_chain_struct_size(which)
 _INTRA_CHROMA_CHAIN_STRUCTS = [IntraChromaTuJob, IntraChromaJointJob, IntraChromaJointResult]   # order of vtmhip_intra_chroma_chain_struct_size(which)
 
 # every symbol include/vtmhip.h declares (tests/test_abi.py checks the exports against the header text)
@@ -530,6 +542,14 @@ _PROTOS = {
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtmhip_intra_chain_make_tu_jobs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int),
                                                   C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vtmhip_lfnst_chain_struct_size": (C.c_int, [C.c_int]),
+    "vtmhip_lfnst_chain_lanes_per_job": (C.c_int, [C.c_int]),
+    "vtmhip_lfnst_mode_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vtmhip_lfnst_chain_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtmhip_intra_chain_lfnst_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtmhip_intra_chain_lfnst_make_jobs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                     C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vtmhip_intra_chroma_chain_struct_size": (C.c_int, [C.c_int]),
     "vtmhip_intra_chroma_chain_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -642,6 +662,10 @@ def load():
         if lib.vtmhip_intra_chain_struct_size(i) != C.sizeof(s):
             raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
                               % (s.__name__, C.sizeof(s), lib.vtmhip_intra_chain_struct_size(i)))
+    for i, s in enumerate(_LFNST_CHAIN_STRUCTS):
+        if lib.vtmhip_lfnst_chain_struct_size(i) != C.sizeof(s):
+            raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
+                              % (s.__name__, C.sizeof(s), lib.vtmhip_lfnst_chain_struct_size(i)))
     for i, s in enumerate(_INTRA_CHROMA_CHAIN_STRUCTS):
         if lib.vtmhip_intra_chroma_chain_struct_size(i) != C.sizeof(s):
             raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
