@@ -206,11 +206,11 @@ __device__ void affine_pred( const AffCtx &c, const Mv3 &m, int16_t *sPred )
   const int thr = 1 << ( iBit + ( c.profIsBi ? 1 : 0 ) );
   prof = prof && ( !c.profLarge || dHX > thr || dHY > thr || dVX > thr || dVY > thr || dHX < -thr || dHY < -thr || dVX < -thr || dVY < -thr );
   const int ifShift = max( 2, 14 - c.bd );
-  const int sbw = w >> 2, nsb = sbw * ( h >> 2 );
+  const int lgsbw = mvr::floor_log2_u( w ) - 2, nsb = ( h >> 2 ) << lgsbw;      // sub-blocks per row: w / 4, a power of two
   const int q = threadIdx.x & 3;
   for( int sb = threadIdx.x >> 2; sb < nsb; sb += blockDim.x >> 2 )   // whole quads enter and leave together
   {
-    const int y = ( sb / sbw ) << 2, x = ( sb - ( sb / sbw ) * sbw ) << 2;
+    const int y = ( sb >> lgsbw ) << 2, x = ( sb & ( ( 1 << lgsbw ) - 1 ) ) << 2;
     int       mh, mv;
     if( !over ) { mh = baseH + dHX * ( 2 + x ) + dVX * ( 2 + y ); mv = baseV + dHY * ( 2 + x ) + dVY * ( 2 + y ); }
     else { mh = baseH + dHX * ( w >> 1 ) + dVX * ( h >> 1 ); mv = baseV + dHY * ( w >> 1 ) + dVY * ( h >> 1 ); }
@@ -270,22 +270,138 @@ __device__ void affine_pred( const AffCtx &c, const Mv3 &m, int16_t *sPred )
   }
 }
 
+// ---- one 8x8 Hadamard unit on a GROUP OF EIGHT LANES ----------------------------------------------------------------------------------------------
+// Lane g of the group holds row g of the unit's differences as four packed words.  The three butterfly levels BETWEEN ROWS run across the lanes on the packed
+// words (|d| <= 4095: 8 * 4095 fits int16, a fourth packed level would not), the levels inside a row in 32 bits in the lane, as in satd8_packed.  Only the sum
+// of |coefficient| and coefficient 0 matter (had.hpp), so a lane may hold any coefficient row with either sign: a lane's partner is lane ^ 1, lane ^ 2 and then
+// the MIRRORED lane 7 - g (row_half_mirror: DPP has no lane ^ 4), and for the two halves of a 16x8 / 8x16 tile, which sit in the two groups of a row of 16
+// lanes, lane 15 - l (row_mirror).  A mirror pairs equal vertical frequencies when the lanes above it took "partner - own" where the lanes below took
+// "own + partner": lane l negates its own word at level 1 when bit 0 ^ bit 2 of l is set, at level 2 when bit 1 ^ bit 2, at level 3 when bit 2 ^ bit 3.
+// Vertical frequency 0 (the dc row) then sits in lane 0 of an even group and in lane 7 of an odd one.
+__device__ __forceinline__ int dpp_xor2( int v ) { return __builtin_amdgcn_mov_dpp( v, 0x4E, 0xF, 0xF, false ); }          // quad_perm [2, 3, 0, 1]: the value of lane ^ 2
+__device__ __forceinline__ int dpp_half_mirror( int v ) { return __builtin_amdgcn_mov_dpp( v, 0x141, 0xF, 0xF, false ); }   // row_half_mirror: lane 7 - g of the group of eight
+__device__ __forceinline__ int dpp_row_mirror( int v ) { return __builtin_amdgcn_mov_dpp( v, 0x140, 0xF, 0xF, false ); }    // row_mirror: lane 15 - l of the row of 16
+
+template<int LEVEL>
+__device__ __forceinline__ v2s lane_butterfly( v2s own, v2s sgn )
+{
+  int o;
+  __builtin_memcpy( &o, &own, 4 );
+  const int p = LEVEL == 0 ? dpp_swap1( o ) : LEVEL == 1 ? dpp_xor2( o ) : dpp_half_mirror( o );
+  v2s       P;
+  __builtin_memcpy( &P, &p, 4 );
+  return own * sgn + P;
+}
+
+// the finished value of this lane's unit (square blocks) or tile (pair: the other half is in the other group of the row of 16), valid in the lane that holds the dc row
+template<bool PAIR>
+__device__ __forceinline__ unsigned satd8_lanes( const int16_t *pred, const int16_t *pat, const v2s sgn[3] )
+{
+  const uint4    a = *reinterpret_cast<const uint4 *>( pred ), b = *reinterpret_cast<const uint4 *>( pat );
+  const unsigned aw[4] = { a.x, a.y, a.z, a.w }, bw[4] = { b.x, b.y, b.z, b.w };
+  int            m[8];
+#pragma unroll
+  for( int k = 0; k < 4; k++ )
+  {
+    v2s p, q;
+    __builtin_memcpy( &p, &aw[k], 4 ); __builtin_memcpy( &q, &bw[k], 4 );
+    v2s d = p - q;
+    d = lane_butterfly<0>( d, sgn[0] ); d = lane_butterfly<1>( d, sgn[1] ); d = lane_butterfly<2>( d, sgn[2] );
+    m[2 * k] = d.x; m[2 * k + 1] = d.y;
+  }
+  int t = 0, dc;
+  if( !PAIR )
+  {
+    // inside the row: levels 1 and 2, then |a + b| + |a - b| = 2 max(|a|, |b|) for the pairs (x, x + 4)
+#pragma unroll
+    for( int len = 1; len < 4; len <<= 1 )
+#pragma unroll
+      for( int i = 0; i < 8; i += len << 1 )
+#pragma unroll
+        for( int j = i; j < i + len; j++ )
+        {
+          const int c = m[j], e = m[j + len];
+          m[j] = c + e; m[j + len] = c - e;
+        }
+#pragma unroll
+    for( int x = 0; x < 4; x++ ) t += max( abs( m[x] ), abs( m[x + 4] ) );
+    dc = abs( m[0] + m[4] );
+  }
+  else
+  {
+    // the level between the two halves of the tile: coefficients A + B and A - B, |A + B| + |A - B| = 2 max(|A|, |B|)
+    wht1d_inl8( m );
+    dc = abs( m[0] + dpp_row_mirror( m[0] ) );
+#pragma unroll
+    for( int x = 0; x < 8; x++ )
+    {
+      const int c = abs( m[x] );
+      t += max( c, dpp_row_mirror( c ) );
+    }
+  }
+  t += dpp_swap1( t ); t += dpp_xor2( t ); t += dpp_half_mirror( t );   // the group's sum, in each of its lanes; in the pair form both groups hold the tile's
+  if( PAIR ) return satd_pair_norm( t << 1, dc );
+  t <<= 1;
+  t = t - dc + ( dc >> 2 );              // as satd8_packed: mean-scaled dc, then the 8x8 rounding
+  return ( unsigned ) ( ( t + 2 ) >> 2 );
+}
+
+// sum over the wave of a value that fits 32 bits (the packed Hadamard: at most 256 units of less than 2^23 each), wave-uniform
+__device__ __forceinline__ unsigned wave_sum_u32( unsigned v )
+{
+  v += ( unsigned ) dpp_swap1( ( int ) v ); v += ( unsigned ) dpp_xor2( ( int ) v ); v += ( unsigned ) dpp_half_mirror( ( int ) v );
+  v += ( unsigned ) dpp_row_mirror( ( int ) v );   // every lane: the sum of its row of 16
+  const int t = ( int ) v;
+  return ( unsigned ) __builtin_amdgcn_readlane( t, 0 ) + ( unsigned ) __builtin_amdgcn_readlane( t, 16 ) + ( unsigned ) __builtin_amdgcn_readlane( t, 32 ) + ( unsigned ) __builtin_amdgcn_readlane( t, 48 );
+}
+
 // getDistPart( DF_HAD / DF_SAD ) of prediction vs pattern over the block (tile shapes of xGetHADs: RdCost.cpp:2837-2931), block-wide sum.
-// packed (bitDepth <= 10: |pattern - prediction| <= 3 * 1023): a lane takes one 8x8 unit with the packed 16-bit Hadamard of had.hpp; the two halves of a
-// 16x8 / 8x16 tile sit in neighbouring lanes (units in pair order), each returns the finished tile value and the even lane counts it.
+// packed (bitDepth <= 10: |pattern - prediction| <= 3 * 1023): the 8x8 units of the packed 16-bit Hadamard, in pair order for the 16x8 / 8x16 tiles of a non-square
+// block.  A job with at most a quarter as many units as lanes gives a unit to a group of eight lanes (satd8_lanes); with more units a lane takes a whole unit (had.hpp),
+// the two halves of a tile in neighbouring lanes, each returns the finished tile value and the even lane counts it.
+// lgw = log2( w ) (block sides are powers of two); par: the half of sRed this call uses, the caller alternates it.
 template<bool packed>
-__device__ __forceinline__ unsigned long long block_dist( const int16_t *sPred, const int16_t *sPat, int w, int h, bool satd, unsigned long long *sRed )
+__device__ __forceinline__ unsigned long long block_dist( const int16_t *sPred, const int16_t *sPat, int w, int h, int lgw, bool satd, unsigned long long ( *sRed )[4], int par )
 {
   unsigned long long acc = 0;
   if( satd && packed )
   {
     const int nu = ( w >> 3 ) * ( h >> 3 );   // 8x8 units; w, h >= 16 here, so nu is even and pair lanes enter the loop together
+    // first unit and pair of a row of the block: square blocks have w / 8 units per row, wide ones w / 16 pairs, tall ones w / 8 pairs
+    const int lgp = w > h ? lgw - 4 : lgw - 3, pm = ( 1 << lgp ) - 1;
+    unsigned  sum = 0;
+    if( 4 * nu <= ( int ) blockDim.x )
+    {
+      const int l = threadIdx.x & 15, g = threadIdx.x & 7;
+      v2s       sgn[3];
+      sgn[0] = ( ( l ^ ( l >> 2 ) ) & 1 ) ? v2s{ -1, -1 } : v2s{ 1, 1 };
+      sgn[1] = ( ( ( l >> 1 ) ^ ( l >> 2 ) ) & 1 ) ? v2s{ -1, -1 } : v2s{ 1, 1 };
+      sgn[2] = ( ( ( l >> 2 ) ^ ( l >> 3 ) ) & 1 ) ? v2s{ -1, -1 } : v2s{ 1, 1 };
+      // whole groups, and both groups of a pair, enter and leave together: the units per pass ( blockDim.x / 8 ) and nu are even
+      for( int u = threadIdx.x >> 3; u < nu; u += blockDim.x >> 3 )
+      {
+        if( w == h )
+        {
+          const int y = ( u >> lgp ) << 3, x = ( u & pm ) << 3, o = ( y + g ) * w + x;
+          const unsigned v = satd8_lanes<false>( sPred + o, sPat + o, sgn );
+          sum += ( l == 0 || l == 15 ) ? v : 0u;      // the lane with the dc row
+        }
+        else
+        {
+          const int p = u >> 1, y = w > h ? ( p >> lgp ) << 3 : ( ( p >> lgp ) << 4 ) + ( ( u & 1 ) << 3 ), x = w > h ? ( ( p & pm ) << 4 ) + ( ( u & 1 ) << 3 ) : ( p & pm ) << 3;
+          const int o = ( y + g ) * w + x;
+          const unsigned v = satd8_lanes<true>( sPred + o, sPat + o, sgn );
+          sum += l == 0 ? v : 0u;                      // lanes 0 and 15 hold the same tile value: counted once
+        }
+      }
+    }
+    else
     for( int u = threadIdx.x; u < nu; u += blockDim.x )
     {
       int x, y;
-      if( w == h ) { const int ux = w >> 3; y = ( u / ux ) << 3; x = ( u - ( u / ux ) * ux ) << 3; }
-      else if( w > h ) { const int px = w >> 4, p = u >> 1; y = ( p / px ) << 3; x = ( ( p - ( p / px ) * px ) << 4 ) + ( ( u & 1 ) << 3 ); }
-      else { const int px = w >> 3, p = u >> 1; y = ( ( p / px ) << 4 ) + ( ( u & 1 ) << 3 ); x = ( p - ( p / px ) * px ) << 3; }
+      if( w == h ) { y = ( u >> lgp ) << 3; x = ( u & pm ) << 3; }
+      else if( w > h ) { const int p = u >> 1; y = ( p >> lgp ) << 3; x = ( ( p & pm ) << 4 ) + ( ( u & 1 ) << 3 ); }
+      else { const int p = u >> 1; y = ( ( p >> lgp ) << 4 ) + ( ( u & 1 ) << 3 ); x = ( p & pm ) << 3; }
       v2s D[8][4];
 #pragma unroll
       for( int r = 0; r < 8; r++ )
@@ -300,9 +416,10 @@ __device__ __forceinline__ unsigned long long block_dist( const int16_t *sPred, 
           D[r][k] = p - q;
         }
       }
-      if( w == h ) acc += satd8_packed( D );
-      else { const unsigned tv = satd8_pair_packed( D ); acc += ( u & 1 ) ? 0u : tv; }
+      if( w == h ) sum += satd8_packed( D );
+      else { const unsigned tv = satd8_pair_packed( D ); sum += ( u & 1 ) ? 0u : tv; }
     }
+    acc = wave_sum_u32( sum );
   }
   else if( satd && !packed )
   {
@@ -318,14 +435,14 @@ __device__ __forceinline__ unsigned long long block_dist( const int16_t *sPred, 
   {
     for( int i = threadIdx.x; i < w * h; i += blockDim.x ) acc += ( unsigned ) abs( ( int ) sPred[i] - ( int ) sPat[i] );
   }
-  acc = wave_reduce_add_u64( acc );
+  if( !( satd && packed ) ) acc = wave_reduce_add_u64( acc );
+  if( blockDim.x == 64 ) return acc;      // one wave per job: the wave's sum is the block's; its LDS accesses are ordered by the wave itself
+  if( ( threadIdx.x & 63 ) == 0 ) sRed[par][threadIdx.x >> 6] = acc;
+  // The one barrier of the four-wave form.  It makes the four sums visible, and a wave that has passed it knows that every wave has finished reading sPred,
+  // so the next prediction may overwrite it.  No barrier protects sRed from the next call: that call writes the OTHER half, and the call after it, which
+  // writes this half again, lies behind the next call's barrier, which no wave passes before all have read their sums here.
   __syncthreads();
-  if( ( threadIdx.x & 63 ) == 0 ) sRed[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  unsigned long long t = 0;
-  for( int wv = 0; wv < ( int ) ( blockDim.x >> 6 ); wv++ ) t += sRed[wv];   // one or four waves per job
-  __syncthreads();
-  return t;
+  return sRed[par][0] + sRed[par][1] + sRed[par][2] + sRed[par][3];
 }
 
 __device__ __forceinline__ unsigned affine_mv_bits( int six, int imv, const Mv3 &m, const int pred[3][2] )
@@ -408,7 +525,7 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( PACKED
 {
   constexpr int NP = SIX ? 6 : 4, NTRI = NP * ( NP + 1 ) / 2, NACC = NTRI + NP, MVNUM = SIX ? 3 : 2;
   extern __shared__ __attribute__( ( aligned( 16 ) ) ) int16_t sMem[];
-  __shared__ unsigned long long sRed[4];
+  __shared__ unsigned long long sRed[2][4];   // the wave sums of a distortion, two halves used in turn (block_dist)
   __shared__ long long          sAcc[4][NACC];
   __shared__ Mv3                sMv;      // the model of the next gradient step (written by thread 0)
   __shared__ Mv3                sPrev[7]; // models of the earlier gradient steps (thread 0; the AMVR encoder option compares against them)
@@ -423,7 +540,7 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( PACKED
   const int  bcw = ( j.bi && j.bcwWeight != 4 ) ? j.bcwWeight : 0;
   const bool wideJob = bcw < 0;
   if( PACKED ? wideJob : ( pic.bitDepth <= 10 && !wideJob ) ) return;
-  const int w = j.width, h = j.height;
+  const int w = j.width, h = j.height, lgw = mvr::floor_log2_u( w );      // block sides are powers of two: rows and columns by shift and mask
   int16_t  *sPat = sMem, *sPred = sMem + w * h;
   AffCtx c;
   c.ref = refBase + j.refOff; c.refStride = j.refStride; c.w = w; c.h = h; c.bd = pic.bitDepth; c.six = SIX; c.interDir = j.interDir; c.imv = j.imv;
@@ -439,7 +556,7 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( PACKED
     const int      nrm = bcw ? mvr::bcw_normaliser( bcw ) : 0, bw0 = mvr::bcw_w0( nrm ), bw1 = mvr::bcw_w1( bcw, nrm );
     for( int i = threadIdx.x; i < w * h; i += blockDim.x )
     {
-      const int y = i / w, x = i - y * w;
+      const int y = i >> lgw, x = i & ( w - 1 );
       const int v = o[( long ) y * j.orgStride + x];
       sPat[i] = ( int16_t ) ( !bi ? v : bcw ? ( v * bw0 - ( int ) p[( long ) y * j.otherPredStride + x] * bw1 + ( 1 << 15 ) ) >> 16 : 2 * v - p[( long ) y * j.otherPredStride + x] );
     }
@@ -469,6 +586,7 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( PACKED
   enum { P_INIT, P_ITER, P_REF_START, P_C1, P_C2, P_C3, P_RND, P_DONE };
   int  phase = P_INIT, iter = 0, k = 0, it = 0, pos = 0, rnd = 0;
   bool modelChange = false, loopChange = false;
+  int  distPar = 0;      // which half of sRed the next distortion uses
   __syncthreads();
 
 #pragma unroll 1
@@ -486,7 +604,7 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( PACKED
       for( int i = 0; i < NACC; i++ ) acc[i] = 0;
       for( int i = threadIdx.x; i < w * h; i += blockDim.x )
       {
-        const int y = i / w, x = i - y * w;
+        const int y = i >> lgw, x = i & ( w - 1 );
         const int yc = min( h - 2, max( 1, y ) ), xc = min( w - 2, max( 1, x ) );
         const int16_t *q = sPred + yc * w + xc;
         const int a = q[1 - w] - q[-1 - w] + ( q[1] << 1 ) - ( q[-1] << 1 ) + q[1 + w] - q[-1 + w];
@@ -662,7 +780,8 @@ __global__ __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( PACKED
     // ---- the one evaluation site: prediction, distortion, bits, comparison ----
     affine_pred( c, cand, sPred );
     __syncthreads();
-    unsigned long long cost = uni( block_dist<PACKED>( sPred, sPat, w, h, satd, sRed ) );
+    unsigned long long cost = uni( block_dist<PACKED>( sPred, sPat, w, h, lgw, satd, sRed, distPar ) );
+    distPar ^= 1;
     unsigned           bits;
     const bool         picking = pickMvp && ( cur == P_INIT || cur == P_ITER );
     if( picking )
