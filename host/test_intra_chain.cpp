@@ -116,7 +116,7 @@ static void test_expansion()
   std::vector<vtmhip_tu_job> out;
   IntraChainPlan plan;
   CHECK( run( T, out, plan ) );
-  CHECK( plan.maxWidth == 64 && plan.maxHeight == 32 && plan.maxTuArea == 1024 && plan.maxBlockArea == 1024 && plan.uniform == 0 );
+  CHECK( plan.tu.maxWidth == 64 && plan.tu.maxHeight == 32 && plan.tu.maxArea == 1024 && plan.maxBlockArea == 1024 && plan.tu.uniform == 0 );
   int perPred[10] = {};
   for( size_t k = 0; k < T.tu.size(); k++ )
   {
@@ -139,12 +139,12 @@ static void test_expansion()
   U.intra = { T.intra[0], T.intra[1] };
   U.intra[0].block = 0; U.intra[1].block = 1; U.intra[1].mode = 66;
   U.tu = { tuOf( 0, VTMHIP_DCT2, VTMHIP_DST7, 4, 0, 0, 1 ), tuOf( 1, VTMHIP_DCT8, VTMHIP_DCT2, 4, 5, 1, 41 ), tuOf( 1, VTMHIP_DCT2, VTMHIP_DCT2, 0, 0, 1, 81 ) };
-  CHECK( run( U, out, plan ) && plan.uniform == 1 && plan.maxWidth == 8 && plan.maxHeight == 4 && plan.maxBlockArea == 32 );
+  CHECK( run( U, out, plan ) && plan.tu.uniform == 1 && plan.tu.maxWidth == 8 && plan.tu.maxHeight == 4 && plan.maxBlockArea == 32 );
   U.tu.push_back( tuOf( 0, VTMHIP_TRSKIP, VTMHIP_TRSKIP, 4, 0, 0, 121 ) );
-  CHECK( run( U, out, plan ) && plan.uniform == 0 );
+  CHECK( run( U, out, plan ) && plan.tu.uniform == 0 );
   // the prediction pass alone; no table at all
   U.tu.clear();
-  CHECK( run( U, out, plan ) && plan.uniform == 0 && plan.maxWidth == 0 && plan.maxHeight == 0 && plan.maxBlockArea == 32 );
+  CHECK( run( U, out, plan ) && plan.tu.uniform == 0 && plan.tu.maxWidth == 0 && plan.tu.maxHeight == 0 && plan.maxBlockArea == 32 );
   CHECK( run( Tables(), out, plan ) && plan.maxBlockArea == 0 );
 }
 

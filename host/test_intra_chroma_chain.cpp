@@ -125,8 +125,8 @@ static void test_expansion()
   IchainPlan plan;
   CHECK( run( T, outTu, outJoint, plan ) );
   CHECK( plan.maxBlockArea == 512 && plan.anyLm == 1 && plan.crs == 1 );
-  CHECK( plan.maxWidth[0] == 32 && plan.maxHeight[0] == 16 && plan.maxArea[0] == 512 && plan.uniform[0] == 0 );
-  CHECK( plan.maxWidth[1] == 32 && plan.maxHeight[1] == 16 && plan.maxArea[1] == 512 && plan.uniform[1] == 0 );
+  CHECK( plan.tu.maxWidth == 32 && plan.tu.maxHeight == 16 && plan.tu.maxArea == 512 && plan.tu.uniform == 0 );
+  CHECK( plan.joint.maxWidth == 32 && plan.joint.maxHeight == 16 && plan.joint.maxArea == 512 && plan.joint.uniform == 0 );
   CHECK( T.tu.size() == 20 && T.joint.size() == 21 );
   for( size_t k = 0; k < T.tu.size(); k++ )
   {
@@ -157,18 +157,18 @@ static void test_expansion()
   U.jobs[0].block = 0; U.jobs[1].block = 1; U.jobs[1].mode = 66;
   U.tu = { tuOf( 0, 0, VTMHIP_DCT2, 4, 0, 0, 0, 1 ), tuOf( 1, 1, VTMHIP_DCT2, 4, 5, 1, 0, 41 ) };
   U.joint = { jointOf( 1, 3, 1, VTMHIP_DCT2, 4, 1, 0, 0, 81 ) };
-  CHECK( run( U, outTu, outJoint, plan ) && plan.uniform[0] == 1 && plan.uniform[1] == 1 && plan.crs == 0 && plan.anyLm == 0 && plan.maxBlockArea == 32 );
-  CHECK( plan.maxWidth[0] == 8 && plan.maxHeight[0] == 4 && plan.maxWidth[1] == 8 && plan.maxHeight[1] == 4 );
+  CHECK( run( U, outTu, outJoint, plan ) && plan.tu.uniform == 1 && plan.joint.uniform == 1 && plan.crs == 0 && plan.anyLm == 0 && plan.maxBlockArea == 32 );
+  CHECK( plan.tu.maxWidth == 8 && plan.tu.maxHeight == 4 && plan.joint.maxWidth == 8 && plan.joint.maxHeight == 4 );
   U.tu.push_back( tuOf( 0, 1, VTMHIP_TRSKIP, 4, 0, 0, 0, 121 ) );
-  CHECK( run( U, outTu, outJoint, plan ) && plan.uniform[0] == 0 && plan.uniform[1] == 1 && plan.crs == 0 );
+  CHECK( run( U, outTu, outJoint, plan ) && plan.tu.uniform == 0 && plan.joint.uniform == 1 && plan.crs == 0 );
   U.tu.pop_back();
   U.joint.push_back( jointOf( 0, 1, 0, VTMHIP_TRSKIP, 4, 0, 0, 1, 121 ) );
-  CHECK( run( U, outTu, outJoint, plan ) && plan.uniform[0] == 1 && plan.uniform[1] == 0 && plan.crs == 1 );
+  CHECK( run( U, outTu, outJoint, plan ) && plan.tu.uniform == 1 && plan.joint.uniform == 0 && plan.crs == 1 );
   // one table empty; the prediction pass alone; no table at all
   U.joint.clear();
-  CHECK( run( U, outTu, outJoint, plan ) && plan.uniform[0] == 1 && plan.uniform[1] == 0 && plan.maxWidth[1] == 0 && plan.maxArea[1] == 0 );
+  CHECK( run( U, outTu, outJoint, plan ) && plan.tu.uniform == 1 && plan.joint.uniform == 0 && plan.joint.maxWidth == 0 && plan.joint.maxArea == 0 );
   U.tu.clear();
-  CHECK( run( U, outTu, outJoint, plan ) && plan.uniform[0] == 0 && plan.maxWidth[0] == 0 && plan.maxHeight[0] == 0 && plan.maxBlockArea == 32 );
+  CHECK( run( U, outTu, outJoint, plan ) && plan.tu.uniform == 0 && plan.tu.maxWidth == 0 && plan.tu.maxHeight == 0 && plan.maxBlockArea == 32 );
   CHECK( run( Tables(), outTu, outJoint, plan ) && plan.maxBlockArea == 0 );
 }
 

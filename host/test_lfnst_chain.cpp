@@ -200,7 +200,7 @@ int main()
   const Run    r = run( T );
   CHECK( r.ok && !r.untouched );
   CHECK( r.lplan.maxArea == 64 * 16 && lfnstLanes( r.lplan.maxArea ) == 64 && r.lplan.jobInts == lfnstJobInts( 64, 16 ) );
-  CHECK( r.plan.maxWidth == 64 && r.plan.maxHeight == 16 && r.plan.uniform == 0 );
+  CHECK( r.plan.tu.maxWidth == 64 && r.plan.tu.maxHeight == 16 && r.plan.tu.uniform == 0 );
   const int nIntra = ( int ) T.intra.size();
   for( size_t i = 0; i < T.lf.size(); i++ )
   {
@@ -232,7 +232,7 @@ int main()
     CHECK( e.ok && e.lplan.maxArea == 0 && e.lplan.jobInts == 0 );
     E = T; E.tu.clear();
     const Run f = run( E );
-    CHECK( f.ok && f.plan.maxWidth == 0 && f.lplan.maxArea == 64 * 16 );
+    CHECK( f.ok && f.plan.tu.maxWidth == 0 && f.lplan.maxArea == 64 * 16 );
     const Run g = run( Tables() );
     CHECK( g.ok );
   }

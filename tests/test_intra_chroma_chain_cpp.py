@@ -9,7 +9,7 @@ EXE = os.path.join(ROOT, "host", "test_intra_chroma_chain")
 
 def _build():
     csrc = os.path.join(ROOT, "vtm_amd", "csrc")
-    srcs = [os.path.join(ROOT, "host", "test_intra_chroma_chain.cpp")] + [os.path.join(csrc, h) for h in ("intra_chroma_chain_rules.hpp", "cclm_rules.hpp", "intra_rules.hpp")]
+    srcs = [os.path.join(ROOT, "host", "test_intra_chroma_chain.cpp")] + [os.path.join(csrc, h) for h in ("intra_chroma_chain_rules.hpp", "chain_rules.hpp", "cclm_rules.hpp", "intra_rules.hpp")]
     if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", EXE, srcs[0]])
 

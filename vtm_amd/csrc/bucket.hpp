@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ctx.hpp"
+#include "stage.hpp"
 
 namespace
 {
@@ -96,17 +97,16 @@ struct BucketPlan
 };
 
 // Buckets `n` jobs: on return plan.d_jobs holds the permuted table (class slices at plan.offset[], sizes plan.count[]); the caller runs its chains over
-// the slices writing plan.d_results, then calls bucket_finish.  Workspace: arena slot 2 of the context's stream.
+// the slices writing plan.d_results, then calls bucket_finish.  Workspace: a WorkPlan (stage.hpp) in the slot VTMHIP_WORK_BUCKET of the context's stream.
 template<typename Job, typename R, typename ClassOf>
 int bucket_begin( vtmhip_ctx *ctx, const Job *d_jobs, int n, ClassOf classOf, BucketPlan &plan )
 {
-  const size_t oJobs = 256, oRes = ( oJobs + ( size_t ) n * sizeof( Job ) + 255 ) & ~( size_t ) 255, oPerm = ( oRes + ( size_t ) n * sizeof( R ) + 255 ) & ~( size_t ) 255;
-  void *arena = nullptr;
-  int   st    = vtmhip_internal_workspace( ctx, oPerm + ( size_t ) n * sizeof( int ), &arena, 2 );
+  WorkPlan     wp;
+  const size_t oHead = wp.region<int>( 3 * BUCKET_CLASSES ), oJobs = wp.region<Job>( n ), oRes = wp.region<R>( n ), oPerm = wp.region<int>( n );
+  int          st    = wp.reserve( ctx, VTMHIP_WORK_BUCKET );
   if( st ) return st;
-  char *base = ( char * ) arena;
-  int  *d_cnt = ( int * ) base, *d_off = d_cnt + BUCKET_CLASSES, *d_cur = d_off + BUCKET_CLASSES;   // three small tables at the head of the arena
-  plan.d_jobs = base + oJobs; plan.d_results = base + oRes; plan.d_perm = ( int * ) ( base + oPerm );
+  int *d_cnt = wp.at<int>( oHead ), *d_off = d_cnt + BUCKET_CLASSES, *d_cur = d_off + BUCKET_CLASSES;   // three small tables, zeroed by one fill
+  plan.d_jobs = wp.at<Job>( oJobs ); plan.d_results = wp.at<R>( oRes ); plan.d_perm = wp.at<int>( oPerm );
   VTMHIP_HIP( ctx, hipMemsetAsync( d_cnt, 0, 3 * BUCKET_CLASSES * sizeof( int ), ctx->stream ) );
   const int blocks = ( n + 255 ) / 256;
   hipLaunchKernelGGL( ( bucket_count_kernel<Job, ClassOf> ), dim3( blocks < 1024 ? blocks : 1024 ), dim3( 256 ), 0, ctx->stream, d_jobs, n, d_cnt, classOf );

@@ -288,7 +288,7 @@ int vtmhip_internal_scratch( vtmhip_ctx *ctx, size_t bytes )
   return VTMHIP_OK;
 }
 
-int vtmhip_internal_workspace( vtmhip_ctx *ctx, size_t bytes, void **out, int slot )
+int vtmhip_internal_workspace( vtmhip_ctx *ctx, size_t bytes, void **out, vtmhip_work_slot slot )
 {
   std::lock_guard<std::mutex> lock( ctx->initMutex );
   vtmhip_ctx::WorkArena &a = ctx->work[std::make_pair( ctx->stream, slot )];

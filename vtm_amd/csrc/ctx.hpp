@@ -14,6 +14,21 @@
 
 #include "../../include/vtmhip.h"
 
+// The device workspaces of one stream (vtmhip_ctx::work), every slot listed once with its owner and how long its contents must live.  Calls on one stream are
+// ordered, so a slot is free again once its owner's launches are queued -- except where the note says otherwise.  Two callers that can be live at once on one
+// stream must not name the same slot.
+enum vtmhip_work_slot
+{
+  VTMHIP_WORK_CALL = 0,           // the multi-stage calls (mest.hip, pis.hip, dist.hip) and the prediction entries' shape word (intra.hip, mip.hip, intra_chroma.hip): until the call's last launch
+  VTMHIP_WORK_NESTED,             // what a multi-stage call nests: the split TZ search's saved states, scan list and totals (me.hip), until its resume launch
+  VTMHIP_WORK_BUCKET,             // the shape bucketing of the TU and ME chains (bucket.hpp), until its gather launch; and the AMVP SADs of the picture loop (pis.hip), which must
+                                  // outlive the fused search's prologue (the search itself takes VTMHIP_WORK_CALL) -- the fused search never buckets, so the two never meet
+  VTMHIP_WORK_SBT,                // the SBT chain (sbt.hip): the fused chain it runs may bucket
+  VTMHIP_WORK_BOX_SUMS,           // the picture loop's 8x8 box sums (driver.hip): attached across a picture, over every call the picture makes on this stream
+  VTMHIP_WORK_INTRA_CHAIN,        // the intra luma residual chain (intra_chain.hip), over the chains it runs
+  VTMHIP_WORK_INTRA_CHROMA_CHAIN, // the intra chroma residual chain (intra_chroma_chain.hip), over the chains it runs
+};
+
 struct vtmhip_ctx
 {
   int         device      = 0;
@@ -29,10 +44,7 @@ struct vtmhip_ctx
   // calls queued on different streams (a level-order driver runs the levels' chains concurrently) never share scratch memory; calls on one stream are
   // ordered and reuse their arena
   struct WorkArena { void *ptr = nullptr; size_t size = 0; };
-  std::map<std::pair<hipStream_t, int>, WorkArena> work;   // key: (stream, slot) -- slot 0: the multi-stage calls, slot 1: calls they nest (the split TZ search)
-                                                            // slot 2: the chain's shape bucketing (bucket.hpp) and the AMVP SADs (pis.hip), 3: the SBT chain (sbt.hip), 4: the picture loop's box sums
-                                                            // (driver.hip; attached for a whole picture), 5: the intra residual chain (intra_chain.hip)
-                                                            // 6: the intra chroma residual chain (intra_chroma_chain.hip)
+  std::map<std::pair<hipStream_t, int>, WorkArena> work;   // key: (stream, vtmhip_work_slot)
   int8_t     *lfnstTab    = nullptr;   // the caller's LFNST core matrices: g_lfnst8x8 [4][2][16][48] then g_lfnst4x4 [4][2][16][16] (vtmhip_lfnst_set_tables)
   uint8_t    *mipTab      = nullptr;   // the caller's MIP matrices: mipMatrix4x4 [16][16][4], mipMatrix8x8 [8][16][8], mipMatrix16x16 [6][64][7] (vtmhip_mip_set_tables, under initMutex)
   int32_t    *wtdFixed    = nullptr;   // DF_SSE_WTD: fixed-point luma-level weights (int64_t)( w * 65536.0 ), 1 << wtdLumaBD entries (vtmhip_set_luma_level_weights)
@@ -174,7 +186,7 @@ int vtmhip_internal_mest_with_amvp( vtmhip_ctx *ctx, const vtmhip_pic_params *pi
                                     vtmhip_me_job *d_jobs, int n, int maxWidth, int maxHeight, vtmhip_me_out *d_results, const unsigned long long *d_amvpDout,
                                     unsigned long long *d_distBiP, int addIdxBits );   // mest.hip
 int vtmhip_internal_mest_fusable( const vtmhip_me_cfg *cfg );
-int vtmhip_internal_workspace( vtmhip_ctx *ctx, size_t bytes, void **out, int slot = 0 ); // the arena (slot) of ctx->stream, grown to `bytes` (device only)
+int vtmhip_internal_workspace( vtmhip_ctx *ctx, size_t bytes, void **out, vtmhip_work_slot slot = VTMHIP_WORK_CALL ); // the arena (slot) of ctx->stream, grown to `bytes` (device only); layouts: WorkPlan (stage.hpp)
 
 // the uniform PU shapes that have tiled search kernels of their own, listed once: X( W, H ) for a shape both the exhaustive search (full_search_sq_kernel, me.hip) and
 // the fractional search (frac_search_sq_kernel, interp.hip) are instantiated for, X_FRAC( W, H ) for the one only the fractional search has.  vtmhip_is_uniform_shape

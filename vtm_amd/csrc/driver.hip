@@ -194,7 +194,7 @@ int picture_sums( vtmhip_ctx *ctx, const vtmhip_pis_level_run *levels, int numLe
   hi += ( int64_t ) ( pic.picH + m ) * stride;
   void *ws = nullptr;
   ctx->stream = main;
-  VTMHIP_TRY( vtmhip_internal_workspace( ctx, ( size_t ) ( hi - lo ) * sizeof( uint16_t ), &ws, 4 ) );      // a slot of its own (0 .. 3 belong to the calls the picture makes on this stream); grown by the first picture of this size, then reused
+  VTMHIP_TRY( vtmhip_internal_workspace( ctx, ( size_t ) ( hi - lo ) * sizeof( uint16_t ), &ws, VTMHIP_WORK_BOX_SUMS ) );      // a slot of its own (the others belong to the calls the picture makes on this stream); grown by the first picture of this size, then reused
   uint16_t *sumBase = ( uint16_t * ) ws - lo;
   hipEvent_t ready = nullptr;
   if( side )

@@ -12,17 +12,17 @@
 //                               its block) and the block index, both in the stream's workspace
 //   the fused chain             vtmhip_internal_tu_chain_launch (transform.hip), unchanged: levels and the reconstructed residual at outOff
 //   intra_chain_finish_kernel<L>  a TU job gets L lanes (16 up to 256 samples: sixteen jobs per workgroup; 64 above: a wave per job), chosen by the host from the largest
-//                               TU.  A lane walks 4-sample row segments: prediction and reconstructed residual are W x H contiguous, the original has its own stride; all
-//                               three come as one 8-byte access at a 2-byte aligned address (pel_pack.hpp).  It overwrites the reconstructed residual with
-//                               clip( prediction + residual ) and sums ( original - reconstruction )^2 with the per-addend 32-bit product of dist_block.hpp's SSE; the
-//                               group's lanes are added by shuffles.  No LDS, no barrier.
-// The entry reads the four tables back and checks them (one stream synchronisation), so the kernels here trust what they are given.
+//                               TU.  It decodes the job and runs chain_finish.hpp's walk: the reconstructed residual becomes clip( prediction + residual ), and
+//                               its SSE against the original joins the chain's result.  No LDS, no barrier.
+// The entry reads the tables back through HostStage (stage.hpp) and checks them (one stream synchronisation), so the kernels here trust what they are given.  Its
+// workspace is a WorkPlan in the slot VTMHIP_WORK_INTRA_CHAIN.
 #include "ctx.hpp"
+#include "stage.hpp"
+#include "chain_finish.hpp"
 #include "intra_body.hpp"   // intra_chunk_body, as intra.hip's kernels use it
 #include "mip_body.hpp"     // mip_chunk_body, as mip.hip's
 #include "intra_chain_rules.hpp"
 #include "lfnst_rules.hpp"
-#include "pel_pack.hpp"
 
 namespace
 {
@@ -84,38 +84,12 @@ __global__ __launch_bounds__( 256 ) void intra_chain_finish_kernel( const int16_
   {
     const vtmhip_tu_job      T = xJobs[i];
     const vtmhip_intra_block B = blocks[tuBlock[i]];
-    const int      lgSegs = intraLog2( T.width ) - 2, items = ( T.width * T.height ) >> 2, maxVal = ( 1 << T.bitDepth ) - 1;
-    const int16_t *pred = predBase + T.resiOff, *org = orgBase + B.orgOff;   // the job's residual lies where its prediction does
-    int16_t       *reco = recoBase + T.outOff;
-    for( int it = l; it < items; it += L )
-    {
-      const int y = it >> lgSegs, x = ( it & ( ( 1 << lgSegs ) - 1 ) ) << 2;
-      int p[4], r[4], o[4];
-      ld4( pred + 4 * it, 4, p );
-      ld4( reco + 4 * it, 4, r );
-      ld4( org + ( long ) y * B.orgStride + x, 4, o );
-#pragma unroll
-      for( int k = 0; k < 4; k++ )
-      {
-        r[k] = min( max( p[k] + r[k], 0 ), maxVal );
-        const int d = o[k] - r[k];
-        acc += ( unsigned long long ) ( ( unsigned ) d * ( unsigned ) d );
-      }
-      st4( reco + 4 * it, 4, r );
-    }
+    // the job's residual lies where its prediction does
+    acc = chain_finish_walk<L>( predBase + T.resiOff, recoBase + T.outOff, orgBase + B.orgOff, B.orgStride, T.width, T.height, T.bitDepth, l );
   }
-#pragma unroll
-  for( int o = L >> 1; o > 0; o >>= 1 ) acc += __shfl_xor( acc, o, 64 );   // a group is L consecutive lanes of one wave, all of them here
-  if( i < n && l == 0 )
-  {
-    const vtmhip_tu_result t = xRes[i];
-    vtmhip_intra_tu_result r;
-    r.sse = acc; r.sseResi = t.sse; r.sumAbs = t.sumAbs; r.absSum = t.absSum;
-    results[i] = r;
-  }
+  acc = chain_finish_group_sum<L>( acc );
+  if( i < n && l == 0 ) results[i] = chain_finish_result( acc, xRes[i] );
 }
-
-size_t align256( size_t v ) { return ( v + 255 ) & ~( size_t ) 255; }
 
 }   // namespace
 
@@ -139,9 +113,9 @@ int vtmhip_intra_chain_make_tu_jobs( const vtmhip_intra_block *blocks, int numBl
   if( ( numBlocks && !blocks ) || ( nIntra && !intraJobs ) || ( nMip && !mipJobs ) || ( nTu && ( !tuJobs || !out ) ) ) return VTMHIP_E_INVALID;
   IntraChainPlan plan;
   if( !intraChainMakeTuJobs( blocks, numBlocks, intraJobs, nIntra, mipJobs, nMip, tuJobs, nTu, out, plan ) ) return VTMHIP_E_INVALID;
-  if( maxWidth ) *maxWidth = plan.maxWidth;
-  if( maxHeight ) *maxHeight = plan.maxHeight;
-  if( uniform ) *uniform = plan.uniform;
+  if( maxWidth ) *maxWidth = plan.tu.maxWidth;
+  if( maxHeight ) *maxHeight = plan.tu.maxHeight;
+  if( uniform ) *uniform = plan.tu.uniform;
   return VTMHIP_OK;
 }
 
@@ -163,27 +137,29 @@ static int intra_chain_level( vtmhip_ctx *ctx, const int16_t *d_refBase, const i
   VTMHIP_REQUIRE( ctx, !nLfnst || ctx->lfnstTab, "vtmhip_lfnst_set_tables has not been called" );
 
   // the tables decide the launches and the chain kernels trust their jobs: read back and checked before anything runs
+  HostStage    hs( ctx );
   const size_t bBlk = ( size_t ) numBlocks * sizeof( vtmhip_intra_block ), bIntra = ( size_t ) nIntra * sizeof( vtmhip_intra_job ),
                bMip = ( size_t ) nMip * sizeof( vtmhip_mip_job ), bTu = ( size_t ) nTu * sizeof( vtmhip_intra_tu_job ),
-               bLf = ( size_t ) nLfnst * sizeof( vtmhip_intra_lfnst_tu_job );   // every record size is a multiple of 8
-  VTMHIP_TRY( vtmhip_internal_scratch( ctx, bBlk + bIntra + bMip + bTu + bLf ) );
-  char *host = ( char * ) ctx->pinned;
-  if( bBlk ) VTMHIP_HIP( ctx, hipMemcpyAsync( host, d_blocks, bBlk, hipMemcpyDeviceToHost, ctx->stream ) );
-  if( bIntra ) VTMHIP_HIP( ctx, hipMemcpyAsync( host + bBlk, d_intraJobs, bIntra, hipMemcpyDeviceToHost, ctx->stream ) );
-  if( bMip ) VTMHIP_HIP( ctx, hipMemcpyAsync( host + bBlk + bIntra, d_mipJobs, bMip, hipMemcpyDeviceToHost, ctx->stream ) );
-  if( bTu ) VTMHIP_HIP( ctx, hipMemcpyAsync( host + bBlk + bIntra + bMip, d_tuJobs, bTu, hipMemcpyDeviceToHost, ctx->stream ) );
-  if( bLf ) VTMHIP_HIP( ctx, hipMemcpyAsync( host + bBlk + bIntra + bMip + bTu, d_lfnstJobs, bLf, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
+               bLf = ( size_t ) nLfnst * sizeof( vtmhip_intra_lfnst_tu_job );
+  const size_t oBlk = hs.region( bBlk ), oIntra = hs.region( bIntra ), oMip = hs.region( bMip ), oTu = hs.region( bTu ), oLf = hs.region( bLf );
+  VTMHIP_TRY( hs.reserve() );
+  VTMHIP_TRY( hs.pull( oBlk, d_blocks, bBlk ) );
+  VTMHIP_TRY( hs.pull( oIntra, d_intraJobs, bIntra ) );
+  VTMHIP_TRY( hs.pull( oMip, d_mipJobs, bMip ) );
+  VTMHIP_TRY( hs.pull( oTu, d_tuJobs, bTu ) );
+  VTMHIP_TRY( hs.pull( oLf, d_lfnstJobs, bLf ) );
+  VTMHIP_TRY( hs.sync() );
+  const vtmhip_intra_block *blocks    = hs.host<vtmhip_intra_block>( oBlk );
+  const vtmhip_intra_job   *intraJobs = hs.host<vtmhip_intra_job>( oIntra );
+  const vtmhip_mip_job     *mipJobs   = hs.host<vtmhip_mip_job>( oMip );
   IntraChainPlan plan;
   VTMHIP_REQUIRE( ctx,
-                  intraChainScan( ( const vtmhip_intra_block * ) host, numBlocks, ( const vtmhip_intra_job * ) ( host + bBlk ), nIntra,
-                                  ( const vtmhip_mip_job * ) ( host + bBlk + bIntra ), nMip, ( const vtmhip_intra_tu_job * ) ( host + bBlk + bIntra + bMip ), nTu, plan ),
+                  intraChainScan( blocks, numBlocks, intraJobs, nIntra, mipJobs, nMip, hs.host<vtmhip_intra_tu_job>( oTu ), nTu, plan ),
                   "intra chain tables: sides 4..64, bitDepth 8..12, multiRefIdx 0..2 (MIP: 0), block index, mode, pred inside the tables, qpRem 0..5, qpPer >= 0, "
                   "two of DCT2 / DCT8 / DST7 (DCT2 above 32) or both TRSKIP (sides up to 32), reserved fields 0" );
   LfnstPlan lplan;
   VTMHIP_REQUIRE( ctx,
-                  lfnstLevelScan( ( const vtmhip_intra_block * ) host, ( const vtmhip_intra_job * ) ( host + bBlk ), nIntra, ( const vtmhip_mip_job * ) ( host + bBlk + bIntra ), nMip,
-                                  ( const vtmhip_intra_lfnst_tu_job * ) ( host + bBlk + bIntra + bMip + bTu ), nLfnst, lplan ),
+                  lfnstLevelScan( blocks, intraJobs, nIntra, mipJobs, nMip, hs.host<vtmhip_intra_lfnst_tu_job>( oLf ), nLfnst, lplan ),
                   "intra chain LFNST table: lfnstIdx 1..2, pred inside the tables, MIP on sides >= 16 only, qpRem 0..5, qpPer >= 0, reserved fields 0" );
 
   const int lanes = intra_lanes( plan.maxBlockArea ), chunk = intra_chunk( lanes );   // what intra_shape_kernel would leave: here the host knows it
@@ -203,19 +179,17 @@ static int intra_chain_level( vtmhip_ctx *ctx, const int16_t *d_refBase, const i
   }
   if( nTu + nLfnst == 0 ) return VTMHIP_OK;
 
-  // workspace (slot 5, unused until now -- ctx.hpp lists the slots: 0 the prediction entries, 2 the chain's bucketing, 3 SBT, 4 the picture loop's box sums, which stay
-  // attached across the calls a picture makes): the block index per TU job, the expanded jobs, their results
+  // workspace: the block index per TU job, the expanded jobs, their results
   // the LFNST jobs follow the plain ones in all three arrays (their vtmhip_tu_job is the mirror the finish kernel reads); the LFNST chain's own jobs come last
-  const int    nAll = nTu + nLfnst;
-  const size_t oJobs = align256( ( size_t ) nAll * sizeof( int ) ), oRes = align256( oJobs + ( size_t ) nAll * sizeof( vtmhip_tu_job ) ),
-               oLf = align256( oRes + ( size_t ) nAll * sizeof( vtmhip_tu_result ) );
-  void *arena = nullptr;
-  VTMHIP_TRY( vtmhip_internal_workspace( ctx, oLf + ( size_t ) nLfnst * sizeof( vtmhip_lfnst_chain_job ), &arena, 5 ) );
-  char *base = ( char * ) arena;
-  int              *d_tuBlock = ( int * ) base;
-  vtmhip_tu_job    *d_xJobs   = ( vtmhip_tu_job * ) ( base + oJobs );
-  vtmhip_tu_result *d_xRes    = ( vtmhip_tu_result * ) ( base + oRes );
-  vtmhip_lfnst_chain_job *d_cJobs = ( vtmhip_lfnst_chain_job * ) ( base + oLf );
+  const size_t nAll = ( size_t ) nTu + nLfnst;
+  WorkPlan     wp;
+  const size_t oBlock = wp.region<int>( nAll ), oJobs = wp.region<vtmhip_tu_job>( nAll ), oRes = wp.region<vtmhip_tu_result>( nAll ),
+               oChain = wp.region<vtmhip_lfnst_chain_job>( nLfnst );
+  VTMHIP_TRY( wp.reserve( ctx, VTMHIP_WORK_INTRA_CHAIN ) );
+  int                    *d_tuBlock = wp.at<int>( oBlock );
+  vtmhip_tu_job          *d_xJobs   = wp.at<vtmhip_tu_job>( oJobs );
+  vtmhip_tu_result       *d_xRes    = wp.at<vtmhip_tu_result>( oRes );
+  vtmhip_lfnst_chain_job *d_cJobs   = wp.at<vtmhip_lfnst_chain_job>( oChain );
   if( nTu )
   {
     VTMHIP_TIME_KERNEL( ctx, "intra_chain_expand_kernel" );
@@ -223,34 +197,18 @@ static int intra_chain_level( vtmhip_ctx *ctx, const int16_t *d_refBase, const i
                         d_tuBlock );
     VTMHIP_LAUNCHED( ctx );
   }
-  if( nTu ) VTMHIP_TRY( vtmhip_internal_tu_chain_launch( ctx, d_resiBase, d_xJobs, nTu, plan.maxWidth, plan.maxHeight, plan.uniform, d_levelsBase, d_recoBase, d_xRes ) );
+  if( nTu ) VTMHIP_TRY( vtmhip_internal_tu_chain_launch( ctx, d_resiBase, d_xJobs, nTu, plan.tu.maxWidth, plan.tu.maxHeight, plan.tu.uniform, d_levelsBase, d_recoBase, d_xRes ) );
   if( nLfnst )
   {
     VTMHIP_TRY( vtmhip_internal_lfnst_expand_launch( ctx, d_blocks, d_intraJobs, nIntra, d_mipJobs, d_lfnstJobs, nLfnst, d_cJobs, d_xJobs + nTu, d_tuBlock + nTu ) );
     VTMHIP_TRY( vtmhip_internal_lfnst_chain_launch( ctx, d_resiBase, d_cJobs, nLfnst, lplan.maxArea, lplan.jobInts, d_levelsBase, d_recoBase, d_xRes + nTu ) );
   }
   if( nTu )
-  {
-    VTMHIP_TIME_KERNEL( ctx, "intra_chain_finish_kernel" );
-    if( plan.maxTuArea <= 256 )
-      hipLaunchKernelGGL( intra_chain_finish_kernel<16>, dim3( ( nTu + 15 ) / 16 ), dim3( 256 ), 0, ctx->stream, d_orgBase, d_predBase, d_blocks, d_tuBlock, d_xJobs, d_xRes, nTu,
-                          d_recoBase, d_results );
-    else
-      hipLaunchKernelGGL( intra_chain_finish_kernel<64>, dim3( ( nTu + 3 ) / 4 ), dim3( 256 ), 0, ctx->stream, d_orgBase, d_predBase, d_blocks, d_tuBlock, d_xJobs, d_xRes, nTu,
-                          d_recoBase, d_results );
-    VTMHIP_LAUNCHED( ctx );
-  }
+    VTMHIP_TRY( chain_finish_launch( ctx, "intra_chain_finish_kernel", intra_chain_finish_kernel<16>, intra_chain_finish_kernel<64>, plan.tu.maxArea, nTu, d_orgBase, d_predBase,
+                                     d_blocks, d_tuBlock, d_xJobs, d_xRes, nTu, d_recoBase, d_results ) );
   if( nLfnst )   // the same finish kernel over the second result table
-  {
-    VTMHIP_TIME_KERNEL( ctx, "intra_chain_finish_kernel" );
-    if( lplan.maxArea <= 256 )
-      hipLaunchKernelGGL( intra_chain_finish_kernel<16>, dim3( ( nLfnst + 15 ) / 16 ), dim3( 256 ), 0, ctx->stream, d_orgBase, d_predBase, d_blocks, d_tuBlock + nTu, d_xJobs + nTu,
-                          d_xRes + nTu, nLfnst, d_recoBase, d_lfnstResults );
-    else
-      hipLaunchKernelGGL( intra_chain_finish_kernel<64>, dim3( ( nLfnst + 3 ) / 4 ), dim3( 256 ), 0, ctx->stream, d_orgBase, d_predBase, d_blocks, d_tuBlock + nTu, d_xJobs + nTu,
-                          d_xRes + nTu, nLfnst, d_recoBase, d_lfnstResults );
-    VTMHIP_LAUNCHED( ctx );
-  }
+    VTMHIP_TRY( chain_finish_launch( ctx, "intra_chain_finish_kernel", intra_chain_finish_kernel<16>, intra_chain_finish_kernel<64>, lplan.maxArea, nLfnst, d_orgBase, d_predBase,
+                                     d_blocks, d_tuBlock + nTu, d_xJobs + nTu, d_xRes + nTu, nLfnst, d_recoBase, d_lfnstResults ) );
   return VTMHIP_OK;
 }
 
@@ -284,9 +242,9 @@ int vtmhip_intra_chain_lfnst_make_jobs( const vtmhip_intra_block *blocks, int nu
   IntraChainPlan plan;
   LfnstPlan      lplan;
   if( !lfnstLevelMakeJobs( blocks, numBlocks, intraJobs, nIntra, mipJobs, nMip, tuJobs, nTu, lfnstJobs, nLfnst, outTu, outLfnst, plan, lplan ) ) return VTMHIP_E_INVALID;
-  if( maxWidth ) *maxWidth = plan.maxWidth;
-  if( maxHeight ) *maxHeight = plan.maxHeight;
-  if( uniform ) *uniform = plan.uniform;
+  if( maxWidth ) *maxWidth = plan.tu.maxWidth;
+  if( maxHeight ) *maxHeight = plan.tu.maxHeight;
+  if( uniform ) *uniform = plan.tu.uniform;
   if( lanesOut ) *lanesOut = nLfnst ? lfnstLanes( lplan.maxArea ) : 0;
   return VTMHIP_OK;
 }

@@ -4,9 +4,11 @@
 //   intraChainTuOk      what a vtmhip_intra_tu_job must satisfy on a W x H block
 //   intraChainExpand    the job as a vtmhip_tu_job of the fused chain: the residual of its prediction at stride W, shape and bit depth from the block
 //   intraChainScan      the host pass over all four tables: every entry is checked (with intraBlockOk / intraModeOk / mipBlockOk / mipJobOk: the rules the prediction
-//                       kernels skip by), and the launch plan falls out of the same walk
+//                       kernels skip by), and the launch plan falls out of the same walk (chain_rules.hpp's ChainShapes over the TU jobs)
+//   intraChainExpandAll the expansion of a whole checked TU table, for both make-jobs entries (lfnst_rules.hpp calls it too)
 // A table with one malformed entry is rejected whole: the chain kernels trust their jobs.
 #pragma once
+#include "chain_rules.hpp"
 #include "intra_rules.hpp"
 #include "mip_rules.hpp"
 
@@ -18,9 +20,8 @@
 
 struct IntraChainPlan
 {
-  int maxBlockArea;   // over the block table: decides the lanes a prediction job gets
-  int maxWidth, maxHeight, maxTuArea;   // over the TU jobs (0 without any)
-  int uniform;        // every TU job has one size and a real transform
+  int         maxBlockArea;   // over the block table: decides the lanes a prediction job gets
+  ChainShapes tu;             // over the TU jobs
 };
 
 ICHAIN_HD void intraChainPred( const vtmhip_intra_job *intraJobs, int nIntra, const vtmhip_mip_job *mipJobs, int p, int &block, int64_t &predOff )
@@ -38,7 +39,7 @@ ICHAIN_HD bool intraChainTrOk( int typeHor, int typeVer, int w, int h )
 
 ICHAIN_HD bool intraChainTuOk( const vtmhip_intra_tu_job &t, int w, int h )
 {
-  return t.qpRem >= 0 && t.qpRem <= 5 && t.qpPer >= 0 && t.reserved == 0 && t.pad == 0 && intraChainTrOk( t.typeHor, t.typeVer, w, h );
+  return chainQpOk( t.qpPer, t.qpRem ) && t.reserved == 0 && t.pad == 0 && intraChainTrOk( t.typeHor, t.typeVer, w, h );
 }
 
 ICHAIN_HD void intraChainExpand( const vtmhip_intra_tu_job &t, const vtmhip_intra_block &b, int64_t predOff, vtmhip_tu_job &out )
@@ -57,7 +58,8 @@ ICHAIN_HD void intraChainExpand( const vtmhip_intra_tu_job &t, const vtmhip_intr
 inline bool intraChainScan( const vtmhip_intra_block *blocks, int numBlocks, const vtmhip_intra_job *intraJobs, int nIntra, const vtmhip_mip_job *mipJobs, int nMip,
                             const vtmhip_intra_tu_job *tuJobs, int nTu, IntraChainPlan &plan )
 {
-  plan.maxBlockArea = plan.maxWidth = plan.maxHeight = plan.maxTuArea = plan.uniform = 0;
+  plan.maxBlockArea = 0;
+  plan.tu.begin( nTu );
   for( int i = 0; i < numBlocks; i++ )
   {
     const vtmhip_intra_block &b = blocks[i];
@@ -76,7 +78,6 @@ inline bool intraChainScan( const vtmhip_intra_block *blocks, int numBlocks, con
     const vtmhip_intra_block &b = blocks[j.block];
     if( !mipBlockOk( b.width, b.height, b.bitDepth, b.multiRefIdx ) || !mipJobOk( mipShape( b.width, b.height ), j.mode, j.transposed ) ) return false;
   }
-  bool uniform = nTu > 0;
   for( int i = 0; i < nTu; i++ )
   {
     const vtmhip_intra_tu_job &t = tuJobs[i];
@@ -86,21 +87,15 @@ inline bool intraChainScan( const vtmhip_intra_block *blocks, int numBlocks, con
     intraChainPred( intraJobs, nIntra, mipJobs, t.pred, blk, predOff );
     const int w = blocks[blk].width, h = blocks[blk].height;
     if( !intraChainTuOk( t, w, h ) ) return false;
-    if( i && ( w != plan.maxWidth || h != plan.maxHeight ) ) uniform = false;   // before the first difference the maxima are the one size
-    if( t.typeHor == VTMHIP_TRSKIP ) uniform = false;
-    if( w > plan.maxWidth ) plan.maxWidth = w;
-    if( h > plan.maxHeight ) plan.maxHeight = h;
-    if( w * h > plan.maxTuArea ) plan.maxTuArea = w * h;
+    plan.tu.add( i, w, h, t.typeHor );
   }
-  plan.uniform = uniform;
   return true;
 }
 
-// vtmhip_intra_chain_make_tu_jobs without its NULL checks: out[i] = TU job i as the chain sees it; nothing is written when a table is rejected
-inline bool intraChainMakeTuJobs( const vtmhip_intra_block *blocks, int numBlocks, const vtmhip_intra_job *intraJobs, int nIntra, const vtmhip_mip_job *mipJobs, int nMip,
-                                  const vtmhip_intra_tu_job *tuJobs, int nTu, vtmhip_tu_job *out, IntraChainPlan &plan )
+// out[i] = TU job i as the chain sees it; the tables have passed intraChainScan
+inline void intraChainExpandAll( const vtmhip_intra_block *blocks, const vtmhip_intra_job *intraJobs, int nIntra, const vtmhip_mip_job *mipJobs,
+                                 const vtmhip_intra_tu_job *tuJobs, int nTu, vtmhip_tu_job *out )
 {
-  if( !intraChainScan( blocks, numBlocks, intraJobs, nIntra, mipJobs, nMip, tuJobs, nTu, plan ) ) return false;
   for( int i = 0; i < nTu; i++ )
   {
     int     blk;
@@ -108,5 +103,13 @@ inline bool intraChainMakeTuJobs( const vtmhip_intra_block *blocks, int numBlock
     intraChainPred( intraJobs, nIntra, mipJobs, tuJobs[i].pred, blk, predOff );
     intraChainExpand( tuJobs[i], blocks[blk], predOff, out[i] );
   }
+}
+
+// vtmhip_intra_chain_make_tu_jobs without its NULL checks: out[i] = TU job i as the chain sees it; nothing is written when a table is rejected
+inline bool intraChainMakeTuJobs( const vtmhip_intra_block *blocks, int numBlocks, const vtmhip_intra_job *intraJobs, int nIntra, const vtmhip_mip_job *mipJobs, int nMip,
+                                  const vtmhip_intra_tu_job *tuJobs, int nTu, vtmhip_tu_job *out, IntraChainPlan &plan )
+{
+  if( !intraChainScan( blocks, numBlocks, intraJobs, nIntra, mipJobs, nMip, tuJobs, nTu, plan ) ) return false;
+  intraChainExpandAll( blocks, intraJobs, nIntra, mipJobs, tuJobs, nTu, out );
   return true;
 }

@@ -12,16 +12,16 @@
 //   the chains                         vtmhip_internal_tu_chain_launch / _crs_launch (transform.hip) and vtmhip_internal_jccr_chain_launch (jccr.hip), unchanged
 //                                      kernels: levels and the reconstructed residuals at outOff.  The CRS instantiations run when some job carries an adj
 //   intra_chroma_chain_finish_kernel<L>  one item per component block: nTu + 2 nJoint of them.  An item gets L lanes (16 up to 256 samples: sixteen items per
-//                                      workgroup; 64 above: a wave per item), chosen by the host from the largest TU.  A lane walks 4-sample row segments as
-//                                      intra_chain_finish_kernel does: prediction and reconstructed residual are W x H contiguous, the original has its own stride;
-//                                      all three come as one 8-byte access at a 2-byte aligned address (pel_pack.hpp).  It overwrites the reconstructed residual
-//                                      with clip( prediction + residual ) and sums ( original - reconstruction )^2 with the per-addend 32-bit product of
-//                                      dist_block.hpp's SSE; the group's lanes are added by shuffles.  No LDS, no barrier.
-// The entry reads the four tables back and checks them (one stream synchronisation), so the kernels here trust what they are given.
+//                                      workgroup; 64 above: a wave per item), chosen by the host from the largest TU.  It decodes the item and runs
+//                                      chain_finish.hpp's walk, as intra_chain_finish_kernel does: the reconstructed residual becomes
+//                                      clip( prediction + residual ), and its SSE against the original joins the chains' results.  No LDS, no barrier.
+// The entry reads the four tables back through HostStage (stage.hpp) and checks them (one stream synchronisation), so the kernels here trust what they are given.
+// Its workspace is a WorkPlan in the slot VTMHIP_WORK_INTRA_CHROMA_CHAIN.
 #include "ctx.hpp"
+#include "stage.hpp"
+#include "chain_finish.hpp"
 #include "intra_chroma_body.hpp"   // ich_chunk_body, as intra_chroma.hip's kernels use it
 #include "intra_chroma_chain_rules.hpp"
-#include "pel_pack.hpp"
 
 namespace
 {
@@ -118,36 +118,12 @@ __global__ __launch_bounds__( 256 ) void intra_chroma_chain_finish_kernel( const
       reco = ( c ? a.recoCrBase : a.recoBase ) + J.outOff;
       B    = a.blocks + a.jointBlock[k];
     }
-    const int      lgSegs = intraLog2( w ) - 2, items = ( w * h ) >> 2, maxVal = ( 1 << bd ) - 1, orgStride = B->orgStride;
-    const int16_t *org = a.orgBase + ( c ? B->crOrgOff : B->cbOrgOff );
-    for( int it = l; it < items; it += L )
-    {
-      const int y = it >> lgSegs, x = ( it & ( ( 1 << lgSegs ) - 1 ) ) << 2;
-      int p[4], r[4], o[4];
-      ld4( pred + 4 * it, 4, p );
-      ld4( reco + 4 * it, 4, r );
-      ld4( org + ( long ) y * orgStride + x, 4, o );
-#pragma unroll
-      for( int q = 0; q < 4; q++ )
-      {
-        r[q] = min( max( p[q] + r[q], 0 ), maxVal );
-        const int d = o[q] - r[q];
-        acc += ( unsigned long long ) ( ( unsigned ) d * ( unsigned ) d );
-      }
-      st4( reco + 4 * it, 4, r );
-    }
+    acc = chain_finish_walk<L>( pred, reco, a.orgBase + ( c ? B->crOrgOff : B->cbOrgOff ), B->orgStride, w, h, bd, l );
   }
-#pragma unroll
-  for( int o = L >> 1; o > 0; o >>= 1 ) acc += __shfl_xor( acc, o, 64 );   // a group is L consecutive lanes of one wave, all of them here
+  acc = chain_finish_group_sum<L>( acc );
   if( i < n && l == 0 )
   {
-    if( i < a.nTu )
-    {
-      const vtmhip_tu_result t = a.xTuRes[k];
-      vtmhip_intra_tu_result r;
-      r.sse = acc; r.sseResi = t.sse; r.sumAbs = t.sumAbs; r.absSum = t.absSum;
-      a.results[k] = r;
-    }
+    if( i < a.nTu ) a.results[k] = chain_finish_result( acc, a.xTuRes[k] );
     else if( c == 0 )   // the Cb item also carries over what the joint chain left; the Cr item owns sseCr alone
     {
       const vtmhip_jccr_result t = a.xJointRes[k];
@@ -157,8 +133,6 @@ __global__ __launch_bounds__( 256 ) void intra_chroma_chain_finish_kernel( const
     else a.jointResults[k].sseCr = acc;
   }
 }
-
-size_t align256( size_t v ) { return ( v + 255 ) & ~( size_t ) 255; }
 
 }   // namespace
 
@@ -184,10 +158,10 @@ int vtmhip_intra_chroma_chain_make_jobs( const vtmhip_intra_chroma_block *blocks
   if( ( numBlocks && !blocks ) || ( nPred && !jobs ) || ( nTu && ( !tuJobs || !outTu ) ) || ( nJoint && ( !jointJobs || !outJoint ) ) ) return VTMHIP_E_INVALID;
   IchainPlan plan;
   if( !ichainMakeJobs( blocks, numBlocks, jobs, nPred, tuJobs, nTu, jointJobs, nJoint, outTu, outJoint, plan ) ) return VTMHIP_E_INVALID;
-  if( maxWidth ) { maxWidth[0] = plan.maxWidth[0]; maxWidth[1] = plan.maxWidth[1]; }
-  if( maxHeight ) { maxHeight[0] = plan.maxHeight[0]; maxHeight[1] = plan.maxHeight[1]; }
-  if( uniformTu ) *uniformTu = plan.uniform[0];
-  if( uniformJoint ) *uniformJoint = plan.uniform[1];
+  if( maxWidth ) { maxWidth[0] = plan.tu.maxWidth; maxWidth[1] = plan.joint.maxWidth; }
+  if( maxHeight ) { maxHeight[0] = plan.tu.maxHeight; maxHeight[1] = plan.joint.maxHeight; }
+  if( uniformTu ) *uniformTu = plan.tu.uniform;
+  if( uniformJoint ) *uniformJoint = plan.joint.uniform;
   if( crs ) *crs = plan.crs;
   return VTMHIP_OK;
 }
@@ -206,20 +180,20 @@ int vtmhip_intra_chroma_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBa
   VTMHIP_REQUIRE( ctx, !nJoint || ( d_jointJobs && d_recoBase && d_recoCrBase && d_jointResults ), "null pointer" );
 
   // the tables decide the launches and the chain kernels trust their jobs: read back and checked before anything runs
+  HostStage    hs( ctx );
   const size_t bBlk = ( size_t ) numBlocks * sizeof( vtmhip_intra_chroma_block ), bJob = ( size_t ) nPred * sizeof( vtmhip_intra_chroma_job ),
-               bTu = ( size_t ) nTu * sizeof( vtmhip_intra_chroma_tu_job ), bJoint = ( size_t ) nJoint * sizeof( vtmhip_intra_chroma_joint_job );   // every record size is a multiple of 8
-  VTMHIP_TRY( vtmhip_internal_scratch( ctx, bBlk + bJob + bTu + bJoint ) );
-  char *host = ( char * ) ctx->pinned;
-  if( bBlk ) VTMHIP_HIP( ctx, hipMemcpyAsync( host, d_blocks, bBlk, hipMemcpyDeviceToHost, ctx->stream ) );
-  if( bJob ) VTMHIP_HIP( ctx, hipMemcpyAsync( host + bBlk, d_jobs, bJob, hipMemcpyDeviceToHost, ctx->stream ) );
-  if( bTu ) VTMHIP_HIP( ctx, hipMemcpyAsync( host + bBlk + bJob, d_tuJobs, bTu, hipMemcpyDeviceToHost, ctx->stream ) );
-  if( bJoint ) VTMHIP_HIP( ctx, hipMemcpyAsync( host + bBlk + bJob + bTu, d_jointJobs, bJoint, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
+               bTu = ( size_t ) nTu * sizeof( vtmhip_intra_chroma_tu_job ), bJoint = ( size_t ) nJoint * sizeof( vtmhip_intra_chroma_joint_job );
+  const size_t oBlk = hs.region( bBlk ), oJob = hs.region( bJob ), oTu = hs.region( bTu ), oJoint = hs.region( bJoint );
+  VTMHIP_TRY( hs.reserve() );
+  VTMHIP_TRY( hs.pull( oBlk, d_blocks, bBlk ) );
+  VTMHIP_TRY( hs.pull( oJob, d_jobs, bJob ) );
+  VTMHIP_TRY( hs.pull( oTu, d_tuJobs, bTu ) );
+  VTMHIP_TRY( hs.pull( oJoint, d_jointJobs, bJoint ) );
+  VTMHIP_TRY( hs.sync() );
   IchainPlan plan;
   VTMHIP_REQUIRE( ctx,
-                  ichainScan( ( const vtmhip_intra_chroma_block * ) host, numBlocks, ( const vtmhip_intra_chroma_job * ) ( host + bBlk ), nPred,
-                              ( const vtmhip_intra_chroma_tu_job * ) ( host + bBlk + bJob ), nTu, ( const vtmhip_intra_chroma_joint_job * ) ( host + bBlk + bJob + bTu ),
-                              nJoint, plan ),
+                  ichainScan( hs.host<vtmhip_intra_chroma_block>( oBlk ), numBlocks, hs.host<vtmhip_intra_chroma_job>( oJob ), nPred,
+                              hs.host<vtmhip_intra_chroma_tu_job>( oTu ), nTu, hs.host<vtmhip_intra_chroma_joint_job>( oJoint ), nJoint, plan ),
                   "intra chroma chain tables: sides 4 / 8 / 16 / 32, bitDepth 8..12, flags 0 / 1, consistent availability, block index, mode 0..69, pred inside the table, "
                   "component 0 / 1, cbfMask 1..3, signFlag 0 / 1, DCT2 or TRSKIP, qpRem 0..5, qpPer >= 0, chromaAdj <= 32767, reserved fields 0" );
   VTMHIP_REQUIRE( ctx, !plan.anyLm || d_lumaBase, "null pointer: an LM job without the luma plane" );
@@ -234,19 +208,17 @@ int vtmhip_intra_chroma_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBa
   }
   if( nTu + nJoint == 0 ) return VTMHIP_OK;
 
-  // workspace (slot 6; ctx.hpp lists the slots): the block index per job, the expanded jobs, the chains' results -- the single jobs' and the joint jobs' side by side
-  const size_t oJBlk = align256( ( size_t ) nTu * sizeof( int ) ), oXTu = align256( oJBlk + ( size_t ) nJoint * sizeof( int ) ),
-               oXJoint = align256( oXTu + ( size_t ) nTu * sizeof( vtmhip_tu_job ) ), oTuRes = align256( oXJoint + ( size_t ) nJoint * sizeof( vtmhip_jccr_job ) ),
-               oJRes = align256( oTuRes + ( size_t ) nTu * sizeof( vtmhip_tu_result ) );
-  void *arena = nullptr;
-  VTMHIP_TRY( vtmhip_internal_workspace( ctx, oJRes + ( size_t ) nJoint * sizeof( vtmhip_jccr_result ), &arena, 6 ) );
-  char *base = ( char * ) arena;
-  int                *d_tuBlock    = ( int * ) base;
-  int                *d_jointBlock = ( int * ) ( base + oJBlk );
-  vtmhip_tu_job      *d_xTu        = ( vtmhip_tu_job * ) ( base + oXTu );
-  vtmhip_jccr_job    *d_xJoint     = ( vtmhip_jccr_job * ) ( base + oXJoint );
-  vtmhip_tu_result   *d_xTuRes     = ( vtmhip_tu_result * ) ( base + oTuRes );
-  vtmhip_jccr_result *d_xJointRes  = ( vtmhip_jccr_result * ) ( base + oJRes );
+  // workspace: the block index per job, the expanded jobs, the chains' results -- the single jobs' and the joint jobs' side by side
+  WorkPlan     wp;
+  const size_t oTuBlk = wp.region<int>( nTu ), oJBlk = wp.region<int>( nJoint ), oXTu = wp.region<vtmhip_tu_job>( nTu ), oXJoint = wp.region<vtmhip_jccr_job>( nJoint ),
+               oTuRes = wp.region<vtmhip_tu_result>( nTu ), oJRes = wp.region<vtmhip_jccr_result>( nJoint );
+  VTMHIP_TRY( wp.reserve( ctx, VTMHIP_WORK_INTRA_CHROMA_CHAIN ) );
+  int                *d_tuBlock    = wp.at<int>( oTuBlk );
+  int                *d_jointBlock = wp.at<int>( oJBlk );
+  vtmhip_tu_job      *d_xTu        = wp.at<vtmhip_tu_job>( oXTu );
+  vtmhip_jccr_job    *d_xJoint     = wp.at<vtmhip_jccr_job>( oXJoint );
+  vtmhip_tu_result   *d_xTuRes     = wp.at<vtmhip_tu_result>( oTuRes );
+  vtmhip_jccr_result *d_xJointRes  = wp.at<vtmhip_jccr_result>( oJRes );
   {
     VTMHIP_TIME_KERNEL( ctx, "intra_chroma_chain_expand_kernel" );
     hipLaunchKernelGGL( intra_chroma_chain_expand_kernel, dim3( ( nTu + nJoint + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, d_blocks, d_jobs, d_tuJobs, nTu, d_jointJobs, nJoint,
@@ -256,25 +228,17 @@ int vtmhip_intra_chroma_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBa
   if( nTu )
   {
     if( plan.crs )
-      VTMHIP_TRY( vtmhip_internal_tu_chain_crs_launch( ctx, d_resiBase, d_xTu, nTu, plan.maxWidth[0], plan.maxHeight[0], plan.uniform[0], d_levelsBase, d_recoBase, d_xTuRes ) );
+      VTMHIP_TRY( vtmhip_internal_tu_chain_crs_launch( ctx, d_resiBase, d_xTu, nTu, plan.tu.maxWidth, plan.tu.maxHeight, plan.tu.uniform, d_levelsBase, d_recoBase, d_xTuRes ) );
     else
-      VTMHIP_TRY( vtmhip_internal_tu_chain_launch( ctx, d_resiBase, d_xTu, nTu, plan.maxWidth[0], plan.maxHeight[0], plan.uniform[0], d_levelsBase, d_recoBase, d_xTuRes ) );
+      VTMHIP_TRY( vtmhip_internal_tu_chain_launch( ctx, d_resiBase, d_xTu, nTu, plan.tu.maxWidth, plan.tu.maxHeight, plan.tu.uniform, d_levelsBase, d_recoBase, d_xTuRes ) );
   }
   if( nJoint )
-    VTMHIP_TRY( vtmhip_internal_jccr_chain_launch( ctx, plan.crs != 0, d_resiBase, d_xJoint, nJoint, plan.maxWidth[1], plan.maxHeight[1], plan.uniform[1], d_levelsBase, d_recoBase,
+    VTMHIP_TRY( vtmhip_internal_jccr_chain_launch( ctx, plan.crs != 0, d_resiBase, d_xJoint, nJoint, plan.joint.maxWidth, plan.joint.maxHeight, plan.joint.uniform, d_levelsBase, d_recoBase,
                                                    d_recoCrBase, d_xJointRes ) );
-  {
-    const IchFinishArgs a = { d_orgBase, d_predBase, d_blocks, d_tuJobs, d_tuBlock, d_jointBlock, d_xTu, d_xTuRes, d_xJoint, d_xJointRes, nTu, nJoint,
-                              d_recoBase, d_recoCrBase, d_results, d_jointResults };
-    const int items = nTu + 2 * nJoint;
-    VTMHIP_TIME_KERNEL( ctx, "intra_chroma_chain_finish_kernel" );
-    if( ( plan.maxArea[0] > plan.maxArea[1] ? plan.maxArea[0] : plan.maxArea[1] ) <= 256 )
-      hipLaunchKernelGGL( intra_chroma_chain_finish_kernel<16>, dim3( ( items + 15 ) / 16 ), dim3( 256 ), 0, ctx->stream, a );
-    else
-      hipLaunchKernelGGL( intra_chroma_chain_finish_kernel<64>, dim3( ( items + 3 ) / 4 ), dim3( 256 ), 0, ctx->stream, a );
-    VTMHIP_LAUNCHED( ctx );
-  }
-  return VTMHIP_OK;
+  const IchFinishArgs a = { d_orgBase, d_predBase, d_blocks, d_tuJobs, d_tuBlock, d_jointBlock, d_xTu, d_xTuRes, d_xJoint, d_xJointRes, nTu, nJoint,
+                            d_recoBase, d_recoCrBase, d_results, d_jointResults };
+  return chain_finish_launch( ctx, "intra_chroma_chain_finish_kernel", intra_chroma_chain_finish_kernel<16>, intra_chroma_chain_finish_kernel<64>,
+                              plan.tu.maxArea > plan.joint.maxArea ? plan.tu.maxArea : plan.joint.maxArea, nTu + 2 * nJoint, a );
 }
 
 }   // extern "C"

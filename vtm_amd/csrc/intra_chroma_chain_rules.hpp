@@ -5,9 +5,11 @@
 //   ichainJointOk       what a vtmhip_intra_chroma_joint_job must satisfy
 //   ichainExpandTu      the single job as a vtmhip_tu_job of the fused chain: the residual of its component at stride W, shape and bit depth from the block
 //   ichainExpandJoint   the joint job as a vtmhip_jccr_job of the joint chain: both residuals of its prediction
-//   ichainScan          the host pass over all four tables: every entry is checked, and the launch plan falls out of the same walk
+//   ichainScan          the host pass over all four tables: every entry is checked, and the launch plan falls out of the same walk (chain_rules.hpp's ChainShapes
+//                       per job table)
 // A table with one malformed entry is rejected whole: the chain kernels trust their jobs.
 #pragma once
+#include "chain_rules.hpp"
 #include "cclm_rules.hpp"
 
 #if defined( __HIPCC__ )
@@ -19,8 +21,7 @@
 struct IchainPlan
 {
   int maxBlockArea;              // over the block table: decides the lanes a prediction job gets
-  int maxWidth[2], maxHeight[2], maxArea[2];   // [0] over the single jobs, [1] over the joint jobs (0 without any)
-  int uniform[2];                // every job of the table has one size and VTMHIP_DCT2
+  ChainShapes tu, joint;         // over the single jobs, over the joint jobs (chain_rules.hpp)
   int anyLm;                     // some prediction job is an LM mode: the luma plane is read
   int crs;                       // some job has a non-zero adj: the CRS instantiations of the chains are dispatched
 };
@@ -35,12 +36,12 @@ ICCHAIN_HD bool ichainTrOk( int typeHor ) { return typeHor == VTMHIP_DCT2 || typ
 
 ICCHAIN_HD bool ichainTuOk( const vtmhip_intra_chroma_tu_job &t )
 {
-  return t.component <= 1 && ichainTrOk( t.typeHor ) && t.qpRem >= 0 && t.qpRem <= 5 && t.qpPer >= 0 && t.chromaAdj <= 32767 && t.reserved == 0 && t.pad == 0;
+  return t.component <= 1 && ichainTrOk( t.typeHor ) && chainQpOk( t.qpPer, t.qpRem ) && t.chromaAdj <= 32767 && t.reserved == 0 && t.pad == 0;
 }
 
 ICCHAIN_HD bool ichainJointOk( const vtmhip_intra_chroma_joint_job &t )
 {
-  return t.cbfMask >= 1 && t.cbfMask <= 3 && t.signFlag <= 1 && ichainTrOk( t.typeHor ) && t.qpRem >= 0 && t.qpRem <= 5 && t.qpPer >= 0 && t.chromaAdj <= 32767 && t.pad == 0;
+  return t.cbfMask >= 1 && t.cbfMask <= 3 && t.signFlag <= 1 && ichainTrOk( t.typeHor ) && chainQpOk( t.qpPer, t.qpRem ) && t.chromaAdj <= 32767 && t.pad == 0;
 }
 
 ICCHAIN_HD void ichainExpandTu( const vtmhip_intra_chroma_tu_job &t, const vtmhip_intra_chroma_block &b, const vtmhip_intra_chroma_job &p, vtmhip_tu_job &out )
@@ -68,17 +69,6 @@ ICCHAIN_HD void ichainExpandJoint( const vtmhip_intra_chroma_joint_job &t, const
   out.reserved1[0] = out.reserved1[1] = out.reserved1[2] = out.reserved1[3] = 0;
 }
 
-// one job of either table joins the walk over its table: the maxima, and whether the table still has one size and real transforms
-inline void ichainAccount( IchainPlan &plan, int tab, int i, int w, int h, int typeHor, int adj, bool &uniform )
-{
-  if( i && ( w != plan.maxWidth[tab] || h != plan.maxHeight[tab] ) ) uniform = false;   // before the first difference the maxima are the one size
-  if( typeHor == VTMHIP_TRSKIP ) uniform = false;
-  if( w > plan.maxWidth[tab] ) plan.maxWidth[tab] = w;
-  if( h > plan.maxHeight[tab] ) plan.maxHeight[tab] = h;
-  if( w * h > plan.maxArea[tab] ) plan.maxArea[tab] = w * h;
-  if( adj ) plan.crs = 1;
-}
-
 // false: an entry the prediction entry would skip or the chains must not see
 inline bool ichainScan( const vtmhip_intra_chroma_block *blocks, int numBlocks, const vtmhip_intra_chroma_job *jobs, int nPred, const vtmhip_intra_chroma_tu_job *tuJobs,
                         int nTu, const vtmhip_intra_chroma_joint_job *jointJobs, int nJoint, IchainPlan &plan )
@@ -95,24 +85,24 @@ inline bool ichainScan( const vtmhip_intra_chroma_block *blocks, int numBlocks, 
     if( j.block < 0 || j.block >= numBlocks || !cclmModeOk( j.mode ) || j.reserved[0] || j.reserved[1] || j.reserved[2] ) return false;
     if( cclmIsLm( j.mode ) ) plan.anyLm = 1;
   }
-  bool uniform = nTu > 0;
+  plan.tu.begin( nTu );
   for( int i = 0; i < nTu; i++ )
   {
     const vtmhip_intra_chroma_tu_job &t = tuJobs[i];
     if( t.pred < 0 || t.pred >= nPred || !ichainTuOk( t ) ) return false;
     const vtmhip_intra_chroma_block &b = blocks[jobs[t.pred].block];
-    ichainAccount( plan, 0, i, b.width, b.height, t.typeHor, t.chromaAdj, uniform );
+    plan.tu.add( i, b.width, b.height, t.typeHor );
+    if( t.chromaAdj ) plan.crs = 1;
   }
-  plan.uniform[0] = uniform;
-  uniform = nJoint > 0;
+  plan.joint.begin( nJoint );
   for( int i = 0; i < nJoint; i++ )
   {
     const vtmhip_intra_chroma_joint_job &t = jointJobs[i];
     if( t.pred < 0 || t.pred >= nPred || !ichainJointOk( t ) ) return false;
     const vtmhip_intra_chroma_block &b = blocks[jobs[t.pred].block];
-    ichainAccount( plan, 1, i, b.width, b.height, t.typeHor, t.chromaAdj, uniform );
+    plan.joint.add( i, b.width, b.height, t.typeHor );
+    if( t.chromaAdj ) plan.crs = 1;
   }
-  plan.uniform[1] = uniform;
   return true;
 }
 

@@ -18,6 +18,8 @@
 // through inv() before the rec stores and the SSEs, which are taken against the unscaled residuals.  The job's adj is 0 for "leave this job alone".
 //
 // Out of scope: ACT, the picture-level sign decision (the caller passes signFlag), the CABAC estimate.
+//
+// The chain entries read their job table back through HostStage (stage.hpp), as the other chains' entries do.
 #include "ctx.hpp"
 #include "stage.hpp"
 #include "lmcs.hpp"
@@ -471,12 +473,9 @@ int jccr_chain_entry( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_j
   if( st ) return st;
   // the job table, checked on the host before anything is launched (the kernels index LDS and the core matrices by these fields)
   {
-    const size_t bytes = ( size_t ) n * sizeof( vtmhip_jccr_job );
-    st = vtmhip_internal_scratch( ctx, bytes );
-    if( st ) return st;
-    VTMHIP_HIP( ctx, hipMemcpyAsync( ctx->pinned, d_jobs, bytes, hipMemcpyDeviceToHost, ctx->stream ) );
-    VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
-    const vtmhip_jccr_job *jobs = ( const vtmhip_jccr_job * ) ctx->pinned;
+    HostStage              hs( ctx );
+    const vtmhip_jccr_job *jobs = nullptr;
+    VTMHIP_TRY( hs.pull_table( d_jobs, n, jobs ) );
     for( int i = 0; i < n; i++ )
     {
       const vtmhip_jccr_job &j = jobs[i];

@@ -11,7 +11,9 @@
 // restaged plain for the inverse ones; the keep x keep region; the 16 / 48 vector of the core multiply; 16 dequantised values; the levels of the top-left 4x4.
 // The passes are lean forms of tu_stages.hpp's lds_fwd_pass / lds_inv_pass -- same sums, same rounding, same clip -- that neither stage nor walk the matrix rows and
 // lines the zero-out drops: keep = 4 or 8 of N frequencies per dimension.  A group past the end of the table repeats the last job in its own slot and stores nothing.
+// The entry reads its job table back through HostStage (stage.hpp) and checks it before anything runs.
 #include "ctx.hpp"
+#include "stage.hpp"
 #include "tu_stages.hpp"
 #include "lfnst_rules.hpp"
 
@@ -248,12 +250,11 @@ int vtmhip_lfnst_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, co
   VTMHIP_BATCH_ENTRY( ctx, n, d_resiBase && d_jobs && d_results );
   VTMHIP_REQUIRE( ctx, ctx->lfnstTab, "vtmhip_lfnst_set_tables has not been called" );
   // the kernel trusts its jobs: the table is read back and checked before anything runs
-  const size_t bytes = ( size_t ) n * sizeof( vtmhip_lfnst_chain_job );
-  VTMHIP_TRY( vtmhip_internal_scratch( ctx, bytes ) );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( ctx->pinned, d_jobs, bytes, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
+  HostStage                     hs( ctx );
+  const vtmhip_lfnst_chain_job *jobs = nullptr;
+  VTMHIP_TRY( hs.pull_table( d_jobs, n, jobs ) );
   LfnstPlan plan;
-  VTMHIP_REQUIRE( ctx, lfnstChainScan( ( const vtmhip_lfnst_chain_job * ) ctx->pinned, n, plan ),
+  VTMHIP_REQUIRE( ctx, lfnstChainScan( jobs, n, plan ),
                   "LFNST chain jobs: sides 4..64, resiStride >= width, bitDepth 8..12, qpRem 0..5, qpPer >= 0, setIdx 0..3, index 0..1, transpose 0..1, pad 0" );
   return vtmhip_internal_lfnst_chain_launch( ctx, d_resiBase, d_jobs, n, plan.maxArea, plan.jobInts, d_levelsBase, d_recBase, d_results );
 }

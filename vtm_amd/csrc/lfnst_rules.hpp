@@ -8,7 +8,8 @@
 //   lfnstScanPos        scan position k -> x + y * width: the rule of vtmhip_lfnst_scan_host
 //   lfnstRegionXY       entry v of the core multiply's vector -> (x, y) of the region (TrQuant.cpp:474-511)
 //   lfnstChainJobOk     what a vtmhip_lfnst_chain_job must satisfy;  lfnstChainScan: the host pass over such a table
-//   lfnstTuOk / lfnstExpand / lfnstLevelScan / lfnstLevelMakeJobs   the LFNST table of the intra level entry, beside intra_chain_rules.hpp's
+//   lfnstTuOk / lfnstExpand / lfnstLevelScan / lfnstLevelMakeJobs   the LFNST table of the intra level entry, beside intra_chain_rules.hpp's (whose expansion loop
+//                       fills the plain jobs here too); the quantiser check is chain_rules.hpp's
 // PU::getWideAngle is NOT IntraPrediction::getModifiedWideAngle (intraWideAngle): a tall block's modes next to 66 go down by 67 there, by 65 here, so that 0 and 1
 // stay planar and DC.  lfnstWideAngle takes intraWideAngle and corrects the tall case.
 #pragma once
@@ -78,7 +79,7 @@ LFNST_HD bool lfnstChainJobOk( const vtmhip_lfnst_chain_job &j )
 {
   for( int i = 0; i < 7; i++ )
     if( j.pad[i] ) return false;
-  return lfnstSideOk( j.width ) && lfnstSideOk( j.height ) && j.resiStride >= j.width && j.bitDepth >= 8 && j.bitDepth <= 12 && j.qpRem >= 0 && j.qpRem <= 5 && j.qpPer >= 0 &&
+  return lfnstSideOk( j.width ) && lfnstSideOk( j.height ) && j.resiStride >= j.width && j.bitDepth >= 8 && j.bitDepth <= 12 && chainQpOk( j.qpPer, j.qpRem ) &&
          j.setIdx <= 3 && j.index <= 1 && j.transpose <= 1;
 }
 
@@ -119,7 +120,7 @@ inline bool lfnstChainScan( const vtmhip_lfnst_chain_job *jobs, int n, LfnstPlan
 // ---- the LFNST table of the intra level entry ------------------------------------------------------------------------------------------------------------------
 LFNST_HD bool lfnstTuOk( const vtmhip_intra_lfnst_tu_job &t, int w, int h, bool isMip )
 {
-  return t.lfnstIdx >= 1 && t.lfnstIdx <= 2 && t.qpRem >= 0 && t.qpRem <= 5 && t.qpPer >= 0 && t.reserved[0] == 0 && t.reserved[1] == 0 && t.pad == 0 && lfnstShapeOk( w, h, isMip );
+  return t.lfnstIdx >= 1 && t.lfnstIdx <= 2 && chainQpOk( t.qpPer, t.qpRem ) && t.reserved[0] == 0 && t.reserved[1] == 0 && t.pad == 0 && lfnstShapeOk( w, h, isMip );
 }
 
 // mode: the regular mode of the prediction (ignored for MIP)
@@ -173,13 +174,7 @@ inline bool lfnstLevelMakeJobs( const vtmhip_intra_block *blocks, int numBlocks,
 {
   if( !intraChainScan( blocks, numBlocks, intraJobs, nIntra, mipJobs, nMip, tuJobs, nTu, plan ) ) return false;
   if( !lfnstLevelScan( blocks, intraJobs, nIntra, mipJobs, nMip, lfnstJobs, nLfnst, lplan ) ) return false;
-  for( int i = 0; i < nTu; i++ )
-  {
-    int     blk;
-    int64_t predOff;
-    intraChainPred( intraJobs, nIntra, mipJobs, tuJobs[i].pred, blk, predOff );
-    intraChainExpand( tuJobs[i], blocks[blk], predOff, outTu[i] );
-  }
+  intraChainExpandAll( blocks, intraJobs, nIntra, mipJobs, tuJobs, nTu, outTu );
   for( int i = 0; i < nLfnst; i++ )
   {
     int blk;

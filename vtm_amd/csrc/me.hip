@@ -11,6 +11,7 @@
 // The sequential dependence that remains is round -> round, which is why a job owns a wave and a launch carries
 // thousands of jobs (all PUs x reference pictures of a picture).
 #include "ctx.hpp"
+#include "stage.hpp"
 #include "mest_glue.hpp"
 #include "mv_rules.hpp"
 #include "pel_pack.hpp"
@@ -2473,19 +2474,18 @@ int vtmhip_internal_tz_search( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, co
     // (every value of rasterParts, the hint's 4 and the 64 MB bound below: tests/test_gpu_tz_batch_sizes.py, raster_parts)
     rasterParts = ( splitScan && n <= 640 ) ? ( 1280 / n < 8 ? 1280 / n : 8 ) : 1;
     if( totCap > RASTER_TOT_CAP && splitScan && n <= 4096 && rasterParts < 4 ) rasterParts = 4;      // big scans (one workgroup per CU by LDS): a few workgroups per scan balance the tail   // aim at the 1280 resident workgroups (5 per CU); twice that measured slower
-    const size_t oList = ( ( size_t ) n * sizeof( TzSaved ) + 255 ) & ~( size_t ) 255;
-    const size_t oTot  = ( oList + ( ( size_t ) n + 1 ) * sizeof( int ) + 255 ) & ~( size_t ) 255;
     // global totals of the split scans (rasterParts > 1): n x (totCap + 1) words, zeroed per call -- bounded to 64 MB (big scans of many jobs keep one workgroup per scan)
     if( rasterParts > 1 && ( size_t ) n * ( totCap + 1 ) * sizeof( unsigned ) > ( ( size_t ) 64 << 20 ) ) rasterParts = 1;
     const size_t totBytes = rasterParts > 1 ? ( size_t ) n * ( totCap + 1 ) * sizeof( unsigned ) : 0;
-    void        *arena = nullptr;
-    int          st    = vtmhip_internal_workspace( ctx, oTot + totBytes, &arena, 1 );
+    WorkPlan     wp;   // the list and the totals are consecutive regions: one fill covers both
+    const size_t oSaved = wp.region<TzSaved>( n ), oList = wp.region<int>( ( size_t ) n + 1 ), oTot = wp.region<char>( totBytes );
+    int          st     = wp.reserve( ctx, VTMHIP_WORK_NESTED );
     if( st ) return st;
-    d_saved = ( TzSaved * ) arena;
-    d_list  = ( int * ) ( ( char * ) arena + oList );
-    d_tot   = ( unsigned * ) ( ( char * ) arena + oTot );
+    d_saved = wp.at<TzSaved>( oSaved );
+    d_list  = wp.at<int>( oList );
+    d_tot   = wp.at<unsigned>( oTot );
     // the list counter and (split scans) the global totals in ONE fill: they sit next to each other in the arena (a fill is a launch on the dependent chain of the call)
-    if( totBytes ) VTMHIP_HIP( ctx, hipMemsetAsync( d_list, 0, ( size_t ) ( ( char * ) d_tot - ( char * ) d_list ) + totBytes, ctx->stream ) );
+    if( totBytes ) VTMHIP_HIP( ctx, hipMemsetAsync( d_list, 0, oTot - oList + totBytes, ctx->stream ) );
     else VTMHIP_HIP( ctx, hipMemsetAsync( d_list, 0, sizeof( int ), ctx->stream ) );
   }
 #define VTMHIP_TZ_LAUNCH_K( W, KK, GRID, MODE ) \

@@ -10,7 +10,9 @@
 //   mid       fractional job (cu.imv 0 / HPEL) or the 9 x numCand SATD jobs of the AMVR refinement (cu.imv 1 / 2)
 //   frac / [dist]
 //   final     rate re-weighting (:3478-3484) or the AMVR selection loop (:4208-4262), fp64 exactly as the reference
+// The job tables between the stages lie in a WorkPlan (stage.hpp) in the stream's slot VTMHIP_WORK_CALL.
 #include "ctx.hpp"
+#include "stage.hpp"
 #include "mest_glue.hpp"
 #include "mv_rules.hpp"
 #include "dist_block.hpp"
@@ -303,8 +305,6 @@ __global__ __launch_bounds__( 576 ) void mest_amvr_kernel( vtmhip_pic_params pic
   out[i] = o;
 }
 
-size_t align_up( size_t v ) { return ( v + 255 ) & ~( size_t ) 255; }
-
 struct MestClassOf
 {
   __device__ int operator()( const vtmhip_me_job &j ) const { return shape_class( j.width, j.height ); }
@@ -376,23 +376,22 @@ int mest_run( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const vtmhip_me_cfg
   wk.direct   = allUni || ( allBi && cfg->biPatternGiven );
   wk.needDist = !( fracOnly && ( allUni || noStart ) );
   wk.hasTz = !allBi; wk.hasFull = !allUni;
-  size_t off = 0;
-  const size_t slotSamples = ( size_t ) maxWidth * maxHeight;
-  const size_t oPattern = off; off = align_up( off + ( wk.direct ? 0 : ( size_t ) n * slotSamples * sizeof( int16_t ) ) );
-  const size_t oTz      = off; off = align_up( off + ( allBi ? 0 : ( size_t ) n * sizeof( vtmhip_tz_job ) ) );
-  const size_t oFull    = off; off = align_up( off + ( allUni ? 0 : ( size_t ) n * sizeof( vtmhip_full_job ) ) );
-  const size_t oIres    = off; off = align_up( off + ( size_t ) n * sizeof( vtmhip_me_result ) );
-  const size_t oFrac    = off; off = align_up( off + ( size_t ) n * sizeof( vtmhip_frac_job ) );
-  const size_t oFres    = off; off = align_up( off + ( size_t ) n * sizeof( vtmhip_frac_result ) );
-  const size_t oDist    = off; off = align_up( off + ( wk.needDist ? ( size_t ) n * REFINE_SLOTS * sizeof( vtmhip_dist_job ) : 0 ) );
-  const size_t oDout    = off; off = align_up( off + ( wk.needDist ? ( size_t ) n * REFINE_SLOTS * sizeof( unsigned long long ) : 0 ) );
-  void *arena = nullptr;
-  int st = vtmhip_internal_workspace( ctx, off + 256, &arena );
+  WorkPlan     wp;
+  const size_t slotSamples = ( size_t ) maxWidth * maxHeight, nDist = wk.needDist ? ( size_t ) n * REFINE_SLOTS : 0;
+  const size_t oPattern = wp.region<int16_t>( wk.direct ? 0 : n * slotSamples );
+  const size_t oTz      = wp.region<vtmhip_tz_job>( allBi ? 0 : n );
+  const size_t oFull    = wp.region<vtmhip_full_job>( allUni ? 0 : n );
+  const size_t oIres    = wp.region<vtmhip_me_result>( n );
+  const size_t oFrac    = wp.region<vtmhip_frac_job>( n );
+  const size_t oFres    = wp.region<vtmhip_frac_result>( n );
+  const size_t oDist    = wp.region<vtmhip_dist_job>( nDist );
+  const size_t oDout    = wp.region<unsigned long long>( nDist );
+  wp.region<char>( 256 );   // slack behind the last table
+  int st = wp.reserve( ctx, VTMHIP_WORK_CALL );
   if( st ) return st;
-  char *base = ( char * ) arena;
-  wk.pattern = ( int16_t * ) ( base + oPattern ); wk.tz = ( vtmhip_tz_job * ) ( base + oTz ); wk.full = ( vtmhip_full_job * ) ( base + oFull );
-  wk.ires = ( vtmhip_me_result * ) ( base + oIres ); wk.frac = ( vtmhip_frac_job * ) ( base + oFrac ); wk.fres = ( vtmhip_frac_result * ) ( base + oFres );
-  wk.dist = ( vtmhip_dist_job * ) ( base + oDist ); wk.dout = ( unsigned long long * ) ( base + oDout ); wk.slotSamples = ( long ) slotSamples;
+  wk.pattern = wp.at<int16_t>( oPattern ); wk.tz = wp.at<vtmhip_tz_job>( oTz ); wk.full = wp.at<vtmhip_full_job>( oFull );
+  wk.ires = wp.at<vtmhip_me_result>( oIres ); wk.frac = wp.at<vtmhip_frac_job>( oFrac ); wk.fres = wp.at<vtmhip_frac_result>( oFres );
+  wk.dist = wp.at<vtmhip_dist_job>( oDist ); wk.dout = wp.at<unsigned long long>( oDout ); wk.slotSamples = ( long ) slotSamples;
 
   const dim3 perJob( ( n + 255 ) / 256 ), tpb( 256 );
   const int  big = maxWidth > maxHeight ? maxWidth : maxHeight;

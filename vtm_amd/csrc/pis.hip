@@ -4,7 +4,9 @@
 //   uni / bi decision :2846-2893                                   (vtmhip_pis_stage)
 // Heavy work stays in the library's kernels (motion_comp_kernel, dist_uniform_kernel, the searches behind vtmhip_xMotionEstimation_batch_dev);
 // here one thread per row / PU turns one stage's results into the next stage's job records, fp64 exactly where the reference uses it.
+// The AMVP SADs lie in a WorkPlan (stage.hpp): the stand-alone entry's in the calls' slot, the picture loop's in VTMHIP_WORK_BUCKET (ctx.hpp says why).
 #include "ctx.hpp"
+#include "stage.hpp"
 #include "mv_rules.hpp"
 
 namespace
@@ -440,8 +442,6 @@ __global__ __launch_bounds__( 256 ) void merge_dist_jobs_kernel( const vtmhip_pr
   out[i] = d;
 }
 
-size_t align_up( size_t v ) { return ( v + 255 ) & ~( size_t ) 255; }
-
 }   // namespace
 
 extern "C"
@@ -453,13 +453,11 @@ int vtmhip_xEstimateMvPredAMVP_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_para
   VTMHIP_BATCH_ENTRY( ctx, n, pic && d_orgBase && d_refBase && d_jobs );
   VTMHIP_REQUIRE( ctx, maxWidth >= 4 && maxWidth <= 128 && maxHeight >= 4 && maxHeight <= 128, "maxWidth / maxHeight" );
   AmvpWork     wk;
-  size_t       off = 0;
-  const size_t oDout = off; off = align_up( off + 2 * ( size_t ) n * sizeof( unsigned long long ) );
-  void *arena = nullptr;
-  int   st    = vtmhip_internal_workspace( ctx, off, &arena );
+  WorkPlan     wp;
+  const size_t oDout = wp.region<unsigned long long>( 2 * ( size_t ) n );
+  int          st    = wp.reserve( ctx, VTMHIP_WORK_CALL );
   if( st ) return st;
-  char *base = ( char * ) arena;
-  wk.dout = ( unsigned long long * ) ( base + oDout );
+  wk.dout = wp.at<unsigned long long>( oDout );
   // xGetTemplateCost (:3162-3183): the candidate's prediction and its SAD against the original in ONE pass (no prediction buffer, no distortion jobs, and no
   // prediction-job table either: the kernel derives job 2 * row + c from the ME row)
   ( void ) uniformSize;
@@ -472,17 +470,18 @@ int vtmhip_xEstimateMvPredAMVP_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_para
 
 }   // extern "C"
 
-// the first half of vtmhip_xEstimateMvPredAMVP_batch_dev: the template SADs of the rows' AMVP candidates ([2 * row + c]) into a workspace of the context's stream (slot 2: it must
-// outlive the start of the fused integer search, whose prologue makes the selection -- mest.hip: vtmhip_internal_mest_with_amvp)
+// the first half of vtmhip_xEstimateMvPredAMVP_batch_dev: the template SADs of the rows' AMVP candidates ([2 * row + c]) into a workspace of the context's stream (not the
+// calls' own slot: it must outlive the start of the fused integer search, whose prologue makes the selection -- mest.hip: vtmhip_internal_mest_with_amvp)
 int vtmhip_internal_amvp_sads( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, const vtmhip_me_job *d_jobs, int n,
                                int maxWidth, int maxHeight, unsigned long long **d_dout )
 {
   VTMHIP_CHECK_CTX( ctx );
   VTMHIP_REQUIRE( ctx, n > 0 && pic && d_orgBase && d_refBase && d_jobs && d_dout, "amvp sads: arguments" );
-  void *arena = nullptr;
-  int   st    = vtmhip_internal_workspace( ctx, align_up( 2 * ( size_t ) n * sizeof( unsigned long long ) ), &arena, 2 );
+  WorkPlan     wp;
+  const size_t oDout = wp.region<unsigned long long>( 2 * ( size_t ) n );
+  int          st    = wp.reserve( ctx, VTMHIP_WORK_BUCKET );
   if( st ) return st;
-  *d_dout = ( unsigned long long * ) arena;
+  *d_dout = wp.at<unsigned long long>( oDout );
   return vtmhip_internal_mc_amvp_launch( ctx, pic, d_orgBase, d_refBase, d_jobs, n, maxWidth, maxHeight, *d_dout );
 }
 

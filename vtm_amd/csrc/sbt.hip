@@ -11,7 +11,10 @@
 //
 // sbt_finish_kernel: a wave per (candidate, component).  The chain has left the compact sub-TU reconstruction at the head of the CU-shaped block; the wave
 // stages it in LDS, then writes the whole block (coded tile from LDS, zero elsewhere) and sums the uncoded tile's residual on the way.
+//
+// The chain entry reads its job table back through HostStage and lays its workspace out with a WorkPlan in the slot VTMHIP_WORK_SBT (stage.hpp).
 #include "ctx.hpp"
+#include "stage.hpp"
 #include "sbt_rules.hpp"
 #include "pel_pack.hpp"
 
@@ -241,8 +244,6 @@ int sbt_scan_jobs( const vtmhip_sbt_job *jobs, int n, int &numTu, int &maxW, int
   return VTMHIP_OK;
 }
 
-size_t align256( size_t v ) { return ( v + 255 ) & ~( size_t ) 255; }
-
 }   // namespace
 
 extern "C"
@@ -303,22 +304,20 @@ int vtmhip_sbt_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_resiBase, cons
 {
   VTMHIP_BATCH_ENTRY( ctx, n, d_resiBase && d_jobs && d_results );
   // the job table decides the launches (sub-TU count, largest sides) and is checked before anything runs
-  const size_t bytes = ( size_t ) n * sizeof( vtmhip_sbt_job );
-  VTMHIP_TRY( vtmhip_internal_scratch( ctx, bytes ) );
-  VTMHIP_HIP( ctx, hipMemcpyAsync( ctx->pinned, d_jobs, bytes, hipMemcpyDeviceToHost, ctx->stream ) );
-  VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
+  HostStage             hs( ctx );
+  const vtmhip_sbt_job *jobs = nullptr;
+  VTMHIP_TRY( hs.pull_table( d_jobs, n, jobs ) );
   int numTu, maxW, maxH;
-  VTMHIP_REQUIRE( ctx, sbt_scan_jobs( ( const vtmhip_sbt_job * ) ctx->pinned, n, numTu, maxW, maxH ) == VTMHIP_OK,
+  VTMHIP_REQUIRE( ctx, sbt_scan_jobs( jobs, n, numTu, maxW, maxH ) == VTMHIP_OK,
                   "sbt job: sides 4..64 (powers of two), a mode the size allows, sbtPos 0..1, bitDepth 8..12, qpRem 0..5, qpPer >= 0, luma offset >= 0" );
 
-  // workspace (slot 3: the chain's bucketing takes slot 2): the slot cursor, tuIdx[3 n], the expanded jobs, their results
-  const size_t oIdx = 256, oJobs = align256( oIdx + ( size_t ) 3 * n * sizeof( int ) ), oRes = align256( oJobs + ( size_t ) numTu * sizeof( vtmhip_tu_job ) );
-  void *arena = nullptr;
-  VTMHIP_TRY( vtmhip_internal_workspace( ctx, oRes + ( size_t ) numTu * sizeof( vtmhip_tu_result ), &arena, 3 ) );
-  char *base = ( char * ) arena;
-  int  *d_cursor = ( int * ) base, *d_tuIdx = ( int * ) ( base + oIdx );
-  vtmhip_tu_job    *d_tuJobs = ( vtmhip_tu_job * ) ( base + oJobs );
-  vtmhip_tu_result *d_tuRes  = ( vtmhip_tu_result * ) ( base + oRes );
+  // workspace: the slot cursor, tuIdx[3 n], the expanded jobs, their results
+  WorkPlan     wp;
+  const size_t oCursor = wp.region<int>( 1 ), oIdx = wp.region<int>( ( size_t ) 3 * n ), oJobs = wp.region<vtmhip_tu_job>( numTu ), oRes = wp.region<vtmhip_tu_result>( numTu );
+  VTMHIP_TRY( wp.reserve( ctx, VTMHIP_WORK_SBT ) );
+  int              *d_cursor = wp.at<int>( oCursor ), *d_tuIdx = wp.at<int>( oIdx );
+  vtmhip_tu_job    *d_tuJobs = wp.at<vtmhip_tu_job>( oJobs );
+  vtmhip_tu_result *d_tuRes  = wp.at<vtmhip_tu_result>( oRes );
   VTMHIP_HIP( ctx, hipMemsetAsync( d_cursor, 0, sizeof( int ), ctx->stream ) );
   hipLaunchKernelGGL( sbt_expand_kernel, dim3( ( n + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, d_jobs, n, d_cursor, d_tuJobs, d_tuIdx );
   VTMHIP_LAUNCHED( ctx );

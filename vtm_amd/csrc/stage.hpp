@@ -1,16 +1,19 @@
 // stage.hpp -- staging of the pointer-surface (host pointer) entries: every such entry copies its blocks compactly into the context's pinned staging area, uploads
 // them with its job, launches a batch of one, downloads the result and copies it back to the caller's stride.  The layout of the staging area is planned by
 // StagePlan (no HIP: host/test_stage.cpp runs it under sanitizers); HostStage binds a plan to the context's staging area and moves regions of it.
+// The same planner at 256 bytes lays out the device workspaces of the multi-stage calls: WorkPlan binds such a plan to an arena of the context's stream.  The
+// level entries read their device tables back through HostStage::pull.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
 
 // ---- the HIP-free part -------------------------------------------------------------------------------------------
-struct StagePlan
+template<size_t A>
+struct RegionPlan
 {
-  static constexpr size_t ALIGN = 64;
-  size_t total = 0;   // bytes planned so far (a multiple of ALIGN): the size the staging area must have
+  static constexpr size_t ALIGN = A;
+  size_t total = 0;   // bytes planned so far (a multiple of ALIGN): the size the planned area must have
   // the next region: `bytes` long, ALIGN-aligned, behind every region handed out before (so no two overlap)
   size_t region( size_t bytes )
   {
@@ -20,6 +23,8 @@ struct StagePlan
   }
   bool inside( size_t off, size_t bytes ) const { return off <= total && bytes <= total - off; }
 };
+using StagePlan = RegionPlan<64>;     // the staging area of the host-pointer entries
+using WorkRegions = RegionPlan<256>;  // a device workspace: an empty region takes no room, so it shares its offset with the region behind it and with nothing before it
 
 // a w x h block of T with a row stride (in elements) <-> compact rows (stride = w)
 template<class T>
@@ -85,12 +90,49 @@ struct HostStage : StagePlan
     VTMHIP_HIP( ctx, hipMemcpyAsync( hp + off, dp + off, bytes, hipMemcpyDeviceToHost, ctx->stream ) );
     return VTMHIP_OK;
   }
-  // the last download of a call: the host copy is valid when this returns
-  int fetch( size_t off, size_t bytes ) const
+  // a device table that is not the staging area's own mirror, device -> its planned region of the host side (an empty table: nothing)
+  int pull( size_t off, const void *d_src, size_t bytes ) const
   {
-    VTMHIP_TRY( download( off, bytes ) );
+    if( !bytes ) return VTMHIP_OK;
+    VTMHIP_REQUIRE( ctx, inside( off, bytes ), "staging: pull outside the planned regions" );
+    VTMHIP_HIP( ctx, hipMemcpyAsync( hp + off, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream ) );
+    return VTMHIP_OK;
+  }
+  // behind the last download / pull of a call: the host copies are valid when this returns
+  int sync() const
+  {
     VTMHIP_HIP( ctx, hipStreamSynchronize( ctx->stream ) );
     return VTMHIP_OK;
   }
+  int fetch( size_t off, size_t bytes ) const
+  {
+    VTMHIP_TRY( download( off, bytes ) );
+    return sync();
+  }
+  // the whole read-back of a call with one job table: planned, pulled and valid on return
+  template<class T> int pull_table( const T *d_src, int n, const T *&table )
+  {
+    const size_t off = region( ( size_t ) n * sizeof( T ) );
+    VTMHIP_TRY( reserve() );
+    VTMHIP_TRY( pull( off, d_src, ( size_t ) n * sizeof( T ) ) );
+    table = host<T>( off );
+    return sync();
+  }
+};
+
+// The device workspace of a multi-stage call: regions planned at 256 bytes, bound to the arena `slot` of the context's stream by one reserve().  A layout's
+// fixed head or tail (a cursor, a few small tables, slack behind the last table) is a region like the others.
+struct WorkPlan : WorkRegions
+{
+  char *base = nullptr;   // valid after reserve()
+  template<class T> size_t region( size_t count ) { return WorkRegions::region( count * sizeof( T ) ); }
+  int reserve( vtmhip_ctx *ctx, vtmhip_work_slot slot )
+  {
+    void *arena = nullptr;
+    VTMHIP_TRY( vtmhip_internal_workspace( ctx, total, &arena, slot ) );
+    base = ( char * ) arena;
+    return VTMHIP_OK;
+  }
+  template<class T> T *at( size_t off ) const { return ( T * ) ( base + off ); }
 };
 #endif
