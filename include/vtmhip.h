@@ -1433,8 +1433,8 @@ int vtmhip_sbt_struct_size( int which );   /* sizeof() of 0 vtmhip_sbt_est_job, 
  *   planar, DC        xPredIntraPlanar :294-348, xGetPredValDc :153-182, their PDPC :244-265
  *   angular           xPredIntraAng :459-643: pure horizontal / vertical with the clipped PDPC, the extension of the main reference through invAngle for negative
  *                     angles, the replication of its last sample for positive ones, the cubic (H.266 table 28) or smoothing taps on fractional slopes, the PDPC column
- * ISP, BDPCM, IntraSmoothingDisabled, the availability analysis that fills the reference samples (xFillReferenceSamples), the mode bits and the
- * candidate lists stay the caller's.  Chroma and MIP have entries of their own below (vtmhip_intra_chroma_*, vtmhip_mip_*). */
+ * BDPCM, IntraSmoothingDisabled, the availability analysis that fills the reference samples (xFillReferenceSamples), the mode bits and the
+ * candidate lists stay the caller's.  Chroma, MIP and ISP have entries of their own below (vtmhip_intra_chroma_*, vtmhip_mip_*, vtmhip_isp_*). */
 typedef struct
 {
   int32_t predMode;            /* the mode after the wide-angle shift: -14 .. 80 (what the angle is taken from) */
@@ -1614,7 +1614,7 @@ int vtmhip_mip_struct_size( int which );   /* sizeof() of 0 vtmhip_mip_job; -1 o
  * there, over one vtmhip_intra_block table (orgOff / orgStride are used here); the chain is the fused chain of vtmhip_tu_chain_batch_dev.  The only upload of a
  * level is its reference lines and the tables; nothing goes through the host between the steps.
  * The lfnstIdx 1 / 2 candidates of a level go through vtmhip_intra_chain_lfnst_batch_dev below.
- * NOT covered, the caller's or a later change: ISP and BDPCM; DF_SSE_WTD / LMCS (the caller hands
+ * NOT covered, the caller's or a later change: BDPCM (ISP has an entry of its own, vtmhip_isp_chain_batch_dev below; LFNST with ISP has none); DF_SSE_WTD / LMCS (the caller hands
  * the original in the domain it codes in); RDOQ / dependent quantisation (the chain is Quant::quant, as everywhere in this library); the CABAC bit estimate, the
  * RD decision and the candidate lists; the encoder hook.  The chroma and JCCR intra chains have an entry of their own below (vtmhip_intra_chroma_chain_batch_dev). */
 typedef struct
@@ -1802,6 +1802,77 @@ int vtmhip_intra_chroma_chain_make_jobs( const vtmhip_intra_chroma_block *blocks
                                          vtmhip_tu_job *outTu, vtmhip_jccr_job *outJoint, int *maxWidth, int *maxHeight, int *uniformTu, int *uniformJoint, int *crs );
 
 int vtmhip_intra_chroma_chain_struct_size( int which );   /* sizeof() of 0 vtmhip_intra_chroma_tu_job, 1 vtmhip_intra_chroma_joint_job, 2 vtmhip_intra_chroma_joint_result; -1 otherwise */
+
+/* ---- intra sub-partitions (ISP), luma: one (CU, intra mode, split direction) candidate per job, every sub-partition of it in one kernel -- per sub-partition the
+ * steps of IntraSearch::xIntraCodingTUBlock with cu.ispMode set (EncoderLib/IntraSearch.cpp:2989-3320): the prediction of its region from the reconstruction of the
+ * one before (initIntraPatternChTypeISP, CommonLib/IntraPrediction.cpp:802-918), residual, xT -> Quant::quant -> Quant::dequant -> xIT with the ISP transform pair
+ * (DST7 on a side of 4 .. 16, else DCT2; TrQuant.cpp:713-724) on TUs down to 1 x N and N x 1, the clipped reconstruction and its SSE.  Nothing of a candidate touches
+ * global memory between the load of its lines and original and the final stores.  The rules have one definition for host and device, vtm_amd/csrc/isp_rules.hpp.
+ * Scope: lfnstIdx 0, multiRefIdx 0, the regular modes 0 .. 66 (the reference forbids MIP and MRL with ISP, IntraSearch.cpp:1049-1050), every CU shape CU::canUseISP
+ * admits with MaxTbSize 64 (sides 4 .. 64 without 4x4), 8 .. 12 bits, Quant::quant with the flat list.
+ * Stays the caller's: the early exits of xIntraCodingLumaISP (IntraSearch.cpp:3516-3553; they need bits, so the device always codes every sub-partition); the bit
+ * estimate; the "at least one non-zero CBF" rule (:3173; absSum is reported per sub-partition); the candidate list (xSortISPCandList / xGetNextISPMode); LFNST with
+ * ISP; the availability analysis that fills the CU's first lines. */
+typedef struct
+{
+  int32_t numParts, partW, partH;    /* the sub-partitions (TUs): 2 for 4x8 / 8x4, else 4 */
+  int32_t numRegions, regW, regH;    /* the prediction regions: the TUs, except 4 wide under a vertical split of a CU of width 4, or of width 8 and height > 4 */
+  int32_t typeHor, typeVer;          /* the transform pair of a TU (VTMHIP_DCT2 / VTMHIP_DST7; a side of 1 is not transformed) */
+} vtmhip_isp_geom;
+
+typedef struct
+{
+  int64_t predOff;      /* the assembled W x H prediction (stride W) inside d_predBase */
+  int64_t outOff;       /* the W x H reconstruction (stride W) inside d_recoBase; the levels of sub-partition k, one contiguous partW x partH block, at
+                           outOff + k * partW * partH inside d_levelsBase */
+  int32_t block;        /* index into d_blocks (a vtmhip_intra_block with multiRefIdx 0; its lines: 2W + 1 and 2H + 1 samples) */
+  int16_t qpPer, qpRem; /* as vtmhip_tu_job */
+  uint8_t mode;         /* 0 planar, 1 DC, 2 .. 66 */
+  uint8_t split;        /* 1 horizontal (rows), 2 vertical (columns): ISPType */
+  uint8_t sideAvail;    /* the left (horizontal split) or above (vertical split) neighbour of the CU exists: the branch of the line update (IntraPrediction.cpp:849, 880) */
+  uint8_t isIRAP;
+  uint8_t reserved[4];  /* 0 */
+} vtmhip_isp_job;
+
+typedef struct
+{
+  uint64_t sse[4];      /* per sub-partition: DF_SSE of the original against the clipped reconstruction */
+  int32_t  absSum[4];   /* as vtmhip_tu_result, per sub-partition (cbf = absSum > 0) */
+  int32_t  sumAbs[4];
+  int32_t  numParts;    /* entries past numParts are 0 */
+  int32_t  reserved;    /* 0 */
+} vtmhip_isp_result;
+
+/* n ISP candidates over the block table of vtmhip_intra_pred_batch_dev (orgOff / orgStride are used).  Job k writes its W x H reconstruction at d_recoBase + outOff,
+ * its levels at d_levelsBase + outOff (d_levelsBase may be NULL), its assembled prediction at d_predBase + predOff (d_predBase may be NULL) and d_results[k].  A job
+ * gets 16 / 64 / 256 lanes by the largest CU the jobs name (vtmhip_intra_lanes_per_job), 256 also where four jobs would not fit the workgroup's LDS (a 64-point
+ * transform among the jobs).  Both tables are read back and checked before anything runs (one stream synchronisation; never under stream capture): a shape
+ * canUseISP refuses, a bitDepth outside 8 .. 12, multiRefIdx != 0, a mode above 66, split outside 1 .. 2, sideAvail / isIRAP above 1, qpRem outside 0 .. 5,
+ * qpPer < 0, a non-zero reserved field or a block index outside the table reject the whole call with VTMHIP_E_INVALID and nothing written; so do NULL d_refBase /
+ * d_orgBase / d_blocks / d_jobs / d_recoBase / d_results with n > 0, n < 0 and numBlocks < 0.  n == 0 is VTMHIP_OK. */
+int vtmhip_isp_chain_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_orgBase, const vtmhip_intra_block *d_blocks, int numBlocks,
+                                const vtmhip_isp_job *d_jobs, int n, int16_t *d_predBase, int32_t *d_levelsBase, int16_t *d_recoBase, vtmhip_isp_result *d_results );
+
+/* The same rules on the host, no context (VTMHIP_E_INVALID for anything outside the scope above).
+ * vtmhip_isp_geometry: CU::getISPSplitDim and the prediction regions of a width x height CU under `split`.
+ * vtmhip_isp_pred_params: m_ipaParam of a regW x regH prediction region of a cuW x cuH CU -- the wide-angle shift from the CU, PDPC and angularScale from the region,
+ * no filter of either kind.
+ * vtmhip_isp_tr_types: the transform pair of a partW x partH TU.
+ * vtmhip_isp_pred_region_host: predIntraAng of one region from given lines, top[0 .. cuW + regW] and left[0 .. cuH + regH]; pred: regW x regH, stride regW.
+ * vtmhip_isp_next_lines_host: the lines region `region` >= 1 sees, from the CU's lines (2W + 1 and 2H + 1 samples) and a reconstruction (W x H, stride W) of which
+ * the row above / the column left of the region is read: topOut[0 .. cuW + regW], leftOut[0 .. cuH + regH].
+ * vtmhip_isp_chain_host: vtmhip_isp_chain_batch_dev as host arithmetic over host tables, same checks, same outputs (predBase and levelsBase may be NULL). */
+int vtmhip_isp_geometry( int width, int height, int split, vtmhip_isp_geom *out );
+int vtmhip_isp_pred_params( int cuW, int cuH, int regW, int regH, int mode, vtmhip_intra_params *out );
+int vtmhip_isp_tr_types( int partW, int partH, int *typeHor, int *typeVer );
+int vtmhip_isp_pred_region_host( int cuW, int cuH, int regW, int regH, int mode, int bitDepth, const int16_t *top, const int16_t *left, int16_t *pred );
+int vtmhip_isp_next_lines_host( int cuW, int cuH, int split, int region, int sideAvail, const int16_t *top, const int16_t *left, const int16_t *reco, int16_t *topOut,
+                                int16_t *leftOut );
+int vtmhip_isp_chain_host( const int16_t *refBase, const int16_t *orgBase, const vtmhip_intra_block *blocks, int numBlocks, const vtmhip_isp_job *jobs, int n,
+                           int16_t *predBase, int32_t *levelsBase, int16_t *recoBase, vtmhip_isp_result *results );
+/* the lanes a job of these (host) tables gets, after the same checks: 16, 64 or 256 */
+int vtmhip_isp_chain_lanes_host( const vtmhip_intra_block *blocks, int numBlocks, const vtmhip_isp_job *jobs, int n, int *lanes );
+int vtmhip_isp_struct_size( int which );   /* sizeof() of 0 vtmhip_isp_job, 1 vtmhip_isp_result, 2 vtmhip_isp_geom; -1 otherwise */
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
-// intra_rules.hpp -- the intra prediction rules of the reference for the regular modes (no ISP, MIP or BDPCM; luma, and chroma through the `chroma` argument), defined once for host and device: plain integer functions without a HIP
-// dependency, so host/test_intra.cpp compiles them with g++ and the kernels of intra.hip use the same text.
+// intra_rules.hpp -- the intra prediction rules of the reference for the regular modes (no MIP or BDPCM; luma, and chroma through the `chroma` argument), defined once for host and device: plain integer functions without a HIP
+// dependency, so host/test_intra.cpp compiles them with g++ and the kernels of intra.hip use the same text.  ISP builds on them in isp_rules.hpp: the parameters take
+// the CU size beside the prediction region's, and the sample rules are templates over the block so that a block with line ends of its own (IspBlk) reads through them.
 //   intraWideAngle          IntraPrediction::getModifiedWideAngle                              CommonLib/IntraPrediction.cpp:184-204
 //   intraPredParams         IntraPrediction::initPredIntraParams, m_aucIntraFilter             :356-444, :58-68
 //   intraFilteredSample     IntraPrediction::xFilterReferenceSamples, one sample of a line     :1166-1200
@@ -50,13 +51,15 @@ INTRA_HD int intraWideAngle( int w, int h, int mode )
 }
 
 // chroma: a chroma block (m = 0) -- no filter of either kind (:409); everything else, wide angles and PDPC included, from the block's own width and height
-INTRA_HD void intraPredParams( int w, int h, int mode, int m, vtmhip_intra_params &p, bool chroma = false )
+// cuW, cuH != 0: w x h is a prediction region of an ISP CU of cuW x cuH (useISP, :361-367, :410) -- the wide-angle shift from the CU, PDPC and angularScale from the
+// region, no filter of either kind
+INTRA_HD void intraPredParams( int w, int h, int mode, int m, vtmhip_intra_params &p, bool chroma = false, int cuW = 0, int cuH = 0 )
 {
   const int angTable[32]    = { 0, 1, 2, 3, 4, 6, 8, 10, 12, 14, 16, 18, 20, 23, 26, 29, 32, 35, 39, 45, 51, 57, 64, 73, 86, 102, 128, 171, 256, 341, 512, 1024 };
   const int invAngTable[32] = { 0,   16384, 8192, 5461, 4096, 2731, 2048, 1638, 1365, 1170, 1024, 910, 819, 712, 630, 565,
                                 512, 468,   420,  364,  321,  287,  256,  224,  191,  161,  128,  96,  64,  48,  32,  16 };   // (512 * 32) / angle
   const int mdisThreshold[8] = { 24, 24, 24, 14, 2, 0, 0, 0 };   // by ( log2 W + log2 H ) >> 1
-  const int predMode = intraWideAngle( w, h, mode );
+  const int predMode = cuW ? intraWideAngle( cuW, cuH, mode ) : intraWideAngle( w, h, mode );
   const int angMode  = predMode >= INTRA_DIA ? predMode - INTRA_VER : -( predMode - INTRA_HOR );
   p.predMode          = predMode;
   p.isModeVer         = predMode >= INTRA_DIA;
@@ -81,7 +84,7 @@ INTRA_HD void intraPredParams( int w, int h, int mode, int m, vtmhip_intra_param
       if( p.angularScale < 0 ) p.applyPDPC = 0;
     }
   }
-  if( m != 0 || mode == INTRA_DC || chroma ) return;
+  if( m != 0 || mode == INTRA_DC || chroma || cuW ) return;
   if( mode == INTRA_PLANAR ) { p.refFilterFlag = w * h > 32; return; }
   const int diff = intraMin( intraAbs( predMode - INTRA_HOR ), intraAbs( predMode - INTRA_VER ) );
   if( diff > mdisThreshold[( intraLog2( w ) + intraLog2( h ) ) >> 1] )
@@ -116,10 +119,13 @@ struct IntraBlk
   const int16_t *top, *left;
   int w, h, log2W, log2H, m, maxVal;
 };
-INTRA_HD int intraTop( const IntraBlk &b, int i ) { return intraAt( b.top, i, 2 * b.w + b.m ); }
-INTRA_HD int intraLeft( const IntraBlk &b, int i ) { return intraAt( b.left, i, 2 * b.h + b.m ); }
+// the last sample of each line; a block type of its own (isp_rules.hpp's IspBlk) overloads the two
+INTRA_HD int intraTopLast( const IntraBlk &b ) { return 2 * b.w + b.m; }
+INTRA_HD int intraLeftLast( const IntraBlk &b ) { return 2 * b.h + b.m; }
+template<class Blk> INTRA_HD int intraTop( const Blk &b, int i ) { return intraAt( b.top, i, intraTopLast( b ) ); }
+template<class Blk> INTRA_HD int intraLeft( const Blk &b, int i ) { return intraAt( b.left, i, intraLeftLast( b ) ); }
 
-INTRA_HD int16_t intraDcVal( const IntraBlk &b )
+template<class Blk> INTRA_HD int16_t intraDcVal( const Blk &b )
 {
   const int denom = b.w == b.h ? b.w << 1 : ( b.w > b.h ? b.w : b.h );
   int       sum   = 0;
@@ -131,7 +137,7 @@ INTRA_HD int16_t intraDcVal( const IntraBlk &b )
 }
 
 // the row sums of the reference, horPred after x + 1 steps and topRow[x] after y + 1, written out
-INTRA_HD int16_t intraPlanarSample( const IntraBlk &b, int x, int y )
+template<class Blk> INTRA_HD int16_t intraPlanarSample( const Blk &b, int x, int y )
 {
   const int top = intraTop( b, x + 1 ), left = intraLeft( b, y + 1 ), topRight = intraTop( b, b.w + 1 ), bottomLeft = intraLeft( b, b.h + 1 );
   const int horPred  = ( left << b.log2W ) + ( x + 1 ) * ( topRight - left );
@@ -139,7 +145,7 @@ INTRA_HD int16_t intraPlanarSample( const IntraBlk &b, int x, int y )
   return ( int16_t ) ( ( ( horPred << b.log2H ) + ( vertPred << b.log2W ) + ( 1 << ( b.log2W + b.log2H ) ) ) >> ( 1 + b.log2W + b.log2H ) );
 }
 
-INTRA_HD int16_t intraPdpcSample( const IntraBlk &b, int x, int y, int val )
+template<class Blk> INTRA_HD int16_t intraPdpcSample( const Blk &b, int x, int y, int val )
 {
   const int scale = ( b.log2W + b.log2H - 2 ) >> 2;
   const int wT = 32 >> intraMin( 31, ( y << 1 ) >> scale ), wL = 32 >> intraMin( 31, ( x << 1 ) >> scale );
@@ -158,12 +164,12 @@ INTRA_HD int intraRefMain( const int16_t *mainLine, const int16_t *sideLine, int
 
 // cubic: the 32 x 4 taps of chroma_taps.hpp.  Horizontal modes are the vertical rule on the transposed block: (r, c) = (row, column) of that block.
 // chroma: a fractional slope takes the two-tap rule without a clip (:592-604) and cubic is not read.
-INTRA_HD int16_t intraAngularSample( const vtmhip_intra_params &p, const IntraBlk &b, const int16_t ( *cubic )[4], int x, int y, bool chroma = false )
+template<class Blk> INTRA_HD int16_t intraAngularSample( const vtmhip_intra_params &p, const Blk &b, const int16_t ( *cubic )[4], int x, int y, bool chroma = false )
 {
   const bool ver = p.isModeVer != 0;
   const int  r = ver ? y : x, c = ver ? x : y, mainSize = ver ? b.w : b.h, sideSize = ver ? b.h : b.w;
   const int16_t *mainLine = ver ? b.top : b.left, *sideLine = ver ? b.left : b.top;
-  const int mainLast = 2 * mainSize + b.m, sideLast = 2 * sideSize + b.m, angle = p.intraPredAngle;
+  const int mainLast = ver ? intraTopLast( b ) : intraLeftLast( b ), sideLast = ver ? intraLeftLast( b ) : intraTopLast( b ), angle = p.intraPredAngle;
   if( angle == 0 )   // pure vertical / horizontal
   {
     int v = intraLineAt( mainLine, b.m + c + 1, mainLast );
@@ -206,7 +212,7 @@ INTRA_HD int16_t intraAngularSample( const vtmhip_intra_params &p, const IntraBl
 }
 
 // b: the lines already chosen by p.refFilterFlag; dcVal: intraDcVal( b ), needed for mode 1 only
-INTRA_HD int16_t intraPredSample( const vtmhip_intra_params &p, int mode, const IntraBlk &b, int dcVal, const int16_t ( *cubic )[4], int x, int y, bool chroma = false )
+template<class Blk> INTRA_HD int16_t intraPredSample( const vtmhip_intra_params &p, int mode, const Blk &b, int dcVal, const int16_t ( *cubic )[4], int x, int y, bool chroma = false )
 {
   if( mode > INTRA_DC ) return intraAngularSample( p, b, cubic, x, y, chroma );
   const int v = mode == INTRA_PLANAR ? intraPlanarSample( b, x, y ) : dcVal;

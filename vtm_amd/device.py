@@ -536,6 +536,12 @@ class Context:
         """the LFNST candidate of n LfnstChainJob TUs: kept-region xT -> forward LFNST -> quant of 8 / 16 positions -> dequant -> inverse LFNST -> xIT -> SSE (TuResult)"""
         self._check(self.L.vtmhip_lfnst_chain_batch_dev(self.h, d_resi, d_jobs, n, d_levels, d_rec, d_results))
 
+    def isp_chain_batch(self, d_ref, d_org, d_blocks, num_blocks, d_jobs, n, d_reco, d_results, d_pred=None, d_levels=None):
+        """n IspJob candidates (CU, mode, split) over num_blocks IntraBlock entries, every sub-partition of a candidate in one kernel: the W x H reconstruction at
+        outOff inside d_reco, an IspResult per job, optionally the assembled prediction (predOff inside d_pred) and the levels (outOff inside d_levels, one TU-shaped
+        block per sub-partition).  A malformed table is rejected whole (VtmHipError, nothing launched)."""
+        self._check(self.L.vtmhip_isp_chain_batch_dev(self.h, d_ref, d_org, d_blocks, num_blocks, d_jobs, n, d_pred, d_levels, d_reco, d_results))
+
     def intra_chroma_pred_batch(self, d_ref, d_luma, d_blocks, num_blocks, d_jobs, n, d_pred):
         """the Cb and Cr predictions (regular modes 0 .. 66, LM 67, MDLM_L 68, MDLM_T 69) of n IntraChromaJob pairs over num_blocks IntraChromaBlock entries"""
         self._check(self.L.vtmhip_intra_chroma_pred_batch_dev(self.h, d_ref, d_luma, d_blocks, num_blocks, d_jobs, n, d_pred))

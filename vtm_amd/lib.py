@@ -391,6 +391,20 @@ class IntraChromaJointResult(C.Structure):
                 ("absSum", C.c_int32)]
 
 
+class IspJob(C.Structure):
+    _fields_ = [("predOff", C.c_int64), ("outOff", C.c_int64), ("block", C.c_int32), ("qpPer", C.c_int16), ("qpRem", C.c_int16), ("mode", C.c_uint8),
+                ("split", C.c_uint8), ("sideAvail", C.c_uint8), ("isIRAP", C.c_uint8), ("reserved", C.c_uint8 * 4)]
+
+
+class IspResult(C.Structure):
+    _fields_ = [("sse", C.c_uint64 * 4), ("absSum", C.c_int32 * 4), ("sumAbs", C.c_int32 * 4), ("numParts", C.c_int32), ("reserved", C.c_int32)]
+
+
+class IspGeom(C.Structure):
+    _fields_ = [("numParts", C.c_int32), ("partW", C.c_int32), ("partH", C.c_int32), ("numRegions", C.c_int32), ("regW", C.c_int32), ("regH", C.c_int32),
+                ("typeHor", C.c_int32), ("typeVer", C.c_int32)]
+
+
 _STRUCTS = [DistJob, TzJob, MeResult, PicParams, IfJob, FracJob, FracResult, TrJob, QuantJob, FullJob, McJob, PelOpJob,
             TuJob, TuResult, AffineJob, MeCfg, MeJob, MeOut, PredJob, MaskedSadJob, GeoBlendJob, DmvrJob, LfnstJob,
             PisRow, PisPu, PisLevel, AffineMeJob, AffineMeOut, LfnstTuJob, PisLevelRun, PisBuffers, SmvdJob, PisPuIn, WtdJob,
@@ -404,6 +418,7 @@ _MIP_STRUCTS = [MipJob]                                       # order of vtmhip_
 _INTRA_CHAIN_STRUCTS = [IntraTuJob, IntraTuResult]            # order of vtmhip_intra_chain_struct_size(which)
 _LFNST_CHAIN_STRUCTS = [LfnstChainJob, IntraLfnstTuJob]       # order of vtmhip_lfnst_chain_struct_size(which)
 _INTRA_CHROMA_CHAIN_STRUCTS = [IntraChromaTuJob, IntraChromaJointJob, IntraChromaJointResult]   # order of vtmhip_intra_chroma_chain_struct_size(which)
+_ISP_STRUCTS = [IspJob, IspResult, IspGeom]                   # order of vtmhip_isp_struct_size(which)
 
 # every symbol include/vtmhip.h declares (tests/test_abi.py checks the exports against the header text)
 _PROTOS = {
@@ -555,6 +570,15 @@ _PROTOS = {
                                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtmhip_intra_chroma_chain_make_jobs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                       C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vtmhip_isp_struct_size": (C.c_int, [C.c_int]),
+    "vtmhip_isp_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(IspGeom)]),
+    "vtmhip_isp_pred_params": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(IntraParams)]),
+    "vtmhip_isp_tr_types": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vtmhip_isp_pred_region_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtmhip_isp_next_lines_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtmhip_isp_chain_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtmhip_isp_chain_lanes_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "vtmhip_isp_chain_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtmhip_intra_cand_cost_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vtmhip_satd8_grid_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p]),
@@ -670,6 +694,10 @@ def load():
         if lib.vtmhip_intra_chroma_chain_struct_size(i) != C.sizeof(s):
             raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
                               % (s.__name__, C.sizeof(s), lib.vtmhip_intra_chroma_chain_struct_size(i)))
+    for i, s in enumerate(_ISP_STRUCTS):
+        if lib.vtmhip_isp_struct_size(i) != C.sizeof(s):
+            raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
+                              % (s.__name__, C.sizeof(s), lib.vtmhip_isp_struct_size(i)))
     _lib = lib
     return lib
 
