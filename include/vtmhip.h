@@ -1087,6 +1087,19 @@ typedef struct
 } vtmhip_smvd_job;
 int vtmhip_smvd_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, vtmhip_smvd_job *d_jobs, int n,
                            int maxWidth, int maxHeight, int op );
+/* Which kernel vtmhip_smvd_batch_dev launches for a call with these arguments (uniform: VTMHIP_SMVD_UNIFORM is set), the one rule the call itself dispatches on:
+ *   VTMHIP_SMVD_KERNEL_GENERAL_64 / _256   one workgroup of 64 / 256 lanes per PU, any size and bit depth (wavesPerPU = slots = pusPerWave = 0)
+ *   VTMHIP_SMVD_KERNEL_TILE_GROUP          the lane-per-tile kernel, a PU inside one wave: wavesPerPU 0, slots = candidates of a pass evaluated at once (8 while the
+ *                                          batch is at most eight eight-slot waves per compute unit, ceil( n / ( 64 / ( 8 * tiles ) ) ) <= 8 * CUs, else 4),
+ *                                          pusPerWave = 64 / ( slots * tiles ), tiles = the PU's 8x8 tiles
+ *   VTMHIP_SMVD_KERNEL_TILE_WORKGROUP      the lane-per-tile kernel, one PU per workgroup of wavesPerPU waves: slots 8, pusPerWave 1 (PUs per workgroup)
+ * Host arithmetic, no device needed: ctx may be NULL (a device of 256 compute units).  VTMHIP_E_INVALID for the sizes and bit depths vtmhip_smvd_batch_dev refuses. */
+#define VTMHIP_SMVD_KERNEL_GENERAL_64 0
+#define VTMHIP_SMVD_KERNEL_GENERAL_256 1
+#define VTMHIP_SMVD_KERNEL_TILE_GROUP 2
+#define VTMHIP_SMVD_KERNEL_TILE_WORKGROUP 3
+int vtmhip_smvd_launch_form( const vtmhip_ctx *ctx, int maxWidth, int maxHeight, int bitDepth, int uniform, int n, int *kernel, int *wavesPerPU, int *slots,
+                             int *pusPerWave );
 /* the reference's names for the four ops */
 int vtmhip_xGetSymmetricCost_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, vtmhip_smvd_job *d_jobs,
                                         int n, int maxWidth, int maxHeight );

@@ -487,3 +487,205 @@ def smvd_search_oracle(scene, j, L):
     r = ol.SmvdResult()
     L.vo_smvd_search(C.byref(t), j["numFixed"], len(j["starts"]), st, j["modeBits"], C.byref(r))
     return r.key()
+
+
+# ---- SMVD job sets of tests/test_gpu_smvd_forms.py (random_smvd_jobs above and its job sets stay what they are) -----------------------------------------------
+SMVD_MAX_START = 18      # VTMHIP_SMVD_MAX_START
+SMVD_TILE_SHAPES = [(8, 8), (16, 8), (8, 16), (16, 16), (32, 8), (8, 32), (32, 16), (16, 32), (32, 32), (64, 16), (16, 64), (64, 32), (32, 64), (64, 64), (128, 64),
+                    (64, 128), (128, 128)]      # the switch of vtmhip_smvd_batch_dev
+
+
+def smvd_search_oracle_at(scene, j, L, grow=0, max_start=SMVD_MAX_START):
+    """smvd_search_oracle with picW, picH and ctuSize each `grow` larger (the limits of clipMv move by that many samples) and the start list cut at `max_start`
+    entries (the device takes VTMHIP_SMVD_MAX_START)."""
+    t = smvd_struct(scene, j)
+    t.picW, t.picH, t.ctuSize = t.picW + grow, t.picH + grow, t.ctuSize + grow
+    starts = j["starts"][:max_start]
+    st = ((C.c_int * 2) * len(starts))(*[(C.c_int * 2)(*v) for v in starts])
+    r = ol.SmvdResult()
+    L.vo_smvd_search(C.byref(t), j["numFixed"], len(starts), st, j["modeBits"], C.byref(r))
+    return r.key()
+
+
+def bulk_smvd_jobs(scene, n, seed, size):
+    """n jobs of one shape with the fields and ranges of random_smvd_jobs, drawn as arrays (tens of thousands of jobs in well under a second)."""
+    rng = np.random.default_rng(seed)
+    w, h = size
+    ri = lambda lo, hi, *shape: rng.integers(lo, hi, (n,) + shape)   # noqa: E731
+    x, y = ri(0, (scene.W - w) // 4 + 1) * 4, ri(0, (scene.H - h) // 4 + 1) * 4
+    imv = np.array([0, 0, 0, 1, 2, 3])[ri(0, 6)]
+    rs = np.array([AMVR_SHIFT[i] for i in range(4)])[imv]
+
+    def rnd(v):      # _round_amvr on arrays whose last axis is (hor, ver)
+        s, o = rs.reshape((n,) + (1,) * (v.ndim - 1)), (1 << (rs - 1)).reshape((n,) + (1,) * (v.ndim - 1))
+        return np.where(v >= 0, (v + o - 1) >> s, (v + o) >> s) << s
+    base = np.stack([ri(-160, 160), ri(-96, 96)], axis=-1)
+    sign = np.array([1, -1]).reshape(1, 2, 1, 1)
+    cands = rnd(base.reshape(n, 1, 1, 2) * sign + ri(-40, 41, 2, 2, 2))                 # [job][list][i][hor / ver]
+    same = ri(0, 6, 2) == 0
+    cands[:, :, 1, :] = np.where(same[:, :, None], cands[:, :, 0, :], cands[:, :, 1, :])   # equal candidates: the SMVD block shortens the list
+    num = np.array([1, 2, 2, 2])[ri(0, 4, 2)]
+    nstart = ri(2, 9)
+    starts = rnd(base.reshape(n, 1, 2) + ri(-60, 61, 8, 2))
+    pick = ri(0, 2, 8)
+    from_cand = ri(0, 4, 8) == 0
+    starts = np.where(from_cand[:, :, None], np.take_along_axis(cands[:, 0], pick[:, :, None], axis=1), starts)
+    starts[:, 3:, 0] += ri(-2, 3, 5)                                                     # history entries need not sit on the AMVR grid
+    satd, clip, bcw = ri(0, 5) != 0, ri(0, 3) == 0, np.array([4, 4, 4, 4, -2, 3, 5, 10])[ri(0, 8)]
+    ib0, ib1, lam, nfix, mode = ri(1, 3), ri(1, 4), rng.uniform(2, 40, n), ri(2, 4), ri(3, 9)
+    cl, sl = cands.tolist(), starts.tolist()
+    return [dict(w=w, h=h, x=int(x[k]), y=int(y[k]), imv=int(imv[k]), satd=int(satd[k]), clip=int(clip[k]), bcw=int(bcw[k]), num=[int(num[k, 0]), int(num[k, 1])],
+                 cands=[[tuple(c) for c in l] for l in cl[k]], idxBits=[int(ib0[k]), int(ib1[k])], lam=float(lam[k]),
+                 starts=[tuple(s) for s in sl[k][:int(nstart[k])]], numFixed=int(nfix[k]), modeBits=int(mode[k])) for k in range(n)]
+
+
+class SmvdNoiseMarginScene(SmvdScene):
+    """The hard scene with both reference planes' margins filled with seeded noise (the picture area unchanged): a block read at a clipped vector lies in the margin,
+    and under edge replication a clipped and an unclipped block would read the same samples."""
+
+    def __init__(self, w=416, h=240, margin=160, bit_depth=10, seed=4100):
+        super().__init__(w, h, hard=True, margin=margin, bit_depth=bit_depth)
+        rng = np.random.default_rng(seed)
+        for buf in (self.ref_buf, self.ref_buf2):
+            v = buf.reshape(-1, self.ref_stride)
+            inside = v[margin:margin + h, margin:margin + w].copy()
+            v[:] = rng.integers(0, 1 << bit_depth, v.shape).astype(np.int16)
+            v[margin:margin + h, margin:margin + w] = inside
+
+
+def smvd_clip_limits(scene, j):
+    """((horMin, horMax), (verMin, verMax)) of clipMv (MVR_CLIP_MIN / MVR_CLIP_MAX, 1/16 sample) for the job's PU"""
+    return (((-128 - 8 - j["x"] + 1) << 4, (scene.W + 8 - j["x"] - 1) << 4), ((-128 - 8 - j["y"] + 1) << 4, (scene.H + 8 - j["y"] - 1) << 4))
+
+
+def clip_smvd_jobs(scene, size, n=48, seed=4200):
+    """PUs at the four picture corners (job k: corner k & 3).  In one list -- list (k >> 2) & 1 -- every AMVP candidate (for list 0 every start vector too) lies between 6
+    samples inside and 14 samples beyond the clipMv limit the corner faces, in both components for the jobs with (k >> 3) & 1 == 0 and horizontally only for the others;
+    the other list points into the picture (with list 1 at the limit the start vectors stay within 3 samples of the first list-0 candidate, so that the mirrored vectors
+    stay at the limit).  All vectors on the AMVR grid.  Returns (jobs, zones): zones[k] = (list, ((lo, hi) hor, (lo, hi) ver or None))."""
+    rng = np.random.default_rng(seed + size[0] * 131 + size[1])
+    w, h = size
+    jobs, zones = [], []
+    for k in range(n):
+        right, bottom, lst, both = k & 1, (k >> 1) & 1, (k >> 2) & 1, not (k >> 3) & 1
+        j = dict(w=w, h=h, x=(scene.W - w) * right, y=(scene.H - h) * bottom, imv=int(rng.choice([0, 0, 0, 1, 2, 3])))
+        step = 1 << AMVR_SHIFT[j["imv"]]
+        lim = smvd_clip_limits(scene, j)
+        zone = []
+        for c, far in ((0, right), (1, bottom)):
+            b = lim[c][far]
+            zone.append((b - 6 * 16, b + 14 * 16) if far else (b - 14 * 16, b + 6 * 16))
+        if not both:
+            zone[1] = None
+
+        def grid(lo, hi):
+            return int(rng.integers(-(-lo // step), hi // step + 1)) * step
+
+        def inward(far, lo, hi):      # lo .. hi sixteenths into the picture
+            return -grid(lo, hi) if far else grid(lo, hi)
+
+        def at_limit():
+            return (grid(*zone[0]), grid(*zone[1]) if both else inward(bottom, 0, 48))
+
+        def inside():
+            return (inward(right, 16, 160), inward(bottom, 16, 96))
+        cands = [[at_limit(), at_limit()], [inside(), inside()]] if lst == 0 else [[inside(), inside()], [at_limit(), at_limit()]]
+        if lst == 0:
+            starts = [at_limit() for _ in range(int(rng.integers(3, 9)))]
+        else:
+            starts = [(cands[0][0][0] + grid(-48, 48), cands[0][0][1] + grid(-48, 48)) for _ in range(int(rng.integers(3, 9)))]
+        j.update(satd=int(rng.integers(0, 5) != 0), clip=int(rng.integers(0, 3) == 0), bcw=int(rng.choice([4, 4, 4, 4, -2, 3, 5, 10])), num=[2, 2], cands=cands,
+                 idxBits=[int(rng.integers(1, 3)), int(rng.integers(1, 4))], lam=float(rng.uniform(2, 40)), starts=starts, numFixed=int(rng.integers(2, 4)),
+                 modeBits=int(rng.integers(3, 9)))
+        jobs.append(j)
+        zones.append((lst, tuple(zone)))
+    return jobs, zones
+
+
+def smvd_evaluated_starts(j, max_start=SMVD_MAX_START):
+    """raw indices of the start entries the SMVD block evaluates (smmvdCandsGen, :2709-2763): the distinct ones in list order -- entries from numFixed on rounded to
+    the AMVR precision and taken while fewer than 5 are collected -- that are not one of list 0's (shortened) predictors"""
+    c0 = j["cands"][0][:1 if j["num"][0] < 2 or j["cands"][0][0] == j["cands"][0][1] else 2]
+    seen, out = [], []
+    for s, v in enumerate(j["starts"][:max_start]):
+        if s >= j["numFixed"]:
+            if len(seen) >= 5:
+                break
+            if j["imv"]:
+                v = (_round_amvr(v[0], j["imv"]), _round_amvr(v[1], j["imv"]))
+        v = tuple(v)
+        if v in seen:
+            continue
+        seen.append(v)
+        if v not in [tuple(c) for c in c0]:
+            out.append(s)
+    return out
+
+
+def long_start_smvd_jobs(scene, n, seed, size, base=None):
+    """Jobs with VTMHIP_SMVD_MAX_START start entries: the numFixed fixed ones, then 6 .. 10 entries that equal a fixed one after the AMVR rounding (dropped as
+    duplicates), then distinct vectors within +-90 sixteenths of the first list-0 candidate.  A job in four carries numStart = 19 .. 22 (the device clamps it, the
+    oracle gets the 18).  base: jobs whose other fields are kept (default: bulk_smvd_jobs)."""
+    rng = np.random.default_rng(seed + 17)
+    jobs = [dict(j) for j in (base if base is not None else bulk_smvd_jobs(scene, n, seed, size))]
+    for k, j in enumerate(jobs):
+        imv, step = j["imv"], 1 << AMVR_SHIFT[j["imv"]]
+        fixed = [(_round_amvr(s[0], imv), _round_amvr(s[1], imv)) for s in (j["starts"] + j["starts"])[:j["numFixed"]]]      # on the grid: a rounded entry can equal them
+        slack = step // 4 if imv else 0
+        dups = []
+        for _ in range(int(rng.integers(6, 11))):
+            f = fixed[int(rng.integers(0, len(fixed)))]
+            dups.append((f[0] + int(rng.integers(-slack, slack + 1)), f[1] + int(rng.integers(-slack, slack + 1))))
+        c = j["cands"][0][0]
+        tail = []      # distinct as listed; the first one also after the rounding, from the fixed entries and list 0's predictors: it is evaluated
+        while len(fixed) + len(dups) + len(tail) < SMVD_MAX_START:
+            v = (c[0] + int(rng.integers(-90, 91)), c[1] + int(rng.integers(-90, 91)))
+            r = (_round_amvr(v[0], imv), _round_amvr(v[1], imv)) if imv else v
+            if v not in tail and (tail or r not in fixed + [tuple(p) for p in j["cands"][0]]):
+                tail.append(v)
+        j["starts"] = fixed + dups + tail
+        if k % 4 == 0:
+            j["numStart"] = SMVD_MAX_START + 1 + k // 4 % 4
+    return jobs
+
+
+class SmvdFlatScene(SmvdScene):
+    """Original and both reference planes constant (three different values): every candidate of a search has the same distortion, so its choices are the
+    first-minimum rules alone."""
+
+    def __init__(self, w=416, h=240, margin=160, bit_depth=10):
+        super().__init__(w, h, hard=False, margin=margin, bit_depth=bit_depth)
+        top = 1 << bit_depth
+        self.cur[:], self.ref_buf[:], self.ref_buf2[:] = top // 2, top // 2 - top // 32, top // 2 + top // 16
+
+
+def _eg_bits(v):
+    """bits of one vector-difference component (RdCost::xGetExpGolombNumberOfBits)"""
+    t = ((-v) << 1) + 1 if v <= 0 else v << 1
+    n = 1
+    while t > 128:
+        n, t = n + 14, t >> 7
+    return n + 2 * (t.bit_length() - 1)
+
+
+def smvd_tie_counts(scene, j, L):
+    """(predictor pairs of least cost, (start entry, pair) candidates of least cost) of a job: xGetSymmetricCost of every predictor pair, and for every evaluated
+    start entry and pair the distortion plus the rate rule floor(lambda * (vector bits at the AMVR precision + the two index bits))"""
+    t = smvd_struct(scene, j)
+    I2 = C.c_int * 2
+    cost = lambda a, b: L.vo_symmetric_cost(C.byref(t), I2(*a), I2(*b))      # noqa: E731
+    n = [1 if j["num"][l] < 2 or j["cands"][l][0] == j["cands"][l][1] else 2 for l in range(2)]
+    pairs = [(i, k) for i in range(n[0]) for k in range(n[1])]
+    pc = [cost(j["cands"][0][i], j["cands"][1][k]) for i, k in pairs]
+    rs = AMVR_SHIFT[j["imv"]]
+    down = lambda v: _round_amvr(v, j["imv"]) >> rs                          # noqa: E731
+    sc = []
+    for s in smvd_evaluated_starts(j):
+        v = j["starts"][s]
+        if s >= j["numFixed"] and j["imv"]:
+            v = (_round_amvr(v[0], j["imv"]), _round_amvr(v[1], j["imv"]))
+        for i, k in pairs:
+            p, q = j["cands"][0][i], j["cands"][1][k]
+            bits = _eg_bits(down(v[0]) - down(p[0])) + _eg_bits(down(v[1]) - down(p[1])) + j["idxBits"][i] + j["idxBits"][k]
+            sc.append(cost(v, (q[0] - v[0] + p[0], q[1] - v[1] + p[1])) + int(j["lam"] * bits))
+    return pc.count(min(pc)), sc.count(min(sc)) if sc else 0

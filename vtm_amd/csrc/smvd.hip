@@ -835,30 +835,73 @@ __global__ __launch_bounds__( NW ? 64 * NW : 64 ) void smvd_tile_kernel( vtmhip_
   }
 }
 
-template<int TX, int TY, int NW>
-void launch_tile( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, vtmhip_smvd_job *d_jobs, int n, int op )
+// ---- the launch form: the ONE rule that vtmhip_smvd_launch_form reports and vtmhip_smvd_batch_dev / launch_tile dispatch on -------------------------------------
+struct SmvdForm { int kernel, wavesPerPU, slots, pusPerWave; };
+
+// waves per PU of a tile shape by its number of 8x8 tiles (0: the group form).  Group form up to four tiles; above: one PU per workgroup, waves by the number of
+// (candidate, tile) items of a pass (8 candidates x tiles)
+constexpr int smvd_tile_waves( int tiles ) { return tiles <= 4 ? 0 : tiles == 8 ? VTMHIP_SMVD_G8 : tiles == 16 ? VTMHIP_SMVD_G16 : 4; }
+// the shapes the tile kernel is instantiated for (the switch of vtmhip_smvd_batch_dev holds exactly these)
+constexpr bool smvd_tile_shape( int w, int h )
 {
+  const int big = w > h ? w : h, small = w > h ? h : w;
+  return big == 128 ? small >= 64 : big == 64 ? small >= 16 : big == 32 || big == 16 || big == 8 ? small >= 8 : false;
+}
+
+SmvdForm smvd_form( int numCUs, int maxWidth, int maxHeight, int bitDepth, bool uniform, int n )
+{
+  SmvdForm f = { maxWidth * maxHeight <= 1024 ? VTMHIP_SMVD_KERNEL_GENERAL_64 : VTMHIP_SMVD_KERNEL_GENERAL_256, 0, 0, 0 };
+  const bool powers = ( maxWidth & ( maxWidth - 1 ) ) == 0 && ( maxHeight & ( maxHeight - 1 ) ) == 0;
+  if( !( uniform && bitDepth <= 10 && maxWidth >= 8 && maxHeight >= 8 && powers && smvd_tile_shape( maxWidth, maxHeight ) ) || getenv( "VTMHIP_SMVD_NO_TILE" ) ) return f;
+  const int T = ( maxWidth >> 3 ) * ( maxHeight >> 3 );
+  f.wavesPerPU = smvd_tile_waves( T );
+  if( f.wavesPerPU ) { f.kernel = VTMHIP_SMVD_KERNEL_TILE_WORKGROUP; f.slots = 8; f.pusPerWave = 1; return f; }
+  // group form: four candidate slots per PU fill the lanes best (the passes of a search hold 3 .. 8 candidates) and are the choice when the batch is larger than
+  // the machine; a batch of at most two waves per SIMD (a rank's share of a picture on eight GPUs) is bound by the latency of ONE wave's
+  // search, and eight slots halve the pass steps of that wave (1/8 share of a 4K picture: 2.60 -> 2.52 ms)
+  const int  wide = 8 * T <= 64 ? 8 : 4, ppwWide = 64 / ( wide * T );
+  const long wavesWide = ( ( long ) n + ppwWide - 1 ) / ppwWide;
+  f.kernel = VTMHIP_SMVD_KERNEL_TILE_GROUP;
+  f.slots = wide == 8 && wavesWide <= 2L * 4 * numCUs ? 8 : 4;
+  f.pusPerWave = 64 / ( f.slots * T );
+  return f;
+}
+
+template<int TX, int TY>
+void launch_tile( vtmhip_ctx *ctx, const SmvdForm &f, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, vtmhip_smvd_job *d_jobs, int n,
+                  int op )
+{
+  constexpr int T = TX * TY, NW = smvd_tile_waves( T );
   if constexpr( NW != 0 )
   {
     hipLaunchKernelGGL( ( smvd_tile_kernel<TX, TY, NW, 8> ), dim3( n ), dim3( 64 * NW ), 0, ctx->stream, *pic, d_orgBase, d_refBase, d_jobs, n, op );
   }
   else
   {
-  // group form: four candidate slots per PU fill the lanes best (the passes of a search hold 3 .. 8 candidates) and are the choice when the batch is larger than
-  // the machine; a batch of at most two waves per SIMD (a rank's share of a picture on eight GPUs) is bound by the latency of ONE wave's
-  // search, and eight slots halve the pass steps of that wave (1/8 share of a 4K picture: 2.60 -> 2.52 ms)
-  constexpr int T = TX * TY, WIDE = 8 * T <= 64 ? 8 : 4, PPW_WIDE = 64 / ( WIDE * T ), PPW4 = 64 / ( 4 * T );
-  const long wavesWide = ( ( long ) n + PPW_WIDE - 1 ) / PPW_WIDE;
-  if( WIDE == 8 && wavesWide <= 2L * 4 * ctx->numCUs )
-    hipLaunchKernelGGL( ( smvd_tile_kernel<TX, TY, 0, WIDE> ), dim3( ( n + PPW_WIDE - 1 ) / PPW_WIDE ), dim3( 64 ), 0, ctx->stream, *pic, d_orgBase, d_refBase, d_jobs, n, op );
+  constexpr int WIDE = 8 * T <= 64 ? 8 : 4;
+  const int     waves = ( n + f.pusPerWave - 1 ) / f.pusPerWave;
+  if( f.slots == WIDE )
+    hipLaunchKernelGGL( ( smvd_tile_kernel<TX, TY, 0, WIDE> ), dim3( waves ), dim3( 64 ), 0, ctx->stream, *pic, d_orgBase, d_refBase, d_jobs, n, op );
   else
-    hipLaunchKernelGGL( ( smvd_tile_kernel<TX, TY, 0, 4> ), dim3( ( n + PPW4 - 1 ) / PPW4 ), dim3( 64 ), 0, ctx->stream, *pic, d_orgBase, d_refBase, d_jobs, n, op );
+    hipLaunchKernelGGL( ( smvd_tile_kernel<TX, TY, 0, 4> ), dim3( waves ), dim3( 64 ), 0, ctx->stream, *pic, d_orgBase, d_refBase, d_jobs, n, op );
   }
 }
 
 }   // namespace
 
 extern "C" {
+
+// what vtmhip_smvd_batch_dev launches for these arguments (host arithmetic; ctx may be NULL: the rule for 256 compute units)
+int vtmhip_smvd_launch_form( const vtmhip_ctx *ctx, int maxWidth, int maxHeight, int bitDepth, int uniform, int n, int *kernel, int *wavesPerPU, int *slots,
+                             int *pusPerWave )
+{
+  if( !kernel || !wavesPerPU || !slots || !pusPerWave || n < 0 ) return VTMHIP_E_INVALID;
+  if( !( maxWidth >= 4 && maxHeight >= 4 && maxWidth <= 128 && maxHeight <= 128 && ( maxWidth & 3 ) == 0 && ( maxHeight & 3 ) == 0 ) ) return VTMHIP_E_INVALID;
+  if( bitDepth < 8 || bitDepth > 12 ) return VTMHIP_E_INVALID;
+  const SmvdForm f = smvd_form( ctx ? ctx->numCUs : 256, maxWidth, maxHeight, bitDepth, uniform != 0, n );
+  *kernel = f.kernel; *wavesPerPU = f.wavesPerPU; *slots = f.slots; *pusPerWave = f.pusPerWave;
+  return VTMHIP_OK;
+}
 
 int vtmhip_smvd_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, vtmhip_smvd_job *d_jobs, int n,
                            int maxWidth, int maxHeight, int op )
@@ -874,37 +917,35 @@ int vtmhip_smvd_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const 
   VTMHIP_REQUIRE( ctx, d_orgBase && d_refBase && d_jobs, "null pointer" );
   // pattern + prediction B + the (h + 7) x w intermediates of the separable filter
   const size_t lds = ( 2 * ( size_t ) maxWidth * maxHeight + ( size_t ) maxWidth * ( maxHeight + 7 ) ) * sizeof( int16_t );
-  const bool tileForm = uniform && pic->bitDepth <= 10 && maxWidth >= 8 && maxHeight >= 8 && !getenv( "VTMHIP_SMVD_NO_TILE" );
+  const SmvdForm form = smvd_form( ctx->numCUs, maxWidth, maxHeight, pic->bitDepth, uniform, n );
+  const bool     tileForm = form.kernel == VTMHIP_SMVD_KERNEL_TILE_GROUP || form.kernel == VTMHIP_SMVD_KERNEL_TILE_WORKGROUP;
   VTMHIP_TIME_KERNEL( ctx, tileForm ? "smvd_tile_kernel" : "smvd_kernel" );
-  bool tiled = true;
   if( tileForm )
   {
-    // group form up to four tiles; above: one PU per workgroup, waves by the number of (candidate, tile) items of a pass (8 candidates x tiles)
+    // the waves per PU of an instantiation come from smvd_tile_waves, the shapes are those of smvd_tile_shape: the form was decided above
     switch( maxWidth * 256 + maxHeight )
     {
-    case 8 * 256 + 8:     launch_tile<1, 1, 0>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 16 * 256 + 8:    launch_tile<2, 1, 0>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 8 * 256 + 16:    launch_tile<1, 2, 0>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 16 * 256 + 16:   launch_tile<2, 2, 0>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 32 * 256 + 8:    launch_tile<4, 1, 0>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 8 * 256 + 32:    launch_tile<1, 4, 0>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 32 * 256 + 16:   launch_tile<4, 2, VTMHIP_SMVD_G8>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 16 * 256 + 32:   launch_tile<2, 4, VTMHIP_SMVD_G8>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 32 * 256 + 32:   launch_tile<4, 4, VTMHIP_SMVD_G16>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 64 * 256 + 16:   launch_tile<8, 2, VTMHIP_SMVD_G16>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 16 * 256 + 64:   launch_tile<2, 8, VTMHIP_SMVD_G16>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 64 * 256 + 32:   launch_tile<8, 4, 4>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 32 * 256 + 64:   launch_tile<4, 8, 4>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 64 * 256 + 64:   launch_tile<8, 8, 4>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 128 * 256 + 64:  launch_tile<16, 8, 4>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 64 * 256 + 128:  launch_tile<8, 16, 4>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    case 128 * 256 + 128: launch_tile<16, 16, 4>( ctx, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
-    default: tiled = false;
+    case 8 * 256 + 8:     launch_tile<1, 1>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 16 * 256 + 8:    launch_tile<2, 1>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 8 * 256 + 16:    launch_tile<1, 2>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 16 * 256 + 16:   launch_tile<2, 2>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 32 * 256 + 8:    launch_tile<4, 1>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 8 * 256 + 32:    launch_tile<1, 4>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 32 * 256 + 16:   launch_tile<4, 2>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 16 * 256 + 32:   launch_tile<2, 4>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 32 * 256 + 32:   launch_tile<4, 4>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 64 * 256 + 16:   launch_tile<8, 2>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 16 * 256 + 64:   launch_tile<2, 8>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 64 * 256 + 32:   launch_tile<8, 4>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 32 * 256 + 64:   launch_tile<4, 8>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 64 * 256 + 64:   launch_tile<8, 8>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 128 * 256 + 64:  launch_tile<16, 8>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 64 * 256 + 128:  launch_tile<8, 16>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    case 128 * 256 + 128: launch_tile<16, 16>( ctx, form, pic, d_orgBase, d_refBase, d_jobs, n, op ); break;
+    default: VTMHIP_REQUIRE( ctx, false, "no tile kernel for this shape" );   // smvd_tile_shape and this switch disagree
     }
   }
-  else tiled = false;
-  if( tiled ) {}
-  else if( maxWidth * maxHeight <= 1024 )
+  else if( form.kernel == VTMHIP_SMVD_KERNEL_GENERAL_64 )
   {
     hipLaunchKernelGGL( smvd_kernel<64>, dim3( n ), dim3( 64 ), lds, ctx->stream, *pic, d_orgBase, d_refBase, d_jobs, n, op, maxWidth, maxHeight );
   }

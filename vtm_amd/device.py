@@ -361,6 +361,13 @@ class Context:
         else:
             self._check(self.L.vtmhip_smvd_batch_dev(self.h, C.byref(pic), d_org, d_ref, d_jobs, n, max_w, max_h, op | (0x100 if uniform else 0)))
 
+    def smvd_launch_form(self, max_w, max_h, bit_depth, uniform, n):
+        """what smvd_batch launches for such a call: (kernel, waves per PU, candidate slots, PUs per wave) -- kernel 0 / 1 the general 64- / 256-lane kernel, 2 the
+        tile kernel's group form, 3 its workgroup form (VTMHIP_SMVD_KERNEL_*)"""
+        out = [C.c_int(-1) for _ in range(4)]
+        self._check(self.L.vtmhip_smvd_launch_form(self.h, max_w, max_h, bit_depth, int(uniform), n, *[C.byref(v) for v in out]))
+        return tuple(v.value for v in out)
+
     def pred_affine_blk_batch(self, pic, d_ref, d_dst, d_jobs, n, max_w, max_h):
         self._check(self.L.vtmhip_xPredAffineBlk_batch_dev(self.h, C.byref(pic), d_ref, d_dst, d_jobs, n, max_w, max_h))
 
