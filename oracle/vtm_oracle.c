@@ -1302,7 +1302,7 @@ void vo_mc_block( int comp, const int16_t *ref, int refStride, int w, int h, int
  * gradFilterCore / calcBIOSumsCore / addBIOAvgCore (CommonLib/Buffer.cpp:88-200).  ref0 / ref1 point at the PU position with MV (0,0).
  * ------------------------------------------------------------------------------------------------ */
 static void vo_bdof_region( const int16_t *ref0, int stride0, const int16_t *ref1, int stride1, int w, int h, const int mv[2][2], int bitDepth,
-                            int16_t *dst, int dstStride )
+                            int16_t *dst, int dstStride, vo_bdof_trace_t *tr )
 {
   enum { S = 16 + 4, G = 16 + 2 };
   int16_t   pred[2][S * S], gx[2][G * G], gy[2][G * G];
@@ -1370,11 +1370,19 @@ static void vo_bdof_region( const int16_t *ref0, int stride0, const int16_t *ref
           sumSignGYGX += tGY < 0 ? -tGX : tGY == 0 ? 0 : tGX;
         }
       int tmpx = sumAbsGX == 0 ? 0 : ( sumDIX * 4 ) >> vo_floor_log2( ( unsigned ) sumAbsGX );   /* rightShiftMSB (:1606-1609) */
+      if( tr )
+      {
+        tr->units++;
+        tr->tmpxLow += tmpx < -limit; tr->tmpxHigh += tmpx > limit;
+        tr->absGXZero += sumAbsGX == 0 && sumAbsGY != 0; tr->absGYZero += sumAbsGY == 0 && sumAbsGX != 0;
+        tr->signGe4096 += sumSignGYGX >= 4096; tr->signLtM4096 += sumSignGYGX < -4096; tr->signNeg += sumSignGYGX < 0;
+      }
       tmpx = tmpx < -limit ? -limit : tmpx > limit ? limit : tmpx;
       const int mains = sumSignGYGX >> 12, secs = sumSignGYGX & 4095;
       int       tmpData = tmpx * mains;
       tmpData = ( tmpData * 4096 + tmpx * secs ) >> 1;
       int tmpy = sumAbsGY == 0 ? 0 : ( sumDIY * 4 - tmpData ) >> vo_floor_log2( ( unsigned ) sumAbsGY );
+      if( tr ) { tr->tmpyLow += tmpy < -limit; tr->tmpyHigh += tmpy > limit; }
       tmpy = tmpy < -limit ? -limit : tmpy > limit ? limit : tmpy;
       for( int y = 0; y < 4; y++ )   /* addBIOAvgCore (Buffer.cpp:88-127) */
         for( int x = 0; x < 4; x++ )
@@ -1382,6 +1390,7 @@ static void vo_bdof_region( const int16_t *ref0, int stride0, const int16_t *ref
           const int gi = ( yu * 4 + y + 1 ) * G + xu * 4 + x + 1, pi = ( yu * 4 + y + 2 ) * S + xu * 4 + x + 2;
           const int b  = tmpx * ( gx[0][gi] - gx[1][gi] ) + tmpy * ( gy[0][gi] - gy[1][gi] );
           const int v  = ( int16_t )( ( pred[0][pi] + pred[1][pi] + b + offset ) >> shiftNum );
+          if( tr ) { tr->clipZero += v < 0; tr->clipMax += v > cmax; }
           dst[( ptrdiff_t )( yu * 4 + y ) * dstStride + xu * 4 + x] = ( int16_t )( v < 0 ? 0 : v > cmax ? cmax : v );
         }
     }
@@ -1419,8 +1428,9 @@ static int vo_div_for_maxq7( int64_t N, int64_t D )   /* :1733-1767 */
   return sign ? -q : q;
 }
 
-void vo_dmvr_pu( const int16_t *plane0, const int16_t *plane1, int stride, int picW, int picH, int ctuSize, int puX, int puY, int w, int h, int mv0Hor,
-                 int mv0Ver, int mv1Hor, int mv1Ver, int bitDepth, int bioApplied, int16_t *dst, int dstStride, int32_t *mvdOut )
+void vo_dmvr_pu_ex( const int16_t *plane0, const int16_t *plane1, int stride, int picW, int picH, int ctuSize, int puX, int puY, int w, int h, int mv0Hor,
+                    int mv0Ver, int mv1Hor, int mv1Ver, int bitDepth, int bioApplied, int16_t *dst, int dstStride, int32_t *mvdOut, vo_dmvr_trace_t *trace,
+                    vo_bdof_trace_t *bdofTrace )
 {
   enum { MAXS = 16, PS = MAXS + 12, BS = MAXS + 4 };
   const int mergeMv[2][2] = { { mv0Hor, mv0Ver }, { mv1Hor, mv1Ver } };
@@ -1481,6 +1491,14 @@ void vo_dmvr_pu( const int16_t *plane0, const int16_t *plane1, int stride, int p
 #undef VO_DMVR_COST
       const int bio = minCost < ( uint64_t )( 2 * dx * dy ) ? 0 : bioApplied;
       total[0] *= 16; total[1] *= 16;
+      vo_dmvr_trace_t *tr = trace ? trace + num : NULL;
+      if( tr )
+      {
+        for( int i = 0; i < 25; i++ ) tr->cost[i] = sads[i];
+        if( !notZero ) tr->cost[12] = minCost;   /* the centre after its discount, also when the search was skipped */
+        tr->best = best; tr->notZero = notZero; tr->bio = bio;
+        tr->surface[0] = tr->surface[1] = !notZero ? VO_DMVR_SURF_NONE : VO_DMVR_SURF_EDGE;
+      }
       if( notZero && total[0] != 32 && total[0] != -32 && total[1] != 32 && total[1] != -32 )   /* xDMVRSubPixelErrorSurface */
       {
         const uint64_t sb[5] = { sads[best], sads[best - 1], sads[best - 5], sads[best + 1], sads[best + 5] };
@@ -1493,6 +1511,7 @@ void vo_dmvr_pu( const int16_t *plane0, const int16_t *plane1, int stride, int p
             if( s1 != sb[0] && s3 != sb[0] ) total[d] += vo_div_for_maxq7( numer, denom );
             else total[d] += s1 == sb[0] ? -8 : 8;
           }
+          if( tr ) tr->surface[d] = denom == 0 ? VO_DMVR_SURF_ZERO_DENOM : s1 != sb[0] && s3 != sb[0] ? VO_DMVR_SURF_DIV : s1 == sb[0] ? VO_DMVR_SURF_MINUS8 : VO_DMVR_SURF_PLUS8;
         }
       }
       total[0] = ( int16_t ) total[0]; total[1] = ( int16_t ) total[1];
@@ -1526,7 +1545,7 @@ void vo_dmvr_pu( const int16_t *plane0, const int16_t *plane1, int stride, int p
         fsrc[l] = pad[l] + 5 * ( PS + 1 ) + dY * PS + dX;
       }
       int16_t *out = dst + ( ptrdiff_t ) sy * dstStride + sx;
-      if( bio ) vo_bdof_region( fsrc[0], PS, fsrc[1], PS, dx, dy, ( const int( * )[2] ) frac, bitDepth, out, dstStride );
+      if( bio ) vo_bdof_region( fsrc[0], PS, fsrc[1], PS, dx, dy, ( const int( * )[2] ) frac, bitDepth, out, dstStride, bdofTrace );
       else
       {
         int16_t p0[MAXS * MAXS], p1[MAXS * MAXS];
@@ -1541,6 +1560,13 @@ void vo_dmvr_pu( const int16_t *plane0, const int16_t *plane1, int stride, int p
           }
       }
     }
+}
+
+void vo_dmvr_pu( const int16_t *plane0, const int16_t *plane1, int stride, int picW, int picH, int ctuSize, int puX, int puY, int w, int h, int mv0Hor,
+                 int mv0Ver, int mv1Hor, int mv1Ver, int bitDepth, int bioApplied, int16_t *dst, int dstStride, int32_t *mvdOut )
+{
+  vo_dmvr_pu_ex( plane0, plane1, stride, picW, picH, ctuSize, puX, puY, w, h, mv0Hor, mv0Ver, mv1Hor, mv1Ver, bitDepth, bioApplied, dst, dstStride, mvdOut, NULL,
+                 NULL );
 }
 
 /* The 4:2:0 chroma planes of the same PU (xProcessDMVR with chroma enabled): a sub-PU that did not move is predicted straight from the reference
@@ -1599,15 +1625,21 @@ void vo_dmvr_chroma( const int16_t *planeC0, const int16_t *planeC1, int strideC
     }
 }
 
-void vo_bdof_pu( const int16_t *ref0, int stride0, const int16_t *ref1, int stride1, int w, int h, int mv0Hor, int mv0Ver, int mv1Hor, int mv1Ver,
-                 int bitDepth, int16_t *dst, int dstStride )
+void vo_bdof_pu_ex( const int16_t *ref0, int stride0, const int16_t *ref1, int stride1, int w, int h, int mv0Hor, int mv0Ver, int mv1Hor, int mv1Ver,
+                    int bitDepth, int16_t *dst, int dstStride, vo_bdof_trace_t *trace )
 {
   const int mv[2][2] = { { mv0Hor, mv0Ver }, { mv1Hor, mv1Ver } };
   const int dx = w < 16 ? w : 16, dy = h < 16 ? h : 16;   /* MAX_BDOF_APPLICATION_REGION, xSubPuBio :414-417 */
   for( int y = 0; y < h; y += dy )
     for( int x = 0; x < w; x += dx )
       vo_bdof_region( ref0 + ( ptrdiff_t ) y * stride0 + x, stride0, ref1 + ( ptrdiff_t ) y * stride1 + x, stride1, dx, dy, mv, bitDepth,
-                      dst + ( ptrdiff_t ) y * dstStride + x, dstStride );
+                      dst + ( ptrdiff_t ) y * dstStride + x, dstStride, trace );
+}
+
+void vo_bdof_pu( const int16_t *ref0, int stride0, const int16_t *ref1, int stride1, int w, int h, int mv0Hor, int mv0Ver, int mv1Hor, int mv1Ver,
+                 int bitDepth, int16_t *dst, int dstStride )
+{
+  vo_bdof_pu_ex( ref0, stride0, ref1, stride1, w, h, mv0Hor, mv0Ver, mv1Hor, mv1Ver, bitDepth, dst, dstStride, NULL );
 }
 
 /* ------------------------------------------------------------------------------------------------

@@ -66,9 +66,33 @@ uint64_t vo_sad_mask( const int16_t *org, int orgStride, const int16_t *cur, int
 /* BDOF of one bi-predicted luma PU: xSubPuBio + xPredInterBlk(bioApplied) + applyBiOptFlow, CommonLib/InterPrediction.cpp:352-443, 733-810, 1233-1334 */
 void vo_bdof_pu( const int16_t *ref0, int stride0, const int16_t *ref1, int stride1, int w, int h, int mv0Hor, int mv0Ver, int mv1Hor, int mv1Ver,
                  int bitDepth, int16_t *dst, int dstStride );
+/* ... and the same with the decisions it took: counts ADDED to *trace (optional; the caller zeroes it).  "Low" / "High": the value before the +-15 clamp was
+ * beyond it; absGXZero: sumAbsGX == 0 while sumAbsGY != 0 (absGYZero: the reverse); sign*: sumSignGY_GX >= 4096, < -4096, < 0; clip*: output samples the final
+ * clip to [0, max] changed. */
+typedef struct
+{
+  int64_t units, tmpxLow, tmpxHigh, tmpyLow, tmpyHigh, absGXZero, absGYZero, signGe4096, signLtM4096, signNeg, clipZero, clipMax;
+} vo_bdof_trace_t;
+void vo_bdof_pu_ex( const int16_t *ref0, int stride0, const int16_t *ref1, int stride1, int w, int h, int mv0Hor, int mv0Ver, int mv1Hor, int mv1Ver,
+                    int bitDepth, int16_t *dst, int dstStride, vo_bdof_trace_t *trace );
 /* DMVR of one bi-predicted luma PU: InterPrediction::xProcessDMVR, CommonLib/InterPrediction.cpp:1997-2195 (luma plane) */
 void vo_dmvr_pu( const int16_t *plane0, const int16_t *plane1, int stride, int picW, int picH, int ctuSize, int puX, int puY, int w, int h, int mv0Hor,
                  int mv0Ver, int mv1Hor, int mv1Ver, int bitDepth, int bioApplied, int16_t *dst, int dstStride, int32_t *mvdOut );
+/* ... and the same with the decisions of every sub-PU (trace[num], optional): the 25 matching costs in raster order (the centre after its discount; UINT64_MAX
+ * where the early termination skipped the search), the winner, notZero (the search ran), bio (BDOF was applied) and per axis what the error surface did.
+ * bdofTrace (optional): the counts of the BDOF regions this PU ran. */
+enum { VO_DMVR_SURF_NONE = 0,         /* early termination: no search, no surface */
+       VO_DMVR_SURF_EDGE = 1,         /* the winner lies on the +-2 border: the sub-sample step is skipped on both axes */
+       VO_DMVR_SURF_ZERO_DENOM = 2,   /* both neighbours on the axis cost what the winner costs */
+       VO_DMVR_SURF_DIV = 3, VO_DMVR_SURF_MINUS8 = 4, VO_DMVR_SURF_PLUS8 = 5 };
+typedef struct
+{
+  uint64_t cost[25];
+  int32_t  best, notZero, bio, surface[2];
+} vo_dmvr_trace_t;
+void vo_dmvr_pu_ex( const int16_t *plane0, const int16_t *plane1, int stride, int picW, int picH, int ctuSize, int puX, int puY, int w, int h, int mv0Hor,
+                    int mv0Ver, int mv1Hor, int mv1Ver, int bitDepth, int bioApplied, int16_t *dst, int dstStride, int32_t *mvdOut, vo_dmvr_trace_t *trace,
+                    vo_bdof_trace_t *bdofTrace );
 /* ... and one 4:2:0 chroma plane of the same PU, given pu.mvdL0SubPu (xPrefetch forLuma = 0, xPad, xFinalPaddedMCForDMVR, addAvg) */
 void vo_dmvr_chroma( const int16_t *planeC0, const int16_t *planeC1, int strideC, int picW, int picH, int ctuSize, int puX, int puY, int w, int h,
                      int mv0Hor, int mv0Ver, int mv1Hor, int mv1Ver, const int32_t *mvd, int bitDepth, int16_t *dst, int dstStride );

@@ -174,5 +174,25 @@ class SmvdResult(C.Structure):   # vo_smvd_result_t
         return (tuple(self.mvCur), tuple(self.mvTar), tuple(self.predSym[0]), tuple(self.predSym[1]), tuple(self.mvpIdxSym), self.cost)
 
 
+class BdofTrace(C.Structure):    # vo_bdof_trace_t: counts that vo_bdof_pu_ex / vo_dmvr_pu_ex add to
+    _fields_ = [(n, C.c_int64) for n in ("units", "tmpxLow", "tmpxHigh", "tmpyLow", "tmpyHigh", "absGXZero", "absGYZero", "signGe4096", "signLtM4096",
+                                         "signNeg", "clipZero", "clipMax")]
+
+    def add(self, other):
+        for n, _ in self._fields_:
+            setattr(self, n, getattr(self, n) + getattr(other, n))
+        return self
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+SURF_NONE, SURF_EDGE, SURF_ZERO_DENOM, SURF_DIV, SURF_MINUS8, SURF_PLUS8 = range(6)   # VO_DMVR_SURF_*
+
+
+class DmvrTrace(C.Structure):    # vo_dmvr_trace_t, one per sub-PU
+    _fields_ = [("cost", C.c_uint64 * 25), ("best", C.c_int32), ("notZero", C.c_int32), ("bio", C.c_int32), ("surface", C.c_int32 * 2)]
+
+
 class AffineMeResult(C.Structure):
     _fields_ = [("mv", (C.c_int * 2) * 3), ("bits", C.c_uint), ("cost", C.c_uint64), ("iterations", C.c_int), ("refinements", C.c_int)]
