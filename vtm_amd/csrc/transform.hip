@@ -264,10 +264,20 @@ struct TuResultStore
   }
 };
 
+// What the chain kernels may leave out (the `flags` argument; on unless the environment says otherwise):
+//   TU_ZERO_SKIP   VTMHIP_TU_ZERO_SKIP=0    the inverse half runs for TUs without a non-zero level too
+enum { TU_ZERO_SKIP = 1 };
+
+static int tu_chain_flags()
+{
+  static const int flags = env_switch( "VTMHIP_TU_ZERO_SKIP", true ) ? TU_ZERO_SKIP : 0;
+  return flags;
+}
+
 template<int TPT, bool CRS>
 __global__ __launch_bounds__( 256 ) void tu_chain_kernel( const int16_t *__restrict__ resiBase, const vtmhip_tu_job *__restrict__ jobs, int numJobs,
                                                          TrTables tabs, int *__restrict__ levelsBase, int16_t *__restrict__ recBase,
-                                                         vtmhip_tu_result *__restrict__ results, int maxW, int maxH )
+                                                         vtmhip_tu_result *__restrict__ results, int maxW, int maxH, int flags )
 {
   extern __shared__ __attribute__( ( aligned( 16 ) ) ) int ldsw[];
   __shared__ long long sRed[4][3];
@@ -337,20 +347,31 @@ __global__ __launch_bounds__( 256 ) void tu_chain_kernel( const int16_t *__restr
         blk[i] = qr.dequant( q );
       }
     }
-    chain_sync<TPT>();
-    // inverse: TrQuant::xIT, then SSE against the residual
-    lds_load_matrix( tabs.m[j.typeVer][lh], h, sM, t, TPT );
-    chain_sync<TPT>();
-    lds_inv_pass( blk, w, sM, h, w, w - skipW, h - skipH, 7, t, TPT, [&]( int, int i, int y, int v ) { tmp[i * h + y] = v; } );
-    chain_sync<TPT>();
-    lds_load_matrix( tabs.m[j.typeHor][lw], w, sM, t, TPT );
-    chain_sync<TPT>();
     int16_t *rec = recBase ? recBase + j.outOff : nullptr;
-    lds_inv_pass( tmp, h, sM, w, h, ALL_LINES, w - skipW, 20 - bd, t, TPT, [&]( int o, int, int, int v ) {
-      if( CRS && adj ) v = lmcs_inv( v, adj, maxAbs );
-      if( rec ) rec[o] = ( int16_t ) v;
-      sse_add( sse, ( int ) sR[o] - ( int ) ( int16_t ) v );
-    } );
+    if( chain_sync_none<TPT>( absSum != 0 ) && ( flags & TU_ZERO_SKIP ) )
+    {
+      // no non-zero level (this wave's TU / this workgroup's): the inverse of zeros is zero, see tu_chain_uni_kernel
+      for( int i = t; i < w * h; i += TPT )
+      {
+        if( rec ) rec[i] = 0;
+        sse_add( sse, ( int ) sR[i] );
+      }
+    }
+    else
+    {
+      // inverse: TrQuant::xIT, then SSE against the residual
+      lds_load_matrix( tabs.m[j.typeVer][lh], h, sM, t, TPT );
+      chain_sync<TPT>();
+      lds_inv_pass( blk, w, sM, h, w, w - skipW, h - skipH, 7, t, TPT, [&]( int, int i, int y, int v ) { tmp[i * h + y] = v; } );
+      chain_sync<TPT>();
+      lds_load_matrix( tabs.m[j.typeHor][lw], w, sM, t, TPT );
+      chain_sync<TPT>();
+      lds_inv_pass( tmp, h, sM, w, h, ALL_LINES, w - skipW, 20 - bd, t, TPT, [&]( int o, int, int, int v ) {
+        if( CRS && adj ) v = lmcs_inv( v, adj, maxAbs );
+        if( rec ) rec[o] = ( int16_t ) v;
+        sse_add( sse, ( int ) sR[o] - ( int ) ( int16_t ) v );
+      } );
+    }
   }
   long long sums[3] = { sumAbs, absSum, sse };
   chain_reduce_store<TPT, 3>( sums, sRed, sub, t, true, TuResultStore{ results + jobIdx } );
@@ -446,7 +467,7 @@ int launch_tu_lane( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_
 template<int LPT, bool CRS>
 __global__ __launch_bounds__( 256 ) void tu_chain_uni_kernel( const int16_t *__restrict__ resiBase, const vtmhip_tu_job *__restrict__ jobs, int numJobs,
                                                              TrTables tabs, int *__restrict__ levelsBase, int16_t *__restrict__ recBase,
-                                                             vtmhip_tu_result *__restrict__ results, int w, int h, int *__restrict__ fwdCoefBase )
+                                                             vtmhip_tu_result *__restrict__ results, int w, int h, int *__restrict__ fwdCoefBase, int flags )
 {
   // fwdCoefBase != nullptr: forward transform only (TrQuant::xT): coefficients to fwdCoefBase + outOff, sum|coef| to results
   extern __shared__ __attribute__( ( aligned( 16 ) ) ) int ldsw[];
@@ -516,14 +537,26 @@ __global__ __launch_bounds__( 256 ) void tu_chain_uni_kernel( const int16_t *__r
         dq16[( ( i & ( w - 1 ) ) << lh ) + ( i >> lw )] = ( int16_t ) qr.dequant( q );   // transposed: the vertical index contiguous
       }
     }
-    chain_sync<LPT>();
-    // inverse (TrQuant::xIT): tmp[i][y] = clip( sum_k blk[k][i] * M_ver[k][y] );  rec[y][x] = clip( sum_k tmp[k][y] * M_hor[k][x] )
-    tuq_pass16<LPT, true>( dq16, h, reinterpret_cast<const unsigned *>( mH0 ), h - skipH, w, h, w - skipW, h, t16, 1, w, 7, t );
-    chain_sync<LPT>();
-    tuq_pass16<LPT, true>( t16, w, reinterpret_cast<const unsigned *>( mW ), w - skipW, h, w, h, w, rec32, w, 1, 20 - bd, t );
-    chain_sync<LPT>();
+    // (The transposed dq16 stores above are wasted on the path below: the vote can only follow the loop that forms the levels.)
+    // No non-zero level in this wave / workgroup (the reference's `if( currAbsSum > 0 )` around invTransformNxN, InterSearch.cpp:6693): the inverse of zeros is
+    // zero -- (0 + rnd) >> shift = 0, clip( 0 ) = 0, lmcs_inv( 0 ) = 0 -- so the reconstruction is written as zeros and the SSE is sum resi^2.
+    const bool allZero = chain_sync_none<LPT>( live && absSum != 0 ) && ( flags & TU_ZERO_SKIP );
+    int16_t   *rec = ( recBase && live ) ? recBase + j.outOff : nullptr;
+    if( allZero )
     {
-      int16_t *rec = ( recBase && live ) ? recBase + j.outOff : nullptr;
+      for( int i = t; i < w * h; i += LPT )
+      {
+        if( rec ) rec[i] = 0;
+        sse_add( sse, ( int ) resi[( long ) ( i >> lw ) * j.resiStride + ( i & ( w - 1 ) )] );
+      }
+    }
+    else
+    {
+      // inverse (TrQuant::xIT): tmp[i][y] = clip( sum_k blk[k][i] * M_ver[k][y] );  rec[y][x] = clip( sum_k tmp[k][y] * M_hor[k][x] )
+      tuq_pass16<LPT, true>( dq16, h, reinterpret_cast<const unsigned *>( mH0 ), h - skipH, w, h, w - skipW, h, t16, 1, w, 7, t );
+      chain_sync<LPT>();
+      tuq_pass16<LPT, true>( t16, w, reinterpret_cast<const unsigned *>( mW ), w - skipW, h, w, h, w, rec32, w, 1, 20 - bd, t );
+      chain_sync<LPT>();
       for( int i = t; i < w * h; i += LPT )
       {
         int v = rec32[i];
@@ -548,7 +581,7 @@ int launch_tu_uni( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_tu_j
     VTMHIP_HIP( ctx, hipFuncSetAttribute( reinterpret_cast<const void *>( tu_chain_uni_kernel<LPT, CRS> ), hipFuncAttributeMaxDynamicSharedMemorySize, ( int ) lds ) );
   VTMHIP_TIME_KERNEL( ctx, "tu_chain_uni_kernel" );
   hipLaunchKernelGGL( ( tu_chain_uni_kernel<LPT, CRS> ), dim3( ( n + TUS - 1 ) / TUS ), dim3( 256 ), lds, ctx->stream, d_resiBase, d_jobs, n, tabs, d_levelsBase, d_recBase,
-                      d_results, w, h, d_fwdCoefBase );
+                      d_results, w, h, d_fwdCoefBase, tu_chain_flags() );
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;
 }
@@ -617,12 +650,12 @@ int tu_chain_generic( vtmhip_ctx *ctx, const int16_t *d_resiBase, const vtmhip_t
   if( maxWidth * maxHeight <= 256 )
   {
     hipLaunchKernelGGL( ( tu_chain_kernel<64, CRS> ), dim3( ( n + 3 ) / 4 ), dim3( 256 ), 4 * perTu * sizeof( int ), ctx->stream, d_resiBase, d_jobs, n,
-                        tabs_of( ctx ), d_levelsBase, d_recBase, d_results, maxWidth, maxHeight );
+                        tabs_of( ctx ), d_levelsBase, d_recBase, d_results, maxWidth, maxHeight, tu_chain_flags() );
   }
   else
   {
     hipLaunchKernelGGL( ( tu_chain_kernel<256, CRS> ), dim3( n ), dim3( 256 ), perTu * sizeof( int ), ctx->stream, d_resiBase, d_jobs, n,
-                        tabs_of( ctx ), d_levelsBase, d_recBase, d_results, maxWidth, maxHeight );
+                        tabs_of( ctx ), d_levelsBase, d_recBase, d_results, maxWidth, maxHeight, tu_chain_flags() );
   }
   VTMHIP_LAUNCHED( ctx );
   return VTMHIP_OK;

@@ -84,6 +84,23 @@ __device__ __forceinline__ void chain_sync()
   else __syncthreads();
 }
 
+// chain_sync that also votes: true when NO lane raised `flag`.  The vote is taken over everything that would have to take the other path together -- the whole
+// wave for LANES <= 64 (a lane group that left the work alone inside a busy wave saves nothing), the whole workgroup above (__syncthreads_or is the barrier, so
+// both paths meet the same number of them) -- and is therefore uniform over the wave / workgroup.  The chains decide "no level of these TUs is non-zero" with
+// it: a lane raises its flag when its partial sum of |level| is not zero (the partials are non-negative, so all partials zero <=> all levels zero); the lanes
+// of dead groups never raise it.
+template<int LANES>
+__device__ __forceinline__ bool chain_sync_none( bool flag )
+{
+  if( LANES <= 64 )
+  {
+    const bool none = __ballot( flag ) == 0;
+    chain_sync<LANES>();
+    return none;
+  }
+  return !__syncthreads_or( flag );
+}
+
 // K sums over the group: xor-shuffles inside a wave, across the LANES / 64 waves of the group through sRed ([waves of the workgroup][K]; unused, may be null, for
 // LANES <= 64).  Lane t == 0 of a live group then calls store( totals ), which packs them into the kernel's result struct.  Every lane of the workgroup must
 // arrive (LANES > 64 meets at barriers).
