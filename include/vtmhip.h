@@ -1117,10 +1117,91 @@ int vtmhip_symmvdCheckBestMvp_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_param
  * motionCompensation( pu, ..., luma ) -- plain uni / bi prediction, BDOF or DMVR (+ BDOF) by the candidate's motion -- and the Hadamard (or SAD)
  * distortion against the original block; the candidate's bits x sqrt(lambda) and the sorted insertion (updateCandList) stay with the host.
  * One call: the three job tables (candidates grouped by the kind of prediction; any may be empty) -> predictions into d_predBase + predOff (kept:
- * they are the encoder's acMergeBuffer) -> d_dist[nPlain + nBdof + nDmvr] in table order.  Jobs: epilogue 0; d_mvd as vtmhip_dmvr_batch_dev. */
+ * they are the encoder's acMergeBuffer) -> d_dist[nPlain + nBdof + nDmvr] in table order.  Jobs: epilogue 0; d_mvd as vtmhip_dmvr_batch_dev.
+ * The MMVD candidates have an entry of their own, vtmhip_mmvd_cand_satd_batch_dev below: it derives them on the device and keeps no prediction. */
 int vtmhip_merge_cand_satd_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, int16_t *d_predBase,
                                       const vtmhip_pred_job *d_plain, int nPlain, const vtmhip_pred_job *d_bdof, int nBdof, const vtmhip_dmvr_job *d_dmvr, int nDmvr,
                                       int32_t *d_mvd, int maxWidth, int maxHeight, int uniformSize, int useSatd, uint64_t *d_dist );
+
+/* ---- MMVD merge candidates: the MMVD loop of the same pre-selection (EncCu.cpp:2524-2562, hook B10) -----------------------------------------
+ * Per CU the reference walks up to MMVD_ADD_NUM = 64 candidates: MergeCtx::setMmvdMergeCandiInfo (ContextModelling.cpp:355-528) turns the index into a motion,
+ * motionCompensation predicts the luma block into ONE buffer (singleMergeTempBuffer, swapped into the list only on an insertion) and the Hadamard (or SAD) against
+ * the original is the candidate's distortion.  Here one job is one CU with its (up to) two base candidates; the 64 motions are derived on the device, the plain
+ * predictions never leave the kernel, and what comes back per (job, candidate) is the distortion and the record the host needs for xCalcPuMeBits, spanMotionInfo and
+ * to predict a survivor again through the motion-compensation entries (the RD stage does that with mmvdEncOptMode 0, EncCu.cpp:2668-2740).
+ *
+ * Candidate index (ContextModelling.cpp:367-373): cand = base * 32 + step * 4 + pos, base 0 / 1, step 0 .. 7, pos 0 .. 3.  The offset is ( 1 << step ) << 2 in 1/16
+ * units, << 2 more under picHeader.getDisFracMMVD() (:374-378); pos 0: +hor, 1: -hor, 2: +ver, 3: -ver.  A bi base gives the offset to the list whose picture is
+ * further away (or to both on equal POC differences) and the other list the offset scaled by PU::getDistScaleFactor / Mv::scaleMv, or -- either picture long-term --
+ * copied / mirrored by the sign of ( poc1 - cur ) * ( poc0 - cur ) (:382-452); a uni base moves its one list (:453-500).  The lists in use go through
+ * clipToStorageBitDepth (:518-524) and PU::restrictBiPredMergeCandsOne (:527, UnitTools.cpp:3262: width + height == 12 makes a bi candidate uni list 0 with the
+ * default BCW weight).  The loop (EncCu.cpp:2528-2534) tests 64 candidates when numValidMergeCand > 1, else 32 -- numBase 2 / 1 here -- and skips step >=
+ * MmvdDisNum -- numSteps.
+ * The prediction (InterPrediction.cpp:527-572): BDOF iff bdofAllowed, the restricted candidate is bi, PU::isBiPredFromDifferentDirEqDistPoc (neither picture
+ * long-term, opposite sides, equal distance), w >= 8, h >= 8, w * h >= 128, default BCW weight and step <= 2 (mmvdEncOptMode 2 for refineStep > 2 switches BDOF
+ * off, :563-565); DMVR never (PU::checkDMVRCondition excludes mmvdMergeFlag).  Otherwise plain: uni, addAvg, or addWeightedAvg under the base's BCW weight; a bi
+ * candidate whose two lists name the same picture (equal pocDiff) with equal vectors is predicted from list 0 alone (xCheckIdenticalMotion :240-272, :1564).  The
+ * vector a prediction uses is clipMv of the stored one at the CU's luma position (Mv.cpp:56-74); the record carries the stored one. */
+typedef struct
+{
+  int32_t mv[2][2];             /* mmvdBaseMv[base][list].mv: [list][hor, ver], internal 1/16 precision */
+  int64_t refOff[2];            /* block position with MV (0,0) in the list-0 / list-1 reference plane, as vtmhip_pred_job (unused where refIdx < 0) */
+  int32_t refStride[2];
+  int32_t pocDiff[2];           /* slice.getRefPOC( list, refIdx ) - slice.getPOC() */
+  int8_t  refIdx[2];            /* mmvdBaseMv[base][list].refIdx; -1: the list is not used.  Not ( -1, -1 ) */
+  uint8_t longTerm[2];          /* slice.getRefPic( list, refIdx )->longTerm */
+  uint8_t useAltHpelIf;         /* mergeCtx.mmvdUseAltHpelIf[base] */
+  int8_t  bcwWeightL1;          /* g_BcwWeights[mergeCtx.BcwIdx[base]] in {-2, 3, 4, 5, 10}: the list-1 weight of vtmhip_add_weighted_avg_batch_dev; used when the base is bi */
+  uint8_t pad[2];
+} vtmhip_mmvd_base;
+
+typedef struct
+{
+  int64_t orgOff;               /* the CU's luma block in the original plane */
+  int32_t orgStride;
+  int32_t posX, posY;           /* cu.lumaPos(): what clipMv sees */
+  int16_t width, height;        /* 4 .. 128, powers of two, not 4 x 4 */
+  uint8_t bitDepth;             /* 8 .. 12 */
+  uint8_t numBase;              /* 1: numValidMergeCand <= 1, candidates 0 .. 31; 2: all 64 */
+  uint8_t numSteps;             /* m_pcEncCfg->getMmvdDisNum(): 1 .. 8, candidates of step >= numSteps are not tested */
+  uint8_t disFracMmvd;          /* picHeader.getDisFracMMVD() */
+  uint8_t bdofAllowed;          /* sps.getBDOFEnabledFlag() && !picHeader.getDisBdofFlag(), no weighted prediction, no scaled reference */
+  uint8_t pad[3];
+  vtmhip_mmvd_base base[2];     /* base[1] is not read when numBase == 1 */
+} vtmhip_mmvd_job;
+
+enum { VTMHIP_MMVD_NOT_TESTED = 0, VTMHIP_MMVD_PLAIN = 1, VTMHIP_MMVD_BDOF = 2, VTMHIP_MMVD_NUM_CAND = 64 };
+
+typedef struct
+{
+  int32_t mv[2][2];             /* pu.mv as setMmvdMergeCandiInfo leaves it (stored vector: before clipMv); ( 0, 0 ) on an unused list */
+  int8_t  refIdx[2];            /* pu.refIdx; -1 on an unused list */
+  uint8_t interDir;             /* pu.interDir after restrictBiPredMergeCandsOne: 1, 2 or 3 */
+  int8_t  bcwWeightL1;          /* the weight of cu.BcwIdx: the base's when interDir == 3, else 4 */
+  uint8_t useAltHpelIf;         /* cu.imv == IMV_HPEL */
+  uint8_t kind;                 /* VTMHIP_MMVD_NOT_TESTED (the loop skips the candidate: every other field 0, refIdx -1), _PLAIN, _BDOF */
+  uint8_t pad[2];
+} vtmhip_mmvd_cand;
+
+int vtmhip_mmvd_struct_size( int which );   /* sizeof() of 0 vtmhip_mmvd_job, 1 vtmhip_mmvd_cand, 2 vtmhip_mmvd_base; -1 otherwise */
+
+/* The derivation alone, as host arithmetic (no device, no context): out[64] as the device leaves d_cand, predMv[cand][list][hor, ver] the clipped vectors the
+ * predictions use (0 on an unused list and where kind == 0).  VTMHIP_E_INVALID for a job the table predicate rejects (below) or pic outside its contract. */
+int vtmhip_mmvd_cands_host( const vtmhip_mmvd_job *job, const vtmhip_pic_params *pic, vtmhip_mmvd_cand out[64], int32_t predMv[64][2][2] );
+
+/* One call per batch of CUs: d_cand[n * 64] and d_dist[n * 64] at [job * 64 + cand]; d_dist is the SATD (useSatd != 0: the tile rules of xGetHADs) or SAD of the
+ * candidate's luma prediction against the original, UINT64_MAX where kind == VTMHIP_MMVD_NOT_TESTED.  maxWidth / maxHeight bound the CU sizes of the batch (lanes per
+ * block as vtmhip_mc_lanes_per_block).  The plain candidates run in one fused kernel (derivation, both predictions and the distortion, nothing but the cost and the
+ * record stored); the BDOF candidates (at most 24 per CU) are expanded into vtmhip_pred_job rows and run through vtmhip_bdof_batch_dev and the distortion call over
+ * an internal workspace.  VTMHIP_MMVD_FUSED=0 in the environment sends every candidate through that expansion (vtmhip_motion_compensation_batch_dev for the plain
+ * ones): a second route to the same tables, and the default for batches whose blocks take a workgroup each (maxWidth x maxHeight above 1024 samples), where it measured faster (VTMHIP_MMVD_FUSED=1: the fused
+ * kernel there too).  A BDOF candidate of a base with useAltHpelIf is predicted with the regular half-sample filter, as vtmhip_bdof_batch_dev predicts every PU.
+ * The job table is read back (n * sizeof( vtmhip_mmvd_job ) bytes, one stream synchronisation; never under stream capture) and checked before anything is launched; a
+ * malformed job REJECTS THE WHOLE CALL with VTMHIP_E_INVALID and nothing written: sides outside 4 .. 128 / not powers of two / 4 x 4 / above maxWidth x maxHeight,
+ * numBase outside 1 .. 2, numSteps outside 1 .. 8, a base in use with refIdx ( -1, -1 ), bitDepth outside 8 .. 12 or different from pic->bitDepth, a stride below
+ * the width, a BCW weight outside {-2, 3, 4, 5, 10}.  Reference planes as described under VTMHIP_PLANE_SLACK. */
+int vtmhip_mmvd_cand_satd_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, const vtmhip_mmvd_job *d_jobs,
+                                     int n, int maxWidth, int maxHeight, int useSatd, vtmhip_mmvd_cand *d_cand, uint64_t *d_dist );
 
 /* ================================================================================================================
  * (4) LEVEL-ORDER predInterSearch -- InterSearch::predInterSearch (InterSearch.cpp:2245-3065, translational part: cu.imv 0, default

@@ -27,6 +27,7 @@ enum vtmhip_work_slot
   VTMHIP_WORK_BOX_SUMS,           // the picture loop's 8x8 box sums (driver.hip): attached across a picture, over every call the picture makes on this stream
   VTMHIP_WORK_INTRA_CHAIN,        // the intra luma residual chain (intra_chain.hip), over the chains it runs
   VTMHIP_WORK_INTRA_CHROMA_CHAIN, // the intra chroma residual chain (intra_chroma_chain.hip), over the chains it runs
+  VTMHIP_WORK_MMVD,               // the MMVD candidates' expansion (mmvd.hip): job rows, predictions and costs, over the prediction and distortion calls it runs
 };
 
 struct vtmhip_ctx

@@ -390,6 +390,11 @@ class Context:
         self._check(self.L.vtmhip_merge_cand_satd_batch_dev(self.h, C.byref(pic), d_org, d_ref, d_pred, d_plain, n_plain, d_bdof, n_bdof, d_dmvr, n_dmvr, d_mvd, max_w, max_h,
                                                             int(uniform), int(use_satd), d_dist))
 
+    def mmvd_cand_satd_batch(self, pic, d_org, d_ref, d_jobs, n, max_w, max_h, d_cand, d_dist, use_satd=True):
+        """the MMVD loop of the same pre-selection: n MmvdJob CUs -> MmvdCand records and uint64 costs at [job * 64 + cand] (UINT64_MAX where kind == 0).  A malformed
+        table is rejected whole (VtmHipError, nothing launched)."""
+        self._check(self.L.vtmhip_mmvd_cand_satd_batch_dev(self.h, C.byref(pic), d_org, d_ref, d_jobs, n, max_w, max_h, int(use_satd), d_cand, d_dist))
+
     def pis_stage(self, level, stage):
         self._check(self.L.vtmhip_pis_stage(self.h, C.byref(level), stage))
 

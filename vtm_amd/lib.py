@@ -405,6 +405,24 @@ class IspGeom(C.Structure):
                 ("typeHor", C.c_int32), ("typeVer", C.c_int32)]
 
 
+class MmvdBase(C.Structure):
+    _fields_ = [("mv", (C.c_int32 * 2) * 2), ("refOff", C.c_int64 * 2), ("refStride", C.c_int32 * 2), ("pocDiff", C.c_int32 * 2), ("refIdx", C.c_int8 * 2),
+                ("longTerm", C.c_uint8 * 2), ("useAltHpelIf", C.c_uint8), ("bcwWeightL1", C.c_int8), ("pad", C.c_uint8 * 2)]
+
+
+class MmvdJob(C.Structure):
+    _fields_ = [("orgOff", C.c_int64), ("orgStride", C.c_int32), ("posX", C.c_int32), ("posY", C.c_int32), ("width", C.c_int16), ("height", C.c_int16),
+                ("bitDepth", C.c_uint8), ("numBase", C.c_uint8), ("numSteps", C.c_uint8), ("disFracMmvd", C.c_uint8), ("bdofAllowed", C.c_uint8), ("pad", C.c_uint8 * 3),
+                ("base", MmvdBase * 2)]
+
+
+class MmvdCand(C.Structure):
+    _fields_ = [("mv", (C.c_int32 * 2) * 2), ("refIdx", C.c_int8 * 2), ("interDir", C.c_uint8), ("bcwWeightL1", C.c_int8), ("useAltHpelIf", C.c_uint8),
+                ("kind", C.c_uint8), ("pad", C.c_uint8 * 2)]
+
+
+MMVD_NUM_CAND, MMVD_NOT_TESTED, MMVD_PLAIN, MMVD_BDOF = 64, 0, 1, 2
+
 _STRUCTS = [DistJob, TzJob, MeResult, PicParams, IfJob, FracJob, FracResult, TrJob, QuantJob, FullJob, McJob, PelOpJob,
             TuJob, TuResult, AffineJob, MeCfg, MeJob, MeOut, PredJob, MaskedSadJob, GeoBlendJob, DmvrJob, LfnstJob,
             PisRow, PisPu, PisLevel, AffineMeJob, AffineMeOut, LfnstTuJob, PisLevelRun, PisBuffers, SmvdJob, PisPuIn, WtdJob,
@@ -419,6 +437,7 @@ _INTRA_CHAIN_STRUCTS = [IntraTuJob, IntraTuResult]            # order of vtmhip_
 _LFNST_CHAIN_STRUCTS = [LfnstChainJob, IntraLfnstTuJob]       # order of vtmhip_lfnst_chain_struct_size(which)
 _INTRA_CHROMA_CHAIN_STRUCTS = [IntraChromaTuJob, IntraChromaJointJob, IntraChromaJointResult]   # order of vtmhip_intra_chroma_chain_struct_size(which)
 _ISP_STRUCTS = [IspJob, IspResult, IspGeom]                   # order of vtmhip_isp_struct_size(which)
+_MMVD_STRUCTS = [MmvdJob, MmvdCand, MmvdBase]                 # order of vtmhip_mmvd_struct_size(which)
 
 # every symbol include/vtmhip.h declares (tests/test_abi.py checks the exports against the header text)
 _PROTOS = {
@@ -602,6 +621,10 @@ _PROTOS = {
     "vtmhip_kernel_timing_read": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "vtmhip_merge_cand_satd_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(PicParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                                    C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vtmhip_mmvd_struct_size": (C.c_int, [C.c_int]),
+    "vtmhip_mmvd_cands_host": (C.c_int, [C.POINTER(MmvdJob), C.POINTER(PicParams), C.c_void_p, C.c_void_p]),
+    "vtmhip_mmvd_cand_satd_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(PicParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                  C.c_void_p]),
     "vtmhip_pis_run_picture": (C.c_int, [C.c_void_p, C.POINTER(PisLevelRun), C.c_int, C.POINTER(PisBuffers), C.c_void_p, C.POINTER(C.c_void_p), C.c_int]),
     "vtmhip_pis_stage": (C.c_int, [C.c_void_p, C.POINTER(PisLevel), C.c_int]),
     "vtmhip_predInterSearch_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(PisLevelRun), C.POINTER(PisBuffers)]),
@@ -699,6 +722,10 @@ def load():
         if lib.vtmhip_isp_struct_size(i) != C.sizeof(s):
             raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
                               % (s.__name__, C.sizeof(s), lib.vtmhip_isp_struct_size(i)))
+    for i, s in enumerate(_MMVD_STRUCTS):
+        if lib.vtmhip_mmvd_struct_size(i) != C.sizeof(s):
+            raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
+                              % (s.__name__, C.sizeof(s), lib.vtmhip_mmvd_struct_size(i)))
     _lib = lib
     return lib
 
