@@ -12,6 +12,8 @@ pytestmark = pytest.mark.gpu
 
 SIZES = [(w, h) for w in (4, 8, 12, 16, 24, 32, 48, 64, 128) for h in (4, 8, 16, 32, 64, 128)]
 SIZES += [(2, 2), (2, 4), (2, 8), (2, 32), (6, 4), (4, 2), (8, 2), (16, 2), (64, 2), (10, 6)]   # chroma / odd shapes the scalar reference accepts
+# shapes at which a Hadamard tile rule narrowed to powers of two, or to sides from 8, picks another tile than xGetHADs: 4x8, 8x4, 4x4, 16x8 and 2x2 tiles
+TILE_RULE_SHAPES = ((8, 24), (16, 4), (12, 12), (48, 16), (6, 4), (2, 2))
 
 
 def test_pointer_surface_matches_oracle(ctx):
@@ -72,6 +74,33 @@ def test_dist_batch_matches_oracle(ctx):
         j.orgOff, j.curOff = y * W + x, off + (y + dy) * stride + x + dx
         j.orgStride, j.curStride, j.width, j.height, j.subShift, j.kind = W, stride, w, h, ss, kind
         exp[k] = ol.o_dist(kind, cur, ref.reshape(-1, stride), w, h, ss, org_off=j.orgOff, cur_off=j.curOff)
+    d_cur, d_ref = ctx.to_device(cur), ctx.to_device(ref)
+    d_jobs = ctx.to_device(np.frombuffer(jobs, np.uint8))
+    d_out = ctx.alloc(8 * n, np.uint64)
+    ctx.dist_batch(d_cur.ptr, d_ref.ptr, d_jobs.ptr, n, d_out.ptr)
+    got = d_out.to_host()
+    bad = np.nonzero(got != exp)[0]
+    assert bad.size == 0, (bad[:10], got[bad[:10]], exp[bad[:10]])
+
+
+def test_dist_batch_satd_tile_rule_shapes(ctx):
+    """The wave-per-job kernel's SATD at TILE_RULE_SHAPES, 16 jobs each."""
+    W, H = 128, 64
+    fr = synth.gen_frames_hard(W, H, 2)
+    cur = np.ascontiguousarray(fr[1])
+    ref, off, stride = synth.extend_plane(fr[0])
+    rng = np.random.default_rng(7)
+    n = 16 * len(TILE_RULE_SHAPES)
+    jobs = (DistJob * n)()
+    exp = np.zeros(n, np.uint64)
+    for k in range(n):
+        w, h = TILE_RULE_SHAPES[k // 16]
+        x, y = int(rng.integers(0, W - w + 1)), int(rng.integers(0, H - h + 1))
+        dx, dy = int(rng.integers(-16, 17)), int(rng.integers(-16, 17))
+        j = jobs[k]
+        j.orgOff, j.curOff = y * W + x, off + (y + dy) * stride + x + dx
+        j.orgStride, j.curStride, j.width, j.height, j.subShift, j.kind = W, stride, w, h, 0, 1
+        exp[k] = ol.o_dist(1, cur, ref.reshape(-1, stride), w, h, 0, org_off=j.orgOff, cur_off=j.curOff)
     d_cur, d_ref = ctx.to_device(cur), ctx.to_device(ref)
     d_jobs = ctx.to_device(np.frombuffer(jobs, np.uint8))
     d_out = ctx.alloc(8 * n, np.uint64)
@@ -148,9 +177,7 @@ def test_dist_uniform_batch_matches_oracle(ctx, kind):
     cur = np.ascontiguousarray((2 * fr[1].astype(np.int32) - rng.integers(0, 1024, fr[1].shape)).astype(np.int16))
     ref, off, stride = synth.extend_plane(fr[0])
     d_org, d_ref = ctx.to_device(cur), ctx.to_device(ref)
-    for (w, h) in ((8, 8), (16, 16), (32, 32), (64, 64), (128, 128), (16, 8), (8, 16), (32, 8), (8, 4), (4, 8), (4, 4), (64, 16), (24, 8), (12, 16)):
-        if kind == 1 and (w % 4 or h % 4):
-            continue
+    for (w, h) in ((8, 8), (16, 16), (32, 32), (64, 64), (128, 128), (16, 8), (8, 16), (32, 8), (8, 4), (4, 8), (4, 4), (64, 16), (24, 8), (12, 16)) + TILE_RULE_SHAPES:
         ss = 1 if (kind == 0 and h > 8 and w <= 64) else 0
         n = 333
         jobs = (DistJob * n)()

@@ -10,8 +10,10 @@
 // (org, or 2*org - otherPred) and the current prediction live in LDS, the normal equations are accumulated in exact 64-bit integers, and the
 // reference's fp64 arithmetic (the solver, the delta-vector rounding, the cost weighting) runs on the device in IEEE double (division and
 // multiplication correctly rounded, no contraction: the build uses -fno-fast-math -ffp-contract=off), so every decision is bit-identical.
+// The SATD of samples above 10 bits is block_dist_walk (dist_block.hpp: the tile is had_tile_shape, had.hpp); the packed Hadamard is specialised on its shapes.
 #include "ctx.hpp"
 #include "had.hpp"
+#include "dist_block.hpp"
 #include "mv_rules.hpp"
 #include "pel_pack.hpp"
 
@@ -355,7 +357,7 @@ __device__ __forceinline__ unsigned wave_sum_u32( unsigned v )
   return ( unsigned ) __builtin_amdgcn_readlane( t, 0 ) + ( unsigned ) __builtin_amdgcn_readlane( t, 16 ) + ( unsigned ) __builtin_amdgcn_readlane( t, 32 ) + ( unsigned ) __builtin_amdgcn_readlane( t, 48 );
 }
 
-// getDistPart( DF_HAD / DF_SAD ) of prediction vs pattern over the block (tile shapes of xGetHADs: RdCost.cpp:2837-2931), block-wide sum.
+// getDistPart( DF_HAD / DF_SAD ) of prediction vs pattern over the block, block-wide sum.
 // packed (bitDepth <= 10: |pattern - prediction| <= 3 * 1023): the 8x8 units of the packed 16-bit Hadamard, in pair order for the 16x8 / 8x16 tiles of a non-square
 // block.  A job with at most a quarter as many units as lanes gives a unit to a group of eight lanes (satd8_lanes); with more units a lane takes a whole unit (had.hpp),
 // the two halves of a tile in neighbouring lanes, each returns the finished tile value and the even lane counts it.
@@ -421,18 +423,10 @@ __device__ __forceinline__ unsigned long long block_dist( const int16_t *sPred, 
     }
     acc = wave_sum_u32( sum );
   }
-  else if( satd && !packed )
-  {
-    const int tw = w > h ? 16 : 8, th = w < h ? 16 : 8, tx = w / tw, nt = tx * ( h / th );
-    for( int t = threadIdx.x; t < nt; t += blockDim.x )
-    {
-      const int      y = ( t / tx ) * th, x = ( t - ( t / tx ) * tx ) * tw;
-      const int16_t *o = sPred + y * w + x, *cc = sPat + y * w + x;
-      acc += tw == 16 ? had_tile<16, 8>( o, w, cc, w ) : th == 16 ? had_tile<8, 16>( o, w, cc, w ) : had_tile<8, 8>( o, w, cc, w );
-    }
-  }
+  else if( satd && !packed ) acc = block_dist_walk( VTMHIP_DIST_SATD, sPred, w, sPat, w, w, h, 0, ( int ) threadIdx.x, ( int ) blockDim.x );
   else
   {
+    // not the walk's SAD: this branch is part of the packed kernels too, and with the walk here the 4-waves-per-SIMD one spills 92 bytes to scratch
     for( int i = threadIdx.x; i < w * h; i += blockDim.x ) acc += ( unsigned ) abs( ( int ) sPred[i] - ( int ) sPat[i] );
   }
   if( !( satd && packed ) ) acc = wave_reduce_add_u64( acc );

@@ -10,6 +10,8 @@
 //   satd8_grid_kernel   8x8 SATD of every aligned 8x8 block x (2r+1)^2 displacements: the reference tile of a
 //                       workgroup is staged ONCE in LDS with coalesced 16-byte loads and re-used by all displacements
 //                       (HBM traffic ~ one read of each picture; the kernel is integer-VALU bound).
+//   dist_uniform_kernel several jobs of one W x H per wave.
+// The SATD tile of a W x H block is had_tile_shape (had.hpp); the walk over a block's tiles is block_dist_walk (dist_block.hpp), here and in the host's tile count.
 #include <cstdlib>
 #include "ctx.hpp"
 #include "stage.hpp"
@@ -153,30 +155,7 @@ __global__ __launch_bounds__( 256 ) void dist_uniform_kernel( const int16_t *__r
   unsigned long long acc = 0;
   if( kind == VTMHIP_DIST_SATD )
   {
-    int tw, th;
-    if( w > h && ( h & 7 ) == 0 && ( w & 15 ) == 0 ) { tw = 16; th = 8; }
-    else if( w < h && ( w & 7 ) == 0 && ( h & 15 ) == 0 ) { tw = 8; th = 16; }
-    else if( w > h && ( h & 3 ) == 0 && ( w & 7 ) == 0 ) { tw = 8; th = 4; }
-    else if( w < h && ( w & 3 ) == 0 && ( h & 7 ) == 0 ) { tw = 4; th = 8; }
-    else if( ( h & 7 ) == 0 && ( w & 7 ) == 0 ) { tw = 8; th = 8; }
-    else if( ( h & 3 ) == 0 && ( w & 3 ) == 0 ) { tw = 4; th = 4; }
-    else { tw = 2; th = 2; }
-    const int tx = w / tw, ty = h / th;
-    for( int it = sub; live && it < tx * ty; it += lpj )
-    {
-      const int      y = ( it / tx ) * th, x = ( it % tx ) * tw;
-      const int16_t *o = org + ( long ) y * os + x;
-      const int16_t *c = cur + ( long ) y * cs + x;
-      unsigned       v;
-      if( tw == 16 ) v = had_tile<16, 8>( o, os, c, cs );
-      else if( th == 16 ) v = had_tile<8, 16>( o, os, c, cs );
-      else if( tw == 8 && th == 4 ) v = had_tile<8, 4>( o, os, c, cs );
-      else if( tw == 4 && th == 8 ) v = had_tile<4, 8>( o, os, c, cs );
-      else if( tw == 8 ) v = had_tile<8, 8>( o, os, c, cs );
-      else if( tw == 4 ) v = had_tile<4, 4>( o, os, c, cs );
-      else v = had_tile<2, 2>( o, os, c, cs );
-      acc += v;
-    }
+    if( live ) acc = block_dist_walk( VTMHIP_DIST_SATD, org, os, cur, cs, w, h, 0, sub, lpj );   // one tile per lane of the job's group
   }
   else
   {
@@ -427,16 +406,8 @@ extern "C" int vtmhip_dist_uniform_batch_dev( vtmhip_ctx *ctx, const int16_t *d_
   int items;
   if( kind == VTMHIP_DIST_SATD )
   {
-    const int w = width, h = height;
-    int tw, th;
-    if( w > h && ( h & 7 ) == 0 && ( w & 15 ) == 0 ) { tw = 16; th = 8; }
-    else if( w < h && ( w & 7 ) == 0 && ( h & 15 ) == 0 ) { tw = 8; th = 16; }
-    else if( w > h && ( h & 3 ) == 0 && ( w & 7 ) == 0 ) { tw = 8; th = 4; }
-    else if( w < h && ( w & 3 ) == 0 && ( h & 7 ) == 0 ) { tw = 4; th = 8; }
-    else if( ( h & 7 ) == 0 && ( w & 7 ) == 0 ) { tw = 8; th = 8; }
-    else if( ( h & 3 ) == 0 && ( w & 3 ) == 0 ) { tw = 4; th = 4; }
-    else { tw = 2; th = 2; }
-    items = ( w / tw ) * ( h / th );
+    const HadTile t = had_tile_shape( width, height );
+    items = ( width / t.w ) * ( height / t.h );
   }
   else items = ( width >> 3 ) * ( kind == VTMHIP_DIST_SAD ? height >> subShift : height );
   // lanes per job: SATD one tile per lane; SAD / SSE up to four 8-sample segments per lane (fewer waves, shorter reductions)

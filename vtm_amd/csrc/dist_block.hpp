@@ -1,24 +1,25 @@
-// dist_block.hpp -- the distortion of ONE (original block, candidate block) pair by one wave: SAD with row sub-sampling (RdCost.cpp:493-1003), SSE (:1783-2133) or SATD by
-// the tile rules of xGetHADs (:2837-2931).  Shared by dist_batch_kernel (dist.hip), the fused AMVR refinement of xMotionEstimation (mest.hip) and the fused intra
-// pre-selection (intra.hip).  The result is in every lane.  lanes_block_dist<L> is the same walk by a group of L <= 64 consecutive lanes of a wave (L a power of two,
-// `lane` the index inside the group): small blocks share a wave, one block per group.
+// dist_block.hpp -- the distortion of ONE (original block, candidate block) pair: SAD with row sub-sampling (RdCost.cpp:493-1003), SSE (:1783-2133) or SATD by the tile
+// rule of xGetHADs (had_tile_shape, had.hpp).  block_dist_walk is the walk over the block's work items -- 4-sample row segments (single samples for widths like 2 / 6),
+// Hadamard tiles -- by one lane of a group of any size: items first, first + step, ...; it returns that lane's partial sum and the caller reduces it its own way.
+// lanes_block_dist<L> is the walk by a group of L <= 64 consecutive lanes of a wave (L a power of two, `lane` the index inside the group) plus the shuffle reduction: the
+// result is in every lane of the group, so small blocks share a wave, one block per group; wave_block_dist is the L = 64 case.  Callers: dist.hip, mest.hip, the intra /
+// MIP / chroma bodies (the shuffle forms); interp.hip, smvd.hip, affine.hip, mmvd.hip (the walk, with a workgroup's reduction).
 #pragma once
 #include "ctx.hpp"
 #include "had.hpp"
 
-template<int L>
-__device__ __forceinline__ unsigned long long lanes_block_dist( int kind, const int16_t *org, int os, const int16_t *cur, int cs, int w, int h, int subShift, int lane )
+__device__ __forceinline__ unsigned long long block_dist_walk( int kind, const int16_t *org, int os, const int16_t *cur, int cs, int w, int h, int subShift, int first, int step )
 {
   unsigned long long acc = 0;
 
   if( kind == VTMHIP_DIST_SAD )
   {
-    // rows y = 0, step, 2*step ...; work items = (row, 4-sample segment), or single samples for widths like 2 / 6 (chroma)
+    // rows y = 0, 1 << ss, 2 << ss ...; work items = (row, 4-sample segment), or single samples for widths like 2 / 6 (chroma)
     const int ss = subShift, rows = ( h + ( 1 << ss ) - 1 ) >> ss, segs = w >> 2;
     unsigned  s = 0;
     if( ( w & 3 ) == 0 )
     {
-      for( int it = lane; it < rows * segs; it += L )
+      for( int it = first; it < rows * segs; it += step )
       {
         const int      r = it / segs, x = ( it - r * segs ) << 2;
         const int16_t *o = org + ( long ) ( r << ss ) * os + x;
@@ -29,7 +30,7 @@ __device__ __forceinline__ unsigned long long lanes_block_dist( int kind, const 
     }
     else
     {
-      for( int it = lane; it < rows * w; it += L )
+      for( int it = first; it < rows * w; it += step )
       {
         const int r = it / w, x = it - r * w;
         s += ( unsigned ) abs( ( int ) org[( long ) ( r << ss ) * os + x] - ( int ) cur[( long ) ( r << ss ) * cs + x] );
@@ -42,7 +43,7 @@ __device__ __forceinline__ unsigned long long lanes_block_dist( int kind, const 
     const int segs = w >> 2;
     if( ( w & 3 ) == 0 )
     {
-      for( int it = lane; it < h * segs; it += L )
+      for( int it = first; it < h * segs; it += step )
       {
         const int      r = it / segs, x = ( it - r * segs ) << 2;
         const int16_t *o = org + ( long ) r * os + x;
@@ -57,7 +58,7 @@ __device__ __forceinline__ unsigned long long lanes_block_dist( int kind, const 
     }
     else
     {
-      for( int it = lane; it < h * w; it += L )
+      for( int it = first; it < h * w; it += step )
       {
         const int r = it / w, x = it - r * w;
         const int d = ( int ) org[( long ) r * os + x] - ( int ) cur[( long ) r * cs + x];
@@ -65,33 +66,23 @@ __device__ __forceinline__ unsigned long long lanes_block_dist( int kind, const 
       }
     }
   }
-  else   // SATD: tile shape by the rules of xGetHADs (RdCost.cpp:2837-2931); one tile per lane
+  else   // SATD: one tile per item
   {
-    int tw, th;
-    if( w > h && ( h & 7 ) == 0 && ( w & 15 ) == 0 ) { tw = 16; th = 8; }
-    else if( w < h && ( w & 7 ) == 0 && ( h & 15 ) == 0 ) { tw = 8; th = 16; }
-    else if( w > h && ( h & 3 ) == 0 && ( w & 7 ) == 0 ) { tw = 8; th = 4; }
-    else if( w < h && ( w & 3 ) == 0 && ( h & 7 ) == 0 ) { tw = 4; th = 8; }
-    else if( ( h & 7 ) == 0 && ( w & 7 ) == 0 ) { tw = 8; th = 8; }
-    else if( ( h & 3 ) == 0 && ( w & 3 ) == 0 ) { tw = 4; th = 4; }
-    else { tw = 2; th = 2; }
-    const int tx = w / tw, ty = h / th;
-    for( int it = lane; it < tx * ty; it += L )
+    const HadTile t = had_tile_shape( w, h );
+    const int     tx = w / t.w, ty = h / t.h;
+    for( int it = first; it < tx * ty; it += step )
     {
-      const int      y = ( it / tx ) * th, x = ( it % tx ) * tw;
-      const int16_t *o = org + ( long ) y * os + x;
-      const int16_t *c = cur + ( long ) y * cs + x;
-      unsigned       v;
-      if( tw == 16 ) v = had_tile<16, 8>( o, os, c, cs );
-      else if( th == 16 ) v = had_tile<8, 16>( o, os, c, cs );
-      else if( tw == 8 && th == 4 ) v = had_tile<8, 4>( o, os, c, cs );
-      else if( tw == 4 && th == 8 ) v = had_tile<4, 8>( o, os, c, cs );
-      else if( tw == 8 ) v = had_tile<8, 8>( o, os, c, cs );
-      else if( tw == 4 ) v = had_tile<4, 4>( o, os, c, cs );
-      else v = had_tile<2, 2>( o, os, c, cs );
-      acc += v;
+      const int y = ( it / tx ) * t.h, x = ( it % tx ) * t.w;
+      acc += had_tile_of( t, org + ( long ) y * os + x, os, cur + ( long ) y * cs + x, cs );
     }
   }
+  return acc;
+}
+
+template<int L>
+__device__ __forceinline__ unsigned long long lanes_block_dist( int kind, const int16_t *org, int os, const int16_t *cur, int cs, int w, int h, int subShift, int lane )
+{
+  unsigned long long acc = block_dist_walk( kind, org, os, cur, cs, w, h, subShift, lane, L );
 #pragma unroll
   for( int o = L >> 1; o > 0; o >>= 1 ) acc += __shfl_xor( acc, o, 64 );
   return acc;

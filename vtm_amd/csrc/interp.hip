@@ -13,11 +13,13 @@
 // (intMv*4 + q) quarter samples: H pass (first, !last) on rows -3..H+3, V pass (!first, last).  Integer phases go
 // through the same FIR with taps {0,0,0,64,0,0,0,0}, which is arithmetically identical to filterCopy.
 // One wave per PU: window -> LDS once, 3 H passes per round (one per horizontal phase), 9 V passes + SATDs.
+// The generic kernel's block cost is block_dist_walk (dist_block.hpp: the SATD tile is had_tile_shape, had.hpp) summed over the wave.
 #include "ctx.hpp"
 #include "stage.hpp"
 #include "mest_glue.hpp"
 #include "mv_rules.hpp"
 #include "had.hpp"
+#include "dist_block.hpp"
 #include "pel_pack.hpp"
 
 #include <type_traits>
@@ -159,50 +161,10 @@ __global__ __launch_bounds__( 256 ) void if_batch_kernel( const int16_t *__restr
   }
 }
 
-// (Hadamard tiles: had.hpp)
-
 // distortion of the W x H block: org from global memory, candidate block in LDS (stride W); whole wave, result uniform
 __device__ __forceinline__ unsigned long long block_dist( const int16_t *org, int os, const int16_t *pred, int w, int h, bool useHad, int lane )
 {
-  unsigned long long acc = 0;
-  if( !useHad )
-  {
-    unsigned s = 0;
-    for( int i = lane; i < w * h; i += 64 )
-    {
-      const int y = i / w, x = i - y * w;
-      s += ( unsigned ) abs( ( int ) org[( long ) y * os + x] - ( int ) pred[y * w + x] );
-    }
-    acc = s;
-  }
-  else
-  {
-    int tw, th;   // xGetHADs tile rules (RdCost.cpp:2837-2931)
-    if( w > h && ( h & 7 ) == 0 && ( w & 15 ) == 0 ) { tw = 16; th = 8; }
-    else if( w < h && ( w & 7 ) == 0 && ( h & 15 ) == 0 ) { tw = 8; th = 16; }
-    else if( w > h && ( h & 3 ) == 0 && ( w & 7 ) == 0 ) { tw = 8; th = 4; }
-    else if( w < h && ( w & 3 ) == 0 && ( h & 7 ) == 0 ) { tw = 4; th = 8; }
-    else if( ( h & 7 ) == 0 && ( w & 7 ) == 0 ) { tw = 8; th = 8; }
-    else if( ( h & 3 ) == 0 && ( w & 3 ) == 0 ) { tw = 4; th = 4; }
-    else { tw = 2; th = 2; }
-    const int tx = w / tw, ty = h / th;
-    for( int it = lane; it < tx * ty; it += 64 )
-    {
-      const int      y = ( it / tx ) * th, x = ( it % tx ) * tw;
-      const int16_t *o = org + ( long ) y * os + x;
-      const int16_t *c = pred + y * w + x;
-      unsigned       v;
-      if( tw == 16 ) v = had_tile<16, 8>( o, os, c, w );
-      else if( th == 16 ) v = had_tile<8, 16>( o, os, c, w );
-      else if( tw == 8 && th == 4 ) v = had_tile<8, 4>( o, os, c, w );
-      else if( tw == 4 && th == 8 ) v = had_tile<4, 8>( o, os, c, w );
-      else if( tw == 8 ) v = had_tile<8, 8>( o, os, c, w );
-      else if( tw == 4 ) v = had_tile<4, 4>( o, os, c, w );
-      else v = had_tile<2, 2>( o, os, c, w );
-      acc += v;
-    }
-  }
-  return wave_reduce_add_u64( acc );
+  return wave_reduce_add_u64( block_dist_walk( useHad ? VTMHIP_DIST_SATD : VTMHIP_DIST_SAD, org, os, pred, w, w, h, 0, lane, 64 ) );
 }
 
 // getCostOfVectorWithPredictor( x, y, 0 ) with m_iCostScale = costScale (RdCost.h:314-315)

@@ -5,7 +5,7 @@
 // Two routes to the same tables:
 //   fused             mmvd_fused_kernel: a lane group (vtmhip_mc_lanes_per_block lanes) takes a slice of one CU's candidates.  It loads the original block into LDS
 //                     once and, per plain candidate, derives the motion, runs mc_block per list with a sink into LDS (clipped samples for a uni candidate; the list-0
-//                     14-bit block, then the average written over it for a bi one) and reduces the block to its cost by had.hpp's tiles straight from LDS.  The BDOF
+//                     14-bit block, then the average written over it for a bi one) and reduces the block to its cost by block_dist_walk (dist_block.hpp; the tile rule is had.hpp's had_tile_shape) straight from LDS.  The BDOF
 //                     candidates (at most 24 per CU) are expanded into vtmhip_pred_job rows and predictions in a workspace: vtmhip_bdof_batch_dev, the distortion
 //                     call, and a scatter of the costs to the candidates' slots.
 //   VTMHIP_MMVD_FUSED=0   every candidate is expanded: vtmhip_motion_compensation_batch_dev (uni, addAvg), vtmhip_mc_batch_dev + vtmhip_add_weighted_avg_batch_dev
@@ -16,7 +16,7 @@
 #include "stage.hpp"
 #include "mc_block.hpp"
 #include "mv_rules.hpp"
-#include "had.hpp"
+#include "dist_block.hpp"
 #include "mmvd_rules.hpp"
 
 // the host / device restatement of clipMvInPic against the device's definition
@@ -58,44 +58,6 @@ struct AvgOver
     *reinterpret_cast<uint4 *>( p + y * w + x0 ) = pack8( r );
   }
 };
-
-// this lane's share of the cost of a w x h block (the prediction in LDS, rows of w; the original with rows of os): SAD over 4-sample segments, or SATD with the tile shape of xGetHADs
-// (RdCost.cpp:2837-2931) for sides that are powers of two from 4 -- the rule of dist_block.hpp -- one tile per step
-template<int THREADS>
-__device__ __forceinline__ unsigned long long mmvd_cost_share( bool satd, const int16_t *org, int os, const int16_t *cur, int w, int h, int lane )
-{
-  unsigned long long acc = 0;
-  if( !satd )
-  {
-    unsigned s = 0;
-    const int lgSegs = 29 - __clz( w );   // 4-sample segments per row
-    for( int it = lane; it < ( w * h ) >> 2; it += THREADS )
-    {
-      const int16_t *o = org + ( it >> lgSegs ) * os + ( ( it & ( ( 1 << lgSegs ) - 1 ) ) << 2 );
-#pragma unroll
-      for( int k = 0; k < 4; k++ ) s += ( unsigned ) abs( ( int ) o[k] - ( int ) cur[4 * it + k] );
-    }
-    return s;
-  }
-  int tw, th;
-  if( w > h && h >= 8 ) { tw = 16; th = 8; }
-  else if( w < h && w >= 8 ) { tw = 8; th = 16; }
-  else if( w > h ) { tw = 8; th = 4; }
-  else if( w < h ) { tw = 4; th = 8; }
-  else { tw = 8; th = 8; }   // squares from 8 x 8 (4 x 4 is no MMVD CU)
-  const int tx = w / tw, tiles = tx * ( h / th );
-  for( int it = lane; it < tiles; it += THREADS )
-  {
-    const int      y = ( it / tx ) * th, x = ( it % tx ) * tw;
-    const int16_t *o = org + y * os + x, *c = cur + y * w + x;
-    if( tw == 16 ) acc += had_tile<16, 8>( o, os, c, w );
-    else if( th == 16 ) acc += had_tile<8, 16>( o, os, c, w );
-    else if( th == 4 ) acc += had_tile<8, 4>( o, os, c, w );
-    else if( tw == 4 ) acc += had_tile<4, 8>( o, os, c, w );
-    else acc += had_tile<8, 8>( o, os, c, w );
-  }
-  return acc;
-}
 
 // THREADS lanes per group and JPB groups per workgroup as motion_comp_kernel (mc.hip); an item is (job, slice): `cpi` consecutive candidates of one CU
 template<int THREADS, int JPB>
@@ -151,7 +113,7 @@ __global__ __launch_bounds__( THREADS * JPB ) void mmvd_fused_kernel( vtmhip_pic
       mc_any<THREADS>( m, refBase, tmp, lane, AvgOver{ pred, w, headRoom + 1, ( 1 << j.bitDepth ) - 1, rec.bcwWeightL1 } );
       block_sync<THREADS>();
     }
-    unsigned long long cost = mmvd_cost_share<THREADS>( useSatd != 0, org, os, pred, w, h, lane );
+    unsigned long long cost = block_dist_walk( useSatd ? VTMHIP_DIST_SATD : VTMHIP_DIST_SAD, org, os, pred, w, w, h, 0, lane, THREADS );   // this lane's share
 #pragma unroll
     for( int o = ( THREADS < 64 ? THREADS : 64 ) >> 1; o > 0; o >>= 1 ) cost += __shfl_xor( cost, o, 64 );
     if( THREADS == 256 )

@@ -4,11 +4,12 @@
 // One workgroup per PU (one wave up to 32x32 samples, four above).  A candidate = two luma predictions (mc_block.hpp) + one distortion:
 //   pattern  = clip?( 2 * org - predA )      written by the sink of prediction A straight into LDS (removeHighFreq fused, BCW form included)
 //   predB                                   into LDS
-//   cost     = floor( fWeight * HAD-or-SAD( pattern, predB ) )    (tile shapes of RdCost::xGetHADs)
+//   cost     = floor( fWeight * HAD-or-SAD( pattern, predB ) )    (the generic kernel: block_dist_walk of dist_block.hpp, tile shapes by had_tile_shape of had.hpp)
 // The search control (rounds, directions, best-so-far) is workgroup-uniform: every lane derives it from the same reduced cost, so no state is shared
 // but the three LDS blocks.  HBM traffic per candidate is the two (w + 7) x (h + 7) windows, which stay in L2 across the ~40 candidates of a PU.
 #include "ctx.hpp"
 #include "had.hpp"
+#include "dist_block.hpp"
 #include "mc_block.hpp"
 #include "mv_rules.hpp"
 #include <cstdlib>
@@ -82,38 +83,11 @@ __device__ __forceinline__ void make_pattern( const SmvdCtx &c, int mvHor, int m
   predict<THREADS>( c, 0, mvHor, mvVer, po );
 }
 
-// getDistPart( DF_HAD / DF_SAD ) of pattern vs prediction B (tile shapes of xGetHADs, RdCost.cpp:2837-2931), workgroup-wide sum, same value in every lane
+// getDistPart( DF_HAD / DF_SAD ) of pattern vs prediction B (block_dist_walk, dist_block.hpp), workgroup-wide sum, same value in every lane
 template<int THREADS>
 __device__ __forceinline__ unsigned long long block_dist( const SmvdCtx &c )
 {
-  const int          w = c.w, h = c.h;
-  unsigned long long acc = 0;
-  if( c.satd )
-  {
-    int tw, th;
-    if( w > h && ( h & 7 ) == 0 && ( w & 15 ) == 0 ) { tw = 16; th = 8; }
-    else if( w < h && ( w & 7 ) == 0 && ( h & 15 ) == 0 ) { tw = 8; th = 16; }
-    else if( w > h && ( h & 3 ) == 0 && ( w & 7 ) == 0 ) { tw = 8; th = 4; }
-    else if( w < h && ( w & 3 ) == 0 && ( h & 7 ) == 0 ) { tw = 4; th = 8; }
-    else if( ( ( w | h ) & 7 ) == 0 ) { tw = 8; th = 8; }
-    else { tw = 4; th = 4; }
-    const int tx = w / tw, nt = tx * ( h / th );
-    for( int t = threadIdx.x; t < nt; t += THREADS )
-    {
-      const int      y = ( t / tx ) * th, x = ( t - ( t / tx ) * tx ) * tw;
-      const int16_t *o = c.sPat + y * w + x, *q = c.sB + y * w + x;
-      if( tw == 16 ) acc += had_tile<16, 8>( o, w, q, w );
-      else if( th == 16 ) acc += had_tile<8, 16>( o, w, q, w );
-      else if( tw == 8 && th == 8 ) acc += had_tile<8, 8>( o, w, q, w );
-      else if( tw == 8 ) acc += had_tile<8, 4>( o, w, q, w );
-      else if( th == 8 ) acc += had_tile<4, 8>( o, w, q, w );
-      else acc += had_tile<4, 4>( o, w, q, w );
-    }
-  }
-  else
-  {
-    for( int i = threadIdx.x; i < w * h; i += THREADS ) acc += ( unsigned ) abs( ( int ) c.sPat[i] - ( int ) c.sB[i] );
-  }
+  unsigned long long acc = block_dist_walk( c.satd ? VTMHIP_DIST_SATD : VTMHIP_DIST_SAD, c.sPat, c.w, c.sB, c.w, c.w, c.h, 0, ( int ) threadIdx.x, THREADS );
   acc = wave_reduce_add_u64( acc );
   if( THREADS == 64 ) return acc;
   if( ( threadIdx.x & 63 ) == 0 ) c.sRed[threadIdx.x >> 6] = acc;
