@@ -1203,6 +1203,104 @@ int vtmhip_mmvd_cands_host( const vtmhip_mmvd_job *job, const vtmhip_pic_params 
 int vtmhip_mmvd_cand_satd_batch_dev( vtmhip_ctx *ctx, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, const vtmhip_mmvd_job *d_jobs,
                                      int n, int maxWidth, int maxHeight, int useSatd, vtmhip_mmvd_cand *d_cand, uint64_t *d_dist );
 
+/* ---- CIIP merge candidates: the combined inter-intra loop of the same pre-selection (EncCu.cpp:2460-2523, hook B10) and its RD-stage blend (:2706-2735) ------
+ * Eligible (EncCu.cpp:2335-2339): sps.getUseCiip(), w * h >= 64, w < 128, h < 128 -- sides 4 .. 64, every combination of at least 64 samples.  The loop tests the
+ * first min( min( NUM_MRG_SATD_CAND = 4, numValidMergeCand ), 4 ) entries of RdModeList after the regular loop: at most four per CU.
+ *   inter part   acMergeTmpBuffer[cand]: the predBufWOBIO of the regular loop's motionCompensation -- the PLAIN prediction from the candidate's stored vectors:
+ *                uni = the rounded and clipped block, bi = the default-weight addAvg of the two 14-bit blocks; no BDOF, no DMVR refinement
+ *                (InterPrediction.cpp:594-599), no BCW weight (:1368), identical motion on both lists from list 0 alone (:1564-1572: the caller sends mode 0)
+ *   intra part   once per CU: planar, multiRefIdx 0, through initIntraPatternChType + predIntraAng under the regular rules (nothing tests ciipFlag): the [1 2 1]
+ *                line filter (refFilterFlag = w * h > 32: always for a CIIP luma block) and PDPC
+ *   blend        IntraPrediction::geneWeightedPred (IntraPrediction.cpp:682-722): wIntra = 3 / 2 / 1 when both / one / none of the PUs left of the bottom-left
+ *                sample and above the top-right sample exist and are intra; dst = ( ( 4 - wIntra ) * inter + wIntra * intra + 2 ) >> 2, no clip
+ *   LMCS         (slice flag and CTU flag) the inter luma block goes through the forward LUT before the blend, the blended block through the inverse LUT before
+ *                the distortion; the intra lines are reconstruction samples: mapped already
+ *   cost         distParam.distFunc -- SATD, or SAD under getDisableSATDForRD -- against the original luma block
+ * The bits, updateCandList and the MRG_FAST_RATIO cut stay with the host.  Outside: explicit weighted prediction, scaled references, 4:2:2 and 4:4:4. */
+
+/* The reshaper's inverse LUT (1 << lumaBD entries) for callers that do not use the weighted SSE; ordering and lifetime as vtmhip_set_lmcs_fwd_lut (copied before
+ * the call returns, visible to every later call on the context).  The slot is its own: vtmhip_set_luma_level_weights keeps the inverse LUT of the DF_SSE_WTD
+ * entries in another one, and neither setter touches the other's, so a caller of both sets the table twice. */
+int vtmhip_set_lmcs_inv_lut( vtmhip_ctx *ctx, const int16_t *invLut, int lumaBD );
+
+enum { VTMHIP_CIIP_MAX_CAND = 4 };
+
+typedef struct
+{
+  int64_t refOff[2];            /* modes 0 .. 2: block position with MV (0,0) in the list-0 / list-1 reference plane inside d_refBase, as vtmhip_pred_job */
+  int64_t srcOff;               /* mode 3: the inter luma block inside d_predBase */
+  int64_t keepOff;              /* -1, or where the blended luma block IN THE MAPPED DOMAIN is written inside d_predBase, stride width: the RD stage's luma prediction */
+  int32_t refStride[2];
+  int32_t mv[2][2];             /* [list][hor, ver], internal 1/16 precision: the vector the prediction uses, clipMv already applied (as vtmhip_pred_job) */
+  int32_t srcStride;            /* mode 3 */
+  uint8_t mode;                 /* 0: list 0, 1: list 1, 2: bi (default-weight addAvg), 3: the inter block is given at srcOff / srcStride -- what a caller holds after
+                                   vtmhip_merge_cand_satd_batch_dev for a candidate whose kept prediction is already the plain one (no BDOF, no DMVR, default BCW) */
+  uint8_t useAltHpelIf;
+  uint8_t pad[2];
+} vtmhip_ciip_cand;
+
+typedef struct
+{
+  int64_t lineOff;              /* inside d_lineBase: the top line of 2W + 1 samples, index 0 = the corner, then the left line of 2H + 1, index 0 = the same corner
+                                   (the lines of a vtmhip_intra_block with multiRefIdx 0) */
+  int64_t orgOff;               /* the CU's luma block in the original plane */
+  int32_t orgStride;
+  int16_t width, height;        /* 4 .. 64 each, width * height >= 64 */
+  uint8_t bitDepth;             /* 8 .. 12 */
+  uint8_t leftIntra;            /* the PU at bottomLeft.offset( -1, 0 ) exists and is intra */
+  uint8_t aboveIntra;           /* the PU at topRight.offset( 0, -1 ) exists and is intra */
+  uint8_t lmcs;                 /* slice.getLmcsEnabledFlag() && reshaper.getCTUFlag() */
+  uint8_t numCand;              /* 1 .. 4 */
+  uint8_t pad[3];
+  vtmhip_ciip_cand cand[VTMHIP_CIIP_MAX_CAND];
+} vtmhip_ciip_job;
+
+typedef struct
+{
+  int64_t lineOff;              /* as vtmhip_ciip_job, for this block's width and height (a chroma block: the lines of that plane) */
+  int64_t predOff;              /* the inter block inside d_predBase; the blend is written over it */
+  int32_t predStride;
+  int16_t width, height;        /* luma: as vtmhip_ciip_job; chroma: width 4 .. 32, height 2 .. 32, at least 16 samples (the 4:2:0 block of a CIIP CU).  A WIDTH of 2 is
+                                   malformed: the caller keeps the inter block, as the reference does (EncCu.cpp:2718); a height of 2 is blended, without PDPC */
+  uint8_t bitDepth;
+  uint8_t chroma;               /* DM_CHROMA of a planar luma: planar without the line filter, PDPC on */
+  uint8_t leftIntra, aboveIntra;   /* the LUMA neighbours, for chroma blocks too */
+  uint8_t mapFwd;               /* luma only: the inter block goes through the forward LUT first (the result stays in the mapped domain) */
+  uint8_t pad[3];
+} vtmhip_ciip_blend_job;
+
+int vtmhip_ciip_struct_size( int which );   /* sizeof() of 0 vtmhip_ciip_job, 1 vtmhip_ciip_cand, 2 vtmhip_ciip_blend_job; -1 otherwise */
+
+/* One CU as host arithmetic (no device, no context).  inter[k]: the plain inter luma block of candidate k, width x height with stride width, for EVERY mode (the
+ * host has no interpolation entry; refOff / mv / srcOff are not read).  fwdLut / invLut: needed iff job->lmcs.  blend: numCand blocks of width * height samples --
+ * the blended blocks in the mapped domain (what keepOff receives); satd[k] / sad[k]: both costs of candidate k against the original, UINT64_MAX from numCand on.
+ * VTMHIP_E_INVALID for a job the table predicate rejects (below, with maxWidth = maxHeight = 64) or a missing pointer. */
+int vtmhip_ciip_host( const vtmhip_ciip_job *job, const int16_t *lineBase, const int16_t *orgBase, const int16_t *const inter[VTMHIP_CIIP_MAX_CAND], const int16_t *fwdLut,
+                      const int16_t *invLut, int16_t *blend, uint64_t satd[VTMHIP_CIIP_MAX_CAND], uint64_t sad[VTMHIP_CIIP_MAX_CAND] );
+/* vtmhip_ciip_blend_batch_dev for one job on the host; fwdLut is needed iff job->mapFwd.  VTMHIP_E_INVALID for a job the device would skip. */
+int vtmhip_ciip_blend_host( const vtmhip_ciip_blend_job *job, const int16_t *lineBase, int16_t *predBase, const int16_t *fwdLut );
+
+/* One call per batch of CUs, one fused kernel: per CU the planar block with PDPC is formed once in LDS, and per candidate the inter block (motion compensation inside
+ * the kernel for modes 0 .. 2, a copy for mode 3), the forward LUT, the blend, the optional kept store, the inverse LUT and the distortion run from LDS.  Apart from
+ * the kept blocks no prediction sample goes to global memory.  d_dist[job * 4 + cand] = the SATD (useSatd != 0: the tile rules of xGetHADs) or SAD; a slot at or
+ * beyond numCand, and every slot of a skipped job, holds UINT64_MAX.  maxWidth x maxHeight (a well-formed CIIP size) bounds the CUs of the batch; lanes per CU as
+ * vtmhip_mc_lanes_per_block.
+ * The job table is never read back and the stream is never synchronised: the call only queues work and may run under stream capture.  A job that fails the
+ * predicate is skipped ON THE DEVICE -- nothing is read through it, its four costs are UINT64_MAX and no kept block is written: sides outside the CIIP set or
+ * above maxWidth x maxHeight, bitDepth outside 8 .. 12, numCand outside 1 .. 4, a mode above 3, a stride (orgStride, the refStride of a list in use, srcStride of
+ * mode 3) below the width, lmcs set in a call whose lmcs argument is 0, or lmcs set with a bitDepth that is not the LUTs'.
+ * lmcs != 0: jobs may set their lmcs flag; the call fails with VTMHIP_E_INVALID before launching anything when either LUT (vtmhip_set_lmcs_fwd_lut,
+ * vtmhip_set_lmcs_inv_lut) is missing or their depths differ.  A LUT index outside the table is held at its ends.  d_predBase may be NULL when no job has a
+ * mode-3 candidate or a kept block.  Reference planes as described under VTMHIP_PLANE_SLACK. */
+int vtmhip_ciip_cand_satd_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_lineBase, const int16_t *d_orgBase, int16_t *d_predBase,
+                                     const vtmhip_ciip_job *d_jobs, int n, int maxWidth, int maxHeight, int useSatd, int lmcs, uint64_t *d_dist );
+
+/* geneWeightedPred in place for n blocks: the RD stage's Cb and Cr blocks (chroma planar, the luma neighbour weights), and luma where the block was not kept.  Luma
+ * and chroma jobs mix freely.  Lanes per job follow the rule of vtmhip_intra_pred_batch_dev (vtmhip_intra_lanes_per_job of the largest well-formed block; a small
+ * kernel finds it: no read-back, no synchronisation).  A malformed job is skipped on the device and its block left as it is: a size outside what vtmhip_ciip_blend_job lists, a
+ * bitDepth outside 8 .. 12, predStride below the width, mapFwd on a chroma job, mapFwd without a forward LUT of the job's depth. */
+int vtmhip_ciip_blend_batch_dev( vtmhip_ctx *ctx, const int16_t *d_lineBase, int16_t *d_predBase, const vtmhip_ciip_blend_job *d_jobs, int n );
+
 /* ================================================================================================================
  * (4) LEVEL-ORDER predInterSearch -- InterSearch::predInterSearch (InterSearch.cpp:2245-3065, translational part: cu.imv 0, default
  *     BCW weight, no SMVD / affine) for ALL PUs of one block size at once, on top of the batched calls above

@@ -110,6 +110,7 @@ int vtmhip_destroy( vtmhip_ctx *ctx )
   if( ctx->wtdFixed ) ( void ) hipFree( ctx->wtdFixed );
   if( ctx->wtdInv ) ( void ) hipFree( ctx->wtdInv );
   if( ctx->lmcsFwd ) ( void ) hipFree( ctx->lmcsFwd );
+  if( ctx->lmcsInv ) ( void ) hipFree( ctx->lmcsInv );
   if( ctx->tzStats ) ( void ) hipFree( ctx->tzStats );
   if( ctx->tzRoundStats ) ( void ) hipFree( ctx->tzRoundStats );
   if( ctx->pinned ) ( void ) hipHostFree( ctx->pinned );

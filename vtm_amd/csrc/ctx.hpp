@@ -56,6 +56,8 @@ struct vtmhip_ctx
   bool        wtdHasInv   = false;
   int16_t    *lmcsFwd     = nullptr;   // LMCS: the reshaper's forward LUT, 1 << lmcsLumaBD entries (vtmhip_set_lmcs_fwd_lut)
   int         lmcsLumaBD  = 0;         // 0: no forward LUT set yet
+  int16_t    *lmcsInv     = nullptr;   // LMCS: the reshaper's inverse LUT, 1 << lmcsInvBD entries (vtmhip_set_lmcs_inv_lut; the DF_SSE_WTD entries keep theirs in wtdInv)
+  int         lmcsInvBD   = 0;         // 0: no inverse LUT set yet
   int16_t    *trTabBuf    = nullptr;   // the transform core matrices of THIS context's device (transform.hip ensure_tables; freed by vtmhip_destroy)
   const int16_t *trTab[3][7] = {};     // [type][log2 N] -> N x N forward matrix inside trTabBuf
   std::mutex  initMutex;               // guards the lazy per-context initialisations (tables, staging / workspace growth)

@@ -1,8 +1,10 @@
 // had.hpp -- 8x8 Hadamard SATD on packed 16-bit differences, the generic 32-bit tiles had_tile<TW, TH>, and the rule that picks the tile of a W x H block
-// (had_tile_shape, with had_tile_of to evaluate the tile it names).  The rule is stated here and nowhere else on the device; the walk over a block's tiles is
+// (had_tile_shape in had_tile_rule.hpp, with had_tile_of here to evaluate the tile it names).  The rule is stated there and nowhere else; the walk over a block's tiles is
 // block_dist_walk (dist_block.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "had_tile_rule.hpp"
 
 namespace
 {
@@ -294,28 +296,7 @@ __device__ __forceinline__ unsigned had_tile( const int16_t *o, int os, const in
   return had_finish<TW, TH>( m );
 }
 
-// ---- the tile that xGetHADs cuts a W x H block into (RdCost.cpp:2837-2931): the one statement of the rule, host and device -------------------
-struct HadTile { int w, h; };
-
-__host__ __device__ constexpr HadTile had_tile_shape( int w, int h )
-{
-  if( w > h && ( h & 7 ) == 0 && ( w & 15 ) == 0 ) return { 16, 8 };
-  if( w < h && ( w & 7 ) == 0 && ( h & 15 ) == 0 ) return { 8, 16 };
-  if( w > h && ( h & 3 ) == 0 && ( w & 7 ) == 0 ) return { 8, 4 };
-  if( w < h && ( w & 3 ) == 0 && ( h & 7 ) == 0 ) return { 4, 8 };
-  if( ( h & 7 ) == 0 && ( w & 7 ) == 0 ) return { 8, 8 };
-  if( ( h & 3 ) == 0 && ( w & 3 ) == 0 ) return { 4, 4 };
-  return { 2, 2 };
-}
-
-constexpr bool had_tile_is( int w, int h, int tw, int th ) { return had_tile_shape( w, h ).w == tw && had_tile_shape( w, h ).h == th; }
-// one shape per branch, and the shapes at which a rule narrowed to powers of two, or to sides from 8, answers differently
-static_assert( had_tile_is( 32, 8, 16, 8 ) && had_tile_is( 8, 32, 8, 16 ), "xGetHADs: 16x8 / 8x16" );
-static_assert( had_tile_is( 24, 8, 8, 4 ) && had_tile_is( 16, 4, 8, 4 ), "xGetHADs: 8x4 (24 is no multiple of 16)" );
-static_assert( had_tile_is( 8, 24, 4, 8 ) && had_tile_is( 12, 16, 4, 8 ), "xGetHADs: 4x8" );
-static_assert( had_tile_is( 8, 8, 8, 8 ), "xGetHADs: 8x8" );
-static_assert( had_tile_is( 12, 12, 4, 4 ) && had_tile_is( 4, 4, 4, 4 ), "xGetHADs: 4x4" );
-static_assert( had_tile_is( 6, 4, 2, 2 ) && had_tile_is( 2, 2, 2, 2 ), "xGetHADs: 2x2" );
+// ---- the tile that xGetHADs cuts a W x H block into: had_tile_rule.hpp (HadTile, had_tile_shape), without a HIP dependency so that host code states it nowhere else
 
 // the SATD of the tile of shape t at (o, os), (c, cs)
 __device__ __forceinline__ unsigned had_tile_of( HadTile t, const int16_t *o, int os, const int16_t *c, int cs )

@@ -15,12 +15,14 @@
 #include "ctx.hpp"
 #include "stage.hpp"
 #include "mc_block.hpp"
+#include "mc_sinks.hpp"   // ToLds, AvgOver: shared with ciip.hip
 #include "mv_rules.hpp"
 #include "dist_block.hpp"
 #include "mmvd_rules.hpp"
 
 // the host / device restatement of clipMvInPic against the device's definition
 static_assert( mmvdClipMax( 416, 24 ) == MVR_CLIP_MAX( 416, 24 ) && mmvdClipMax( 3840, 3832 ) == MVR_CLIP_MAX( 3840, 3832 ), "mmvd_rules.hpp: clipMvInPic maximum" );
+static_assert( ( int ) AVG_BCW_DEFAULT == ( int ) MMVD_BCW_DEFAULT, "mc_sinks.hpp: the weight that means addAvg" );
 static_assert( mmvdClipMin( 128, 0 ) == -( ( 128 + 8 - 1 ) << 4 ) && mmvdClipMin( 64, 200 ) == -( ( 64 + 8 + 200 - 1 ) << 4 ), "mmvd_rules.hpp: clipMvInPic minimum" );
 
 namespace
@@ -31,33 +33,6 @@ constexpr unsigned long long MMVD_NO_COST = ~0ull;
 // LDS of one lane group, in samples: the original block (orgInLds: the groups of up to a wave; a workgroup per block reads it from global memory, so that two
 // 128 x 128 workgroups fit a CU), the prediction, the H-pass intermediates of mc_block
 __host__ __device__ inline int mmvd_group_samples( int maxW, int maxH, bool orgInLds ) { return ( ( orgInLds ? 2 : 1 ) * maxW * maxH + maxW * ( maxH + 7 ) + 7 ) & ~7; }
-
-struct ToLds
-{
-  int16_t *p; int w;
-  __device__ __forceinline__ void operator()( int y, int x, int16_t v ) const { p[y * w + x] = v; }
-  __device__ __forceinline__ void vec( int y, int x0, const int v[8] ) const { *reinterpret_cast<uint4 *>( p + y * w + x0 ) = pack8( v ); }
-};
-// the list-1 block meets the list-0 block where it lies: addAvg (Buffer.cpp:467-507) or, under a BCW weight, addWeightedAvg (Buffer.cpp:365-397; bcw = the list-1
-// weight of 8) written over it.  Every sample is read and written by one lane.
-struct AvgOver
-{
-  int16_t *p; int w; int shift, cmax, bcw;
-  __device__ __forceinline__ int one( int a, int b ) const
-  {
-    const int v = bcw == MMVD_BCW_DEFAULT ? ( a + b + ( 1 << ( shift - 1 ) ) + 2 * 8192 ) >> shift : ( a * ( 8 - bcw ) + b * bcw + ( 1 << ( shift + 1 ) ) + ( 8192 << 3 ) ) >> ( shift + 2 );
-    return min( cmax, max( 0, v ) );
-  }
-  __device__ __forceinline__ void operator()( int y, int x, int16_t v ) const { p[y * w + x] = ( int16_t ) one( p[y * w + x], v ); }
-  __device__ __forceinline__ void vec( int y, int x0, const int v[8] ) const
-  {
-    int a[8], r[8];
-    load8s( p + y * w + x0, a );
-#pragma unroll
-    for( int k = 0; k < 8; k++ ) r[k] = one( a[k], v[k] );
-    *reinterpret_cast<uint4 *>( p + y * w + x0 ) = pack8( r );
-  }
-};
 
 // THREADS lanes per group and JPB groups per workgroup as motion_comp_kernel (mc.hip); an item is (job, slice): `cpi` consecutive candidates of one CU
 template<int THREADS, int JPB>

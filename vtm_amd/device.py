@@ -240,6 +240,12 @@ class Context:
         assert lut.size >= 1 << luma_bd
         self._check(self.L.vtmhip_set_lmcs_fwd_lut(self.h, lut.ctypes.data, luma_bd))
 
+    def set_lmcs_inv_lut(self, inv_lut, luma_bd):
+        """The reshaper's inverse LUT (int16, 1 << luma_bd entries) for ciip_cand_satd_batch; a slot of its own, beside set_luma_level_weights' inv_lut."""
+        lut = np.ascontiguousarray(inv_lut, np.int16)
+        assert lut.size >= 1 << luma_bd
+        self._check(self.L.vtmhip_set_lmcs_inv_lut(self.h, lut.ctypes.data, luma_bd))
+
     def rspSignal(self, buf, lut):
         """AreaBuf<Pel>::rspSignal( lut ), in place on a 2-D int16 host array (any row stride)."""
         h, w = buf.shape
@@ -394,6 +400,16 @@ class Context:
         """the MMVD loop of the same pre-selection: n MmvdJob CUs -> MmvdCand records and uint64 costs at [job * 64 + cand] (UINT64_MAX where kind == 0).  A malformed
         table is rejected whole (VtmHipError, nothing launched)."""
         self._check(self.L.vtmhip_mmvd_cand_satd_batch_dev(self.h, C.byref(pic), d_org, d_ref, d_jobs, n, max_w, max_h, int(use_satd), d_cand, d_dist))
+
+    def ciip_cand_satd_batch(self, d_ref, d_line, d_org, d_pred, d_jobs, n, max_w, max_h, d_dist, use_satd=True, lmcs=False):
+        """the CIIP loop of the same pre-selection: n CiipJob CUs -> uint64 costs at [job * 4 + cand] (UINT64_MAX from numCand on and in every slot of a malformed
+        job, which the device skips); kept blocks at their keepOff inside d_pred.  Queues one launch: no read-back, no synchronisation.  lmcs: jobs may set
+        their lmcs flag; both LUTs (set_lmcs_fwd_lut, set_lmcs_inv_lut) must then be there, of one depth."""
+        self._check(self.L.vtmhip_ciip_cand_satd_batch_dev(self.h, d_ref, d_line, d_org, d_pred, d_jobs, n, max_w, max_h, int(use_satd), int(lmcs), d_dist))
+
+    def ciip_blend_batch(self, d_line, d_pred, d_jobs, n):
+        """geneWeightedPred in place for n CiipBlendJob blocks (luma and 4:2:0 chroma mixed); a malformed job is skipped on the device"""
+        self._check(self.L.vtmhip_ciip_blend_batch_dev(self.h, d_line, d_pred, d_jobs, n))
 
     def pis_stage(self, level, stage):
         self._check(self.L.vtmhip_pis_stage(self.h, C.byref(level), stage))

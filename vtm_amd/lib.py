@@ -423,6 +423,24 @@ class MmvdCand(C.Structure):
 
 MMVD_NUM_CAND, MMVD_NOT_TESTED, MMVD_PLAIN, MMVD_BDOF = 64, 0, 1, 2
 
+
+class CiipCand(C.Structure):
+    _fields_ = [("refOff", C.c_int64 * 2), ("srcOff", C.c_int64), ("keepOff", C.c_int64), ("refStride", C.c_int32 * 2), ("mv", (C.c_int32 * 2) * 2),
+                ("srcStride", C.c_int32), ("mode", C.c_uint8), ("useAltHpelIf", C.c_uint8), ("pad", C.c_uint8 * 2)]
+
+
+class CiipJob(C.Structure):
+    _fields_ = [("lineOff", C.c_int64), ("orgOff", C.c_int64), ("orgStride", C.c_int32), ("width", C.c_int16), ("height", C.c_int16), ("bitDepth", C.c_uint8),
+                ("leftIntra", C.c_uint8), ("aboveIntra", C.c_uint8), ("lmcs", C.c_uint8), ("numCand", C.c_uint8), ("pad", C.c_uint8 * 3), ("cand", CiipCand * 4)]
+
+
+class CiipBlendJob(C.Structure):
+    _fields_ = [("lineOff", C.c_int64), ("predOff", C.c_int64), ("predStride", C.c_int32), ("width", C.c_int16), ("height", C.c_int16), ("bitDepth", C.c_uint8),
+                ("chroma", C.c_uint8), ("leftIntra", C.c_uint8), ("aboveIntra", C.c_uint8), ("mapFwd", C.c_uint8), ("pad", C.c_uint8 * 3)]
+
+
+CIIP_MAX_CAND, CIIP_MODE_L0, CIIP_MODE_L1, CIIP_MODE_BI, CIIP_MODE_GIVEN = 4, 0, 1, 2, 3
+
 _STRUCTS = [DistJob, TzJob, MeResult, PicParams, IfJob, FracJob, FracResult, TrJob, QuantJob, FullJob, McJob, PelOpJob,
             TuJob, TuResult, AffineJob, MeCfg, MeJob, MeOut, PredJob, MaskedSadJob, GeoBlendJob, DmvrJob, LfnstJob,
             PisRow, PisPu, PisLevel, AffineMeJob, AffineMeOut, LfnstTuJob, PisLevelRun, PisBuffers, SmvdJob, PisPuIn, WtdJob,
@@ -438,6 +456,7 @@ _LFNST_CHAIN_STRUCTS = [LfnstChainJob, IntraLfnstTuJob]       # order of vtmhip_
 _INTRA_CHROMA_CHAIN_STRUCTS = [IntraChromaTuJob, IntraChromaJointJob, IntraChromaJointResult]   # order of vtmhip_intra_chroma_chain_struct_size(which)
 _ISP_STRUCTS = [IspJob, IspResult, IspGeom]                   # order of vtmhip_isp_struct_size(which)
 _MMVD_STRUCTS = [MmvdJob, MmvdCand, MmvdBase]                 # order of vtmhip_mmvd_struct_size(which)
+_CIIP_STRUCTS = [CiipJob, CiipCand, CiipBlendJob]             # order of vtmhip_ciip_struct_size(which)
 
 # every symbol include/vtmhip.h declares (tests/test_abi.py checks the exports against the header text)
 _PROTOS = {
@@ -625,6 +644,14 @@ _PROTOS = {
     "vtmhip_mmvd_cands_host": (C.c_int, [C.POINTER(MmvdJob), C.POINTER(PicParams), C.c_void_p, C.c_void_p]),
     "vtmhip_mmvd_cand_satd_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(PicParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                   C.c_void_p]),
+    "vtmhip_set_lmcs_inv_lut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "vtmhip_ciip_struct_size": (C.c_int, [C.c_int]),
+    "vtmhip_ciip_host": (C.c_int, [C.POINTER(CiipJob), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_uint64)]),
+    "vtmhip_ciip_blend_host": (C.c_int, [C.POINTER(CiipBlendJob), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtmhip_ciip_cand_satd_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.c_void_p]),
+    "vtmhip_ciip_blend_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "vtmhip_pis_run_picture": (C.c_int, [C.c_void_p, C.POINTER(PisLevelRun), C.c_int, C.POINTER(PisBuffers), C.c_void_p, C.POINTER(C.c_void_p), C.c_int]),
     "vtmhip_pis_stage": (C.c_int, [C.c_void_p, C.POINTER(PisLevel), C.c_int]),
     "vtmhip_predInterSearch_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(PisLevelRun), C.POINTER(PisBuffers)]),
@@ -726,6 +753,10 @@ def load():
         if lib.vtmhip_mmvd_struct_size(i) != C.sizeof(s):
             raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
                               % (s.__name__, C.sizeof(s), lib.vtmhip_mmvd_struct_size(i)))
+    for i, s in enumerate(_CIIP_STRUCTS):
+        if lib.vtmhip_ciip_struct_size(i) != C.sizeof(s):
+            raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
+                              % (s.__name__, C.sizeof(s), lib.vtmhip_ciip_struct_size(i)))
     _lib = lib
     return lib
 
