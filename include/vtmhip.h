@@ -1301,6 +1301,104 @@ int vtmhip_ciip_cand_satd_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, 
  * bitDepth outside 8 .. 12, predStride below the width, mapFwd on a chroma job, mapFwd without a forward LUT of the job's depth. */
 int vtmhip_ciip_blend_batch_dev( vtmhip_ctx *ctx, const int16_t *d_lineBase, int16_t *d_predBase, const vtmhip_ciip_blend_job *d_jobs, int n );
 
+/* ---- GEO merge candidates: EncCu::xCheckRDCostMergeGeo2Nx2N up to its RD stage (EncCu.cpp:2811-3031, hook B10) ------------------------------------------------
+ * Eligible: sides 8, 16, 32 or 64 with w < 8h and h < 8w (14 shapes).  Per CU the reference runs, in this order: numCand = sps.getMaxNumGeoCand() uni-predictions
+ * kept as 14-bit blocks (geoBuffer), their rounded copies' whole-block SADs, 64 x numCand masked SADs (sadLarge; sadSmall = sadWhole - sadLarge), the cost filter
+ * over 64 x numCand x ( numCand - 1 ) (split, candidate pair) combinations, the sort, and for the first min( passed, 60 ) of the list the blend of the two 14-bit
+ * blocks with the distortion (SATD, or SAD under getDisableSATDForRD) against the original.
+ *   weights      a plane entry is Clip3( 0, 8, ( 32 + wIdx + 4 ) >> 3 ), a mask entry wIdx > 0, with wIdx in closed form per sample: no plane is uploaded
+ *   first pass   in double, exactly as written: side cost = (double) sad + (double) ( cand + 1 ) * sqrtLambda; bestWholeBlkCost from the first strict minimum of
+ *                the whole-block SADs; a combination is dropped when cost0 + cost1 > bestWholeBlkCost and otherwise kept with + 6 * sqrtLambda
+ *   list order   ascending cost; ties by splitDir, then by index in the pair order m_GeoModeTest -- a total order and one valid outcome of the reference's unstable
+ *                std::sort; this is the project's rule
+ * With the host: PU::getGeoMergeCandidates, the all-duplicates early return (such a CU is not sent), MCTS, the second-pass cost from dist and the bits,
+ * updateCandList and the MRG_FAST_RATIO / best-SATD cuts, spanGeoMotionInfo, 4:2:2 and 4:4:4. */
+enum { VTMHIP_GEO_MAX_CAND = 6, VTMHIP_GEO_MAX_TRY = 60 };
+
+typedef struct
+{
+  int64_t refOff;               /* block position with MV (0,0) in the plane of the ONE list the candidate uses, inside d_refBase */
+  int64_t keepOff;              /* -1, or where the candidate's 14-bit luma block is written inside d_predBase, stride width: the encoder's geoBuffer */
+  int32_t refStride;
+  int32_t mv[2];                /* hor, ver, internal 1/16 precision, clipMv already applied (as vtmhip_ciip_cand); cu.imv is 0: no alternative half-sample filter */
+  int32_t pad;
+} vtmhip_geo_cand;
+
+typedef struct
+{
+  int64_t orgOff;               /* the CU's luma block in the original plane */
+  double  sqrtLambda;           /* RdCost::getMotionLambda(): finite, not negative */
+  int32_t orgStride;
+  int16_t width, height;        /* one of the 14 shapes */
+  uint8_t bitDepth;             /* 8 .. 12 */
+  uint8_t numCand;              /* 2 .. 6 */
+  uint8_t pad[6];
+  vtmhip_geo_cand cand[VTMHIP_GEO_MAX_CAND];
+} vtmhip_geo_job;
+
+typedef struct
+{
+  double   cost;                /* the first-pass cost of the list */
+  uint64_t dist;                /* the blended luma block against the original: SATD (the tile rules of xGetHADs) or SAD; UINT64_MAX in an unused slot */
+  uint8_t  splitDir, cand0, cand1;
+  uint8_t  pad[5];
+} vtmhip_geo_combo;
+
+typedef struct
+{
+  uint64_t sadWhole[VTMHIP_GEO_MAX_CAND];   /* UINT64_MAX from numCand on */
+  int32_t  numPassed;                       /* combinations that passed the filter */
+  int32_t  numTested;                       /* min( numPassed, 60 ) */
+  vtmhip_geo_combo combo[VTMHIP_GEO_MAX_TRY];   /* list order; from numTested on: dist UINT64_MAX, every other field 0 */
+} vtmhip_geo_result;
+
+typedef struct
+{
+  int64_t src0Off, src1Off;     /* the two 14-bit blocks of this plane inside d_srcBase */
+  int64_t dstOff;               /* inside d_dstBase */
+  int32_t src0Stride, src1Stride, dstStride;
+  int16_t width, height;        /* the CU's LUMA size, for chroma jobs too: a chroma job blends ( width / 2 ) x ( height / 2 ) samples */
+  uint8_t splitDir;             /* 0 .. 63 */
+  uint8_t chroma;               /* 0: luma; 1: a 4:2:0 Cb / Cr block (the plane is read two entries apart) */
+  uint8_t bitDepth;
+  uint8_t pad[5];
+} vtmhip_geo_cu_blend_job;
+
+int vtmhip_geo_struct_size( int which );   /* sizeof() of 0 vtmhip_geo_job, 1 vtmhip_geo_cand, 2 vtmhip_geo_combo, 3 vtmhip_geo_result, 4 vtmhip_geo_cu_blend_job; -1 otherwise */
+/* lanes that work on one CU of a vtmhip_geo_cand_satd_batch_dev call: 64 up to 1024 samples, 256 above; 0 when maxWidth x maxHeight is none of the 14 shapes */
+int vtmhip_geo_lanes_per_job( int maxWidth, int maxHeight );
+
+/* The weights (chroma = 0: width x height, chroma = 1: ( width / 2 ) x ( height / 2 ), stride = that width) and the SAD mask (always luma, width x height) of one
+ * split of a width x height CU, from the closed form.  Either output may be NULL.  VTMHIP_E_INVALID for a size outside the 14 shapes or a splitDir outside 0 .. 63. */
+int vtmhip_geo_tables_host( int splitDir, int width, int height, int chroma, int16_t *weightOut, int16_t *maskOut );
+
+/* One CU as host arithmetic (no device, no context) from given 14-bit blocks: pred[k] is candidate k's block, width x height with stride width (refOff / mv are not
+ * read; a keepOff is ignored).  result: as the device leaves it with useSatd.  sadSplit (may be NULL): 64 x 6 sadLarge at [split * 6 + cand], UINT64_MAX from numCand
+ * on.  blend (may be NULL): result->numTested blocks of width * height samples, in list order.  VTMHIP_E_INVALID for a job the table predicate rejects (with
+ * maxWidth = maxHeight = 64) or a missing pointer: nothing is written then. */
+int vtmhip_geo_host( const vtmhip_geo_job *job, const int16_t *orgBase, const int16_t *const pred[VTMHIP_GEO_MAX_CAND], int useSatd, vtmhip_geo_result *result,
+                     uint64_t *sadSplit, int16_t *blend );
+
+/* One call per batch of CUs, one fused kernel: per CU the candidates' motion compensation as 14-bit intermediates into LDS, the kept stores, the whole-block and the
+ * 64 x numCand masked SADs of the rounded blocks (the mask from the closed form), the filter and the ordered list in LDS, and per listed combination the blend with
+ * closed-form weights and the distortion straight from LDS.  Apart from the kept blocks and the result tables no sample goes to global memory.
+ * d_result[job]; d_sadSplit (may be NULL): [job * 384 + split * 6 + cand], UINT64_MAX from numCand on.  maxWidth x maxHeight (one of the 14 shapes) bounds the CUs
+ * of the batch; lanes per CU as vtmhip_geo_lanes_per_job.
+ * The job table is never read back and the stream is never synchronised: the call only queues work and may run under stream capture (the first call of a process
+ * on a device whose bound is above 1024 samples also raises the kernel's dynamic-LDS limit, once; that is no stream operation).  A job that fails the
+ * predicate is skipped ON THE DEVICE -- nothing is read through it, numPassed and numTested are 0, sadWhole, every dist and every d_sadSplit entry of the job are
+ * UINT64_MAX, every other field 0 and no kept block is written: a size outside the 14 shapes or above maxWidth x maxHeight, bitDepth outside 8 .. 12, numCand
+ * outside 2 .. 6, a stride (orgStride, a candidate's refStride) below the width, a sqrtLambda that is not finite or is negative, a keepOff >= 0 with d_predBase
+ * NULL.  Reference planes as described under VTMHIP_PLANE_SLACK. */
+int vtmhip_geo_cand_satd_batch_dev( vtmhip_ctx *ctx, const int16_t *d_refBase, const int16_t *d_orgBase, int16_t *d_predBase, const vtmhip_geo_job *d_jobs, int n,
+                                    int maxWidth, int maxHeight, int useSatd, vtmhip_geo_result *d_result, uint64_t *d_sadSplit );
+
+/* weightedGeoBlk for n blocks with closed-form weights: the RD stage's luma, Cb and Cr blocks of the survivors (EncCu.cpp:3023-3031, :3073), from 14-bit blocks --
+ * kept luma blocks, chroma blocks of vtmhip_mc_batch_dev with bi = 1, chroma = 1.  Luma and chroma jobs mix freely; d_srcBase and d_dstBase may be the same array when
+ * no job's destination overlaps another job's source.  A malformed job is skipped on the device and its destination left as it is: a size outside the 14 shapes, a
+ * splitDir above 63, chroma above 1, bitDepth outside 8 .. 12, a stride below the block's width.  Queues work only. */
+int vtmhip_geo_blend_batch_dev( vtmhip_ctx *ctx, const int16_t *d_srcBase, int16_t *d_dstBase, const vtmhip_geo_cu_blend_job *d_jobs, int n );
+
 /* ================================================================================================================
  * (4) LEVEL-ORDER predInterSearch -- InterSearch::predInterSearch (InterSearch.cpp:2245-3065, translational part: cu.imv 0, default
  *     BCW weight, no SMVD / affine) for ALL PUs of one block size at once, on top of the batched calls above

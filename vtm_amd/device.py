@@ -411,6 +411,15 @@ class Context:
         """geneWeightedPred in place for n CiipBlendJob blocks (luma and 4:2:0 chroma mixed); a malformed job is skipped on the device"""
         self._check(self.L.vtmhip_ciip_blend_batch_dev(self.h, d_line, d_pred, d_jobs, n))
 
+    def geo_cand_satd_batch(self, d_ref, d_org, d_pred, d_jobs, n, max_w, max_h, d_result, d_sad_split=None, use_satd=True):
+        """the GEO loop of the same pre-selection: n GeoJob CUs -> GeoResult records (whole SADs, the ordered list with SATD / SAD of each blend) and, where asked,
+        the sadLarge table [job * 384 + split * 6 + cand]; kept 14-bit blocks go into d_pred.  Malformed jobs are skipped on the device; nothing is read back."""
+        self._check(self.L.vtmhip_geo_cand_satd_batch_dev(self.h, d_ref, d_org, d_pred, d_jobs, n, max_w, max_h, int(use_satd), d_result, d_sad_split))
+
+    def geo_blend_batch(self, d_src, d_dst, d_jobs, n):
+        """weightedGeoBlk for n GeoCuBlendJob blocks (luma and 4:2:0 chroma), the weights from the closed form"""
+        self._check(self.L.vtmhip_geo_blend_batch_dev(self.h, d_src, d_dst, d_jobs, n))
+
     def pis_stage(self, level, stage):
         self._check(self.L.vtmhip_pis_stage(self.h, C.byref(level), stage))
 

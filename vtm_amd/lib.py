@@ -441,6 +441,31 @@ class CiipBlendJob(C.Structure):
 
 CIIP_MAX_CAND, CIIP_MODE_L0, CIIP_MODE_L1, CIIP_MODE_BI, CIIP_MODE_GIVEN = 4, 0, 1, 2, 3
 
+
+class GeoCand(C.Structure):
+    _fields_ = [("refOff", C.c_int64), ("keepOff", C.c_int64), ("refStride", C.c_int32), ("mv", C.c_int32 * 2), ("pad", C.c_int32)]
+
+
+class GeoJob(C.Structure):
+    _fields_ = [("orgOff", C.c_int64), ("sqrtLambda", C.c_double), ("orgStride", C.c_int32), ("width", C.c_int16), ("height", C.c_int16), ("bitDepth", C.c_uint8),
+                ("numCand", C.c_uint8), ("pad", C.c_uint8 * 6), ("cand", GeoCand * 6)]
+
+
+class GeoCombo(C.Structure):
+    _fields_ = [("cost", C.c_double), ("dist", C.c_uint64), ("splitDir", C.c_uint8), ("cand0", C.c_uint8), ("cand1", C.c_uint8), ("pad", C.c_uint8 * 5)]
+
+
+class GeoResult(C.Structure):
+    _fields_ = [("sadWhole", C.c_uint64 * 6), ("numPassed", C.c_int32), ("numTested", C.c_int32), ("combo", GeoCombo * 60)]
+
+
+class GeoCuBlendJob(C.Structure):
+    _fields_ = [("src0Off", C.c_int64), ("src1Off", C.c_int64), ("dstOff", C.c_int64), ("src0Stride", C.c_int32), ("src1Stride", C.c_int32), ("dstStride", C.c_int32),
+                ("width", C.c_int16), ("height", C.c_int16), ("splitDir", C.c_uint8), ("chroma", C.c_uint8), ("bitDepth", C.c_uint8), ("pad", C.c_uint8 * 5)]
+
+
+GEO_MAX_CAND, GEO_MAX_TRY, GEO_NUM_SPLIT = 6, 60, 64
+
 _STRUCTS = [DistJob, TzJob, MeResult, PicParams, IfJob, FracJob, FracResult, TrJob, QuantJob, FullJob, McJob, PelOpJob,
             TuJob, TuResult, AffineJob, MeCfg, MeJob, MeOut, PredJob, MaskedSadJob, GeoBlendJob, DmvrJob, LfnstJob,
             PisRow, PisPu, PisLevel, AffineMeJob, AffineMeOut, LfnstTuJob, PisLevelRun, PisBuffers, SmvdJob, PisPuIn, WtdJob,
@@ -457,6 +482,7 @@ _INTRA_CHROMA_CHAIN_STRUCTS = [IntraChromaTuJob, IntraChromaJointJob, IntraChrom
 _ISP_STRUCTS = [IspJob, IspResult, IspGeom]                   # order of vtmhip_isp_struct_size(which)
 _MMVD_STRUCTS = [MmvdJob, MmvdCand, MmvdBase]                 # order of vtmhip_mmvd_struct_size(which)
 _CIIP_STRUCTS = [CiipJob, CiipCand, CiipBlendJob]             # order of vtmhip_ciip_struct_size(which)
+_GEO_STRUCTS = [GeoJob, GeoCand, GeoCombo, GeoResult, GeoCuBlendJob]   # order of vtmhip_geo_struct_size(which)
 
 # every symbol include/vtmhip.h declares (tests/test_abi.py checks the exports against the header text)
 _PROTOS = {
@@ -652,6 +678,12 @@ _PROTOS = {
     "vtmhip_ciip_cand_satd_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                   C.c_void_p]),
     "vtmhip_ciip_blend_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "vtmhip_geo_struct_size": (C.c_int, [C.c_int]),
+    "vtmhip_geo_lanes_per_job": (C.c_int, [C.c_int, C.c_int]),
+    "vtmhip_geo_tables_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vtmhip_geo_host": (C.c_int, [C.POINTER(GeoJob), C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(GeoResult), C.c_void_p, C.c_void_p]),
+    "vtmhip_geo_cand_satd_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vtmhip_geo_blend_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "vtmhip_pis_run_picture": (C.c_int, [C.c_void_p, C.POINTER(PisLevelRun), C.c_int, C.POINTER(PisBuffers), C.c_void_p, C.POINTER(C.c_void_p), C.c_int]),
     "vtmhip_pis_stage": (C.c_int, [C.c_void_p, C.POINTER(PisLevel), C.c_int]),
     "vtmhip_predInterSearch_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(PisLevelRun), C.POINTER(PisBuffers)]),
@@ -757,6 +789,10 @@ def load():
         if lib.vtmhip_ciip_struct_size(i) != C.sizeof(s):
             raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
                               % (s.__name__, C.sizeof(s), lib.vtmhip_ciip_struct_size(i)))
+    for i, s in enumerate(_GEO_STRUCTS):
+        if lib.vtmhip_geo_struct_size(i) != C.sizeof(s):
+            raise ImportError("ABI mismatch: %s is %d bytes in Python, %d in libvtmhip.so"
+                              % (s.__name__, C.sizeof(s), lib.vtmhip_geo_struct_size(i)))
     _lib = lib
     return lib
 
