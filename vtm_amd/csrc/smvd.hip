@@ -295,8 +295,12 @@ __global__ __launch_bounds__( THREADS ) void smvd_kernel( vtmhip_pic_params pic,
 // packed 16-bit words, the Hadamard is the packed 8x8 form of had.hpp (two lanes = one 16x8 / 8x16 tile).  No LDS, no barriers: the only cross-lane traffic
 // is the tile sum and the (cost, slot) minimum of a group.  The sequential "first candidate below the best so far" rule of the reference equals the
 // lexicographic (cost, evaluation order) minimum of a pass compared with the cost on entry.
-// The integer phases run the same two passes with the taps {0,0,0,64,0,0,0,0}: for rounded uni-prediction that is exactly filterCopy / the single-pass forms
-// ((sum >> s) + 2^(h-1)) >> h == (sum + 32) >> 6 for sum = 2^s q + r.
+// A zero fraction selects the taps {0,0,0,64,0,0,0,0} (under either half-sample table): the two passes then compute, for rounded uni-prediction, exactly filterCopy /
+// the single-pass forms -- ((sum >> s) + 2^(h-1)) >> h == (sum + 32) >> 6 for sum = 2^s q + r.  Where EVERY active lane of the wave evaluates integer vectors on
+// both lists (one vote per evaluation, after clipMv: tile_eval_vote; VTMHIP_SMVD_IDENTITY=0 turns it off) the lanes copy their two tiles instead, as xPredInterBlk
+// does (pred_tile_copy): the predictor pairs and start vectors of a PU over integer motion, every pass under cu.imv 1 and 2.  One fractional lane in the wave and
+// the wave runs both passes as before.  (Per-axis and per-list forms of the shortcut were built and dropped: any branch inside an evaluation took the group forms
+// from 254 to 256 + 7 .. 15 registers, one wave per SIMD instead of two -- DESIGN 4.)
 // =====================================================================================================================================
 #ifndef VTMHIP_SMVD_PREFETCH
 #define VTMHIP_SMVD_PREFETCH 1
@@ -394,6 +398,32 @@ __device__ __forceinline__ void pred_tile( const int16_t *__restrict__ ref, int 
   }
 }
 
+// pred_tile for a vector whose two fractions are 0, i.e. whose taps are {0,0,0,64,0,0,0,0} in both passes.  From TileFir, with g = 6 - shH (the head room;
+// offH = -(8192 << shH), shV = 6 + g, offV = 2^(shV - 1) + (8192 << 6)): the first pass gives (64 v + offH) >> shH = (v << g) - 8192 without losing a bit (shH <= 6),
+// the second (64 t + offV) >> shV = (t + 8192 + 2^(g - 1)) >> g for t of row y + 3 (64 | offV), together ((v << g) + 2^(g - 1)) >> g = v, and the clip leaves a
+// sample of [0, cmax] alone: the tile is copied, which is what xPredInterBlk does (filterCopy).
+template<class RowOut>
+__device__ __forceinline__ void pred_tile_copy( const int16_t *__restrict__ ref, int stride, int mvHor, int mvVer, RowOut out )
+{
+  const int16_t *src = ref + ( long ) ( mvVer >> 4 ) * stride + ( mvHor >> 4 );
+  // two halves of four rows: the barrier keeps the second half's loads (and the original rows the sink loads with them) from being hoisted over the first half's
+  // arithmetic -- registers, as in pred_tile: the 64x64 form holds 168 of them, the last count of three waves per SIMD
+#pragma unroll
+  for( int y0 = 0; y0 < 8; y0 += 4 )
+  {
+    Pel8 p[4];
+#pragma unroll
+    for( int y = 0; y < 4; y++ ) p[y] = *reinterpret_cast<const Pel8 *>( src + ( long ) ( y0 + y ) * stride );
+#pragma unroll
+    for( int y = 0; y < 4; y++ )
+    {
+      const unsigned w[4] = { p[y].v[0], p[y].v[1], p[y].v[2], p[y].v[3] };
+      out( y0 + y, w );
+    }
+    __builtin_amdgcn_sched_barrier( 0 );
+  }
+}
+
 // The packed Hadamard of had.hpp runs three butterfly levels in 16 bits: |difference| <= 4095.  The BCW weight -2 makes the target -4 org + 5 pred (up to 5115
 // for 10-bit samples) and the difference to predB up to 6138: two packed levels (x4 fits 16 bits), the third vertical one and the horizontal ones in 32 bits.
 __device__ __forceinline__ void rows_unpack( const v2s r[4], int m[8] )
@@ -448,12 +478,13 @@ struct TileJob   // what a lane needs of its PU for the evaluation (workgroup- /
   int horMin, horMax, verMin, verMax;
   int w0, w1;                         // BCW form of removeHighFreq (w0 == 0: the default 2 * org - pred)
   bool clip, alt, satd, wide;         // wide: differences beyond the packed Hadamard's range (BCW weight -2)
+  bool identity;                      // the wave votes on zero fractions (tile_eval_vote); false: VTMHIP_SMVD_IDENTITY=0
   TileFir f;
 };
 
 // distortion of the tile at (tx, ty) (in tiles) for the vector pair (A, B); PAIR: lanes 2k, 2k + 1 hold the halves of one 16x8 / 8x16 Hadamard tile (both return
 // its value)
-template<bool PAIR>
+template<bool PAIR, bool COPY>
 __device__ __forceinline__ unsigned tile_eval( const TileJob &t, int tx, int ty, int ax, int ay, int bx, int by )
 {
   ax = min( t.horMax, max( t.horMin, ax ) ); ay = min( t.verMax, max( t.verMin, ay ) );   // clipMv
@@ -463,7 +494,7 @@ __device__ __forceinline__ unsigned tile_eval( const TileJob &t, int tx, int ty,
 #if VTMHIP_SMVD_PREFETCH
   Pel8 onx = *reinterpret_cast<const Pel8 *>( org );      // the original block's rows arrive one output row ahead, like the reference rows in pred_tile
 #endif
-  pred_tile( t.refA + ( long ) ( ty * 8 ) * t.strideA + tx * 8, t.strideA, ax, ay, t.alt, t.f, [&]( int y, const unsigned w[4] )
+  auto outA = [&]( int y, const unsigned w[4] )
   {
 #if VTMHIP_SMVD_PREFETCH
     const Pel8 o = onx;
@@ -479,8 +510,8 @@ __device__ __forceinline__ unsigned tile_eval( const TileJob &t, int tx, int ty,
       if( t.clip ) { r0 = min( t.f.cmax, max( 0, r0 ) ); r1 = min( t.f.cmax, max( 0, r1 ) ); }
       D[y][k].x = ( short ) r0; D[y][k].y = ( short ) r1;
     }
-  } );
-  pred_tile( t.refB + ( long ) ( ty * 8 ) * t.strideB + tx * 8, t.strideB, bx, by, t.alt, t.f, [&]( int y, const unsigned w[4] )
+  };
+  auto outB = [&]( int y, const unsigned w[4] )
   {
 #pragma unroll
     for( int k = 0; k < 4; k++ )
@@ -489,7 +520,10 @@ __device__ __forceinline__ unsigned tile_eval( const TileJob &t, int tx, int ty,
       __builtin_memcpy( &b, &w[k], 4 );
       D[y][k] = D[y][k] - b;     // |pattern - predB| <= 2 * 1023 + 1023; BCW weights 3, 5, 10 stay below that, -2 reaches 6138 (t.wide)
     }
-  } );
+  };
+  const int16_t *refA = t.refA + ( long ) ( ty * 8 ) * t.strideA + tx * 8, *refB = t.refB + ( long ) ( ty * 8 ) * t.strideB + tx * 8;
+  if( COPY ) { pred_tile_copy( refA, t.strideA, ax, ay, outA ); pred_tile_copy( refB, t.strideB, bx, by, outB ); }
+  else       { pred_tile( refA, t.strideA, ax, ay, t.alt, t.f, outA ); pred_tile( refB, t.strideB, bx, by, t.alt, t.f, outB ); }
   if( !t.satd )
   {
     int s = 0;
@@ -501,6 +535,18 @@ __device__ __forceinline__ unsigned tile_eval( const TileJob &t, int tx, int ty,
   }
   if( t.wide ) return satd8_wide<PAIR>( D );
   return PAIR ? satd8_pair_packed( D ) : satd8_packed( D );
+}
+
+// tile_eval with the copy form where every active lane of the wave has four zero fractions after clipMv (frac == 8 under the alternative half-sample taps is a
+// filter, frac == 0 the identity under either table).  Empty slots and finished PUs evaluate the zero vector and vote yes; the lanes a workgroup-form pass does not
+// need are inactive.  One fractional lane and the wave takes the filters, as before.
+template<bool PAIR, bool VOTE>
+__device__ __forceinline__ unsigned tile_eval_vote( const TileJob &t, int tx, int ty, int ax, int ay, int bx, int by )
+{
+  const int cax = min( t.horMax, max( t.horMin, ax ) ), cay = min( t.verMax, max( t.verMin, ay ) );   // clipMv, as tile_eval applies it
+  const int cbx = min( t.horMax, max( t.horMin, bx ) ), cby = min( t.verMax, max( t.verMin, by ) );
+  if( VOTE && t.identity && __all( ( ( cax | cay | cbx | cby ) & 15 ) == 0 ) ) return tile_eval<PAIR, true>( t, tx, ty, ax, ay, bx, by );
+  return tile_eval<PAIR, false>( t, tx, ty, ax, ay, bx, by );
 }
 
 __device__ __forceinline__ int      shfl_x( int v, int m ) { return __shfl_xor( v, m, 64 ); }
@@ -521,13 +567,16 @@ enum { PH_INIT = 0, PH_STARTS, PH_DIAMOND, PH_CROSS, PH_FINAL, PH_COST, PH_DONE 
 #endif
 template<int TX, int TY, int NW, int NSLOT>
 __global__ __launch_bounds__( NW ? 64 * NW : 64 ) void smvd_tile_kernel( vtmhip_pic_params pic, const int16_t *__restrict__ orgBase, const int16_t *__restrict__ refBase,
-                                                                        vtmhip_smvd_job *__restrict__ jobs, int n, int op )
+                                                                        vtmhip_smvd_job *__restrict__ jobs, int n, int op, int identity )
 {
   // group form: NSLOT candidate slots per PU and pass step; a pass of the search (up to 8 candidates: the diamond's first round, two start vectors x four predictor
   // pairs) runs as ceil( candidates / NSLOT ) steps.  Four slots instead of eight: the passes with <= 4 candidates (predictor pairs, later diamond rounds, cross, final
   // check) no longer carry four idle slots, and a wave holds twice as many PUs.
   constexpr int  T = TX * TY, LPP = ( NW ? 8 : NSLOT ) * T, PPW = NW ? 1 : 64 / LPP, NT = NW ? 64 * NW : 64;
   constexpr bool PAIR = TX != TY, GROUP = NW == 0;
+  // 32x32 and 128x128 take no vote: with the second evaluation form their bodies need 179 and 190 registers instead of 167 and 168 -- two waves per SIMD instead of three.
+  // The rule is read off one compiler's register counts (profiles/smvd_identity_kernel_resources_*.txt): check it again (scripts/resource_usage.sh) when the compiler changes
+  constexpr bool VOTE = !( TX == TY && ( TX == 4 || TX == 16 ) );
   static_assert( NW != 0 || NSLOT * T <= 64, "the group form keeps a PU inside one wave" );
   __shared__ unsigned sDist[8];
   const int lane = threadIdx.x, g = GROUP ? lane / LPP : 0, l = GROUP ? lane - g * LPP : lane, slot = GROUP ? l / T : 0, tile = GROUP ? l - slot * T : 0;
@@ -548,6 +597,7 @@ __global__ __launch_bounds__( NW ? 64 * NW : 64 ) void smvd_tile_kernel( vtmhip_
   const int normalizer = bcw != 4 ? mvr::bcw_normaliser( bcw ) : 0;
   t.w0 = normalizer * 8; t.w1 = ( 8 - bcw ) * normalizer;   // (as in make_pattern)
   t.clip = j.clipBiPred != 0; t.alt = j.imv == 3; t.satd = j.useSatd != 0; t.wide = bcw < 0 && !t.clip;
+  t.identity = identity != 0;
   {
     const int bd = pic.bitDepth, headRoom = max( 2, 14 - bd );
     t.f.shH = 6 - headRoom; t.f.offH = -( 8192 << t.f.shH ); t.f.shV = 6 + headRoom; t.f.offV = ( 1 << ( t.f.shV - 1 ) ) + ( 8192 << 6 ); t.f.cmax = ( 1 << bd ) - 1;
@@ -689,7 +739,7 @@ __global__ __launch_bounds__( NW ? 64 * NW : 64 ) void smvd_tile_kernel( vtmhip_
         int ax, ay, bx, by;
         unsigned bits;
         const bool valid = slot_params( s, ax, ay, bx, by, bits ) && s < nSl;
-        unsigned d = tile_eval<PAIR>( t, tx, ty, ax, ay, bx, by );
+        unsigned d = tile_eval_vote<PAIR, VOTE>( t, tx, ty, ax, ay, bx, by );
         // PU sum over the tile lanes of the slot; a Hadamard pair already holds its tile's value in both lanes
 #pragma unroll
         for( int off = 1; off < T; off <<= 1 )
@@ -720,7 +770,7 @@ __global__ __launch_bounds__( NW ? 64 * NW : 64 ) void smvd_tile_kernel( vtmhip_
         unsigned bits;
         if( !slot_params( s, ax, ay, bx, by, bits ) ) continue;    // the skipped pair of the final check (whole tiles: pair lanes stay together)
         tile_xy( tl, tx, ty );
-        const unsigned d = tile_eval<PAIR>( t, tx, ty, ax, ay, bx, by );
+        const unsigned d = tile_eval_vote<PAIR, VOTE>( t, tx, ty, ax, ay, bx, by );
         if( !PAIR || !t.satd || !( tl & 1 ) ) atomicAdd( &sDist[s], d );
       }
       __syncthreads();
@@ -841,23 +891,31 @@ SmvdForm smvd_form( int numCUs, int maxWidth, int maxHeight, int bitDepth, bool 
   return f;
 }
 
+// VTMHIP_SMVD_IDENTITY=0: the tile kernel takes no votes, every prediction runs both filter passes (the `identity` argument)
+static int smvd_identity()
+{
+  static const int identity = env_switch( "VTMHIP_SMVD_IDENTITY", true ) ? 1 : 0;
+  return identity;
+}
+
 template<int TX, int TY>
 void launch_tile( vtmhip_ctx *ctx, const SmvdForm &f, const vtmhip_pic_params *pic, const int16_t *d_orgBase, const int16_t *d_refBase, vtmhip_smvd_job *d_jobs, int n,
                   int op )
 {
   constexpr int T = TX * TY, NW = smvd_tile_waves( T );
+  const int     identity = smvd_identity();
   if constexpr( NW != 0 )
   {
-    hipLaunchKernelGGL( ( smvd_tile_kernel<TX, TY, NW, 8> ), dim3( n ), dim3( 64 * NW ), 0, ctx->stream, *pic, d_orgBase, d_refBase, d_jobs, n, op );
+    hipLaunchKernelGGL( ( smvd_tile_kernel<TX, TY, NW, 8> ), dim3( n ), dim3( 64 * NW ), 0, ctx->stream, *pic, d_orgBase, d_refBase, d_jobs, n, op, identity );
   }
   else
   {
   constexpr int WIDE = 8 * T <= 64 ? 8 : 4;
   const int     waves = ( n + f.pusPerWave - 1 ) / f.pusPerWave;
   if( f.slots == WIDE )
-    hipLaunchKernelGGL( ( smvd_tile_kernel<TX, TY, 0, WIDE> ), dim3( waves ), dim3( 64 ), 0, ctx->stream, *pic, d_orgBase, d_refBase, d_jobs, n, op );
+    hipLaunchKernelGGL( ( smvd_tile_kernel<TX, TY, 0, WIDE> ), dim3( waves ), dim3( 64 ), 0, ctx->stream, *pic, d_orgBase, d_refBase, d_jobs, n, op, identity );
   else
-    hipLaunchKernelGGL( ( smvd_tile_kernel<TX, TY, 0, 4> ), dim3( waves ), dim3( 64 ), 0, ctx->stream, *pic, d_orgBase, d_refBase, d_jobs, n, op );
+    hipLaunchKernelGGL( ( smvd_tile_kernel<TX, TY, 0, 4> ), dim3( waves ), dim3( 64 ), 0, ctx->stream, *pic, d_orgBase, d_refBase, d_jobs, n, op, identity );
   }
 }
 
